@@ -83,6 +83,32 @@ def stage_bytes(n, nv, ni, ni_blended, pixels, tiles, coeffs, list_share=1.0, gr
     }
 
 
+DUMP_BUDGET = 64 * 10**6   # bytes of --dump-outputs in all (64 MB), .npy headers included
+
+
+def dump_outputs(out_dir, arrays, n):
+    """arrays (name -> float32 / float64 host array) -> out_dir/<name>.npy.  Arrays with one row per splat are cut, when together
+    they would not fit the budget, to the same seeded sample of rows (a function of n and the row size alone: the same rows in
+    every run with the same arguments), whose indices go to sample_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {k: a for k, a in arrays.items() if a.ndim >= 1 and a.shape[0] == n and n > 1}
+    fixed = {k: a for k, a in arrays.items() if k not in rows}
+    room = DUMP_BUDGET - 256 * (len(arrays) + 1) - sum(a.nbytes for a in fixed.values())
+    row_bytes = sum(a.nbytes // n for a in rows.values())
+    out = dict(fixed)
+    if rows and row_bytes * n > room:
+        k = max(1, room // (row_bytes + 8))   # (+ 8: the row's index in sample_rows)
+        idx = np.sort(np.random.default_rng(0xD0A7).choice(n, size=min(n, k), replace=False))
+        out.update({name: np.ascontiguousarray(a[idx]) for name, a in rows.items()})
+        out["sample_rows"] = idx.astype(np.float64)
+    else:
+        out.update(rows)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -233,6 +259,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)   # 0.12 s of GPU time; 20 steps read 3-5 % slower (clock ramp)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step left to its caller (the updated splats, the "
+                         "step's loss and counts) as DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded sample of splat rows "
+                         "beyond that, their indices in sample_rows.npy): two builds run with the same arguments compare output for output")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--sh-degree", type=int, default=0)
     ap.add_argument("--workload", default="1m_1080p")
@@ -242,7 +272,7 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="do not re-run a short bench under rocprofv3 --pmc for the counter figures (use the committed CSVs, marked stale)")
     ap.add_argument("--no-stages", action="store_true", help="skip the per-stage HIP-event pass (child runs under rocprofv3 use it)")
     ap.add_argument("--views", type=int, default=2,
-                    help="views each rank cycles through in the timed region (step k trains view k % V).  2 (the default) is the reference's own "
+                    help="views each rank cycles through in the timed region (step k trains view k %% V).  2 (the default) is the reference's own "
                          "training bench: two cameras 2 units apart in x, alternating (crates/brush-bench-test/src/benches.rs:198-220); "
                          "1 = one camera replayed (the round 1-3 headline); >= 3 = an orbit of V cameras")
     ap.add_argument("--no-view-ids", action="store_true", help="do not tell the library which view a batch is (BhTrainBatch.view_id = 0): all views share one per-tile cut table (A/B)")
@@ -280,6 +310,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,10 +414,12 @@ def main():
 
     direct_checked = [False]
 
-    def measure(workload, steps, warmup, with_stages, sh_degree=None, nviews=None, windows=1, exchange=None, algo=None, growth_stop_iter=None):
+    def measure(workload, steps, warmup, with_stages, sh_degree=None, nviews=None, windows=1, exchange=None, algo=None, growth_stop_iter=None,
+                capture=False):
         """Time `windows` windows of `steps` train steps of `workload`, cycling through `nviews` views; returns a dict of raw
         measurements (rank-local; dt = the median window).  exchange / algo: override --exchange / --allreduce (the N > 1 A/B);
-        growth_stop_iter: TrainConfig.growth_stop_iter (1 = every step runs the blend backward without the refine weight)."""
+        growth_stop_iter: TrainConfig.growth_stop_iter (1 = every step runs the blend backward without the refine weight);
+        capture: also return, as host arrays, what the last timed step left to its caller (`outputs`, see --dump-outputs)."""
         sh_degree = args.sh_degree if sh_degree is None else sh_degree
         exchange = exchange or args.exchange
         algo = algo or args.allreduce
@@ -493,6 +527,13 @@ def main():
             for k, (ms, calls) in ctx.profile_fetch().items():   # the dominant kernel over the timed steps of every window
                 a = dominant.get(k, (0.0, 0))
                 dominant[k] = (a[0] + ms, a[1] + calls)
+        outputs = None
+        if capture:   # the last window's last step: the splats updated in place, and the step's own figures
+            last = trainer.stats()
+            outputs = {"transforms": splats.transforms, "sh_coeffs": splats.sh_coeffs, "raw_opacities": splats.raw_opacities}
+            outputs = {k: v.detach().to(device="cpu", dtype=torch.float32).numpy() for k, v in outputs.items()}
+            outputs.update({"loss": np.array([last.loss], np.float64), "num_visible": np.array([last.num_visible], np.float64),
+                            "num_intersections": np.array([last.num_intersections], np.float64)})
         if pg is not None:   # every window: the slowest rank's time
             import torch.distributed as dist
             tmax = torch.tensor(window_dt, dtype=torch.float64, device=dev)
@@ -574,7 +615,7 @@ def main():
         return dict(scene=scene, cp=cp, w=w, h=h, n=n, coeffs=coeffs, dt=dt, window_dt=window_dt, stages=stages, stats=st, isect_blended=isect_blended,
                     nv=nv_mean, ni=ni_mean, per_view=per_view, nviews=nviews, loader=loader is not None, list_share=list_share,
                     near_share_min=min(shares) if shares else 1.0, near_share_max=max(shares) if shares else 1.0, far_slices_queued=far_queued,
-                    timed_steps=steps * max(1, windows), forward_only=fwd_only, dt_plain=dt_plain)
+                    timed_steps=steps * max(1, windows), forward_only=fwd_only, dt_plain=dt_plain, outputs=outputs)
 
     def blend_rooflines(m, steps):
         """HBM and VALU rooflines of the two blend kernels from one measurement."""
@@ -797,7 +838,10 @@ def main():
         lo = train_loop(args.workload, max(2, args.loop_views), args.loop_steps, segment=max(50, args.loop_segment), modes=tuple(x for x in args.loop_only.split(",") if x))
         os.write(real_stdout, (json.dumps({"train_loop": lo}) + "\n").encode())
         return
-    m = measure(args.workload, args.steps, args.warmup, "forward_only" if (world == 1 and not args.no_extra) else True, windows=args.windows)
+    m = measure(args.workload, args.steps, args.warmup, "forward_only" if (world == 1 and not args.no_extra) else True, windows=args.windows,
+                capture=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["outputs"], m["n"])
 
     loop = None
     if world == 1 and not args.no_extra and args.loop_steps > 0 and args.feed == "resident" and not args.splats and args.lists == "sliced":

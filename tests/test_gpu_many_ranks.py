@@ -1,7 +1,9 @@
-"""The multi-rank paths at the world sizes they exist for (BASELINE.json configs[3]: 8 ranks data parallel over cameras;
-configs[4]: 8 ranks, one frame cut into strips of tile rows) — rehearsed on ONE GPU: `world` processes share the device and
-a gloo process group carries the buffers (the gpurun boxes have a single GPU; the collectives' arithmetic, the union
-listing, uneven strips, re-balancing, vis_weight counting and the dense fall-back do not care which transport sums).
+"""The multi-rank paths beyond two ranks (BASELINE.json configs[3]: data parallel over cameras; configs[4]: one frame cut into
+strips of tile rows) — rehearsed on ONE GPU: `world` processes share the device and a gloo process group carries the buffers
+(the collectives' arithmetic, the union listing, uneven strips, re-balancing, vis_weight counting and the dense fall-back do
+not care which transport sums).  A shared GPU admits at most 6 processes at once and the test process holds it too, so no test
+here starts more than MAX_RANKS ranks: configs[3] / [4] name 8, rehearsed at 4 and 5 (an odd world size, whose ring and
+reduce-scatter chunks do not divide evenly).
 Contract: SURVEY.md §8e — all-reduced update == the oracle's step on the mean of the K single-view gradients, replicas
 bit-identical; a K-strip step == the single-GPU step."""
 import math
@@ -18,6 +20,9 @@ import util
 
 pytestmark = pytest.mark.gpu
 
+# worker processes with the GPU open at once, beside the test process itself (which has it open as well): 6 in all
+MAX_RANKS = 5
+
 
 def _free_port():
     s = socket.socket()
@@ -28,6 +33,7 @@ def _free_port():
 
 
 def _run(world, target, args, timeout=900):
+    assert world <= MAX_RANKS, "%d ranks: more processes than a shared GPU admits" % world
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -116,8 +122,8 @@ def _check_against_oracle_mean(bo, problem, world, first, vis):
     return ot
 
 
-@pytest.mark.parametrize("world,sparse", [(4, True), (4, False), (8, True), (8, False)])
-def test_dp_over_cameras_at_4_and_8_ranks_matches_the_oracle_mean_gradient(oracle_lib, world, sparse):
+@pytest.mark.parametrize("world,sparse", [(4, True), (4, False), (5, True), (5, False)])
+def test_dp_over_cameras_at_4_and_5_ranks_matches_the_oracle_mean_gradient(oracle_lib, world, sparse):
     steps = 2
     res = _run(world, _dp_worker, ("small", sparse, steps))
     for key in (1, 2, 3):   # parameters after step 1, after the last step, refine statistics: identical on every rank
@@ -136,11 +142,11 @@ def test_dp_over_cameras_at_4_and_8_ranks_matches_the_oracle_mean_gradient(oracl
     assert np.array_equal(ot.state["vis"] > 0, vis > 0) or np.mean((ot.state["vis"] > 0) != (vis > 0)) <= 2e-3
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 4, 5])
 def test_dp_dense_direct_allreduce_matches_the_oracle_mean_gradient(oracle_lib, world):
     """the dense gradient block summed by the DIRECT all-reduce (reduce-scatter + all-gather over point-to-point
     messages: comm.hip comm_allreduce_direct, restated for the hook path in parallel.allreduce_direct) instead of the collective
-    library's all-reduce: same update as the oracle's step on the mean gradient, replicas bit-identical, at 2 / 4 / 8 ranks."""
+    library's all-reduce: same update as the oracle's step on the mean gradient, replicas bit-identical, at 2 / 4 / 5 ranks."""
     steps = 2
     res = _run(world, _dp_worker, ("small", False, steps, "direct"))
     for key in (1, 2, 3):
@@ -164,10 +170,10 @@ def test_dp_4_ranks_at_1m_1080p_matches_the_oracle_mean_gradient(oracle_lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# one frame over 8 ranks
+# one frame over 4 ranks
 # ---------------------------------------------------------------------------------------------------------------
 def _tile_problem():
-    n, w, h = 12000, 208, 400        # 25 tile rows over 8 ranks: strips of 4 and 3 rows before the first re-cut
+    n, w, h = 12000, 208, 400        # 25 tile rows over 4 ranks: strips of 7 and 6 rows before the first re-cut
     sc = synth.make_scene(n, 0xE8, sh_degree=1, log_scale_range=(math.log(0.02), math.log(0.25)),
                           tan_half_fov=(math.tan(math.radians(30)), math.tan(math.radians(30)) * h / w), spread=2.0)
     cp = synth.default_camera_params(w, h)
@@ -204,9 +210,9 @@ def _tile_worker(rank, world, port, q, strip_loss, sparse, steps):
 
 
 @pytest.mark.parametrize("strip_loss,sparse", [(True, True), (False, True), (True, False)])
-def test_one_frame_over_8_uneven_rebalanced_strips_equals_the_single_gpu_step(dev, strip_loss, sparse):
+def test_one_frame_over_4_uneven_rebalanced_strips_equals_the_single_gpu_step(dev, strip_loss, sparse):
     import brush_amd as ba
-    world, steps = 8, 3
+    world, steps = 4, 3
     res = _run(world, _tile_worker, (strip_loss, sparse, steps))
     r0 = res[0]
     for r in res[1:]:
@@ -218,7 +224,7 @@ def test_one_frame_over_8_uneven_rebalanced_strips_equals_the_single_gpu_step(de
         spans = [r[9][s] for r in res]
         assert spans[0][0] == 0 and spans[-1][1] == 25 and all(a[1] == b[0] for a, b in zip(spans[:-1], spans[1:]))
         assert all(e > b for b, e in spans)
-    assert len({e - b for b, e in [r[9][0] for r in res]}) > 1            # 25 rows over 8 ranks
+    assert len({e - b for b, e in [r[9][0] for r in res]}) > 1            # 25 rows over 4 ranks
     assert [r[9][0] for r in res] != [r[9][steps - 1] for r in res]       # re-balanced
     if sparse:
         assert all(0 < x[1] for x in r0[8])
