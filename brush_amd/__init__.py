@@ -17,6 +17,7 @@ Names and argument meaning follow the reference (paths under
     splat_to_ply / load_splat_from_ply   brush-serde/src/export.rs:179-204, import.rs:166-330 (plain PLY)
     BatchUploader / SceneLoader          brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
     SplatTrainer      brush-train/src/train.rs:140-429 (step) and :431-893 (refine)
+    compute_pup_scores / decimate_to_count   brush-train/src/lod.rs:13-142 (LOD boundary, brush-process/src/train_stream.rs:248-303)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -26,6 +27,6 @@ from .host import (  # noqa: F401
     get_context, image_loss, image_loss_backward, image_loss_value_and_grad, prefix_sum, radix_argsort, tile_sort_offsets, render_splats,
     render_splats_bwd, adam_step, gather_stats, RefineStats, splat_bounds, bounds_median_size, fov_to_focal, focal_to_fov,
     splat_to_ply, load_splat_from_ply, ply_parse_header, ParseMetadata, BatchUploader, SceneLoader, set_list_slicing, last_list_counts, set_view_id,
-    render_splats_diff, RenderNode,
+    render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -1398,3 +1398,127 @@ class SplatTrainer:
         (ctx or self.ctx or get_context()).sync()
         s = self._last_stats
         return TrainStepStats(s.num_visible, s.num_intersections, s.lr_mean, s.loss, s.exchange_rows)
+
+
+# ---------------------------------------------------------------------------
+# LOD decimation (brush-train/src/lod.rs; called at every LOD boundary, brush-process/src/train_stream.rs:248-303)
+# ---------------------------------------------------------------------------
+PUP_PLANES = 21   # lower-triangle entries of the 6x6 H: entry (i, k), i >= k, lives in plane i (i + 1) / 2 + k of the [21, N] accumulator
+
+
+def lod_target_count(n: int, keep_pct: int) -> int:
+    """`(before as f32 * lod_keep_pct as f32 / 100.0).max(1.0) as u32` (train_stream.rs:261), in f32 like the reference."""
+    import numpy as np
+    v = max(np.float32(n) * np.float32(keep_pct) / np.float32(100.0), np.float32(1.0))
+    if v != v:   # `as u32` saturates: NaN -> 0, +inf / huge -> u32::MAX
+        return 0
+    return int(min(float(v), 4294967295.0))
+
+
+def pup_accumulate(v_transforms, hessian=None, rows=None, ctx: Optional[Context] = None):
+    """hessian [21, N] += J Jᵀ of the rows of v_transforms [N, 10] (J = columns 0..2 and 7..9), lod.rs:120-126; rows: optional
+    device list of row ids (only those rows are added).  A new zero accumulator when hessian is None.  Returns the accumulator."""
+    dev = v_transforms.device
+    ctx = ctx or get_context(dev)
+    v = _f32c(v_transforms, dev).reshape(-1, 10)
+    n = v.shape[0]
+    if hessian is None:
+        hessian = torch.zeros((PUP_PLANES, n), dtype=torch.float32, device=dev)
+    if tuple(hessian.shape) != (PUP_PLANES, n) or hessian.dtype != torch.float32 or not hessian.is_contiguous():
+        raise ValueError("hessian must be a contiguous f32 [21, N] tensor")
+    r = None if rows is None else _as_u32(rows, dev).reshape(-1)
+    ctx.check(ctx.lib.bh_pup_accumulate(ctx._h, _ptr(v), n, _ptr(r) if r is not None else None, 0 if r is None else r.numel(), _ptr(hessian)))
+    return hessian
+
+
+def pup_scores(hessian, ctx: Optional[Context] = None):
+    """log_det_6x6 (lod.rs:44-70) of every splat's accumulated H ([21, N]) -> scores [N] f32 (-inf: not positive definite)."""
+    dev = hessian.device
+    ctx = ctx or get_context(dev)
+    h = _f32c(hessian, dev)
+    if h.dim() != 2 or h.shape[0] != PUP_PLANES:
+        raise ValueError("hessian must be [21, N]")
+    n = h.shape[1]
+    scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_pup_scores(ctx._h, _ptr(h), n, _ptr(scores)))
+    return scores
+
+
+def pup_accumulate_view(splats: "Splats", camera, gt_packed, hessian, ctx: Optional[Context] = None):
+    """One view of compute_pup_scores (bh_pup_accumulate_view): forward, L1 loss against gt_packed ([H, W] rgba8 as int32),
+    backward, hessian += J Jᵀ over the visible splats.  Makes the ctx's last unretained forward stale."""
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    gt = _as_u32(gt_packed, dev)
+    h, w = gt.shape
+    cam = camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((w, h))
+    n = splats.num_splats()
+    if tuple(hessian.shape) != (PUP_PLANES, n) or hessian.dtype != torch.float32 or not hessian.is_contiguous():
+        raise ValueError("hessian must be a contiguous f32 [21, N] tensor")
+    ms = splats.min_scale
+    ctx.check(ctx.lib.bh_pup_accumulate_view(ctx._h, C.byref(cam), n, splats.sh_degree(), _ptr(splats.transforms), _ptr(splats.sh_coeffs),
+                                             _ptr(splats.raw_opacities), _ptr(ms) if ms is not None else None,
+                                             _ffi.FLAG_MIP if splats.render_mip else 0, _ptr(gt), _ptr(hessian)))
+    return hessian
+
+
+def compute_pup_scores(splats: "Splats", views, ctx: Optional[Context] = None, return_hessian=False):
+    """compute_pup_scores (lod.rs:78-142): PUP sensitivity score of every splat over the training views -> scores [N] f32 on the
+    device (and the [21, N] accumulator with return_hessian).  `views` has SceneLoader's shape: (image uint8 [H,W,3|4] or a
+    callable returning one, Camera[, alpha_is_mask]); the GT is packed like view_to_packed_data (premultiplied unless the alpha is a
+    mask) through a BatchUploader.  One bh_pup_accumulate_view per view, in list order, then bh_pup_scores."""
+    import numpy as np
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    n = splats.num_splats()
+    hessian = torch.zeros((PUP_PLANES, n), dtype=torch.float32, device=dev)
+    up = None
+    try:
+        for view in views:
+            img = view[0]() if callable(view[0]) else view[0]
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            mask = bool(view[2]) if len(view) > 2 else False
+            pixels = img.shape[0] * img.shape[1]
+            if up is None or up.max_pixels < pixels:
+                if up is not None:
+                    ctx.sync()   # (the slots of the old ring may still be read by queued views)
+                    up.close()
+                up = BatchUploader(pixels, 2, ctx)
+            slot = up.submit(img, premultiply=not mask)
+            gt, _ = up.acquire(slot)
+            pup_accumulate_view(splats, view[1], gt, hessian, ctx)
+            up.release(slot)
+        scores = pup_scores(hessian, ctx)
+    finally:
+        if up is not None:
+            ctx.sync()
+            up.close()
+    return (scores, hessian) if return_hessian else scores
+
+
+def decimate_to_count(splats: "Splats", scores, target_count: int, ctx: Optional[Context] = None, return_indices=False):
+    """decimate_to_count (lod.rs:13-38): new Splats of the target_count highest-scored splats in score-descending order (ties:
+    ascending index; NaN after -inf).  min_scale, when set, is gathered too.  target_count >= N returns `splats` itself.
+    return_indices: also the kept source rows (int32 [K] device)."""
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    n = splats.num_splats()
+    s = _f32c(scores, dev).reshape(-1)
+    if s.numel() != n:
+        raise ValueError("one score per splat")
+    target_count = int(target_count)
+    if target_count >= n:
+        return (splats, torch.arange(n, dtype=torch.int32, device=dev)) if return_indices else splats
+    k = max(target_count, 0)
+    c = splats.sh_coeffs.shape[1]
+    ot = torch.empty((k, 10), dtype=torch.float32, device=dev)
+    osh = torch.empty((k, c, 3), dtype=torch.float32, device=dev)
+    oo = torch.empty((k,), dtype=torch.float32, device=dev)
+    oms = None if splats.min_scale is None else torch.empty((k,), dtype=torch.float32, device=dev)
+    idx = torch.empty((k,), dtype=torch.int32, device=dev)
+    ms = splats.min_scale
+    ctx.check(ctx.lib.bh_decimate_to_count(ctx._h, _ptr(s), n, k, c, _ptr(splats.transforms), _ptr(splats.sh_coeffs), _ptr(splats.raw_opacities),
+                                           _ptr(ms) if ms is not None else None, _ptr(ot), _ptr(osh), _ptr(oo),
+                                           _ptr(oms) if oms is not None else None, _ptr(idx)))
+    out = Splats(ot, osh, oo, splats.render_mip, dev, oms)
+    return (out, idx) if return_indices else out

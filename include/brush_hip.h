@@ -19,6 +19,8 @@
  *   bh_train_step       <- SplatTrainer::step                 brush-train/src/train.rs:176-429
  *   bh_fold_min_scale[_backward] <- fold_min_scale (+ its autodiff)  brush-render/src/gaussian_splats.rs:86-111
  *   bh_compute_min_scale <- compute_min_scale                brush-train/src/train.rs:102-125
+ *   bh_pup_accumulate[_view] / bh_pup_scores <- compute_pup_scores + log_det_6x6   brush-train/src/lod.rs:44-142
+ *   bh_decimate_to_count <- decimate_to_count                brush-train/src/lod.rs:13-38
  *   bh_uploader_*       <- view_to_packed_data + the SceneLoader hand-off   brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
  *   bh_splat_to_ply     <- splat_to_ply                       brush-serde/src/export.rs:86-204
  *   bh_ply_parse_header / bh_splats_from_ply[_strided] <- load_splat_from_ply (plain + SuperSplat-compressed PLY, subsample)  brush-serde/src/import.rs:49-74,166-600
@@ -562,6 +564,41 @@ int bh_refine_apply(bh_ctx* ctx, const BhRefineConfig* cfg /*host*/, const BhTra
 /* get_splat_bounds / bounds_from_pos (brush-train/src/splat_init.rs:130-160): per-axis percentile
  * box of the means ([N,10] transforms, columns 0..2), non-finite values ignored; blocking. */
 int bh_splat_bounds(bh_ctx* ctx, const float* transforms, uint32_t n, float percentile, float* center /*host[3]*/, float* extent /*host[3]*/);
+
+/* ---- LOD decimation (brush-train/src/lod.rs) ------------------------------------ */
+/* What a LOD boundary of the training loop does (brush-process/src/train_stream.rs:248-303): score every splat by PUP sensitivity
+ * over the training views, keep the target_count best, build a fresh trainer.  The Hessian accumulator is the 21 lower-triangle
+ * entries of each splat's 6x6 H = sum over views of J Jᵀ, J = [dL/dmean (3), dL/dlog_scale (3)], as planes of N floats:
+ * hessian [21,N], entry (i,k) with i >= k in plane i(i+1)/2 + k (84 B per splat; the reference holds [N,6,6]).  The caller zeroes
+ * it before the first view.  All asynchronous on the ctx stream except where a forward reads its counts back. */
+/* hessian += J Jᵀ of v_transforms' rows (v_transforms [N,10]: J = columns 0..2 and 7..9) in f32, one multiply then one add per
+ * entry: lod.rs:120-126.  rows == NULL: all n rows; else the m row ids listed at rows (device; ids >= n are skipped).  A row whose
+ * six components are all +-0 is skipped, which is bit-identical. */
+int bh_pup_accumulate(bh_ctx* ctx, const float* v_transforms, uint32_t n, const uint32_t* rows, uint32_t m, float* hessian);
+/* One view of compute_pup_scores (lod.rs:91-127): forward with complete lists (BH_FLAG_BWD_INFO | (flags & BH_FLAG_MIP),
+ * background 0) of fold_min_scale(params) when min_scale != NULL, loss = mean_{H,W,3} |pred.rgb - gt.rgb| (l1 1, ssim 0, no
+ * composite, no mask, whatever the GT's alpha), backward, fold backward, then bh_pup_accumulate of the gradient (only the rows of
+ * splats that reached a pixel are non-zero; the others are skipped, which is bit-identical to accumulating the visible list).  gt_packed [H,W] rgba8 device, as view_to_packed_data makes
+ * it.  This IS a forward like any other: it makes the ctx's last unretained forward stale (bh_render_backward_saved on it fails).
+ * Gradient scratch comes from the ctx arena and stays allocated: v_transforms + v_sh_coeffs + 2 [N] vectors = 4 N (12 + 3C) bytes
+ * (C = (sh_degree+1)^2: the [N,C,3] SH gradient alone is 1.15 GB at 6 M splats / SH degree 3), + 44 N bytes with min_scale, +
+ * 16 H W bytes for dL/dimg.  Blocks while the forward reads its counts back, like bh_render_forward. */
+int bh_pup_accumulate_view(bh_ctx* ctx, const BhCamera* cam /*host*/, uint32_t n, uint32_t sh_degree, const float* transforms,
+                           const float* sh_coeffs, const float* raw_opacities, const float* min_scale /*[N] or NULL*/, uint32_t flags,
+                           const uint32_t* gt_packed, float* hessian /*[21,N]*/);
+/* log_det_6x6 (lod.rs:44-70) of every splat's H: the reference's Cholesky in its loop order, f32, no FMA, correctly rounded divide
+ * and sqrt; a pivot <= 0 gives -inf, a NaN propagates; score = 2 sum ln l_ii.  scores [N]. */
+int bh_pup_scores(bh_ctx* ctx, const float* hessian /*[21,N]*/, uint32_t n, float* scores);
+/* decimate_to_count (lod.rs:13-38): the min(target_count, n) splats of highest score, in score-descending order, ties in
+ * ascending index (the reference's stable sort_by with partial_cmp; -0 == +0).  NaN scores sort after -inf (the reference's order
+ * with NaN is unspecified).  Rows of transforms [N,10], sh_coeffs [N,num_coeffs,3], raw_opacities [N] and — unlike the reference,
+ * which leaves it at the old length — min_scale [N] (NULL: none) are gathered into the outputs, which must not overlap the inputs.
+ * target_count >= n: the inputs are copied unchanged, in their order (lod.rs:15-17).  keep_idx (device, [min(target, n)], or
+ * NULL): the source row of every output row. */
+int bh_decimate_to_count(bh_ctx* ctx, const float* scores, uint32_t n, uint32_t target_count, uint32_t num_coeffs,
+                         const float* transforms, const float* sh_coeffs, const float* raw_opacities, const float* min_scale,
+                         float* out_transforms, float* out_sh, float* out_raw_opacities, float* out_min_scale,
+                         uint32_t* keep_idx);
 
 /* ---- PLY at the edges (brush-serde) -------------------------------------------- */
 /* splat_to_ply (brush-serde/src/export.rs:179-204): the INRIA-layout binary_little_endian PLY Brush writes —

@@ -18,6 +18,7 @@
 //   brush_hip::adam_step / gather_stats              brush-train/src/adam_scaled.rs:75-147, stats.rs:40-50
 //   brush_hip::BatchUploader / SceneLoader           brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
 //   brush_hip::sample_background / normal_samples    train.rs:896-908, 389-416 (the library's counter-based generator)
+//   brush_hip::pup_accumulate[_view] / pup_scores / decimate_to_count / lod_target_count   brush-train/src/lod.rs:13-142, train_stream.rs:261
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -853,5 +854,57 @@ class SplatTrainer {
     bool have_seed_ = false;
     std::vector<float> view_cams_;
 };
+
+// ---- LOD decimation (brush-train/src/lod.rs; the LOD boundary of brush-process/src/train_stream.rs:248-303) -------------------
+constexpr uint32_t kPupPlanes = 21;  // the [21,N] accumulator: entry (i,k), i >= k, of a splat's 6x6 H in plane i(i+1)/2 + k
+// `(n as f32 * keep_pct as f32 / 100.0).max(1.0) as u32` (train_stream.rs:261)
+inline uint32_t lod_target_count(uint32_t n, uint32_t keep_pct) {
+    const float v = std::max((float)n * (float)keep_pct / 100.0f, 1.0f);
+    return v >= 4294967295.0f ? UINT32_MAX : (uint32_t)v;
+}
+// hessian [21,N] += J Jᵀ of v_transforms' rows (lod.rs:120-126); rows: optional device list of row ids
+inline void pup_accumulate(const Context& ctx, const float* v_transforms, uint32_t n, DeviceBuffer<float>& hessian, const uint32_t* rows = nullptr,
+                           uint32_t num_rows = 0) {
+    if (hessian.size() != (size_t)kPupPlanes * n) throw Error(BH_ERR_INVALID_ARG, "pup_accumulate: hessian must hold [21,N] floats");
+    ctx.check(bh_pup_accumulate(ctx.get(), v_transforms, n, rows, num_rows, hessian.data()));
+    ctx.sync();
+}
+// one view of compute_pup_scores (lod.rs:91-127): forward, L1 loss against gt_packed ([h,w] rgba8 device), backward, accumulate
+inline void pup_accumulate_view(const Context& ctx, const Splats& splats, const Camera& camera, const uint32_t* gt_packed, uint32_t img_w, uint32_t img_h,
+                                DeviceBuffer<float>& hessian) {
+    if (hessian.size() != (size_t)kPupPlanes * splats.num_splats()) throw Error(BH_ERR_INVALID_ARG, "pup_accumulate_view: hessian must hold [21,N] floats");
+    const BhCamera cam = camera.uniforms(img_w, img_h);
+    ctx.check(bh_pup_accumulate_view(ctx.get(), &cam, splats.num_splats(), splats.sh_degree(), splats.transforms.data(), splats.sh_coeffs.data(),
+                                     splats.raw_opacities.data(), splats.min_scale ? splats.min_scale->data() : nullptr,
+                                     splats.render_mip ? BH_FLAG_MIP : 0u, gt_packed, hessian.data()));
+    ctx.sync();
+}
+// log_det_6x6 (lod.rs:44-70) of every splat's H -> scores [N]
+inline DeviceBuffer<float> pup_scores(const Context& ctx, const DeviceBuffer<float>& hessian, uint32_t n) {
+    if (hessian.size() != (size_t)kPupPlanes * n) throw Error(BH_ERR_INVALID_ARG, "pup_scores: hessian must hold [21,N] floats");
+    DeviceBuffer<float> scores(n);
+    ctx.check(bh_pup_scores(ctx.get(), hessian.data(), n, scores.data()));
+    ctx.sync();
+    return scores;
+}
+// decimate_to_count (lod.rs:13-38): the target_count highest-scored splats, score-descending (ties: ascending index; NaN last),
+// min_scale gathered too.  keep_idx (optional): the source row of every kept splat.  target_count >= N: a copy of the splats.
+inline Splats decimate_to_count(const Context& ctx, const Splats& splats, const float* scores, uint32_t target_count,
+                                std::vector<uint32_t>* keep_idx = nullptr) {
+    const uint32_t n = splats.num_splats(), k = std::min(target_count, n), c = splats.num_coeffs();
+    Splats out;
+    out.render_mip = splats.render_mip;
+    out.transforms.resize((size_t)k * 10);
+    out.sh_coeffs.resize((size_t)k * c * 3);
+    out.raw_opacities.resize(k);
+    if (splats.min_scale) out.min_scale.emplace(k);
+    DeviceBuffer<uint32_t> idx(k);
+    ctx.check(bh_decimate_to_count(ctx.get(), scores, n, target_count, c, splats.transforms.data(), splats.sh_coeffs.data(), splats.raw_opacities.data(),
+                                   splats.min_scale ? splats.min_scale->data() : nullptr, out.transforms.data(), out.sh_coeffs.data(),
+                                   out.raw_opacities.data(), out.min_scale ? out.min_scale->data() : nullptr, idx.data()));
+    ctx.sync();
+    if (keep_idx) *keep_idx = idx.download();
+    return out;
+}
 
 }  // namespace brush_hip
