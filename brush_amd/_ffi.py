@@ -161,6 +161,7 @@ SYMBOLS = {
     "bh_refine_plan_flags": (C.c_void_p, [C.c_void_p, C.c_int]),
     "bh_refine_apply": (C.c_int, [C.c_void_p, C.POINTER(BhRefineConfig), C.POINTER(BhTrainState), C.POINTER(BhTrainState)]),
     "bh_splat_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "bh_knn_log_scales": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bh_fold_min_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bh_fold_min_scale_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bh_compute_min_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, fp, C.c_uint32, C.c_float, C.c_void_p]),
@@ -170,6 +171,7 @@ SYMBOLS = {
     "bh_decimate_to_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 9),
     "bh_splat_to_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, fp, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "bh_ply_parse_header": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(BhPlyInfo)]),
+    "bh_ply_vertex_has_property": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p]),
     "bh_splats_from_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bh_splats_from_ply_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bh_uploader_create": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_uint32]),

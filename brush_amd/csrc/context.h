@@ -71,6 +71,7 @@ enum Slot : int {
     SLOT_LOD_FOLDED,         // ... fold_min_scale(params): transforms [N,10] | raw_opac [N]
     SLOT_LOD_LOSS,           // ... dL/dimg [H,W,4] | the loss scalar
     SLOT_LOD_SORT,           // bh_decimate_to_count: keys [N] | sorted keys [N] | sorted ids [N]
+    SLOT_KNN,                // bh_knn_log_scales: control | keys | sorted keys | order | rank cells [N] | x y z [N] | tree boxes (knn.hip)
     SLOT_COUNT
 };
 

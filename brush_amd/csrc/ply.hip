@@ -279,6 +279,7 @@ struct ParsedHeader {
     CompressedLayout comp{};
     PlyByteCols bytes{};
     bool mixed = false;   // some vertex property is not a float, or a colour override is present: the byte-offset path
+    std::vector<std::string> vertex_props;   // names of the vertex element's properties, in file order (plain files)
     std::string error;
 };
 
@@ -474,6 +475,7 @@ static bool parse_header(const uint8_t* bytes, uint64_t len, ParsedHeader& out) 
                 return false;
             }
             if (code != PS_F32) out.mixed = true;
+            out.vertex_props.push_back(nm);
             int slot = -1;
             if (nm == "x") slot = PLY_SLOT_XYZ; else if (nm == "y") slot = PLY_SLOT_XYZ + 1; else if (nm == "z") slot = PLY_SLOT_XYZ + 2;
             else if (nm == "scale_0") slot = PLY_SLOT_SCALE; else if (nm == "scale_1") slot = PLY_SLOT_SCALE + 1; else if (nm == "scale_2") slot = PLY_SLOT_SCALE + 2;
@@ -580,6 +582,31 @@ int bh_ply_parse_header(const void* bytes, uint64_t len, BhPlyInfo* info) {
     ParsedHeader ph;
     if (!parse_header((const uint8_t*)bytes, len, ph)) return ph.error.rfind("unsupported", 0) == 0 ? BH_ERR_UNSUPPORTED : BH_ERR_INVALID_ARG;
     *info = ph.info;
+    return 0;
+}
+
+int bh_ply_vertex_has_property(const void* bytes, uint64_t len, const char* name) {
+    if (!bytes || !name) return BH_ERR_INVALID_ARG;
+    ParsedHeader ph;
+    if (!parse_header((const uint8_t*)bytes, len, ph)) return ph.error.rfind("unsupported", 0) == 0 ? BH_ERR_UNSUPPORTED : BH_ERR_INVALID_ARG;
+    const std::string nm = name;
+    if (ph.info.compressed) {
+        // the packed_* properties of the file, and the fields of the splat they decode to (import.rs:407-600): a compressed file
+        // always carries positions, scales, rotations, opacity and colour, plus f_rest_k for k < its `sh` properties
+        for (const char* k : kVertexNames)
+            if (nm == k) return 1;
+        static const char* const decoded[] = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3",
+                                              "opacity", "f_dc_0", "f_dc_1", "f_dc_2"};
+        for (const char* k : decoded)
+            if (nm == k) return 1;
+        if (nm.rfind("f_rest_", 0) == 0 && nm.size() > 7 && nm.find_first_not_of("0123456789", 7) == std::string::npos) {
+            const long k = std::strtol(nm.c_str() + 7, nullptr, 10);
+            return k >= 0 && k < (long)ph.comp.sh_props ? 1 : 0;
+        }
+        return 0;
+    }
+    for (const std::string& p : ph.vertex_props)
+        if (p == nm) return 1;
     return 0;
 }
 

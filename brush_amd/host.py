@@ -1522,3 +1522,78 @@ def decimate_to_count(splats: "Splats", scores, target_count: int, ctx: Optional
                                            _ptr(oms) if oms is not None else None, _ptr(idx)))
     out = Splats(ot, osh, oo, splats.render_mip, dev, oms)
     return (out, idx) if return_indices else out
+
+
+# ---------------------------------------------------------------------------
+# point-cloud initialisation (brush-train/src/splat_init.rs:179-242, brush-process/src/train_stream.rs:100-123)
+# ---------------------------------------------------------------------------
+def ply_vertex_has_property(data: bytes, name: str) -> bool:
+    """Whether the PLY's vertex element has property `name` (host only).  has_property("scale_0") is how import.rs:332 decides
+    that SplatData::log_scales is None; a SuperSplat-compressed file always has scales."""
+    rc = _ffi.load().bh_ply_vertex_has_property(data, len(data), name.encode())
+    if rc < 0:
+        raise BrushHipError("malformed or unsupported PLY (%d)" % rc)
+    return rc == 1
+
+
+def knn_log_scales(splats_or_transforms, ctx: Optional[Context] = None, return_distances=False, return_stats=False):
+    """compute_knn_scales (splat_init.rs:179-216) on the device: per row ln(clamp((d1 + d2) / 4, 1e-3, 0.1 median_size)), d1 <= d2
+    the f32 distances to the two nearest other rows, median_size from the 0.75-percentile box; n < 3 gives 0.  A non-finite row is
+    nobody's neighbour and a missing neighbour is at +inf (such rows get the upper clamp).
+    A Splats is updated in place (transforms columns 7..9); a tensor ([N,10] transforms or [N,3] means) is not modified.
+    Returns log_scales [N,3] f32 (the three columns are equal), then nn_dist [N,2] (d1, d2) with return_distances, then
+    {"pairs_tested": distance evaluations performed} with return_stats."""
+    if isinstance(splats_or_transforms, Splats):
+        dev = splats_or_transforms.device
+        tr = splats_or_transforms.transforms
+    else:
+        t = splats_or_transforms
+        dev = t.device if isinstance(t, torch.Tensor) and t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        t = _f32c(t, dev)
+        if t.dim() != 2 or t.shape[1] not in (3, 10):
+            raise ValueError("expected Splats, transforms [N,10] or means [N,3]")
+        tr = torch.zeros((t.shape[0], 10), dtype=torch.float32, device=dev)
+        tr[:, : t.shape[1]] = t
+    ctx = ctx or get_context(dev)
+    n = tr.shape[0]
+    nn = torch.empty((n, 2), dtype=torch.float32, device=dev) if return_distances else None
+    pairs = C.c_uint64(0)
+    ctx.check(ctx.lib.bh_knn_log_scales(ctx._h, _ptr(tr), n, _ptr(nn) if nn is not None else None, C.byref(pairs)))
+    out = [tr[:, 7:10].clone()]
+    if return_distances:
+        out.append(nn)
+    if return_stats:
+        out.append({"pairs_tested": int(pairs.value)})
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def to_init_splats(means, rotations=None, log_scales=None, sh_coeffs=None, raw_opacities=None, render_mip=False, device=None,
+                   ctx: Optional[Context] = None) -> Splats:
+    """to_init_splats (splat_init.rs:218-242): Splats from a point cloud's SplatData, with the reference's defaults for what is
+    absent — log-scales by compute_knn_scales (knn_log_scales, only when log_scales is None), rotation (1, 0, 0, 0) (w x y z),
+    raw opacity inverse_sigmoid(0.5) = 0, SH a single grey coefficient 0.5 per channel."""
+    device = torch.device(device) if device is not None else (means.device if isinstance(means, torch.Tensor) and means.is_cuda
+                                                               else torch.device("cuda", torch.cuda.current_device()))
+    m = _f32c(means, device).reshape(-1, 3)
+    n = m.shape[0]
+    rot = (_f32c(rotations, device).reshape(n, 4) if rotations is not None
+           else torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device).repeat(n, 1))
+    ls = _f32c(log_scales, device).reshape(n, 3) if log_scales is not None else torch.zeros((n, 3), dtype=torch.float32, device=device)
+    sh = _f32c(sh_coeffs, device).reshape(n, -1, 3) if sh_coeffs is not None else torch.full((n, 1, 3), 0.5, dtype=torch.float32, device=device)
+    op = _f32c(raw_opacities, device).reshape(n) if raw_opacities is not None else torch.zeros((n,), dtype=torch.float32, device=device)
+    splats = Splats(torch.cat([m, rot, ls], dim=1), sh, op, render_mip, device)
+    if log_scales is None:
+        knn_log_scales(splats, ctx)
+    return splats
+
+
+def load_init_splats(data: bytes, max_splats: Optional[int] = None, subsample_points: Optional[int] = None, device=None, render_mip=None,
+                     ctx: Optional[Context] = None):
+    """What the training stream does with an init PLY (train_stream.rs:100-123): load_splat_from_ply with subsampling
+    (subsample_points, then SplatData::subsample(max_splats)), then to_init_splats — compute_knn_scales over the KEPT rows when the
+    file has no scale_0 (import.rs:332), the file's scales otherwise.  Rotation / opacity / SH defaults are the loader's, which
+    are to_init_splats' own.  -> (Splats, ParseMetadata)."""
+    splats, meta = load_splat_from_ply(data, device=device, render_mip=render_mip, ctx=ctx, subsample_points=subsample_points, max_splats=max_splats)
+    if not ply_vertex_has_property(data, "scale_0"):
+        knn_log_scales(splats, ctx)
+    return splats, meta

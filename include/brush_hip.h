@@ -21,6 +21,8 @@
  *   bh_compute_min_scale <- compute_min_scale                brush-train/src/train.rs:102-125
  *   bh_pup_accumulate[_view] / bh_pup_scores <- compute_pup_scores + log_det_6x6   brush-train/src/lod.rs:44-142
  *   bh_decimate_to_count <- decimate_to_count                brush-train/src/lod.rs:13-38
+ *   bh_knn_log_scales   <- compute_knn_scales (to_init_splats)  brush-train/src/splat_init.rs:179-242
+ *   bh_ply_vertex_has_property <- PlyHeader has_property("scale_0")  brush-serde/src/import.rs:332
  *   bh_uploader_*       <- view_to_packed_data + the SceneLoader hand-off   brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
  *   bh_splat_to_ply     <- splat_to_ply                       brush-serde/src/export.rs:86-204
  *   bh_ply_parse_header / bh_splats_from_ply[_strided] <- load_splat_from_ply (plain + SuperSplat-compressed PLY, subsample)  brush-serde/src/import.rs:49-74,166-600
@@ -564,6 +566,22 @@ int bh_refine_apply(bh_ctx* ctx, const BhRefineConfig* cfg /*host*/, const BhTra
 /* get_splat_bounds / bounds_from_pos (brush-train/src/splat_init.rs:130-160): per-axis percentile
  * box of the means ([N,10] transforms, columns 0..2), non-finite values ignored; blocking. */
 int bh_splat_bounds(bh_ctx* ctx, const float* transforms, uint32_t n, float percentile, float* center /*host[3]*/, float* extent /*host[3]*/);
+
+/* ---- point-cloud initialisation (brush-train/src/splat_init.rs) ------------------- */
+/* compute_knn_scales (brush-train/src/splat_init.rs:179-216) in place: reads columns 0..2 of transforms, writes 7..9.
+ * Per row: d1 <= d2 the two smallest f32 distances sqrt((dx*dx + dy*dy) + dz*dz) to rows j != i (duplicates at 0), then
+ * ln(clamp((d1 + d2) / 4, 1e-3, 0.1 median_size)) in all three columns, median_size = max(2 * middle extent of
+ * bh_splat_bounds(0.75), 0.01); n < 3: every log-scale is 0.  A non-finite row (NaN / +-inf coordinate) is nobody's neighbour
+ * and a missing neighbour is at +inf: such a row, and a finite row with fewer than two finite neighbours, gets ln(0.1 median_size).
+ * Exact (d1, d2 bit-identical to an f32 brute force) and not quadratic: Morton order + implicit box tree + one wave per 64
+ * queries (knn.hip).  Scratch from the ctx arena: 28 B per point + the radix sorts' 16 B + bh_splat_bounds' 12 B.
+ * nn_dist (device [N,2], nullable): d1, d2 per row.  pairs_tested (host, nullable): distance evaluations performed.  Blocking. */
+int bh_knn_log_scales(bh_ctx* ctx, float* transforms, uint32_t n, float* nn_dist, uint64_t* pairs_tested);
+/* Host only: 1 if the PLY's vertex element has property `name`, 0 if not, < 0 on a bad header.
+ * This is how a caller tells SplatData::log_scales == None (import.rs:332: has_property("scale_0")) from a file with scales.
+ * A SuperSplat-compressed file answers for the splat it decodes to (x y z, scale_0..2, rot_0..3, opacity, f_dc_0..2, its
+ * f_rest_k) as well as for its own packed_* vertex properties: it always has scales. */
+int bh_ply_vertex_has_property(const void* bytes, uint64_t len, const char* name);
 
 /* ---- LOD decimation (brush-train/src/lod.rs) ------------------------------------ */
 /* What a LOD boundary of the training loop does (brush-process/src/train_stream.rs:248-303): score every splat by PUP sensitivity

@@ -19,6 +19,7 @@
 //   brush_hip::BatchUploader / SceneLoader           brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
 //   brush_hip::sample_background / normal_samples    train.rs:896-908, 389-416 (the library's counter-based generator)
 //   brush_hip::pup_accumulate[_view] / pup_scores / decimate_to_count / lod_target_count   brush-train/src/lod.rs:13-142, train_stream.rs:261
+//   brush_hip::knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242, train_stream.rs:100-123
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -905,6 +906,47 @@ inline Splats decimate_to_count(const Context& ctx, const Splats& splats, const 
     ctx.sync();
     if (keep_idx) *keep_idx = idx.download();
     return out;
+}
+
+// ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
+// compute_knn_scales in place: columns 7..9 of splats.transforms = ln(clamp((d1 + d2) / 4, 1e-3, 0.1 median_size)) (bh_knn_log_scales).
+// nn_dist (optional): resized to [N,2], d1 and d2 per splat.  Returns the number of distance evaluations performed.
+inline uint64_t knn_log_scales(const Context& ctx, Splats& splats, DeviceBuffer<float>* nn_dist = nullptr) {
+    const uint32_t n = splats.num_splats();
+    if (nn_dist) nn_dist->resize((size_t)n * 2);
+    uint64_t pairs = 0;
+    ctx.check(bh_knn_log_scales(ctx.get(), splats.transforms.data(), n, nn_dist ? nn_dist->data() : nullptr, &pairs));
+    return pairs;
+}
+// to_init_splats (splat_init.rs:218-242) from host arrays: means [N,3]; every other argument may be empty and then takes the
+// reference's default — rotation (1,0,0,0), log-scales by compute_knn_scales, SH one grey coefficient 0.5, raw opacity 0.
+inline Splats to_init_splats(const Context& ctx, const std::vector<float>& means, const std::vector<float>& rotations = {},
+                             const std::vector<float>& log_scales = {}, const std::vector<float>& sh_coeffs = {},
+                             const std::vector<float>& raw_opacities = {}, bool render_mip = false) {
+    const size_t n = means.size() / 3;
+    if (means.size() != n * 3 || (!rotations.empty() && rotations.size() != n * 4) || (!log_scales.empty() && log_scales.size() != n * 3) ||
+        (!raw_opacities.empty() && raw_opacities.size() != n) || (!sh_coeffs.empty() && (n == 0 || sh_coeffs.size() % (3 * n) != 0)))
+        throw Error(BH_ERR_INVALID_ARG, "to_init_splats: means [N,3], rotations [N,4], log_scales [N,3], sh_coeffs [N,C,3], raw_opacities [N]");
+    std::vector<float> tr(n * 10);
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) tr[i * 10 + k] = means[i * 3 + k];
+        for (int k = 0; k < 4; ++k) tr[i * 10 + 3 + k] = rotations.empty() ? (k == 0 ? 1.0f : 0.0f) : rotations[i * 4 + k];
+        for (int k = 0; k < 3; ++k) tr[i * 10 + 7 + k] = log_scales.empty() ? 0.0f : log_scales[i * 3 + k];
+    }
+    Splats s = Splats::from_host(tr, sh_coeffs.empty() ? std::vector<float>(n * 3, 0.5f) : sh_coeffs,
+                                 raw_opacities.empty() ? std::vector<float>(n, 0.0f) : raw_opacities, render_mip);
+    if (log_scales.empty()) knn_log_scales(ctx, s);
+    return s;
+}
+// the init point cloud of the training stream (train_stream.rs:100-123): load_splat_from_ply with subsampling, then
+// compute_knn_scales over the kept rows when the file has no scale_0 (import.rs:332)
+inline std::pair<Splats, BhPlyInfo> load_init_splats(const Context& ctx, const std::vector<uint8_t>& bytes, uint32_t subsample_points = 1,
+                                                     size_t max_splats = 0) {
+    auto loaded = load_splat_from_ply(ctx, bytes, subsample_points, max_splats);
+    const int has = bh_ply_vertex_has_property(bytes.data(), bytes.size(), "scale_0");
+    if (has < 0) throw Error(has, "malformed PLY");
+    if (has == 0) knn_log_scales(ctx, loaded.first);
+    return loaded;
 }
 
 }  // namespace brush_hip
