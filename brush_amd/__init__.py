@@ -20,6 +20,8 @@ Names and argument meaning follow the reference (paths under
     compute_pup_scores / decimate_to_count   brush-train/src/lod.rs:13-142 (LOD boundary, brush-process/src/train_stream.rs:248-303)
     knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242 (compute_knn_scales, to_init_splats),
                                          brush-process/src/train_stream.rs:100-123 (the init point cloud)
+    eval_metrics / eval_stats / run_eval   brush-train/src/eval.rs:23-63 (PSNR / SSIM of held-out views),
+                                         brush-process/src/train_stream.rs:506-566 (run_eval)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -30,6 +32,6 @@ from .host import (  # noqa: F401
     render_splats_bwd, adam_step, gather_stats, RefineStats, splat_bounds, bounds_median_size, fov_to_focal, focal_to_fov,
     splat_to_ply, load_splat_from_ply, ply_parse_header, ParseMetadata, BatchUploader, SceneLoader, set_list_slicing, last_list_counts, set_view_id,
     render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
-    knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property,
+    knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
 )
 from ._ffi import BrushHipError  # noqa: F401

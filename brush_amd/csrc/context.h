@@ -68,10 +68,11 @@ enum Slot : int {
     SLOT_NEAR_COUNTS,        // [N] tiles hit per splat at or in front of the tile's depth cut (per-tile cut lists)
     SLOT_TILE_ORDER,         // [8][ceil(T/8)] the forward blend's block -> tile map: every XCD band's tiles by descending forecast work
     SLOT_LOD_GRADS,          // bh_pup_accumulate_view: v_transforms [N,10] | v_sh [N,C,3] | v_raw_opac [N] | v_refine [N] (lod.hip)
-    SLOT_LOD_FOLDED,         // ... fold_min_scale(params): transforms [N,10] | raw_opac [N]
+    SLOT_LOD_FOLDED,         // ... and bh_eval_view: fold_min_scale(params): transforms [N,10] | raw_opac [N]
     SLOT_LOD_LOSS,           // ... dL/dimg [H,W,4] | the loss scalar
     SLOT_LOD_SORT,           // bh_decimate_to_count: keys [N] | sorted keys [N] | sorted ids [N]
     SLOT_KNN,                // bh_knn_log_scales: control | keys | sorted keys | order | rank cells [N] | x y z [N] | tree boxes (knn.hip)
+    SLOT_EVAL,               // bh_eval_metrics: per-tile (squared error, SSIM) f64 partial sums (eval.hip)
     SLOT_COUNT
 };
 

@@ -1525,6 +1525,122 @@ def decimate_to_count(splats: "Splats", scores, target_count: int, ctx: Optional
 
 
 # ---------------------------------------------------------------------------
+# held-out evaluation (brush-train/src/eval.rs:23-63, run_eval of brush-process/src/train_stream.rs:506-566)
+# ---------------------------------------------------------------------------
+@dataclass
+class EvalSample:
+    """EvalSample (eval.rs:14-20) of one view: mse, psnr and ssim read back from `metrics`, the device [3] f32 tensor (mse, psnr,
+    ssim) bh_eval_view wrote; `image` (keep_image) is the quantised render as rgba8 [H, W] (int32 bit pattern, alpha 255)."""
+    mse: float
+    psnr: float
+    ssim: float
+    metrics: torch.Tensor
+    image: Optional[torch.Tensor] = None
+
+
+@dataclass
+class EvalResult:
+    """What run_eval reports (train_stream.rs:559-560): the per-view PSNRs and SSIMs averaged in f32, and the per-view table
+    [V, 3] (mse, psnr, ssim) on the host; `images` (keep_images) the views' rgba8 renders, in view order."""
+    avg_psnr: float
+    avg_ssim: float
+    per_view: torch.Tensor
+    images: Optional[list] = None
+
+
+def _aligned_hwc4(img_hwc4, dev):
+    img = _f32c(img_hwc4, dev)
+    if img.dim() != 3 or img.shape[2] != 4:
+        raise ValueError("img must be [H,W,4]")
+    return img if img.data_ptr() % 16 == 0 else img.clone()   # (float4 loads: a sliced view may start off a 16-byte boundary)
+
+
+def eval_metrics(img_hwc4, gt_packed, ctx: Optional[Context] = None, keep_image=False, out=None):
+    """eval_stats' metrics (eval.rs:38-55) of a rendered [H, W, 4] f32 image against gt_packed ([H, W] rgba8 as int32), in one fused
+    kernel (bh_eval_metrics): -> device f32 [3] = (mse, psnr, ssim), written into `out` when given; with keep_image also the
+    quantised RGB as rgba8 [H, W].  Queued on the ctx stream: nothing is read back."""
+    dev = img_hwc4.device
+    ctx = ctx or get_context(dev)
+    img = _aligned_hwc4(img_hwc4, dev)
+    h, w = int(img.shape[0]), int(img.shape[1])
+    gt = _as_u32(gt_packed, dev).reshape(h, w)
+    metrics = out if out is not None else torch.empty((3,), dtype=torch.float32, device=dev)
+    rgb8 = torch.empty((h, w), dtype=torch.int32, device=dev) if keep_image else None
+    ctx.check(ctx.lib.bh_eval_metrics(ctx._h, _ptr(img), _ptr(gt), h, w, _ptr(metrics), _ptr(rgb8) if rgb8 is not None else None))
+    return (metrics, rgb8) if keep_image else metrics
+
+
+def _eval_view(ctx, splats, camera, gt, metrics, rgb8):
+    h, w = int(gt.shape[0]), int(gt.shape[1])
+    cam = camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((w, h))
+    ms = splats.min_scale
+    ctx.check(ctx.lib.bh_eval_view(ctx._h, C.byref(cam), splats.num_splats(), splats.sh_degree(), _ptr(splats.transforms), _ptr(splats.sh_coeffs),
+                                   _ptr(splats.raw_opacities), _ptr(ms) if ms is not None else None, _ffi.FLAG_MIP if splats.render_mip else 0,
+                                   _ptr(gt), _ptr(metrics), _ptr(rgb8) if rgb8 is not None else None))
+
+
+def eval_stats(splats: "Splats", camera, gt_packed, ctx: Optional[Context] = None, keep_image=False) -> EvalSample:
+    """eval_stats (eval.rs:23-63) of one view through bh_eval_view: render (background 0, f32, the 3D-filter floor folded in) and
+    score against gt_packed ([H, W] rgba8 as int32, packed like view_to_packed_data).  Reads the three metrics back.  Makes the
+    ctx's last unretained forward stale."""
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    gt = _as_u32(gt_packed, dev)
+    if gt.dim() != 2:
+        raise ValueError("gt_packed must be [H, W]")
+    metrics = torch.empty((3,), dtype=torch.float32, device=dev)
+    rgb8 = torch.empty(tuple(gt.shape), dtype=torch.int32, device=dev) if keep_image else None
+    _eval_view(ctx, splats, camera, gt, metrics, rgb8)
+    ctx.sync()
+    mse, psnr, ssim = (float(v) for v in metrics.cpu())
+    return EvalSample(mse=mse, psnr=psnr, ssim=ssim, metrics=metrics, image=rgb8)
+
+
+def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images=False) -> EvalResult:
+    """run_eval (train_stream.rs:506-566): eval_stats of every held-out view, the per-view PSNR and SSIM averaged in f32 (not the
+    PSNR of a mean MSE).  `views` has compute_pup_scores' shape: (image uint8 [H,W,3|4] or a callable returning one, Camera[,
+    alpha_is_mask]), packed through a BatchUploader.  Every view's metrics go to its row of one device table; one readback at the end."""
+    import numpy as np
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    views = list(views)
+    table = torch.empty((len(views), 3), dtype=torch.float32, device=dev)
+    images = [] if keep_images else None
+    up = None
+    try:
+        for i, view in enumerate(views):
+            img = view[0]() if callable(view[0]) else view[0]
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            mask = bool(view[2]) if len(view) > 2 else False
+            pixels = img.shape[0] * img.shape[1]
+            if up is None or up.max_pixels < pixels:
+                if up is not None:
+                    ctx.sync()   # (the slots of the old ring may still be read by queued views)
+                    up.close()
+                up = BatchUploader(pixels, 2, ctx)
+            slot = up.submit(img, premultiply=not mask)
+            gt, _ = up.acquire(slot)
+            rgb8 = torch.empty(tuple(gt.shape), dtype=torch.int32, device=dev) if keep_images else None
+            _eval_view(ctx, splats, view[1], gt, table[i], rgb8)
+            up.release(slot)
+            if keep_images:
+                images.append(rgb8)
+    finally:
+        if up is not None:
+            ctx.sync()
+            up.close()
+    per_view = table.cpu()
+    psnr, ssim = np.float32(0.0), np.float32(0.0)
+    for r in per_view.numpy():   # train_stream.rs:540-541: psnr += the view's psnr (f32), in view order
+        psnr = np.float32(psnr + r[1])
+        ssim = np.float32(ssim + r[2])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        psnr = np.float32(psnr / np.float32(len(views)))   # :559-560 (no views: 0 / 0 = NaN, as in the reference)
+        ssim = np.float32(ssim / np.float32(len(views)))
+    return EvalResult(avg_psnr=float(psnr), avg_ssim=float(ssim), per_view=per_view, images=images)
+
+
+# ---------------------------------------------------------------------------
 # point-cloud initialisation (brush-train/src/splat_init.rs:179-242, brush-process/src/train_stream.rs:100-123)
 # ---------------------------------------------------------------------------
 def ply_vertex_has_property(data: bytes, name: str) -> bool:

@@ -21,6 +21,7 @@
  *   bh_compute_min_scale <- compute_min_scale                brush-train/src/train.rs:102-125
  *   bh_pup_accumulate[_view] / bh_pup_scores <- compute_pup_scores + log_det_6x6   brush-train/src/lod.rs:44-142
  *   bh_decimate_to_count <- decimate_to_count                brush-train/src/lod.rs:13-38
+ *   bh_eval_metrics / bh_eval_view <- eval_stats (PSNR, SSIM of one held-out view)  brush-train/src/eval.rs:23-63
  *   bh_knn_log_scales   <- compute_knn_scales (to_init_splats)  brush-train/src/splat_init.rs:179-242
  *   bh_ply_vertex_has_property <- PlyHeader has_property("scale_0")  brush-serde/src/import.rs:332
  *   bh_uploader_*       <- view_to_packed_data + the SceneLoader hand-off   brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
@@ -617,6 +618,33 @@ int bh_decimate_to_count(bh_ctx* ctx, const float* scores, uint32_t n, uint32_t 
                          const float* transforms, const float* sh_coeffs, const float* raw_opacities, const float* min_scale,
                          float* out_transforms, float* out_sh, float* out_raw_opacities, float* out_min_scale,
                          uint32_t* keep_idx);
+
+/* ---- held-out evaluation (brush-train/src/eval.rs) ------------------------------ */
+/* What run_eval (brush-process/src/train_stream.rs:506-566) does per held-out view: eval_stats (eval.rs:23-63).
+ * metrics is a DEVICE float[3] = { mse, psnr, ssim } of the rendered RGB quantised as q = round(x * 255) / 255 (f32, round half to
+ * even, a true divide, NOT clamped: values above 1 stay above 1) against gt_packed [H,W] rgba8 (device, as view_to_packed_data makes
+ * it; its alpha is ignored):
+ *   mse  = mean over H, W, 3 of the squared L1 map |q - g| of image_loss_forward (l1 1, ssim 0, no composite, no mask)
+ *   psnr = ln(1 / mse) * 10 / ln 10 in f32, from the f32 mse (+inf when mse == 0)
+ *   ssim = mean over H, W, 3 of the SSIM map of image_loss_forward (l1 0, ssim 1): 11-tap sigma 1.5, zero padding, clamped to +-1
+ * GT bytes are read as byte * (1/255) and the render as k / 255, like the reference: a render equal to its own GT may score mse ~1e-15.
+ * The per-pixel terms are the loss maps' f32 values; the means are f64 sums in a fixed order rounded to f32: the same inputs give
+ * the same bits, whatever else runs.  rgb8 (device [H,W] or NULL): the quantised RGB as rgba8, each channel clamped to [0, 255],
+ * alpha 255 (what into_rgb8 / save_to_disk write).  Scratch from the ctx arena (16 bytes per 16x16 tile); calls for several views
+ * may be queued back to back, each into its own float[3].
+ * img_hwc4 [H,W,4] f32 (the rasterizer's BH_FLAG_BWD_INFO image; 16-byte aligned).  Does not block. */
+int bh_eval_metrics(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, float* metrics /*device [3]*/,
+                    uint32_t* rgb8 /*device [H,W] or NULL*/);
+/* One view of eval_stats: fold_min_scale(params) when min_scale != NULL (as bh_pup_accumulate_view does), the forward with complete
+ * lists (BH_FLAG_BWD_INFO | (flags & BH_FLAG_MIP): render_splats(.., background 0, TextureMode::Float)), then bh_eval_metrics on
+ * its [H,W,4] image.  n == 0 scores a black image.  flags other than BH_FLAG_MIP, and a tile-row window on cam, are
+ * BH_ERR_INVALID_ARG (a view is scored whole).  This IS a forward like any other: it makes the ctx's last unretained forward stale
+ * (bh_render_backward_saved on it fails).  It reads and refreshes the per-view tables like any forward (bh_set_view_id): those can
+ * only change how long it takes, never the metrics.  Scratch: the forward's, + 44 N bytes with min_scale.  Blocks while the forward
+ * reads its counts back, like bh_render_forward; the metrics themselves are queued on the ctx stream. */
+int bh_eval_view(bh_ctx* ctx, const BhCamera* cam /*host*/, uint32_t n, uint32_t sh_degree, const float* transforms, const float* sh_coeffs,
+                 const float* raw_opacities, const float* min_scale /*[N] or NULL*/, uint32_t flags /*BH_FLAG_MIP only*/,
+                 const uint32_t* gt_packed, float* metrics /*device [3]: mse, psnr, ssim*/, uint32_t* rgb8 /*device [H,W] or NULL*/);
 
 /* ---- PLY at the edges (brush-serde) -------------------------------------------- */
 /* splat_to_ply (brush-serde/src/export.rs:179-204): the INRIA-layout binary_little_endian PLY Brush writes —

@@ -20,6 +20,7 @@
 //   brush_hip::sample_background / normal_samples    train.rs:896-908, 389-416 (the library's counter-based generator)
 //   brush_hip::pup_accumulate[_view] / pup_scores / decimate_to_count / lod_target_count   brush-train/src/lod.rs:13-142, train_stream.rs:261
 //   brush_hip::knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242, train_stream.rs:100-123
+//   brush_hip::eval_metrics / eval_stats / run_eval   brush-train/src/eval.rs:23-63, train_stream.rs:506-566 (held-out PSNR / SSIM)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -906,6 +907,76 @@ inline Splats decimate_to_count(const Context& ctx, const Splats& splats, const 
     ctx.sync();
     if (keep_idx) *keep_idx = idx.download();
     return out;
+}
+
+// ---- held-out evaluation (brush-train/src/eval.rs:23-63; run_eval of brush-process/src/train_stream.rs:506-566) ----------------
+// eval_stats' metrics of a rendered [h,w,4] f32 image against gt_packed ([h,w] rgba8 device): metrics (device float[3]) = mse, psnr,
+// ssim; rgb8 (device [h,w] or null) = the quantised RGB as rgba8.  Queued on the ctx stream (bh_eval_metrics).
+inline void eval_metrics(const Context& ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, float* metrics,
+                         uint32_t* rgb8 = nullptr) {
+    ctx.check(bh_eval_metrics(ctx.get(), img_hwc4, gt_packed, h, w, metrics, rgb8));
+}
+struct EvalSample {  // eval.rs:14-20: the view's metrics, read back; image (keep_image): the quantised render as rgba8 [H,W]
+    float mse = 0.0f, psnr = 0.0f, ssim = 0.0f;
+    std::optional<DeviceBuffer<uint32_t>> image;
+};
+// eval_stats of one view (bh_eval_view): render on black with the floor folded in, quantise, score against gt_packed
+inline EvalSample eval_stats(const Context& ctx, const Splats& splats, const Camera& camera, const uint32_t* gt_packed, uint32_t img_w, uint32_t img_h,
+                             bool keep_image = false) {
+    const BhCamera cam = camera.uniforms(img_w, img_h);
+    DeviceBuffer<float> metrics(3);
+    EvalSample out;
+    if (keep_image) out.image.emplace((size_t)img_w * img_h);
+    ctx.check(bh_eval_view(ctx.get(), &cam, splats.num_splats(), splats.sh_degree(), splats.transforms.data(), splats.sh_coeffs.data(),
+                           splats.raw_opacities.data(), splats.min_scale ? splats.min_scale->data() : nullptr, splats.render_mip ? BH_FLAG_MIP : 0u,
+                           gt_packed, metrics.data(), out.image ? out.image->data() : nullptr));
+    ctx.sync();
+    const std::vector<float> m = metrics.download();
+    out.mse = m[0];
+    out.psnr = m[1];
+    out.ssim = m[2];
+    return out;
+}
+struct EvalResult {  // train_stream.rs:559-560: per-view PSNR and SSIM averaged in f32; per_view rows (mse, psnr, ssim) in view order
+    float avg_psnr = 0.0f, avg_ssim = 0.0f;
+    std::vector<std::array<float, 3>> per_view;
+    std::vector<DeviceBuffer<uint32_t>> images;   // keep_images: every view's rgba8 render
+};
+// run_eval over held-out views given as the loader's views (decoded into the uploader's pinned slots, packed like
+// view_to_packed_data: premultiplied unless the alpha is a mask); the metrics stay on the device until one readback at the end
+inline EvalResult run_eval(const Context& ctx, const Splats& splats, const std::vector<LoaderView>& views, bool keep_images = false) {
+    EvalResult r;
+    uint64_t max_pixels = 1;
+    for (const LoaderView& v : views) max_pixels = std::max<uint64_t>(max_pixels, (uint64_t)v.w * v.h);
+    DeviceBuffer<float> table(std::max<size_t>(views.size(), 1) * 3);
+    {
+        BatchUploader up(ctx, max_pixels, 2);
+        for (size_t i = 0; i < views.size(); ++i) {
+            const LoaderView& v = views[i];
+            if (v.channels != 3 && v.channels != 4) throw Error(BH_ERR_INVALID_ARG, "run_eval: views must have 3 or 4 channels");
+            auto [slot, dst] = up.map((uint64_t)v.w * v.h * v.channels);
+            v.decode(dst);
+            up.commit(slot, v.w, v.h, v.channels, v.channels == 4 && !v.alpha_is_mask);
+            const BatchUploader::Packed gt = up.acquire(slot);
+            const BhCamera cam = v.camera.uniforms(gt.w, gt.h);
+            if (keep_images) r.images.emplace_back((size_t)gt.w * gt.h);
+            ctx.check(bh_eval_view(ctx.get(), &cam, splats.num_splats(), splats.sh_degree(), splats.transforms.data(), splats.sh_coeffs.data(),
+                                   splats.raw_opacities.data(), splats.min_scale ? splats.min_scale->data() : nullptr,
+                                   splats.render_mip ? BH_FLAG_MIP : 0u, gt.img, table.data() + 3 * i, keep_images ? r.images.back().data() : nullptr));
+            up.release(slot);
+        }
+        ctx.sync();   // (before the uploader's slots go)
+    }
+    const std::vector<float> t = table.download();
+    float psnr = 0.0f, ssim = 0.0f;
+    for (size_t i = 0; i < views.size(); ++i) {
+        r.per_view.push_back({t[3 * i], t[3 * i + 1], t[3 * i + 2]});
+        psnr += t[3 * i + 1];
+        ssim += t[3 * i + 2];
+    }
+    r.avg_psnr = psnr / (float)views.size();
+    r.avg_ssim = ssim / (float)views.size();
+    return r;
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
