@@ -204,6 +204,17 @@ SYMBOLS = {
     "bh_profile_fetch": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), fp, u32p, C.c_int]),
 }
 
+# every symbol include/brush_hip_lpips.h declares (LPIPS, a header of its own on top of brush_hip.h), bound on the same handle
+LPIPS_PARAM_COUNT = 14716160   # BH_LPIPS_PARAM_COUNT
+LPIPS_SYMBOLS = {
+    "bh_lpips_create": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_float), C.c_uint64]),
+    "bh_lpips_destroy": (None, [C.c_void_p]),
+    "bh_lpips_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_void_p]),
+    "bh_lpips_value_and_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_float,
+                                          C.c_void_p, C.c_void_p]),
+    "bh_train_set_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -243,7 +254,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, SYMBOLS)
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS))
     return _lib
 
 
@@ -252,5 +263,5 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -1826,6 +1826,9 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     if (native_tiles && !batch->strip_loss)
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a tile-row window without an image hook needs strip_loss = 1 (the library exchanges the strips' halos, not whole frames)");
     const bool tile_mode = batch->image_hook != nullptr || native_tiles;
+    const bool lpips_on = ctx->lpips != nullptr && ctx->lpips_weight > 0.0f;
+    if (lpips_on && (tile_mode || window_partial))
+        return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the LPIPS term needs the whole frame on this rank (no tile-row partition)");
     const bool masked_grads = !exchanging && !tile_mode && !ctx->knob_zero_grads && n > 0;
     if (masked_grads) {
         ctx->ext_grad_begin = exch + o_ref;
@@ -1917,6 +1920,9 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
             BH_TRY(queue_loss());
         }
     }
+    // ---- LPIPS (train.rs:265-273): on the frame's final image, GT composited as the loss above does it; loss and dL/dimg grow
+    // in place on the device (no host wait)
+    if (lpips_on) BH_TRY(lpips_train_term(ctx, ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
     // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/brush_hip.h"
+#include "../../include/brush_hip_lpips.h"
 #include "device_math.h"
 
 namespace bh {
@@ -73,6 +74,7 @@ enum Slot : int {
     SLOT_LOD_SORT,           // bh_decimate_to_count: keys [N] | sorted keys [N] | sorted ids [N]
     SLOT_KNN,                // bh_knn_log_scales: control | keys | sorted keys | order | rank cells [N] | x y z [N] | tree boxes (knn.hip)
     SLOT_EVAL,               // bh_eval_metrics: per-tile (squared error, SSIM) f64 partial sums (eval.hip)
+    SLOT_LPIPS,              // bh_lpips_*: f64 partials | normalised inputs | scratch pair | activations of both images (lpips.hip)
     SLOT_COUNT
 };
 
@@ -360,6 +362,8 @@ struct bh_ctx {
     // flags: every fact is tied to the forward (generation) whose kernels established it and is consumed exactly once.
     bh::GradClears clears;
     float* pending_loss_dst = nullptr; // where bh_sync delivers the last step's loss
+    const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
+    float lpips_weight = 0.0f;
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
@@ -464,6 +468,9 @@ inline void deliver_pending_loss(bh_ctx* ctx) {
     }
 }
 int check_hip(bh_ctx* ctx, hipError_t e, const char* what);
+// lpips.hip: the train step's LPIPS term on the frame's image: *loss += w * LPIPS (and loss_host), v_output.rgb += w * dLPIPS/dimg
+int lpips_train_term(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, const float* bg, float* v_output,
+                     float* loss, float* loss_host);
 // Grow-only allocation of a scratch slot; returns nullptr (and sets the error) on failure.
 void* ensure(bh_ctx* ctx, Slot s, size_t bytes);
 

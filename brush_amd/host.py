@@ -804,6 +804,8 @@ class TrainConfig:
     growth_stop_iter: int = 15000
     split_at_screen_size: float = 0.5
     opac_decay: float = 0.004
+    # config.rs:92: > 0 adds lpips_loss_weight * LPIPS(pred, GT) to the loss; needs SplatTrainer(..., lpips=Lpips)
+    lpips_loss_weight: float = 0.0
 
 
 @dataclass
@@ -1034,7 +1036,7 @@ class SplatTrainer:
 
     def __init__(self, config: TrainConfig, median_scene_scale: float = 1.0, process_group=None, ctx: Optional[Context] = None,
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
-                 allreduce: str = "ring"):
+                 allreduce: str = "ring", lpips: Optional["Lpips"] = None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -1043,7 +1045,10 @@ class SplatTrainer:
 
         partition (only with a process_group): "cameras" = data parallel, every rank its own view,
         mean gradient; "tiles" = every rank renders a strip of tile rows of the SAME view, strips are
-        all-gathered before the loss and the partial gradients summed."""
+        all-gathered before the loss and the partial gradients summed.
+
+        lpips: the LpipsModel the step uses when config.lpips_loss_weight > 0 (train.rs:153, 265-273; bh_train_set_lpips).
+        Not with partition "tiles"."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if allreduce not in ("ring", "direct"):
@@ -1085,6 +1090,7 @@ class SplatTrainer:
         self.strip_loss = True
         self._strip_loss_now = False
         self.batch_patch = None   # optional callable(BhTrainBatch): edits the C struct right before bh_train_step
+        self.lpips = lpips
 
     MIN_SCALE_FACTOR = 0.1       # train.rs:44
     MIN_SCALE_FREEZE_FRAC = 0.9  # train.rs:37
@@ -1255,6 +1261,11 @@ class SplatTrainer:
             hook, scale = self._hook, (1.0 if tiles else 1.0 / self._world)
         if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
             self.batch_patch(b)
+        lw = float(getattr(c, "lpips_loss_weight", 0.0))
+        if lw > 0.0 and self.lpips is None:
+            raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
+        # the term is ctx state (bh_train_set_lpips): set it for THIS trainer's step, whatever another trainer on the ctx left
+        ctx.check(ctx.lib.bh_train_set_lpips(ctx._h, self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0))
         ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                         float(scale), C.byref(stats)))
         self.step_count = st.step_count
@@ -1638,6 +1649,146 @@ def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images
         psnr = np.float32(psnr / np.float32(len(views)))   # :559-560 (no views: 0 / 0 = NaN, as in the reference)
         ssim = np.float32(ssim / np.float32(len(views)))
     return EvalResult(avg_psnr=float(psnr), avg_ssim=float(ssim), per_view=per_view, images=images)
+
+
+# ---------------------------------------------------------------------------
+# LPIPS (crates/lpips/src/lib.rs; the lpips_loss_weight term of brush-train/src/train.rs:153, 265-273)
+# ---------------------------------------------------------------------------
+LPIPS_CONVS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+               (512, 512), (512, 512), (512, 512))   # (Cin, Cout) in forward order
+LPIPS_BLOCK_CONVS = (2, 2, 3, 3, 3)
+LPIPS_HEAD_CHANNELS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+# the torch `lpips` package's VGG: conv i of block b sits at features index _LPIPS_TORCH_IDX[b][i] of net.slice{b+1}
+_LPIPS_TORCH_IDX = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))
+
+
+def _np32(t):
+    import numpy as np
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu()
+    return np.asarray(t, dtype=np.float32)
+
+
+class Lpips:
+    """LpipsModel (crates/lpips/src/lib.rs) on one device: the 13 VGG16 convs and 5 heads, uploaded and repacked once
+    (bh_lpips_create).  Parameters in canonical order (`flat`, LPIPS_PARAM_COUNT f32): per conv weight [Cout,Cin,3,3] then bias
+    [Cout], then the heads [C].  No weights ship with the library: load them with from_state_dict, or Lpips.random for tests."""
+
+    def __init__(self, flat, ctx: Optional[Context] = None):
+        import numpy as np
+        flat = np.ascontiguousarray(_np32(flat).reshape(-1))
+        ctx = ctx or get_context()
+        self.ctx = ctx
+        self.device = ctx.device
+        self.lib = ctx.lib
+        h = ctx.lib.bh_lpips_create(ctx._h, flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size))
+        if not h:
+            raise BrushHipError("bh_lpips_create: %s" % ctx.lib.bh_last_error(ctx._h).decode())
+        self._h = C.c_void_p(h)
+
+    @classmethod
+    def from_params(cls, flat, ctx: Optional[Context] = None) -> "Lpips":
+        return cls(flat, ctx)
+
+    @classmethod
+    def from_state_dict(cls, sd, ctx: Optional[Context] = None) -> "Lpips":
+        """From the reference's burn field names (blocks.{b}.convs.{j}.{weight,bias}, heads.{b}.weight) or the torch `lpips`
+        package's (net.slice{s}.{idx}.{weight,bias}, lin{b}.model.1.weight; scaling_layer.shift / scale, if present, must be the
+        constants this model hard-codes)."""
+        return cls(cls.flat_from_state_dict(sd), ctx)
+
+    @staticmethod
+    def flat_from_state_dict(sd):
+        import numpy as np
+        burn = any(k.startswith("blocks.") for k in sd)
+        if not burn:
+            for name, want in (("scaling_layer.shift", LPIPS_SHIFT), ("scaling_layer.scale", LPIPS_SCALE)):
+                if name in sd and not np.allclose(_np32(sd[name]).reshape(-1), np.asarray(want, np.float32), rtol=0, atol=1e-6):
+                    raise ValueError("%s is %s, this model hard-codes %s" % (name, _np32(sd[name]).reshape(-1), want))
+        parts = []
+        L = 0
+        for b, n in enumerate(LPIPS_BLOCK_CONVS):
+            for j in range(n):
+                ci, co = LPIPS_CONVS[L]
+                key = "blocks.%d.convs.%d" % (b, j) if burn else "net.slice%d.%d" % (b + 1, _LPIPS_TORCH_IDX[b][j])
+                w, bias = _np32(sd[key + ".weight"]), _np32(sd[key + ".bias"])
+                if w.shape != (co, ci, 3, 3) or bias.shape != (co,):
+                    raise ValueError("%s: shape %s / %s, expected (%d, %d, 3, 3) / (%d,)" % (key, w.shape, bias.shape, co, ci, co))
+                parts += [w.reshape(-1), bias]
+                L += 1
+        for b, c in enumerate(LPIPS_HEAD_CHANNELS):
+            key = "heads.%d.weight" % b if burn else "lin%d.model.1.weight" % b
+            h = _np32(sd[key])
+            if h.size != c:
+                raise ValueError("%s: %d values, expected %d" % (key, h.size, c))
+            parts.append(h.reshape(-1))
+        flat = np.concatenate(parts)
+        assert flat.size == _ffi.LPIPS_PARAM_COUNT
+        return flat
+
+    @staticmethod
+    def random_params(seed=0):
+        """Test weights (not a trained model): He-normal convs, small biases, non-negative heads, so that activations stay O(1)."""
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        parts = []
+        for ci, co in LPIPS_CONVS:
+            parts.append((rng.standard_normal(co * ci * 9) * math.sqrt(2.0 / (9 * ci))).astype(np.float32))
+            parts.append((rng.uniform(-0.05, 0.05, co)).astype(np.float32))
+        for c in LPIPS_HEAD_CHANNELS:
+            parts.append((np.abs(rng.standard_normal(c)) * 0.1).astype(np.float32))
+        return np.concatenate(parts)
+
+    @classmethod
+    def random(cls, seed=0, ctx: Optional[Context] = None) -> "Lpips":
+        return cls(cls.random_params(seed), ctx)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.bh_lpips_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _lpips_args(img_hwc4, gt_packed, composite_bg, dev):
+    img = _aligned_hwc4(img_hwc4, dev)
+    h, w = int(img.shape[0]), int(img.shape[1])
+    gt = _as_u32(gt_packed, dev).reshape(h, w)
+    bg = (C.c_float * 3)(*[float(v) for v in composite_bg]) if composite_bg is not None else None
+    return img, gt, h, w, bg
+
+
+def lpips(img_hwc4, gt_packed, model: Lpips, composite_bg=None, ctx: Optional[Context] = None):
+    """LpipsModel::lpips(img rgb, unpack_gt_rgb(gt_packed, composite_bg)) -> device f32 [1] (bh_lpips_forward).  img_hwc4 [H,W,4]
+    f32 (alpha ignored), gt_packed [H,W] rgba8 as int32; H, W >= 16.  Queued on the ctx stream: nothing is read back."""
+    dev = img_hwc4.device
+    ctx = ctx or get_context(dev)
+    img, gt, h, w, bg = _lpips_args(img_hwc4, gt_packed, composite_bg, dev)
+    value = torch.empty((1,), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_lpips_forward(ctx._h, model._h, _ptr(img), _ptr(gt), h, w, bg, _ptr(value)))
+    return value
+
+
+def lpips_value_and_grad(img_hwc4, gt_packed, model: Lpips, composite_bg=None, weight=1.0, v_output=None, ctx: Optional[Context] = None):
+    """(LPIPS [1], v_output [H,W,4]) with v_output.rgb += weight * dLPIPS/dimg (bh_lpips_value_and_grad); v_output defaults to
+    zeros and is updated in place when given."""
+    dev = img_hwc4.device
+    ctx = ctx or get_context(dev)
+    img, gt, h, w, bg = _lpips_args(img_hwc4, gt_packed, composite_bg, dev)
+    value = torch.empty((1,), dtype=torch.float32, device=dev)
+    if v_output is None:
+        v_output = torch.zeros((h, w, 4), dtype=torch.float32, device=dev)
+    if v_output.shape != (h, w, 4) or v_output.dtype != torch.float32 or not v_output.is_contiguous():
+        raise ValueError("v_output must be a contiguous f32 [H,W,4]")
+    ctx.check(ctx.lib.bh_lpips_value_and_grad(ctx._h, model._h, _ptr(img), _ptr(gt), h, w, bg, float(weight), _ptr(value), _ptr(v_output)))
+    return value, v_output
 
 
 # ---------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 //   brush_hip::pup_accumulate[_view] / pup_scores / decimate_to_count / lod_target_count   brush-train/src/lod.rs:13-142, train_stream.rs:261
 //   brush_hip::knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242, train_stream.rs:100-123
 //   brush_hip::eval_metrics / eval_stats / run_eval   brush-train/src/eval.rs:23-63, train_stream.rs:506-566 (held-out PSNR / SSIM)
+//   brush_hip::Lpips / lpips / lpips_value_and_grad / train_set_lpips   crates/lpips/src/lib.rs, train.rs:265-273 (lpips_loss_weight)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -43,6 +44,7 @@
 #include <vector>
 
 #include "brush_hip.h"
+#include "brush_hip_lpips.h"
 
 namespace brush_hip {
 
@@ -977,6 +979,43 @@ inline EvalResult run_eval(const Context& ctx, const Splats& splats, const std::
     r.avg_psnr = psnr / (float)views.size();
     r.avg_ssim = ssim / (float)views.size();
     return r;
+}
+
+// ---- LPIPS (crates/lpips/src/lib.rs; the lpips_loss_weight term of brush-train/src/train.rs:265-273) ------------------------------
+// The VGG16 LpipsModel on the ctx's device (bh_lpips_create): params = BH_LPIPS_PARAM_COUNT floats in the canonical order of
+// brush_hip_lpips.h.  Move-only; the model must outlive any ctx it is attached to (train_set_lpips).
+class Lpips {
+public:
+    Lpips(const Context& ctx, const std::vector<float>& params) {
+        h_ = bh_lpips_create(ctx.get(), params.data(), params.size());
+        if (!h_) throw Error(BH_ERR_INVALID_ARG, bh_last_error(ctx.get()));
+    }
+    Lpips(const Lpips&) = delete;
+    Lpips& operator=(const Lpips&) = delete;
+    Lpips(Lpips&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Lpips& operator=(Lpips&& o) noexcept {
+        if (this != &o) { bh_lpips_destroy(h_); h_ = o.h_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~Lpips() { bh_lpips_destroy(h_); }
+    const bh_lpips* get() const { return h_; }
+
+private:
+    bh_lpips* h_ = nullptr;
+};
+// value (device float[1]) = LPIPS(img_hwc4 rgb, GT [+ (1 - a) bg when composite_bg]); queued on the ctx stream (bh_lpips_forward)
+inline void lpips(const Context& ctx, const Lpips& model, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, float* value,
+                  const float* composite_bg = nullptr) {
+    ctx.check(bh_lpips_forward(ctx.get(), model.get(), img_hwc4, gt_packed, h, w, composite_bg, value));
+}
+// ... and v_output [h,w,4] += weight * dLPIPS/dimg on rgb (bh_lpips_value_and_grad)
+inline void lpips_value_and_grad(const Context& ctx, const Lpips& model, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w,
+                                 float weight, float* value, float* v_output, const float* composite_bg = nullptr) {
+    ctx.check(bh_lpips_value_and_grad(ctx.get(), model.get(), img_hwc4, gt_packed, h, w, composite_bg, weight, value, v_output));
+}
+// bh_train_step on this ctx adds weight * LPIPS (model == nullptr or weight 0: detached)
+inline void train_set_lpips(const Context& ctx, const Lpips* model, float weight) {
+    ctx.check(bh_train_set_lpips(ctx.get(), model ? model->get() : nullptr, weight));
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
