@@ -16,13 +16,19 @@ backward and Adam (weak scaling).  Started either by `python -m torch.distribute
 case this process re-executes itself through torch.distributed.run with N ranks on 127.0.0.1.  It
 fails loudly when fewer than N devices are visible: it never prints an N=1 line for an N>1 request.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement), including
+Prints ONE JSON line on rank 0 (contract: see the task statement).  A plain run does what that line's headline needs and nothing
+else: it sets up, warms up, times the windows, writes --dump-outputs and prints metric / value / unit / ms_per_step and the
+description of what was timed.  --full adds everything else, including
   roofline      — dominant kernel (rasterize_backward_kernel) against HBM: the bytes the launch actually
                   touches / its average duration measured with HIP events on the ctx stream
   roofline_valu — the same kernel (and the forward blend) against the VALU issue rate, which is what bounds them
+  stages        — the per-stage table (kernel timestamps of rocprofv3 child runs, or HIP events around each stage)
   cpu_baseline  — the CPU oracle (a C++ restatement of Brush's kernels; Brush has no CPU backend) timed on the
                   host cores on full steps of the same workload
   non_saturating — a second, non-headline measurement on a scene whose tiles do not saturate early
+and the training loop, the other view counts, SH degree 3, the object-centric frame, the forward-only render, and with
+N > 1 ranks the exchange stages and the exchange A/B.  The N > 1 self-check of the exchange path runs in either mode: it
+decides which path is timed.
 """
 import argparse
 import gc
@@ -145,7 +151,7 @@ def dry_run(args):
     dist.all_reduce(t)
     if dist.get_rank() == 0:
         print(json.dumps({"metric": "dry run", "n_gpus": dist.get_world_size(), "ranks_joined": int(t.item()), "steps": args.steps,
-                          "warmup": args.warmup, "dry_run": True}), flush=True)
+                          "warmup": args.warmup, "full": args.full, "dry_run": True}), flush=True)
     dist.destroy_process_group()
 
 
@@ -267,10 +273,14 @@ def main():
     ap.add_argument("--sh-degree", type=int, default=0)
     ap.add_argument("--workload", default="1m_1080p")
     ap.add_argument("--splats", type=int, default=0, help="override the splat count (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the second (non-saturating scene) measurement")
-    ap.add_argument("--no-pmc", action="store_true", help="do not re-run a short bench under rocprofv3 --pmc for the counter figures (use the committed CSVs, marked stale)")
-    ap.add_argument("--no-stages", action="store_true", help="skip the per-stage HIP-event pass (child runs under rocprofv3 use it)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: the per-stage table, rooflines and counters (rocprofv3 child runs), "
+                         "the CPU baseline, the side measurements (training loop, other view counts, SH 3, non-saturating and object-centric "
+                         "scenes, forward-only render; N > 1: exchange stages and A/B).  The --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the side measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not re-run a short bench under rocprofv3 for the kernel trace and the counter figures (use the committed CSVs, marked stale)")
+    ap.add_argument("--no-stages", action="store_true", help="--full: skip the per-stage HIP-event pass (child runs under rocprofv3 use it)")
     ap.add_argument("--views", type=int, default=2,
                     help="views each rank cycles through in the timed region (step k trains view k %% V).  2 (the default) is the reference's own "
                          "training bench: two cameras 2 units apart in x, alternating (crates/brush-bench-test/src/benches.rs:198-220); "
@@ -419,7 +429,8 @@ def main():
         """Time `windows` windows of `steps` train steps of `workload`, cycling through `nviews` views; returns a dict of raw
         measurements (rank-local; dt = the median window).  exchange / algo: override --exchange / --allreduce (the N > 1 A/B);
         growth_stop_iter: TrainConfig.growth_stop_iter (1 = every step runs the blend backward without the refine weight);
-        capture: also return, as host arrays, what the last timed step left to its caller (`outputs`, see --dump-outputs)."""
+        capture: also return, as host arrays, what the last timed step left to its caller (`outputs`, see --dump-outputs).
+        Without --full it returns after the timed windows: no stage table, per-view counts, plain-replica time or forward-only render."""
         sh_degree = args.sh_degree if sh_degree is None else sh_degree
         exchange = exchange or args.exchange
         algo = algo or args.allreduce
@@ -540,6 +551,18 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             window_dt = [float(x) for x in tmax.tolist()]
         dt = sorted(window_dt)[len(window_dt) // 2]
+        res = dict(scene=scene, cp=cp, w=w, h=h, n=n, coeffs=coeffs, dt=dt, window_dt=window_dt, nviews=nviews, loader=loader is not None,
+                   list_share=(sum(shares) / len(shares)) if shares else 1.0, near_share_min=min(shares) if shares else 1.0,
+                   near_share_max=max(shares) if shares else 1.0, far_slices_queued=far_queued, timed_steps=steps * max(1, windows), outputs=outputs)
+        if not args.full:
+            # a plain run: the headline needs nothing beyond the timed windows (the stats of their last step feed the N > 1 exchange record)
+            res["stats"] = trainer.stats()
+            ctx.profile(0)
+            if loader is not None:
+                loader.close()
+            if native:
+                ctx.set_option("grad_allreduce", args.allreduce)
+            return res
         # one more replica of the timed steps WITHOUT the two HIP events on the dominant kernel (each is a barrier packet: ~6 us of
         # bubble in front of / behind that kernel): what a caller of bh_train_step gets; reported beside the contractual figure
         dt_plain = None
@@ -572,7 +595,6 @@ def main():
         pv1 = view_stats()
         stages.update(dominant)   # the dominant kernel's duration is the one measured inside the timed windows
         st = trainer.stats()
-        list_share = (sum(shares) / len(shares)) if shares else 1.0
         per_view = [{k: int(round((a[k] + b[k]) / 2.0)) for k in a} for a, b in zip(pv0, pv1)]
         for v, a, b in zip(per_view, pv0, pv1):
             v["intersections_blended_first_last_timed_step"] = [a["intersections_blended"], b["intersections_blended"]]
@@ -612,10 +634,8 @@ def main():
                 if sl:
                     fwd_only["near_share"] = round(float(ctx.lib.bh_last_list_share(ctx._h)), 4)
                     fwd_only["far_slices_queued"] = int(ctx.lib.bh_far_slices_queued(ctx._h)) - far1
-        return dict(scene=scene, cp=cp, w=w, h=h, n=n, coeffs=coeffs, dt=dt, window_dt=window_dt, stages=stages, stats=st, isect_blended=isect_blended,
-                    nv=nv_mean, ni=ni_mean, per_view=per_view, nviews=nviews, loader=loader is not None, list_share=list_share,
-                    near_share_min=min(shares) if shares else 1.0, near_share_max=max(shares) if shares else 1.0, far_slices_queued=far_queued,
-                    timed_steps=steps * max(1, windows), forward_only=fwd_only, dt_plain=dt_plain, outputs=outputs)
+        res.update(stages=stages, stats=st, isect_blended=isect_blended, nv=nv_mean, ni=ni_mean, per_view=per_view, forward_only=fwd_only, dt_plain=dt_plain)
+        return res
 
     def blend_rooflines(m, steps):
         """HBM and VALU rooflines of the two blend kernels from one measurement."""
@@ -838,19 +858,20 @@ def main():
         lo = train_loop(args.workload, max(2, args.loop_views), args.loop_steps, segment=max(50, args.loop_segment), modes=tuple(x for x in args.loop_only.split(",") if x))
         os.write(real_stdout, (json.dumps({"train_loop": lo}) + "\n").encode())
         return
-    m = measure(args.workload, args.steps, args.warmup, "forward_only" if (world == 1 and not args.no_extra) else True, windows=args.windows,
+    extras = args.full and not args.no_extra   # the side measurements
+    m = measure(args.workload, args.steps, args.warmup, "forward_only" if (world == 1 and extras) else True, windows=args.windows,
                 capture=bool(args.dump_outputs))
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, m["outputs"], m["n"])
 
     loop = None
-    if world == 1 and not args.no_extra and args.loop_steps > 0 and args.feed == "resident" and not args.splats and args.lists == "sliced":
+    if world == 1 and extras and args.loop_steps > 0 and args.feed == "resident" and not args.splats and args.lists == "sliced":
         loop = train_loop(args.workload, max(2, args.loop_views), args.loop_steps, segment=max(50, args.loop_segment))
 
     # the round 1-3 headline (ONE camera replayed: the slicing feedback, the tile order and every cache see the same frame every
     # step) next to the multi-view number, and an 8-view orbit
     view_runs = None
-    if world == 1 and not args.no_extra and args.feed == "resident" and not args.splats:
+    if world == 1 and extras and args.feed == "resident" and not args.splats:
         view_runs = {}
         for nvw in (1, 8):
             if nvw == args.views:
@@ -864,7 +885,7 @@ def main():
                                            "intersections_blended_per_view": [v["intersections_blended"] for v in mv["per_view"]]}
 
     extra = None
-    if world == 1 and not args.no_extra and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats:
+    if world == 1 and extras and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats:
         ex_steps = max(10, min(args.steps, 30))
         me = measure("1m_1080p_lowopac", ex_steps, 3, True)
         ehbm, evalu = blend_rooflines(me, ex_steps)
@@ -879,7 +900,7 @@ def main():
                  "stages_ms": {k: round(ms / max(c, 1), 4) for k, (ms, c) in me["stages"].items()}}
 
     centered = None
-    if world == 1 and not args.no_extra and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
+    if world == 1 and extras and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
         # an object in front of an empty background (what a NeRF-synthetic view looks like to the blend kernels: half of the tiles are
         # empty, the heaviest blends 15x the mean): the frame on which one wave per TILE made the backward last as long as its
         # heaviest tile.  With the backward's jobs (checkpointed 128-entry segments, the default) and, same call, with whole tiles.
@@ -904,7 +925,7 @@ def main():
                     "one_wave_per_tile_forward": {"option": "k16_split=0", "ms_per_step": round(mc1["dt"] / c_steps * 1e3, 4), "k16_ms": stg(mc1, "Rasterize")}}
 
     sh3 = None
-    if world == 1 and not args.no_extra and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
+    if world == 1 and extras and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
         s3_steps = max(10, min(args.steps, 30))
         m3 = measure("1m_1080p", s3_steps, 3, True, sh_degree=3)
         sh3 = {"workload": "1m_1080p at SH degree 3 (the reference's ModelConfig default, 16 coefficients per splat)", "steps": s3_steps,
@@ -932,7 +953,7 @@ def main():
         dist.all_gather_object(per_rank, mine)
 
     late = None
-    if world == 1 and not args.no_extra and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
+    if world == 1 and extras and args.workload == "1m_1080p" and args.feed == "resident" and not args.splats and args.sh_degree == 0:
         # the second half of a default training run (iter >= growth_stop_iter = 15000 of 30000, config.rs:72): nobody reads the refine
         # weight any more (train.rs:589-614), bh_train_step runs the blend backward without it.  Same protocol as the headline.
         ml = measure(args.workload, args.steps, args.warmup, True, windows=1, growth_stop_iter=1)
@@ -942,12 +963,9 @@ def main():
                 "ms_per_step": round(ml["dt"] / args.steps * 1e3, 4), "views_per_s": round(args.steps / ml["dt"], 2),
                 "k17_ms_hip_events_around_the_stage": round(k17[0] / max(k17[1], 1), 4)}
 
-    final_out = None
-    if rank == 0:
-        steps = args.steps
-        dt, st = m["dt"], m["stats"]
+    def full_figures(m, steps, ms_per_step):
+        """--full: the per-stage table (kernel timestamps of a rocprofv3 child run, else HIP events), the rooflines and the counters."""
         n, w, h, coeffs = m["n"], m["w"], m["h"], m["coeffs"]
-        ms_per_step = dt / steps * 1e3
         nv, ni = m["nv"], m["ni"]   # means over the views of the timed region
         pixels, tiles = w * h, ((w + 15) // 16) * ((h + 15) // 16)
         sb = stage_bytes(n, nv, ni, m["isect_blended"], pixels, tiles, coeffs, list_share=m.get("list_share", 1.0),
@@ -1013,6 +1031,30 @@ def main():
         for v in valu.values():
             v.setdefault("stale", True)
         step_bytes = sum(sb[k] for k in stage_out if k in sb)
+        return {
+            "fwd_ms": round(fwd_ms, 4),
+            "fwd_bwd_ms": round(fwd_ms + bwd_ms, 4),
+            "fwd_bwd_source": fwd_src,
+            "kernel_trace": ({"steps": ktrace["steps"], "kernels": ktrace["kernels"], "wall_us_per_step": ktrace.get("wall_us_per_step"),
+                              "idle_us_per_step": ktrace.get("idle_us_per_step"),
+                              "idle_is": "inside the SAME (child) run: from the first kernel's start to the last kernel's end of the timed steps, minus the kernels' "
+                                         "own durations - the step's true idle time (kernel_ms_per_step vs ms_per_step compares two different runs, one of them "
+                                         "under the profiler)"} if ktrace else None),
+            "kernel_ms_per_step": round(sum(e["ms"] for e in stage_out.values()), 4),
+            "roofline": hbm,
+            "roofline_valu": valu,
+            "step_hbm": {"bytes_per_step": step_bytes, "GBps": round(step_bytes / 1e9 / (ms_per_step * 1e-3), 1),
+                         "frac": round(step_bytes / 1e9 / (ms_per_step * 1e-3) / HBM_PEAK_GBS, 4),
+                         "note": "sum of the per-stage bytes (blend kernels: touched bytes) / ms_per_step"},
+            "stages": stage_out,
+        }
+
+    final_out = None
+    if rank == 0:
+        steps = args.steps
+        dt, st = m["dt"], m["stats"]
+        n, w, h = m["n"], m["w"], m["h"]
+        ms_per_step = dt / steps * 1e3
         out = {
             "metric": "train views/sec @ 1M Gaussians, 1080p (fwd + L1/SSIM loss + bwd + Adam per view)",
             "value": round((1 if tile_mode else world) * steps / dt, 3),
@@ -1030,16 +1072,17 @@ def main():
             "windows_spread": round((max(m["window_dt"]) - min(m["window_dt"])) / max(dt, 1e-12), 4),
             "windows_are": "replicas: every window times steps [warmup, warmup + steps) of the same training run from the same initial state (parameters, Adam "
                            "moments, step counter, view cycle and the library's per-view tables reset before each): their spread is noise, not drift",
-            "ms_per_step_without_kernel_events": (round(m["dt_plain"] / steps * 1e3, 4) if m.get("dt_plain") else None),
+            **({"ms_per_step_without_kernel_events": (round(m["dt_plain"] / steps * 1e3, 4) if m.get("dt_plain") else None)} if args.full else {}),
             "timed_phase": "steps %d..%d of a training run from the untrained synthetic scene (the heaviest phase: the blended pairs per frame fall as the scene "
-                           "trains, see config.per_view[].intersections_blended_first_last_timed_step).  Rounds 1-4 timed consecutive windows of a scene that "
+                           "trains, see config.per_view[].intersections_blended_first_last_timed_step of a --full line).  Rounds 1-4 timed consecutive windows of a scene that "
                            "kept training (round 4: ~60 steps, 7.5 %% monotone drift between its windows): their views/s are not comparable with this line"
                            % (args.warmup, args.warmup + steps - 1),
             "config": {"workload": "%s: %d splats, %dx%d, SH degree %d, one view per rank per step (BASELINE.json configs[2])" % (args.workload, n, w, h, args.sh_degree),
                        "views": m["nviews"],
                        "view_cycle": ("step k trains view k %% %d; " % m["nviews"]) + ("two cameras 2 units apart in x as crates/brush-bench-test/src/benches.rs:198-220" if m["nviews"] == 2 else
                                                                                    ("one camera replayed" if m["nviews"] == 1 else "an orbit of cameras on a circle of radius 1")),
-                       "num_visible": nv, "num_intersections": ni, "per_view": m["per_view"],
+                       # means over the views of the timed region, counted in an untimed replica of its steps (--full)
+                       **({"num_visible": m["nv"], "num_intersections": m["ni"], "per_view": m["per_view"]} if args.full else {}),
                        "near_share": {"min": round(m["near_share_min"], 4), "max": round(m["near_share_max"], 4), "mean": round(m["list_share"], 4),
                                       "of": "every step of the timed windows"} if args.lists == "sliced" else None,
                        "far_slices_queued": m["far_slices_queued"] if args.lists == "sliced" else None,
@@ -1056,22 +1099,9 @@ def main():
                                                                          "listing (on the communicator's side stream beside the backward), GradExchange = row gather + all-reduce + scatter "
                                                                          "(or the dense all-reduce), ImageExchange = the strips' halos (tiles only)",
                           "ab": None} if pg is not None else None),
-            "fwd_ms": round(fwd_ms, 4),
-            "fwd_bwd_ms": round(fwd_ms + bwd_ms, 4),
-            "fwd_bwd_source": fwd_src,
-            "kernel_trace": ({"steps": ktrace["steps"], "kernels": ktrace["kernels"], "wall_us_per_step": ktrace.get("wall_us_per_step"),
-                              "idle_us_per_step": ktrace.get("idle_us_per_step"),
-                              "idle_is": "inside the SAME (child) run: from the first kernel's start to the last kernel's end of the timed steps, minus the kernels' "
-                                         "own durations - the step's true idle time (kernel_ms_per_step vs ms_per_step compares two different runs, one of them "
-                                         "under the profiler)"} if ktrace else None),
-            "kernel_ms_per_step": round(sum(e["ms"] for e in stage_out.values()), 4),
-            "roofline": hbm,
-            "roofline_valu": valu,
-            "step_hbm": {"bytes_per_step": step_bytes, "GBps": round(step_bytes / 1e9 / (ms_per_step * 1e-3), 1),
-                         "frac": round(step_bytes / 1e9 / (ms_per_step * 1e-3) / HBM_PEAK_GBS, 4),
-                         "note": "sum of the per-stage bytes (blend kernels: touched bytes) / ms_per_step"},
-            "stages": stage_out,
         }
+        if args.full:
+            out.update(full_figures(m, steps, ms_per_step))
         if loop is not None:
             out["train_loop"] = loop
         if view_runs:
@@ -1088,13 +1118,13 @@ def main():
             out["forward_only"] = {"workload": "%s, RasterPass::Forward (BASELINE.json configs[1]): packed rgba8 image, no backward state; ms per render call incl. its count readback" % args.workload,
                                    "ms_exact_lists": m["forward_only"]["exact_lists"], "ms_sliced_lists": m["forward_only"]["sliced_lists"],
                                    "near_share": m["forward_only"].get("near_share"), "far_slices_queued": m["forward_only"].get("far_slices_queued")}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(m["scene"], m["cp"], w, h)
         final_out = out
     # ---- N > 1 side measurements, behind the line's own figures and under a watchdog: a collective that hangs here (the direct
     # all-reduce has never met a second rank on hardware) costs the side measurements, not the line
     exchange_stages, exchange_ab = None, None
-    if pg is not None and not args.no_extra:
+    if pg is not None and extras:
         import threading
 
         def bail():
@@ -1107,7 +1137,7 @@ def main():
         side_timer = threading.Timer(300.0, bail)
         side_timer.daemon = True
         side_timer.start()
-    if pg is not None and not args.no_extra:
+    if pg is not None and extras:
         # The first multi-GPU run has to explain itself: (a) what the exchange stages cost per step on every rank
         # (HIP events around FlagExchange / GradExchange / ImageExchange, 10 steps from the same initial state), (b) a 10-step A/B of
         # the exchange modes and of the two all-reduce algorithms (every figure the MAX over the ranks, like the headline)
@@ -1171,8 +1201,9 @@ KERNEL_STAGE = (("project_forward_kernel", "ProjectSplats"), ("dsort_", "DepthSo
 
 def _child_cmd(args, extra):
     """This command again as a child process under rocprofv3: the SAME warm-up and step counts (so that its timed steps are the same
-    piece of the same training run as the parent's: VERDICT r4 weak #5 / #6), one window, nothing but the headline measurement."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-extra", "--no-pmc",
+    piece of the same training run as the parent's: VERDICT r4 weak #5 / #6), one window, nothing but the headline measurement and
+    the counts of its views (--full without its side measurements: the --pmc passes read `roofline.intersections_blended` of its line)."""
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-extra", "--no-pmc",
            "--lists", args.lists, "--views", str(args.views), "--windows", "1"] + extra
     if args.no_noise:
         cmd.append("--no-noise")

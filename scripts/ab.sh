@@ -46,7 +46,7 @@ case "$verb" in
   stages)
     cd $ROOT
     for v in "$@"; do setup "$v"
-      env $ENVV python bench.py --no-cpu-baseline --no-extra --steps ${STEPS:-50} ${BENCH_ARGS} | python -c "
+      env $ENVV python bench.py --full --no-cpu-baseline --no-extra --steps ${STEPS:-50} ${BENCH_ARGS} | python -c "
 import json,sys
 d=json.load(sys.stdin)
 print('$v', d['ms_per_step'], ' '.join('%s=%.1f'%(k[:12],v['ms']*1e3) for k,v in d['stages'].items()))"

@@ -5,10 +5,10 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for lib in "$@"; do
   if [ $lib = default ]; then E="X_AB=1"; else E="BRUSH_HIP_LIB=$GRAFT_REPO_ROOT/brush_amd/variants/libbrush_hip_$lib.so"; fi
-  env $E python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
+  env $E python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); print('$lib headline', d['ms_per_step'], 'K16', d['stages']['Rasterize']['ms'], 'K17', d['stages']['RasterizeBackwards']['ms'])"
-  env $E python bench.py --workload 1m_1080p_centered --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
+  env $E python bench.py --full --workload 1m_1080p_centered --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); print('$lib centered', d['ms_per_step'], 'K16', d['stages']['Rasterize']['ms'], 'K17', d['stages']['RasterizeBackwards']['ms'])"
   env $E python bench.py --loop-only exact_lists --loop-steps 1500 2>/dev/null | python -c "

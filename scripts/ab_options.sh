@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for opt in "$@"; do
-  BH_OPTIONS=$opt python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
+  BH_OPTIONS=$opt python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc 2>/dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); print('$opt headline', d['ms_per_step'], 'K16', d['stages']['Rasterize']['ms'], 'K17', d['stages']['RasterizeBackwards']['ms'])"
   BH_OPTIONS=$opt python bench.py --loop-only exact_lists --loop-steps 1500 2>/dev/null | python -c "

@@ -2,13 +2,15 @@
 # Runs on the GPU box (via gpurun): rocprofv3 kernel trace + separate PMC passes of bench.py.
 # Usage: scripts/profile_bench.sh <tag>   -> gpurun_out/prof_<tag>/
 TAG=${1:-r1}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# Every pass profiles THE DRIVER'S COMMAND (--steps 20 --warmup 5) without its side measurements: the windows of bench.py are replicas
+# Every pass profiles THE DRIVER'S COMMAND (--steps 20 --warmup 5) without its side measurements (--full for the view counts of the
+# roofline object, which scripts/collect_profiles.py reads from the SQ pass's line): the windows of bench.py are replicas
 # of the same 20 steps of the same training run, so the kernels of every pass are the kernels of the headline (VERDICT r4 weak #5/#6:
 # a 200-step trace of a scene that trains while it is timed was a different workload from the 20 steps the driver times).
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc --no-stages"
+CMD="python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra --no-pmc --no-stages"
 LONG="$CMD"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $LONG > $OUT/bench_trace.json 2> $OUT/trace.err
 echo "trace exit $?"

@@ -3,8 +3,8 @@
 # Every step under its own timeout: a hung step must not eat the box.
 TAG=${1:-r2}
 cd $GRAFT_REPO_ROOT; O=gpurun_out
-# the driver's own command
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench.err; echo "bench rc $?"
+# the driver's own command, with everything else it measures (design_figures.py reads the stage table and the side measurements)
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench.err; echo "bench rc $?"
 timeout 200 python bench.py --steps 20 --warmup 5 --lists exact --no-cpu-baseline --no-extra --no-pmc > $O/${TAG}_bench_exact_lists_n1.json 2>> $O/${TAG}_bench.err; echo "exact lists rc $?"
 timeout 200 python bench.py --steps 20 --warmup 5 --sh-degree 3 --no-cpu-baseline --no-extra --no-pmc > $O/${TAG}_bench_sh3_n1.json 2>> $O/${TAG}_bench.err; echo "sh3 rc $?"
 timeout 300 python bench.py --workload 6m_4k --sh-degree 3 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-pmc > $O/${TAG}_bench_6m_4k_sh3_n1.json 2>> $O/${TAG}_bench.err; echo "6m4k rc $?"

@@ -27,6 +27,15 @@ def test_gpus_2_spawns_two_ranks():
     assert d["n_gpus"] == 2 and d["ranks_joined"] == 2 and d["steps"] == 3 and d["warmup"] == 1
 
 
+def test_full_is_off_by_default_and_reaches_every_rank():
+    for extra, want in (([], False), (["--full"], True)):
+        r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"] + extra, {"BH_BENCH_DRYRUN": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        assert json.loads(lines[0])["full"] is want
+
+
 def test_gpus_2_on_a_box_without_two_devices_fails_loudly():
     import torch
     if torch.cuda.is_available() and torch.cuda.device_count() >= 2:
