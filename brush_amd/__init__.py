@@ -15,6 +15,7 @@ Names and argument meaning follow the reference (paths under
     prefix_sum        brush-prefix-sum/src/lib.rs:11
     image_loss        brush-loss/src/lib.rs:1075-1104
     splat_to_ply / load_splat_from_ply   brush-serde/src/export.rs:179-204, import.rs:166-330 (plain PLY)
+    splat_to_compressed_ply               the SuperSplat compressed.ply the reader of import.rs:407-600 takes
     BatchUploader / SceneLoader          brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
     SplatTrainer      brush-train/src/train.rs:140-429 (step) and :431-893 (refine)
     compute_pup_scores / decimate_to_count   brush-train/src/lod.rs:13-142 (LOD boundary, brush-process/src/train_stream.rs:248-303)
@@ -34,6 +35,6 @@ from .host import (  # noqa: F401
     splat_to_ply, load_splat_from_ply, ply_parse_header, ParseMetadata, BatchUploader, SceneLoader, set_list_slicing, last_list_counts, set_view_id,
     render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
     knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
-    Lpips, lpips, lpips_value_and_grad,
+    Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -215,6 +215,12 @@ LPIPS_SYMBOLS = {
     "bh_train_set_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float]),
 }
 
+# every symbol include/brush_hip_compressed_ply.h declares (compressed PLY export, a header of its own on top of brush_hip.h)
+COMPRESSED_PLY_SYMBOLS = {
+    "bh_splat_to_compressed_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, fp,
+                                             C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -254,7 +260,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS))
     return _lib
 
 
@@ -263,5 +269,5 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **TEST_HOOK_SYMBOLS))
     return _lib_th

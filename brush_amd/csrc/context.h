@@ -75,6 +75,7 @@ enum Slot : int {
     SLOT_KNN,                // bh_knn_log_scales: control | keys | sorted keys | order | rank cells [N] | x y z [N] | tree boxes (knn.hip)
     SLOT_EVAL,               // bh_eval_metrics: per-tile (squared error, SSIM) f64 partial sums (eval.hip)
     SLOT_LPIPS,              // bh_lpips_*: f64 partials | normalised inputs | scratch pair | activations of both images (lpips.hip)
+    SLOT_PLY_COMPRESS,       // bh_splat_to_compressed_ply: box partials | box | Morton keys [N] | sorted keys [N] | row order [N] (ply_compress.hip)
     SLOT_COUNT
 };
 
@@ -471,6 +472,8 @@ int check_hip(bh_ctx* ctx, hipError_t e, const char* what);
 // lpips.hip: the train step's LPIPS term on the frame's image: *loss += w * LPIPS (and loss_host), v_output.rgb += w * dLPIPS/dimg
 int lpips_train_term(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, const float* bg, float* v_output,
                      float* loss, float* loss_host);
+// ply.hip: the comment lines every exported PLY header carries (export.rs:188-193), shared by both writers
+std::string ply_header_comments(uint32_t sh_degree, bool render_mip, const float* up_axis);
 // Grow-only allocation of a scratch slot; returns nullptr (and sets the error) on failure.
 void* ensure(bh_ctx* ctx, Slot s, size_t bytes);
 

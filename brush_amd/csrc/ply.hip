@@ -245,13 +245,18 @@ static std::string f32_display(float v) {  // Rust's `{}` for f32: shortest roun
     return std::string(buf, r.ptr);
 }
 
-static std::string ply_header(uint64_t n, uint32_t sh_degree, bool render_mip, const float* up_axis) {
-    std::string h = "ply\nformat binary_little_endian 1.0\n";
-    h += "comment Exported from Brush\n";                       // export.rs:188
+std::string ply_header_comments(uint32_t sh_degree, bool render_mip, const float* up_axis) {
+    std::string h = "comment Exported from Brush\n";           // export.rs:188
     if (up_axis) h += "comment Vertical axis: " + f32_display(up_axis[0]) + " " + f32_display(up_axis[1]) + " " + f32_display(up_axis[2]) + "\n";
     else h += "comment Vertical axis: y\n";                      // export.rs:189-193
     h += "comment SH degree: " + std::to_string(sh_degree) + "\n";
     h += std::string("comment SplatRenderMode: ") + (render_mip ? "mip" : "default") + "\n";
+    return h;
+}
+
+static std::string ply_header(uint64_t n, uint32_t sh_degree, bool render_mip, const float* up_axis) {
+    std::string h = "ply\nformat binary_little_endian 1.0\n";
+    h += ply_header_comments(sh_degree, render_mip, up_axis);
     h += "element vertex " + std::to_string(n) + "\n";
     static const char* core[] = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "opacity", "rot_0", "rot_1", "rot_2", "rot_3", "f_dc_0", "f_dc_1", "f_dc_2"};
     for (const char* p : core) h += std::string("property float ") + p + "\n";

@@ -596,6 +596,24 @@ def splat_to_ply(splats: Splats, up_axis=None, ctx: Optional[Context] = None) ->
     return bytes(buf)
 
 
+def splat_to_compressed_ply(splats: Splats, up_axis=None, ctx: Optional[Context] = None, return_order=False):
+    """The splats as a SuperSplat / PlayCanvas compressed.ply (include/brush_hip_compressed_ply.h), the format
+    load_splat_from_ply reads back: Morton-ordered rows, per-256-row chunk ranges, 16 B per splat + 3K bytes of SH.  The 3D-filter
+    floor is baked first, as in splat_to_ply.  return_order: also the file row -> input row map (int32 [N] device)."""
+    ctx = ctx or get_context(splats.device)
+    n = splats.num_splats()
+    up = (C.c_float * 3)(*[float(v) for v in up_axis]) if up_axis is not None else None
+    order = torch.empty((n,), dtype=torch.int32, device=splats.device) if return_order else None
+    need = C.c_uint64(0)
+    args = (_ptr(splats.transforms), _ptr(splats.sh_coeffs), _ptr(splats.raw_opacities),
+            _ptr(splats.min_scale) if splats.min_scale is not None else None, n, splats.sh_degree(), int(splats.render_mip), up,
+            _ptr(order) if order is not None and n else None)
+    ctx.check(ctx.lib.bh_splat_to_compressed_ply(ctx._h, *args, None, 0, C.byref(need)))
+    buf = (C.c_char * need.value)()
+    ctx.check(ctx.lib.bh_splat_to_compressed_ply(ctx._h, *args, buf, need.value, C.byref(need)))
+    return (bytes(buf), order) if return_order else bytes(buf)
+
+
 @dataclass
 class ParseMetadata:
     """brush-serde/src/import.rs:19-24"""

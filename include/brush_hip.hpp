@@ -13,6 +13,7 @@
 //   brush_hip::tile_sort_offsets render.rs:228-243 + kernels/get_tile_offset.rs:11-58
 //   brush_hip::SplatTrainer      brush-train/src/train.rs:140-893           (step, refine, set_view_cams)
 //   brush_hip::splat_to_ply / load_splat_from_ply   brush-serde/src/export.rs:179-204, import.rs:166-170
+//   brush_hip::splat_to_compressed_ply   the SuperSplat compressed.ply of import.rs:407-600 (brush_hip_compressed_ply.h)
 //   brush_hip::image_loss / image_loss_backward      brush-loss/src/lib.rs:718-733, 1075-1104 (LossOps; [H,W,C] in, [H,W,C] out)
 //   brush_hip::image_loss_value_and_grad             the composition SplatTrainer::step makes of it (train.rs:227-260)
 //   brush_hip::adam_step / gather_stats              brush-train/src/adam_scaled.rs:75-147, stats.rs:40-50
@@ -45,6 +46,7 @@
 
 #include "brush_hip.h"
 #include "brush_hip_lpips.h"
+#include "brush_hip_compressed_ply.h"
 
 namespace brush_hip {
 
@@ -528,6 +530,21 @@ inline std::vector<uint8_t> splat_to_ply(const Context& ctx, const Splats& s, co
     std::vector<uint8_t> out(need);
     ctx.check(bh_splat_to_ply(ctx.get(), s.transforms.data(), s.sh_coeffs.data(), s.raw_opacities.data(), f, s.num_splats(), s.sh_degree(),
                               s.render_mip ? 1 : 0, up_axis, out.data(), need, &need));
+    return out;
+}
+// SuperSplat compressed.ply (brush_hip_compressed_ply.h): Morton-ordered rows, per-chunk ranges; order, when given, is resized to
+// n and receives file row -> input row
+inline std::vector<uint8_t> splat_to_compressed_ply(const Context& ctx, const Splats& s, const float* up_axis = nullptr,
+                                                    DeviceBuffer<uint32_t>* order = nullptr) {
+    uint64_t need = 0;
+    const float* f = s.min_scale ? s.min_scale->data() : nullptr;
+    if (order && order->size() != s.num_splats()) order->resize(s.num_splats());
+    uint32_t* o = order ? order->data() : nullptr;
+    ctx.check(bh_splat_to_compressed_ply(ctx.get(), s.transforms.data(), s.sh_coeffs.data(), s.raw_opacities.data(), f, s.num_splats(),
+                                         s.sh_degree(), s.render_mip ? 1 : 0, up_axis, o, nullptr, 0, &need));
+    std::vector<uint8_t> out(need);
+    ctx.check(bh_splat_to_compressed_ply(ctx.get(), s.transforms.data(), s.sh_coeffs.data(), s.raw_opacities.data(), f, s.num_splats(),
+                                         s.sh_degree(), s.render_mip ? 1 : 0, up_axis, o, out.data(), need, &need));
     return out;
 }
 // subsample_points = s keeps every s-th file row (s-1, 2s-1, ...: import.rs:346-349), max_splats then caps the count the way
