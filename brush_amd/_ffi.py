@@ -221,6 +221,22 @@ COMPRESSED_PLY_SYMBOLS = {
                                              C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
+# every symbol include/brush_hip_image.h declares (mask merge + resampling of LoadImage::load, a header of its own on top of brush_hip.h)
+FILTER_LANCZOS3, FILTER_TRIANGLE = 0, 1   # BH_FILTER_*
+
+
+class BhViewLoad(C.Structure):
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("channels", C.c_uint32), ("mask_w", C.c_uint32), ("mask_h", C.c_uint32),
+                ("invert_mask", C.c_int32), ("mask_offset", C.c_uint64), ("max_resolution", C.c_uint32), ("scale", C.c_float),
+                ("premultiply", C.c_int32), ("reserved", C.c_uint32)]
+
+
+IMAGE_SYMBOLS = {
+    "bh_view_output_size": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u32p, u32p]),
+    "bh_resize_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bh_uploader_commit_view": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BhViewLoad)]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -260,7 +276,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS))
     return _lib
 
 
@@ -269,5 +285,5 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -506,6 +506,8 @@ void bh_destroy(bh_ctx* ctx) {
     if (ctx->dsort_spl) (void)hipFree(ctx->dsort_spl);
     if (ctx->readback_ev) (void)hipEventDestroy(ctx->readback_ev);
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
+    if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);
+    if (ctx->image_tab_ev) (void)hipEventDestroy(ctx->image_tab_ev);
     if (ctx->comm) (void)bh_comm_destroy(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

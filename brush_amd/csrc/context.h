@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/brush_hip.h"
 #include "../../include/brush_hip_lpips.h"
+#include "../../include/brush_hip_image.h"
 #include "device_math.h"
 
 namespace bh {
@@ -76,6 +78,7 @@ enum Slot : int {
     SLOT_EVAL,               // bh_eval_metrics: per-tile (squared error, SSIM) f64 partial sums (eval.hip)
     SLOT_LPIPS,              // bh_lpips_*: f64 partials | normalised inputs | scratch pair | activations of both images (lpips.hip)
     SLOT_PLY_COMPRESS,       // bh_splat_to_compressed_ply: box partials | box | Morton keys [N] | sorted keys [N] | row order [N] (ply_compress.hip)
+    SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
     SLOT_COUNT
 };
 
@@ -363,6 +366,9 @@ struct bh_ctx {
     // flags: every fact is tied to the forward (generation) whose kernels established it and is consumed exactly once.
     bh::GradClears clears;
     float* pending_loss_dst = nullptr; // where bh_sync delivers the last step's loss
+    void* image_tab_host = nullptr;   // bh_resize_u8: pinned staging of the weight tables (image.hip) ...
+    size_t image_tab_cap = 0;
+    hipEvent_t image_tab_ev = nullptr; // ... free again once this event (behind their copy) has completed
     const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
     float lpips_weight = 0.0f;
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
@@ -474,6 +480,19 @@ int lpips_train_term(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_pack
                      float* loss, float* loss_host);
 // ply.hip: the comment lines every exported PLY header carries (export.rs:188-193), shared by both writers
 std::string ply_header_comments(uint32_t sh_degree, bool render_mip, const float* up_axis);
+// image.hip: image::imageops::resize.  A pass's weight table is built on the host (resize_table_bytes bytes,
+// 16-byte multiple); enqueue_resize runs the vertical pass into tmp (w * nh * channels floats), then the horizontal one into out.
+enum ResizeOut : int { RESIZE_OUT_U8 = 0, RESIZE_OUT_PACKED = 1, RESIZE_OUT_PACKED_PREMUL = 2 };
+size_t resize_table_bytes(uint32_t src, uint32_t dst, uint32_t filter);
+void build_resize_table(uint32_t src, uint32_t dst, uint32_t filter, void* host);
+// ... the same table from a process-wide cache (built on a miss; thread-safe)
+using ResizeTable = std::shared_ptr<const std::vector<uint8_t>>;
+ResizeTable resize_table(uint32_t src, uint32_t dst, uint32_t filter);
+hipError_t enqueue_resize(hipStream_t st, const uint8_t* src, uint32_t w, uint32_t h, uint32_t channels, uint32_t nw, uint32_t nh,
+                          const int32_t* vtab, const int32_t* htab, float* tmp, void* out, int mode);
+// img (RGB8 / RGBA8) + mask [pixels] u8 -> packed rgba8 with alpha = mask (255 - mask), premultiplied or not
+hipError_t enqueue_mask_merge(hipStream_t st, const uint8_t* img, uint32_t channels, const uint8_t* mask, uint64_t pixels, int invert,
+                              int premultiply, uint32_t* out);
 // Grow-only allocation of a scratch slot; returns nullptr (and sets the error) on failure.
 void* ensure(bh_ctx* ctx, Slot s, size_t bytes);
 

@@ -877,6 +877,39 @@ class TrainStepStats:
     exchange_rows: int = 0  # mask-keyed exchange: gradient rows sent this step (0 = the dense block)
 
 
+def view_output_size(w: int, h: int, max_resolution: int = 1920, scale: float = 1.0):
+    """-> (width, height) LoadImage::load resizes a w x h view to (load_image.rs output_scale: the long edge capped to
+    max_resolution, times the LOD image scale, never enlarged).  max_resolution 0 or None: no cap.  Host only."""
+    lib = _ffi.load()
+    ow, oh = C.c_uint32(), C.c_uint32()
+    rc = lib.bh_view_output_size(int(w), int(h), int(max_resolution or 0), float(scale), C.byref(ow), C.byref(oh))
+    if rc < 0:
+        raise ValueError("view_output_size: w, h > 0 and a finite scale > 0")
+    return int(ow.value), int(oh.value)
+
+
+_FILTERS = {"lanczos3": _ffi.FILTER_LANCZOS3, "triangle": _ffi.FILTER_TRIANGLE}
+
+
+def resize_image(t, size, filter="lanczos3", ctx: Optional[Context] = None):
+    """image::imageops::resize(t, width, height, filter) of the image crate 0.25, bit for bit (DESIGN.md §6h): t uint8 [H,W]
+    or [H,W,C] (C = 1, 3, 4) on the device, size = (width, height); -> uint8 tensor [height, width(, C)] on t's device.  Alpha is
+    filtered like any other channel.  The same size is a copy."""
+    if filter not in _FILTERS:
+        raise ValueError("filter must be 'lanczos3' or 'triangle'")
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3, 4)):
+        raise ValueError("resize_image: a uint8 [H,W] or [H,W,1|3|4] tensor")
+    if t.device.type != "cuda":
+        raise ValueError("resize_image: the image must be on the device")
+    ctx = ctx or get_context(t.device)
+    nw, nh = int(size[0]), int(size[1])
+    c = 1 if t.dim() == 2 else int(t.shape[2])
+    src = t.contiguous()
+    out = torch.empty((nh, nw) + tuple(t.shape[2:]), dtype=torch.uint8, device=t.device)
+    ctx.check(ctx.lib.bh_resize_u8(ctx._h, _ptr(src), int(t.shape[1]), int(t.shape[0]), c, _ptr(out), nw, nh, _FILTERS[filter]))
+    return out
+
+
 class BatchUploader:
     """Ring of pinned staging slots + a copy stream that turns decoded host images into packed rgba8
     device batches while the previous batch trains (bh_uploader_*: view_to_packed_data of
@@ -927,6 +960,43 @@ class BatchUploader:
         h, w, c = a.shape
         return self._check(self.lib.bh_uploader_submit(self._h, a.ctypes.data_as(C.c_void_p), w, h, c, int(bool(premultiply) and c == 4)))
 
+    def submit_view(self, img_u8, mask=None, invert_mask=False, max_resolution=1920, scale=1.0, premultiply=None):
+        """LoadImage::load (load_image.rs:60-131) of a decoded view, on the device: img_u8 uint8 [H,W,3|4]; mask (optional) uint8
+        [h,w] of one channel (an RGBA mask reduced to its alpha, a colour mask to luma, by the caller), Triangle-resized to the
+        image when its size differs, becomes the alpha channel (255 - mask with invert_mask); then Lanczos3 down to
+        view_output_size(W, H, max_resolution, scale); then view_to_packed_data.  premultiply: AlphaMode::Transparent (default:
+        True without a mask, False with one, as LoadImage::new picks).  Returns the slot; acquire() gives the output size."""
+        import numpy as np
+        a = np.ascontiguousarray(img_u8, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError("image must be [H,W,3] or [H,W,4] uint8")
+        h, w, c = a.shape
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            if m.ndim == 3 and m.shape[2] == 1:
+                m = m[:, :, 0]
+            if m.ndim != 2 or m.size == 0:
+                raise ValueError("mask must be a one-channel uint8 [h,w] array")
+        if premultiply is None:
+            premultiply = m is None
+        img_bytes = a.size
+        total = img_bytes + (m.size if m is not None else 0)
+        slot, buf = self.map(total)
+        try:
+            buf[:img_bytes] = a.reshape(-1)
+            if m is not None:
+                buf[img_bytes:total] = m.reshape(-1)
+        except Exception:
+            # a mapped slot must be committed or the ring stalls: commit a view the library refuses, which frees it
+            self.lib.bh_uploader_commit_view(self._h, int(slot), C.byref(_ffi.BhViewLoad()))
+            raise
+        d = _ffi.BhViewLoad(w=w, h=h, channels=c, mask_w=m.shape[1] if m is not None else 0, mask_h=m.shape[0] if m is not None else 0,
+                            invert_mask=int(bool(invert_mask)), mask_offset=img_bytes if m is not None else 0,
+                            max_resolution=int(max_resolution or 0), scale=float(scale), premultiply=int(bool(premultiply)))
+        self._check(self.lib.bh_uploader_commit_view(self._h, int(slot), C.byref(d)))
+        return slot
+
     def acquire(self, slot):
         """-> (packed int32 [H,W] device tensor aliasing the slot, has_alpha).  Work queued on the ctx stream
         afterwards is ordered behind the upload; call release(slot) once the step that reads it is queued."""
@@ -943,25 +1013,36 @@ class SceneLoader:
     a list of views, prefetched by a loader thread through a BatchUploader so the H2D copy + packing of the
     next views overlap the current train step.
 
-    views: sequence of (image, Camera[, alpha_is_mask]) with image a uint8 [H,W,3|4] array or a callable
-    returning one (the decode).  Shuffling: every epoch is a seeded Fisher-Yates permutation (SplitMix64) of
+    views: sequence of (image, Camera[, alpha_is_mask[, mask]]) with image a uint8 [H,W,3|4] array or a callable
+    returning one (the decode), and mask an optional one-channel uint8 [h,w] array or callable (load_image.rs:69-112: it
+    becomes the view's alpha; alpha_is_mask None then means True, AlphaMode::Masked).  max_resolution / image_scale: the
+    views are resampled on the device as LoadImage::load does (BatchUploader.submit_view; LoadImage::with_scale for a LOD
+    level), invert_masks as LoadDatasetConfig's.  With the defaults (None, 1.0) and no masks the views go through
+    BatchUploader.submit unchanged.  Shuffling: every epoch is a seeded Fisher-Yates permutation (SplitMix64) of
     this rank's views — the reference's order comes from rand::StdRng inside racing loader tasks and is not
     reproducible, so only the "every view once per epoch" property is kept.  `rank`/`world` shard the view
     list for data-parallel training (view i belongs to rank i % world)."""
 
-    def __init__(self, views, seed=0, uploader: Optional[BatchUploader] = None, slots=3, rank=0, world=1, ctx: Optional[Context] = None):
+    def __init__(self, views, seed=0, uploader: Optional[BatchUploader] = None, slots=3, rank=0, world=1, ctx: Optional[Context] = None,
+                 max_resolution: Optional[int] = None, image_scale: float = 1.0, invert_masks: bool = False):
         import queue
         import threading
         self.views = [v for i, v in enumerate(views) if i % world == rank]
         self.view_ids = [i + 1 for i in range(len(views)) if i % world == rank]   # dataset index + 1 (0 = "unknown view")
         if not self.views:
             raise ValueError("Need at least one view in dataset")  # scene_loader.rs:130
+        self.max_resolution, self.image_scale, self.invert_masks = max_resolution, float(image_scale), bool(invert_masks)
+        if not (self.image_scale > 0.0 and math.isfinite(self.image_scale)):
+            raise ValueError("image_scale must be finite and > 0")
         self._own_uploader = uploader is None
         if uploader is None:
             mp = 0
             for v in self.views:
                 img = v[0]() if callable(v[0]) else v[0]
-                mp = max(mp, img.shape[0] * img.shape[1])
+                mask = self._view_mask(v)
+                px = img.shape[0] * img.shape[1]
+                staged = img.size + (mask.size if mask is not None else 0)   # image + mask bytes in one pinned slot
+                mp = max(mp, px, (staged + 3) // 4)
             uploader = BatchUploader(mp, slots, ctx)
         self.up = uploader
         self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -970,6 +1051,11 @@ class SceneLoader:
         self._held = None
         self._thread = threading.Thread(target=self._run, name="brush-hip-loader", daemon=True)
         self._thread.start()
+
+    @staticmethod
+    def _view_mask(view):
+        m = view[3] if len(view) > 3 else None
+        return m() if callable(m) else m
 
     @staticmethod
     def _splitmix(state):
@@ -998,13 +1084,19 @@ class SceneLoader:
                 for idx in self.epoch_order(epoch):
                     view = self.views[idx]
                     img = view[0]() if callable(view[0]) else view[0]
-                    mask = bool(view[2]) if len(view) > 2 else False
+                    mask_img = self._view_mask(view)
+                    flag = view[2] if len(view) > 2 else None
+                    mask = bool(flag) if flag is not None else mask_img is not None   # alpha_is_mask (AlphaMode::Masked)
                     # wait for a free place in the queue BEFORE mapping a slot, so a mapped slot is never parked
                     while not self._stop.is_set() and self._q.full():
                         self._stop.wait(0.0005)
                     if self._stop.is_set():
                         return
-                    slot = self.up.submit(img, premultiply=not mask)
+                    if mask_img is None and self.max_resolution is None and self.image_scale == 1.0:
+                        slot = self.up.submit(img, premultiply=not mask)
+                    else:
+                        slot = self.up.submit_view(img, mask=mask_img, invert_mask=self.invert_masks, max_resolution=self.max_resolution or 0,
+                                                   scale=self.image_scale, premultiply=not mask)
                     self._q.put((slot, idx, view[1], mask))
                 epoch += 1
         except Exception as e:  # surface loader failures to the consumer ("Scene loader failed to load an image")

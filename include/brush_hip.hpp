@@ -18,6 +18,7 @@
 //   brush_hip::image_loss_value_and_grad             the composition SplatTrainer::step makes of it (train.rs:227-260)
 //   brush_hip::adam_step / gather_stats              brush-train/src/adam_scaled.rs:75-147, stats.rs:40-50
 //   brush_hip::BatchUploader / SceneLoader           brush-dataset/src/scene.rs:97-136, scene_loader.rs:59-174
+//   brush_hip::view_output_size / resize_u8 / BatchUploader::submit_view   load_image.rs:60-131 (brush_hip_image.h)
 //   brush_hip::sample_background / normal_samples    train.rs:896-908, 389-416 (the library's counter-based generator)
 //   brush_hip::pup_accumulate[_view] / pup_scores / decimate_to_count / lod_target_count   brush-train/src/lod.rs:13-142, train_stream.rs:261
 //   brush_hip::knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242, train_stream.rs:100-123
@@ -47,6 +48,7 @@
 #include "brush_hip.h"
 #include "brush_hip_lpips.h"
 #include "brush_hip_compressed_ply.h"
+#include "brush_hip_image.h"
 
 namespace brush_hip {
 
@@ -597,6 +599,19 @@ struct SceneBatch {  // brush-dataset/src/scene.rs:139-147
 struct TrainStepStats { uint32_t num_visible, num_intersections; double lr_mean; float loss; };
 
 // ---- host image -> packed device batch (brush-dataset) ---------------------------------------------------------------
+// LoadImage::output_scale (load_image.rs): the (width, height) load() resizes a w x h view to; max_resolution 0: no cap
+inline std::pair<uint32_t, uint32_t> view_output_size(uint32_t w, uint32_t h, uint32_t max_resolution = 1920, float scale = 1.0f) {
+    uint32_t ow = 0, oh = 0;
+    const int rc = bh_view_output_size(w, h, max_resolution, scale, &ow, &oh);
+    if (rc != 0) throw Error(rc, "view_output_size: w, h > 0 and a finite scale > 0");
+    return {ow, oh};
+}
+// image::imageops::resize of device bytes [h][w][channels] -> [nh][nw][channels] on the ctx stream (channels 1 | 3 | 4)
+inline void resize_u8(const Context& ctx, const uint8_t* src, uint32_t w, uint32_t h, uint32_t channels, uint8_t* dst, uint32_t nw, uint32_t nh,
+                      uint32_t filter = BH_FILTER_LANCZOS3) {
+    ctx.check(bh_resize_u8(ctx.get(), src, w, h, channels, dst, nw, nh, filter));
+}
+
 // view_to_packed_data (scene.rs:97-136) on the device behind a ring of pinned staging slots and a copy stream: the decoded RGB8 / RGBA8
 // bytes cross PCIe unpacked, widening (a = 255), the byte-space premultiply of AlphaMode::Transparent and the packing run in a kernel
 // on the copy stream while the previous batch trains.  Life of a slot: map -> (decode into the pinned bytes) -> commit -> acquire
@@ -622,6 +637,23 @@ class BatchUploader {
     int submit(const uint8_t* pixels, uint32_t w, uint32_t h, uint32_t channels, bool premultiply = true) {
         if (channels != 3 && channels != 4) throw Error(BH_ERR_INVALID_ARG, "image must be [H,W,3] or [H,W,4] uint8");
         return check(bh_uploader_submit(up_, pixels, w, h, channels, (premultiply && channels == 4) ? 1 : 0));
+    }
+    // LoadImage::load of a decoded view (brush_hip_image.h): pixels [H,W,3|4]; mask (or nullptr) one channel [mask_h][mask_w], merged
+    // into alpha; then Lanczos3 to view_output_size(w, h, max_resolution, scale) and the pack.  acquire() gives the output size.
+    int submit_view(const uint8_t* pixels, uint32_t w, uint32_t h, uint32_t channels, const uint8_t* mask = nullptr, uint32_t mask_w = 0,
+                    uint32_t mask_h = 0, bool invert_mask = false, uint32_t max_resolution = 1920, float scale = 1.0f, bool premultiply = true) {
+        if (channels != 3 && channels != 4) throw Error(BH_ERR_INVALID_ARG, "image must be [H,W,3] or [H,W,4] uint8");
+        const uint64_t img_bytes = (uint64_t)w * h * channels, mask_bytes = mask ? (uint64_t)mask_w * mask_h : 0;
+        const std::pair<int, uint8_t*> m = map(img_bytes + mask_bytes);
+        std::memcpy(m.second, pixels, (size_t)img_bytes);
+        if (mask_bytes) std::memcpy(m.second + img_bytes, mask, (size_t)mask_bytes);
+        BhViewLoad d{};
+        d.w = w; d.h = h; d.channels = channels;
+        d.mask_w = mask ? mask_w : 0; d.mask_h = mask ? mask_h : 0; d.invert_mask = invert_mask ? 1 : 0;
+        d.mask_offset = mask ? img_bytes : 0;
+        d.max_resolution = max_resolution; d.scale = scale; d.premultiply = premultiply ? 1 : 0;
+        check(bh_uploader_commit_view(up_, m.first, &d));
+        return m.first;
     }
     struct Packed { const uint32_t* img; uint32_t w, h; bool has_alpha; };   // device [H,W] rgba8, aliasing the slot
     Packed acquire(int slot) {
