@@ -59,7 +59,7 @@ static inline void cpu_relax() {
     __asm__ __volatile__("yield");
 #endif
 }
-static int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what) {
+int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what) {
     // Spins for at most ~2 ms (a healthy step delivers its tag within tens of microseconds), then stops burning the core: an event
     // behind everything queued so far and a blocking wait on it — the tag's kernel is in front of that event, so afterwards the tag
     // is there, or its kernel was never launched (an error, not a hang).
@@ -203,214 +203,6 @@ ProfScope::~ProfScope() {
     ctx->prof.pending.push_back({idx, a, b});
 }
 
-
-// ---- the far slice of a depth-sliced forward (see bh_render_forward) -------------------------------------------------------------
-// count -> emit (the scan between them folded into the emit kernel) the remaining splats into the tiles that still have live pixels, sort them behind the near list (absolute
-// offsets: one array for the backward), blend from the parked state.  Every kernel is gated on the device by the number of
-// unsaturated tiles, so queueing it for a frame that does not need it is correct, just ~50 us of empty launches.
-int enqueue_far_slice(bh_ctx* ctx, const FarJob& j) {
-    const uint32_t* gate = j.slice_info + 2;
-    const uint32_t far_max = j.ni;   // the host's bound; the live count is slice_info[3] on the device (the emit kernel's last block)
-    {
-        ProfScope ps(ctx, "MapGaussiansToIntersect");
-        BH_TRY(launch_map_gaussians_far(ctx, j.nv, j.u, j.proj_by_gid, j.gfc, j.projected, j.cum, j.budget, j.done_bits, gate, j.far_counts, j.far_block_totals,
-                                        j.far_group_totals, j.slice_info, j.tile_ids, j.isect_gids));
-    }
-    {
-        ProfScope ps(ctx, "TileSort");
-        BH_TRY(radix_argsort_dev(ctx, j.tile_ids, j.isect_gids, far_max, j.slice_info + 3, gate, j.slice_info + 1, j.tile_bits, j.tile_ids_sorted,
-                                 j.isect_gids_sorted));
-    }
-    {
-        ProfScope ps(ctx, "GetTileOffsets");
-        BH_TRY(launch_tile_offsets_dev(ctx, j.tile_ids_sorted, far_max, j.slice_info + 3, gate, j.slice_info + 1, j.num_tiles, j.tile_offsets_far));
-    }
-    {
-        ProfScope ps(ctx, "Rasterize");
-        BH_TRY(launch_rasterize(ctx, j.u, j.bg, j.bwd_info, j.smooth, j.isect_gids_sorted, j.tile_offsets_far, j.projected, j.gfc, j.out_f32, j.out_u8, j.visible,
-                                j.lpt, j.class_width, /*phase=*/2, &j.rs));
-    }
-    ctx->far_launches++;
-    return 0;
-}
-
-// Which table a frame uses.  A caller that knows its views names them (bh_set_view_id / BhTrainBatch.view_id); one that does not
-// — the reference's SplatTrainer::step receives a SceneBatch without a view index (train.rs:176, brush-dataset/src/scene.rs:138-147)
-// — is keyed by the camera itself: a dataset's views are fixed cameras, and the same camera gives the same bits every time.
-// Bit 63 separates the two key spaces.
-static uint64_t view_key(const bh_ctx* ctx, const BhCamera& c) {
-    if (ctx->view_id != 0u || ctx->knob_no_view_hash) return (uint64_t)ctx->view_id;
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    auto mix = [&](uint32_t w) {   // splitmix64 finaliser over a running sum: order-sensitive, cheap, well spread
-        h += (uint64_t)w + 0x9E3779B97F4A7C15ull;
-        uint64_t z = h;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        h = z ^ (z >> 31);
-    };
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    for (int i = 0; i < 12; ++i) mix(bits(c.vm[i]));
-    mix(bits(c.fx)); mix(bits(c.fy)); mix(bits(c.cx)); mix(bits(c.cy));
-    mix(c.img_w); mix(c.img_h); mix(c.tile_row_begin); mix(c.tile_row_end); mix(c.model);
-    if (c.model != BH_CAMERA_PINHOLE) for (int i = 0; i < 8; ++i) mix(bits(c.dist[i]));
-    return h | (1ull << 63);
-}
-
-// The per-tile depth-cut table of view `key` for a (tile_bw x tile_bh) grid: created (all ZCUT_ALL = "list everything") on first
-// use, re-created when the grid changes; beyond MAX_VIEW_STATES tables (or VIEW_TABLE_BYTES of them) the least recently used view
-// gives its table up — to the new view when the grids match (no free, no host wait: the clears are ordered on the stream).
-// touch = false: a second attempt at the frame that has just been counted (finish_far_slice): the view's gap and stamp stay
-// casual = a forward-only frame keyed by its camera hash (viewer / eval renders): never more than CASUAL_VIEW_STATES such tables,
-// and none at all for a camera met for the first time (returns nullptr: the frame runs in index order, nothing is allocated).
-static ViewState* view_state(bh_ctx* ctx, uint64_t key, uint32_t tile_bw, uint32_t tile_bh, bool touch = true, bool casual = false) {
-    const size_t words = (size_t)tile_bw * tile_bh ? (size_t)tile_bw * tile_bh : 1;
-    auto it = ctx->views.find(key);
-    uint32_t* recycled = nullptr;
-    auto forget = [&](std::unordered_map<uint64_t, ViewState>::iterator v, bool keep_block) {
-        if (ctx->gate_view == &v->second) ctx->gate_view = nullptr;
-        if (ctx->far_job.view == &v->second) ctx->far_job.view = nullptr;
-        if (v->second.casual && ctx->casual_views) ctx->casual_views--;
-        if (keep_block) recycled = v->second.zcut;
-        else {
-            (void)hipStreamSynchronize(ctx->stream);   // queued kernels may still use the block
-            (void)hipFree(v->second.zcut);
-        }
-        ctx->views.erase(v);
-    };
-    if (it != ctx->views.end() && (it->second.tile_bw != tile_bw || it->second.tile_bh != tile_bh)) {
-        forget(it, false);
-        it = ctx->views.end();
-    }
-    if (it == ctx->views.end()) {
-        if (casual) {
-            bool seen = false;
-            for (uint64_t k : ctx->seen_keys) seen = seen || k == key;
-            if (!seen) {   // first meeting: remember the camera, allocate nothing
-                ctx->seen_keys[ctx->seen_pos++ % SEEN_KEYS] = key;
-                return nullptr;
-            }
-            while (ctx->casual_views >= CASUAL_VIEW_STATES) {   // the least recently used casual table makes room (its block is reused when the grids match)
-                auto old = ctx->views.end();
-                for (auto k = ctx->views.begin(); k != ctx->views.end(); ++k)
-                    if (k->second.casual && (old == ctx->views.end() || k->second.last_used < old->second.last_used)) old = k;
-                if (old == ctx->views.end()) { ctx->casual_views = 0; break; }
-                forget(old, recycled == nullptr && old->second.tile_bw == tile_bw && old->second.tile_bh == tile_bh);
-            }
-        }
-        const size_t max_views = std::min(MAX_VIEW_STATES, std::max<size_t>(8, VIEW_TABLE_BYTES / ((2 * words + VIEW_SPL_WORDS) * 4)));
-        while (ctx->views.size() >= max_views) {
-            auto old = ctx->views.begin();
-            for (auto k = ctx->views.begin(); k != ctx->views.end(); ++k)
-                if (k->second.last_used < old->second.last_used) old = k;
-            forget(old, recycled == nullptr && old->second.tile_bw == tile_bw && old->second.tile_bh == tile_bh);
-        }
-        ViewState vs;
-        vs.tile_bw = tile_bw;
-        vs.tile_bh = tile_bh;
-        vs.casual = casual;
-        // [T] depth cuts (all "everything") | [T] per-tile work of the last frame (all zero) | [VIEW_SPL_WORDS] depth-sort splitter tables (none valid)
-        vs.zcut = recycled;
-        if (!vs.zcut && hipMalloc((void**)&vs.zcut, (2 * words + VIEW_SPL_WORDS) * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vs.zcut), (int)ZCUT_ALL, words, ctx->stream) != hipSuccess ||
-            hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vs.zcut + words), 0, words + VIEW_SPL_WORDS, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(vs.zcut);
-            return nullptr;
-        }
-        vs.gap = (uint32_t)ctx->views.size() + 1u;   // (a new view of a dataset: it will come back after about as many frames as there are views)
-        vs.last_used = ++ctx->view_clock;
-        if (casual) ctx->casual_views++;
-        return &ctx->views.emplace(key, vs).first->second;
-    }
-    if (it->second.casual && !casual) {   // a training frame adopts the table: it now counts as a dataset view
-        it->second.casual = false;
-        if (ctx->casual_views) ctx->casual_views--;
-    }
-    if (touch) {
-        const uint64_t now = ++ctx->view_clock;
-        it->second.gap = (uint32_t)std::min<uint64_t>(now - it->second.last_used, 1u << 20);
-        it->second.last_used = now;
-    }
-    return &it->second;
-}
-
-// margin (in % of a tile's depth rank) the blend kernel of this frame writes behind every tile's last useful splat
-static uint32_t cut_margin_pct(const bh_ctx* ctx, const ViewState* vs) {
-    const float gap = vs && vs->gap > 2u ? (float)vs->gap : 2.0f;
-    const float m = (float)ctx->knob_cut_margin_pct * ctx->margin_scale * std::pow(gap * 0.5f, ctx->ctrl_gap_exp);
-    return m < 6400.0f ? (m > 10.0f ? (uint32_t)m : 10u) : 6400u;
-}
-
-// Outcome of a per-tile-cut frame of `vs`: did the forecast fail for some tile (the frame was then rendered a second time with
-// complete lists, which re-seeds the table)?  Every outcome moves the ctx's margin factor (x ctrl_up on a miss, x ctrl_down on a
-// hit: about one miss in 200 cut frames at equilibrium).  Six misses within the view's last eight cut frames (a scene that
-// changes faster than any margin) and the view's next eight frames are rendered with complete lists from the start.
-static void view_outcome(bh_ctx* ctx, ViewState* vs, bool missed, bool shared_table) {
-    if (!ctx->knob_fixed_margin) {
-        const float s = ctx->margin_scale * (missed ? ctx->ctrl_up : ctx->ctrl_down);
-        ctx->margin_scale = s < ctx->ctrl_floor ? ctx->ctrl_floor : (s > 16.0f ? 16.0f : s);
-    }
-    if (!vs) return;
-    vs->penalty = ((vs->penalty << 1) | (missed ? 1u : 0u)) & 0xFFu;   // (the history of the last eight cut frames, one bit each)
-    // (BH_NO_VIEW_HASH only: the table of view id 0 shared by every frame that names no view — alternating cameras miss on every
-    //  other frame there: three misses are enough, and the table stays untrusted for longer)
-    if (__builtin_popcount(vs->penalty) >= (shared_table ? 3 : 6)) {
-        vs->exact_frames = shared_table ? 32u : 8u;
-        vs->penalty = 0u;
-    }
-}
-
-static int forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_degree, const float* transforms, const float* sh_coeffs,
-                        const float* raw_opacities, const float* background, uint32_t flags, BhRenderOut* out, bool allow_cut);
-
-// A sliced forward that left the decision to the host: wait for the near pass's gate word.  Slot-budget slices: queue the far slice
-// if some tile is still unsaturated.  Per-tile cuts: there is no far pass (only the splats that own a near pair were sorted) — a
-// tile that is still live behind a cut list means the view's forecast failed, and the whole forward is run again with complete
-// lists (which also re-seeds the view's table).  *launched (optional) tells the caller whether out_img changed after the near pass.
-int finish_far_slice(bh_ctx* ctx, bool* launched) {
-    if (launched) *launched = false;
-    if (!ctx->far_job.pending) return 0;
-    ctx->far_job.pending = false;
-    if (!ctx->far_job.gate_event_recorded && ctx->gate_signal_queued) {
-        // (bh_train_step: its loss kernel, queued behind the near blend, stores the job's tag when it starts)
-        BH_TRY(wait_host_tag(ctx, reinterpret_cast<const volatile uint32_t*>(ctx->host_counters) + HOST_GATE_TAG_WORD, ctx->far_job.gate_tag, "near-pass gate"));
-    } else {
-        if (!ctx->far_job.gate_event_recorded) BH_HIP(ctx, hipEventRecord(ctx->gate_ev, ctx->stream));   // (nobody queued a signal: an event behind whatever is queued now)
-        BH_HIP(ctx, hipEventSynchronize(ctx->gate_ev));
-    }
-    ctx->gate_signal_queued = false;
-    const uint32_t unsat = reinterpret_cast<const volatile uint32_t*>(ctx->host_counters)[HOST_GATE_WORD];
-    if (ctx->far_job.by_cut) {
-        FarJob& j = ctx->far_job;
-        view_outcome(ctx, j.view, unsat != 0u, j.view_shared);
-        if (unsat == 0u) return 0;
-        if (launched) *launched = true;
-        ctx->far_launches++;
-        // the same call again, with the redirections of the train step that were in force and the same view, complete lists
-        const FarJob keep = j;
-        struct Saved { float* ev; float* er; size_t evf; float* eg; size_t egf; uint32_t vid; bool defer; } sv{ctx->ext_visible, ctx->ext_max_radius, ctx->ext_visible_floats,
-                                                                                                      ctx->ext_grad_begin, ctx->ext_grad_floats, ctx->view_id, ctx->defer_far};
-        ctx->ext_visible = keep.ext_visible; ctx->ext_max_radius = keep.ext_max_radius; ctx->ext_visible_floats = keep.ext_visible_floats;
-        ctx->ext_grad_begin = keep.ext_grad_begin; ctx->ext_grad_floats = keep.ext_grad_floats;
-        ctx->view_id = keep.view_id;
-        ctx->defer_far = false;
-        BhRenderOut again;
-        const int rc = forward_impl(ctx, &keep.cam, keep.n, keep.sh_degree, keep.transforms, keep.sh_coeffs, keep.raw_opacities, keep.bg, keep.flags, &again,
-                                    /*allow_cut=*/false);
-        ctx->ext_visible = sv.ev; ctx->ext_max_radius = sv.er; ctx->ext_visible_floats = sv.evf;
-        ctx->ext_grad_begin = sv.eg; ctx->ext_grad_floats = sv.egf;
-        ctx->view_id = sv.vid;
-        ctx->defer_far = sv.defer;
-        return rc;
-    }
-    ctx->far_direct = unsat != 0u;   // ... and the next sliced frame starts from what this one needed
-    if (unsat == 0u) return 0;
-    if (launched) *launched = true;
-    return enqueue_far_slice(ctx, ctx->far_job);
-}
 
 }  // namespace bh
 
@@ -819,33 +611,49 @@ int bh_camera_setup(const float* pos, const float* rot_xyzw, double fov_x, doubl
 }
 
 // ---- forward -------------------------------------------------------------------
-int bh_render_forward(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_degree, const float* transforms,
-                      const float* sh_coeffs, const float* raw_opacities, const float* background, uint32_t flags,
-                      BhRenderOut* out) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!cam || !out || !background) return set_error(ctx, BH_ERR_INVALID_ARG, "render_forward: null argument");
-    if (cam->img_w == 0 || cam->img_h == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "Can't render images with 0 size.");  // render.rs:50-53
-    if (sh_degree > 4) return set_error(ctx, BH_ERR_INVALID_ARG, "sh_degree must be 0..4");
-    if (cam->model > BH_CAMERA_THIN_PRISM_FISHEYE) return set_error(ctx, BH_ERR_INVALID_ARG, "unknown camera model");
-    // (a splat's candidate box is walked with a 24-bit index: tile grids up to 4095 x 4095)
-    if (cam->img_w > 65520 || cam->img_h > 65520) return set_error(ctx, BH_ERR_UNSUPPORTED, "images larger than 65520 px per side are not supported (tile grid <= 4095 x 4095)");
-    if (n > 0 && (!transforms || !sh_coeffs || !raw_opacities)) return set_error(ctx, BH_ERR_INVALID_ARG, "render_forward: null splat tensor");
-    if ((flags & BH_FLAG_SMOOTH_CUTOFF) && !(flags & BH_FLAG_BWD_INFO)) return set_error(ctx, BH_ERR_INVALID_ARG, "smooth cutoff requires the backward pass flag");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));   // (a deferred decision nobody collected)
-    return forward_impl(ctx, cam, n, sh_degree, transforms, sh_coeffs, raw_opacities, background, flags, out, /*allow_cut=*/true);
-}
-
 }  // extern "C"
 
-// The forward pipeline (arguments validated by bh_render_forward).  allow_cut = false: complete lists whatever the view's table says
-// (the second attempt after a failed forecast, finish_far_slice).
-int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_degree, const float* transforms, const float* sh_coeffs,
-                            const float* raw_opacities, const float* background, uint32_t flags, BhRenderOut* out, bool allow_cut) {
+// bh_render_forward and the train step: the request's checks, a deferred far-slice decision collected, then the pipeline
+static int render_forward(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
+    const BhCamera& cam = req.cam;
+    if (cam.img_w == 0 || cam.img_h == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "Can't render images with 0 size.");  // render.rs:50-53
+    if (req.sh_degree > 4) return set_error(ctx, BH_ERR_INVALID_ARG, "sh_degree must be 0..4");
+    if (cam.model > BH_CAMERA_THIN_PRISM_FISHEYE) return set_error(ctx, BH_ERR_INVALID_ARG, "unknown camera model");
+    // (a splat's candidate box is walked with a 24-bit index: tile grids up to 4095 x 4095)
+    if (cam.img_w > 65520 || cam.img_h > 65520) return set_error(ctx, BH_ERR_UNSUPPORTED, "images larger than 65520 px per side are not supported (tile grid <= 4095 x 4095)");
+    if (req.n > 0 && (!req.transforms || !req.sh_coeffs || !req.raw_opacities)) return set_error(ctx, BH_ERR_INVALID_ARG, "render_forward: null splat tensor");
+    if ((req.flags & BH_FLAG_SMOOTH_CUTOFF) && !(req.flags & BH_FLAG_BWD_INFO)) return set_error(ctx, BH_ERR_INVALID_ARG, "smooth cutoff requires the backward pass flag");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));   // (a deferred decision nobody collected)
+    return forward_impl(ctx, req, out);
+}
+
+extern "C" int bh_render_forward(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_degree, const float* transforms,
+                                 const float* sh_coeffs, const float* raw_opacities, const float* background, uint32_t flags,
+                                 BhRenderOut* out) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!cam || !out || !background) return set_error(ctx, BH_ERR_INVALID_ARG, "render_forward: null argument");
+    ForwardRequest req;
+    req.cam = *cam;
+    req.n = n; req.sh_degree = sh_degree; req.flags = flags;
+    req.transforms = transforms; req.sh_coeffs = sh_coeffs; req.raw_opacities = raw_opacities;
+    req.bg[0] = background[0]; req.bg[1] = background[1]; req.bg[2] = background[2];
+    req.view_id = ctx->view_id;
+    return render_forward(ctx, req, out);
+}
+
+// The forward pipeline (arguments validated by render_forward).  req.allow_cut = false: complete lists whatever the view's table
+// says (the second attempt after a failed forecast, finish_far_slice).
+int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
+    const uint32_t n = req.n, sh_degree = req.sh_degree, flags = req.flags;
+    const float* transforms = req.transforms;
+    const float* sh_coeffs = req.sh_coeffs;
+    const float* raw_opacities = req.raw_opacities;
+    const float* background = req.bg;
     ctx->have_forward = false;
     ctx->clears.begin_forward();   // (filled in below only by the kernels of THIS forward)
     const bool mip = flags & BH_FLAG_MIP, bwd_info = flags & BH_FLAG_BWD_INFO, smooth = flags & BH_FLAG_SMOOTH_CUTOFF;
-    const ViewUniforms u = make_uniforms(*cam);
+    const ViewUniforms u = make_uniforms(req.cam);
     if (u.tile_y0 >= u.tile_y1 || u.tile_y1 > u.tile_bh) return set_error(ctx, BH_ERR_INVALID_ARG, "tile_row window must satisfy begin < end <= ceil(img_h / 16)");
     const uint32_t num_tiles = u.tile_bw * u.tile_bh;
     const size_t npad = n ? n : 1;
@@ -857,7 +665,7 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     uint32_t* counters = counter_pairs ? counter_pairs + counter_set_words * (ctx->counter_phase & 1u) : nullptr;
     auto* depth_keys = (uint32_t*)ensure(ctx, SLOT_DEPTH_KEYS, npad * 4);
     auto* isect_counts = (uint32_t*)ensure(ctx, SLOT_ISECT_COUNTS, npad * 4);
-    auto* max_radius = ctx->ext_max_radius ? ctx->ext_max_radius : (float*)ensure(ctx, SLOT_MAX_RADIUS, npad * 4);
+    auto* max_radius = req.max_radius ? req.max_radius : (float*)ensure(ctx, SLOT_MAX_RADIUS, npad * 4);
     auto* proj_by_gid = (float*)ensure(ctx, SLOT_PROJECTED_BY_GID, npad * 9 * 4);
     if (!counters || !depth_keys || !isect_counts || !max_radius || !proj_by_gid) return BH_ERR_OOM;
 
@@ -869,9 +677,9 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     const bool bwd_jobs = bwd_info && ctx->knob_bwd_jobs && !ctx->knob_no_lpt && !((flags & BH_FLAG_SLICED_LISTS) && ctx->slice_fraction > 0.0f);
     const size_t lpt_words = LPT_HEADER_WORDS + (size_t)8 * LPT_CLASSES * band_slots(num_tiles);
     auto* tile_offsets = (uint32_t*)ensure(ctx, SLOT_TILE_OFFSETS, ((size_t)num_tiles * 2 + lpt_words) * 4);
-    auto* visible = (bwd_info && ctx->ext_visible) ? ctx->ext_visible : (float*)ensure(ctx, SLOT_VISIBLE, (bwd_info ? npad : 1) * 4);
+    auto* visible = (bwd_info && req.visible) ? req.visible : (float*)ensure(ctx, SLOT_VISIBLE, (bwd_info ? npad : 1) * 4);
     if (!tile_offsets || !visible) return BH_ERR_OOM;
-    const size_t visible_words = bwd_info ? ((ctx->ext_visible && ctx->ext_visible_floats) ? ctx->ext_visible_floats : npad) : 0;
+    const size_t visible_words = bwd_info ? ((req.visible && req.visible_floats) ? req.visible_floats : npad) : 0;
     // depth-sliced lists: [0] near-slice splats  [1] near-slice pairs  [2] tiles the near slice left unsaturated  [3] far-slice pairs |
     // done bits | far tile offsets [T,2] | far pairs per block group.  Cleared by K1 with the tile table, whether or not this frame ends up slicing.
     const bool want_sliced = (flags & BH_FLAG_SLICED_LISTS) != 0;
@@ -883,8 +691,6 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
         slice_tab = (uint32_t*)ensure(ctx, SLOT_SLICE, slice_words * 4);
         if (!slice_tab) return BH_ERR_OOM;
     }
-    // where THIS forward's blend kernel leaves its slicing hint: the feedback words of the counter set the NEXT forward reads back
-    uint32_t* feedback_next = counter_pairs ? counter_pairs + counter_set_words * ((ctx->counter_phase & 1u) ^ 1u) + COUNTER_FB_WORD : nullptr;
     // ---- per-tile depth cuts (BH_FLAG_SLICED_LISTS with the automatic share) ------------------------------------------------
     // A training loop comes back to each of its views every V steps with parameters that moved by a learning rate: how deep every
     // TILE of the view had to go last time is a near-exact forecast of how deep it has to go now.  So every blend launch leaves,
@@ -904,26 +710,12 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     // work they had at the same camera's last frame (K16 193 -> ~150 us at 1 M splats / 1080p), and it refreshes the table.
     const bool order_only = !want_sliced && ctx->knob_k16_order != 0u && n >= 8u * 256u;
     if (n > 0 && (auto_cuts || order_only)) {
-        const uint64_t vkey = view_key(ctx, *cam);
-        // (a forward-only frame without a view id — a viewer's moving camera, an eval render — must not mint a table per frame)
-        const bool casual = order_only && !bwd_info && (vkey >> 63) != 0ull;
-        view = view_state(ctx, vkey, u.tile_bw, u.tile_bh, /*touch=*/allow_cut, casual);
+        view = frame_view(ctx, req, u.tile_bw, u.tile_bh, /*casual=*/order_only && !bwd_info);
         if (!view && auto_cuts) return set_error(ctx, BH_ERR_OOM, "hipMalloc for the per-view tile table failed");
         if (!view) (void)hipGetLastError();   // (ordering is optional: carry on in index order)
-        // (a frame with few pairs has nothing to save: the near count in K1 and an occasional second attempt cost more than listing and
-        //  sorting them all — 100 k splats at 512 x 512 trained 4 % slower with cuts; the view's last frame tells)
-        if (!auto_cuts || !view) {
-            // (complete lists by request)
-        } else if (!allow_cut) {
-            // (the forecast has just failed: this attempt re-seeds the table)
-        } else if (view->seeded && view->exact_frames == 0u && view->last_pairs >= ctx->cut_min_pairs) {
-            // (a view whose last cut frame listed nearly everything — a scene whose tiles no longer saturate early: a converging
-            //  training run ends up there, bench.py train_loop — gains nothing from its cuts and pays for them: the near count in K1,
-            //  and a whole second frame whenever a forecast fails.  Such a view renders complete lists, and tries a cut again later)
-            if (view->complete_frames) view->complete_frames--;
-            else cut_active = true;
-        } else if (view->exact_frames) view->exact_frames--;
+        cut_active = auto_cuts && view && cut_this_frame(ctx, view, req.allow_cut);
     }
+    uint32_t* const vtab = view_table(view);   // [T] depth cuts | [T] per-tile work of the view's last frame | splitter tables
     uint32_t* near_counts = nullptr;
     uint32_t* tile_order = nullptr;
     uint32_t* tile_split = nullptr;
@@ -933,9 +725,6 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     }
 
     uint32_t nv = 0, ni = 0, near_total = 0, nv_true = 0;
-    uint32_t fb_need = 0;                  // previous forward: most exact-list slots any saturated tile needed
-    unsigned long long fb_unsat_pairs = 0; // ... and pairs it listed for tiles that never saturated
-    uint32_t fb_unsat_tiles = 0;           // ... and how many such tiles there were (empty ones included)
     bool fused_scan = false;
     uint32_t* cum_early = nullptr;
     bool k5_queued = false;   // K5 was queued before the counts were read (below): valid unless the pairs overflowed its buffers
@@ -961,7 +750,7 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
                 const uint32_t win_t = u.tile_bw * (u.tile_y1 - u.tile_y0);
                 tile_order = (uint32_t*)ensure(ctx, SLOT_TILE_ORDER, ((size_t)8 * band_slots(win_t) + SPLIT_TAIL_WORDS) * 4);
                 if (!tile_order) return BH_ERR_OOM;
-                prep.order_work = view->zcut + (size_t)num_tiles;
+                prep.order_work = vtab + (size_t)num_tiles;
                 prep.order_out = tile_order;
                 prep.order_tiles = win_t;
                 prep.order_tile_begin = u.tile_bw * u.tile_y0;
@@ -975,14 +764,14 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
                     prep.split_of_max = (float)ctx->knob_k16_split_of_max * 0.01f;
                 }
             }
-            if (bwd_info && ctx->ext_grad_begin && ctx->ext_grad_floats && (ctx->ext_grad_floats & 3u) == 0 &&
-                (reinterpret_cast<uintptr_t>(ctx->ext_grad_begin) & 15u) == 0 && ctx->ext_grad_floats / 4 <= 0xFFFFFFFFull) {
-                prep.span = reinterpret_cast<float4*>(ctx->ext_grad_begin);   // the train step's gradient span
-                prep.span_f4 = (uint32_t)(ctx->ext_grad_floats / 4);
+            if (bwd_info && req.grad_begin && req.grad_floats && (req.grad_floats & 3u) == 0 &&
+                (reinterpret_cast<uintptr_t>(req.grad_begin) & 15u) == 0 && req.grad_floats / 4 <= 0xFFFFFFFFull) {
+                prep.span = reinterpret_cast<float4*>(req.grad_begin);   // the train step's gradient span
+                prep.span_f4 = (uint32_t)(req.grad_floats / 4);
                 ctx->clears.k1_cleared_span();
             }
             BH_TRY(launch_project_forward(ctx, u, n, mip, sh_degree, transforms, sh_coeffs, raw_opacities, depth_keys, isect_counts, max_radius,
-                                          proj_by_gid, counters, prep, cut_active ? view->zcut : nullptr, near_counts));
+                                          proj_by_gid, counters, prep, cut_active ? vtab : nullptr, near_counts));
             ctx->counter_phase ^= 1u;
             ctx->counters_ready = true;
         }
@@ -1011,11 +800,11 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
                 if (!cum_early) return BH_ERR_OOM;
                 // (per-tile cuts: the scan of the NEAR counts = the slot ranges of the near pass's list)
                 if (poll_tag && ++ctx->readback_tag == 0u) ctx->readback_tag = 1u;
+                bool* spl_written = nullptr;
+                uint32_t* spl = view_splitters(view, cut_active, &spl_written);
                 BH_TRY(depth_sort_scan(ctx, depth_keys, counters + COUNTER_MINMAX_WORD, cut_active ? near_counts : isect_counts, n, depths_sorted, gfc, cum_early,
                                        sums_on_device ? counters : nullptr, ctx->host_counters + 16, ctx->readback_ev, poll_tag ? ctx->readback_tag : 0u,
-                                       sums_on_device ? dev_sums : nullptr,
-                                       view ? view->zcut + 2 * (size_t)num_tiles + (cut_active ? DSORT_SPL_STRIDE : 0u) : nullptr,
-                                       view ? &view->spl_written[cut_active ? 1 : 0] : nullptr));
+                                       sums_on_device ? dev_sums : nullptr, spl, spl_written));
             } else {
                 BH_TRY(radix_argsort(ctx, depth_keys, nullptr, n, 32, depths_sorted, gfc));
             }
@@ -1039,7 +828,7 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
                 ProfScope ps(ctx, "MapGaussiansToIntersect");
                 BH_TRY(launch_map_gaussians(ctx, n, u, proj_by_gid, gfc, spec_projected, cum_early, spec_tile_ids, spec_isect_gids, spec_vc,
                                             spec_vc ? (uint32_t)(((size_t)n * 10 + 3) / 4) : 0u, 0xFFFFFFFFu, cut_active ? slice_tab : nullptr,
-                                            cut_active ? view->zcut : nullptr, cut_active ? depths_sorted : nullptr, dev_sums + (cut_active ? 3 : 0), spec_pair_cap));
+                                            cut_active ? vtab : nullptr, cut_active ? depths_sorted : nullptr, dev_sums + (cut_active ? 3 : 0), spec_pair_cap));
                 k5_queued = true;
             }
         }
@@ -1053,14 +842,9 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
         if (sums_on_device) {
             const volatile unsigned long long* hs = hslots;
             for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) hc[c] = hs[c];
-            const volatile uint32_t* hfb = reinterpret_cast<const volatile uint32_t*>(hslots) + 2 * COUNTER_K1_U64;
-            fb_need = hfb[0]; fb_unsat_pairs = hfb[1]; fb_unsat_tiles = hfb[2];   // the previous forward's slicing hint
         } else {
             for (uint32_t k = 0; k < COUNTER_SLOTS; ++k)
                 for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) hc[c] += hslots[COUNTER_K1_U64 * k + c];
-            // the previous forward's slicing hint came along in the same copy
-            const uint32_t* hfb = reinterpret_cast<const uint32_t*>(hslots) + COUNTER_FB_WORD;
-            for (uint32_t k = 0; k < COUNTER_SLOTS; ++k) { if (hfb[3 * k] > fb_need) fb_need = hfb[3 * k]; fb_unsat_pairs += hfb[3 * k + 1]; fb_unsat_tiles += hfb[3 * k + 2]; }
         }
         if (hc[1] > 0xFFFFFFFFull) return set_error(ctx, BH_ERR_UNSUPPORTED, "more than 2^32-1 tile intersections");
         nv_true = (uint32_t)hc[0];
@@ -1072,9 +856,6 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     } else {   // no K1 to clear them on the way
         BH_HIP(ctx, hipMemsetAsync(tile_offsets, 0, ((size_t)num_tiles * 2 + LPT_HEADER_WORDS) * 4, ctx->stream));
         if (visible_words) BH_HIP(ctx, hipMemsetAsync(visible, 0, visible_words * 4, ctx->stream));
-        if (counter_pairs) {   // counter_phase does not flip without K1: clear what this frame's blend kernel will add to
-            BH_HIP(ctx, hipMemsetAsync(feedback_next, 0, COUNTER_SLOTS * 12, ctx->stream));
-        }
     }
 
     const size_t nvpad = nv ? nv : 1, nipad = ni ? ni : 1;
@@ -1101,40 +882,12 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     // (count -> emit against the bit table), sorted behind the near list and blended from the parked pixel state.
     // Everything the far slice launches is a no-op when no tile is left (a device-side gate: no host round trip).  Per pixel the
     // same splats are folded in the same order: out_img, visible[], the blended part of every list and the gradients are those
-    // of the exact path.  The near slice's size comes from the PREVIOUS forward on this ctx (how many slots its slowest
-    // saturating tile needed, + 25 %), or from bh_set_list_slicing; scenes that do not saturate keep the single exact list.
-    uint32_t budget = ni;   // == ni: one slice, the exact lists
-    bool sliced = false;
-    if (want_sliced && ni > 0) {
-        const float share = ctx->slice_fraction;
-        if (share > 0.0f) {   // a fixed share of the pair list (bh_set_list_slicing: tests, A/B): the slot-budget slices
-            if (share < 1.0f) {
-                const double b = (double)share * (double)ni;
-                const uint32_t floor_b = ni < 1024u ? ni : 1024u;
-                budget = b < (double)floor_b ? floor_b : (uint32_t)b;
-                if (budget > ni) budget = ni;
-            }
-            sliced = budget < ni;
-            ctx->last_slice_share = (float)((double)budget / (double)ni);
-        } else if (cut_active && near_total < ni) {   // per-tile depth cuts from this view's last frame
-            sliced = true;
-            budget = near_total;
-            ctx->last_slice_share = (float)((double)near_total / (double)ni);
-            view->last_share = ctx->last_slice_share;
-            if (ctx->auto_exact_share > 0.0f && view->last_share > ctx->auto_exact_share) view->complete_frames = AUTO_EXACT_FRAMES;
-        } else {
-            if (cut_active) {   // (the cut removed nothing at all)
-                view->last_share = 1.0f;
-                if (ctx->auto_exact_share > 0.0f) view->complete_frames = AUTO_EXACT_FRAMES;
-            }
-            // no history for this view yet (or its forecast keeps failing, or it cut nothing): complete lists; the blend
-            // kernel seeds / refreshes the view's table
-            ctx->last_slice_share = 1.0f;
-        }
-    }
-    (void)fb_need; (void)fb_unsat_pairs; (void)fb_unsat_tiles;
+    // of the exact path.  The near slice's size comes from the per-tile cuts of the view's last frame (lists.hip list_budget), or
+    // from bh_set_list_slicing.
+    const uint32_t budget = want_sliced && ni > 0 ? list_budget(ctx, cut_active ? view : nullptr, near_total, ni) : ni;   // == ni: one slice, the exact lists
+    const bool sliced = budget < ni;
     const bool by_cut = cut_active && sliced;           // this frame's lists end at the per-tile cuts
-    const uint32_t* zcut_lists = cut_active ? view->zcut : nullptr;   // (cut_active but not sliced: the cut removed nothing — K5 still filters, and keeps everything)
+    const uint32_t* zcut_lists = cut_active ? vtab : nullptr;   // (cut_active but not sliced: the cut removed nothing — K5 still filters, and keeps everything)
     uint32_t* slice_info = slice_tab;
     uint32_t* done_bits = slice_tab ? slice_tab + SLICE_CTRL_WORDS : nullptr;
     uint32_t* tile_offsets_far = slice_tab ? slice_tab + SLICE_CTRL_WORDS + slice_bit_words : nullptr;
@@ -1142,7 +895,6 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     uint32_t tile_bits = 0;
     while (tile_bits < 32 && (num_tiles >> tile_bits) != 0) tile_bits++;  // render.rs:228
     RasterSlice rs;
-    rs.cum = cum;
     ctx->jobs = BwdJobs{};
     if (bwd_jobs) {
         // checkpoint slots are addressed by list position (context.h BwdJobs): listed pairs / BWD_SEG + tiles of them
@@ -1155,15 +907,13 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
         if (!rs.jobs.ckpt || !rs.jobs.top_list) return BH_ERR_OOM;
         ctx->jobs = rs.jobs;
     }
-    rs.feedback = nullptr;   // (the slot-budget heuristics that read it are gone: the automatic mode cuts per tile)
-    (void)feedback_next;
     if (view) {   // every forward of a view refreshes its table
-        rs.zcut = view->zcut;
+        rs.zcut = vtab;
         rs.depth_keys_sorted = depths_sorted;
         rs.nv = nv;
         rs.cut_active = by_cut;
-        rs.margin_pct = ctx->knob_fixed_margin ? ctx->knob_cut_margin_pct : cut_margin_pct(ctx, view);
-        rs.work = view->zcut + (size_t)num_tiles;
+        rs.margin_pct = cut_margin_pct(ctx, view);
+        rs.work = vtab + (size_t)num_tiles;
         rs.order = tile_order;
         rs.order_mode = ctx->knob_k16_order;
         rs.split = tile_split;
@@ -1268,14 +1018,8 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
         j.out_f32 = out_f32; j.out_u8 = out_u8; j.visible = visible; j.lpt = ctx->lpt; j.class_width = class_width; j.rs = rs;
         j.by_cut = by_cut;
         j.view = by_cut ? view : nullptr;
-        j.view_shared = ctx->view_id == 0u && ctx->knob_no_view_hash;   // (one table shared by every frame without an id: the A/B knob only)
-        if (by_cut) {   // what a second attempt with complete lists needs (finish_far_slice)
-            j.cam = *cam;
-            j.n = n; j.sh_degree = sh_degree; j.flags = flags; j.view_id = ctx->view_id;
-            j.transforms = transforms; j.sh_coeffs = sh_coeffs; j.raw_opacities = raw_opacities;
-            j.ext_visible = ctx->ext_visible; j.ext_max_radius = ctx->ext_max_radius; j.ext_visible_floats = ctx->ext_visible_floats;
-            j.ext_grad_begin = ctx->ext_grad_begin; j.ext_grad_floats = ctx->ext_grad_floats;
-        }
+        j.view_shared = req.view_id == 0u && ctx->knob_no_view_hash;   // (one table shared by every frame without an id: the A/B knob only)
+        if (by_cut) j.req = req;   // what a second attempt with complete lists needs (finish_far_slice)
         if (ctx->knob_readback_copy)
             BH_HIP(ctx, hipMemcpyAsync(ctx->host_counters + HOST_GATE_WORD, slice_info + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
         // (per-tile cuts: the forecast is expected to hold — the host decides every time, bh_train_step hides the wait behind its
@@ -1284,15 +1028,15 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
             BH_TRY(enqueue_far_slice(ctx, j));
             ctx->gate_learn = true;
         } else {
-            // bh_train_step (defer_far) queues its loss kernels next and lets the first of them signal "the blend is done" through a
+            // bh_train_step (req.defer_decision) queues its loss kernels next and lets the first of them signal "the blend is done" through a
             // tag word: no event behind the blend (finish_far_slice records one late if nobody queued the signal)
             if (++ctx->gate_tag == 0u) ctx->gate_tag = 1u;
             j.gate_tag = ctx->gate_tag;
             ctx->gate_signal_queued = false;
-            j.gate_event_recorded = !(ctx->defer_far && !ctx->knob_event_waits && !ctx->knob_readback_copy);
+            j.gate_event_recorded = !(req.defer_decision && !ctx->knob_event_waits && !ctx->knob_readback_copy);
             if (j.gate_event_recorded) BH_HIP(ctx, hipEventRecord(ctx->gate_ev, ctx->stream));
             j.pending = true;
-            if (!ctx->defer_far) {
+            if (!req.defer_decision) {
                 bool again = false;
                 BH_TRY(finish_far_slice(ctx, &again));
                 if (by_cut && again) {   // the forecast failed and the frame was rendered a second time, with complete lists: that is the result
@@ -1330,20 +1074,14 @@ int bh::forward_impl(bh_ctx* ctx, const BhCamera* cam, uint32_t n, uint32_t sh_d
     *out = r;
     ctx->last = r;
     ctx->last_listed_splats = nv;
-    ctx->cam = *cam;
+    ctx->cam = req.cam;
     ctx->uniforms = u;
     ctx->n = n;
     ctx->sh_degree = sh_degree;
     ctx->flags = flags;
     ctx->bg[0] = background[0]; ctx->bg[1] = background[1]; ctx->bg[2] = background[2];
     ctx->have_forward = true;
-    ctx->had_forward = true;
-    ctx->prev_intersections = ni;
-    ctx->last_one_slice = !sliced;
-    if (view) {   // this frame's blend kernel leaves what every tile needed
-        view->seeded = true;
-        view->last_pairs = ni;
-    }
+    if (view) view_rendered(view, ni);   // this frame's blend kernel leaves what every tile needed
     return 0;
 }
 
@@ -1382,7 +1120,6 @@ int bh_forget_views(bh_ctx* ctx) {
     ctx->views.clear();
     ctx->casual_views = 0;
     for (uint64_t& k : ctx->seen_keys) k = 0ull;
-    ctx->gate_view = nullptr;
     ctx->far_job.view = nullptr;
     ctx->margin_scale = 1.0f;
     return 0;
@@ -1410,9 +1147,11 @@ static ForwardState latest_forward(const bh_ctx* ctx) {
 
 // The two backward kernels on the saved state `fs` (bwd/render_bwd.rs:21-171).  What the forward's kernels cleared on their way is
 // recorded in ctx->clears under that forward's generation: a backward of any other forward (a retained, older one) finds nothing
-// there and clears everything itself.
+// there and clears everything itself.  span_floats != 0 (the train step): the four gradient outputs are one span of that many
+// floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
 static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
-                         const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight) {
+                         const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
+                         size_t span_floats, bool want_refine) {
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
@@ -1422,7 +1161,7 @@ static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_out
     {
         ProfScope ps(ctx, "ZeroGradBuffers");
         // what the forward's kernels cleared on their way (K5: v_combined; K1: the train step's gradient span) is done
-        const bool one_span = n > 0 && ctx->ext_grad_begin == v_transforms && ctx->ext_grad_floats;
+        const bool one_span = n > 0 && span_floats;
         // Consumed here, whichever forward this backward belongs to: the accumulator and the span are dirty from now on, and a
         // backward of ANOTHER forward (a retained one) finds nothing to trust (take_* check the generation).
         const bool vc_done = ctx->clears.take_accum(r.generation);
@@ -1431,10 +1170,10 @@ static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_out
         // (ROW_MARKS: the single-GPU train step reads only the rows K18 writes and marks — its forward cleared the marks)
         if (row_marks && !one_span) return set_error(ctx, BH_ERR_STATE, "internal: row-marked gradients without the train step's gradient span");
         const bool span_done = one_span && span != GradClears::NONE;
-        if (one_span && (ctx->ext_grad_floats & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_transforms) & 15u) == 0) {
+        if (one_span && (span_floats & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_transforms) & 15u) == 0) {
             // v_combined and the exchange buffer's gradient span cleared by ONE launch (hipMemsetAsync spends two or
             // three launches on them, each ~5 us of latency beyond the bytes)
-            const size_t na = vc_done ? 0 : (nvpad * 10 + 3) / 4, nb = span_done ? 0 : ctx->ext_grad_floats / 4;
+            const size_t na = vc_done ? 0 : (nvpad * 10 + 3) / 4, nb = span_done ? 0 : span_floats / 4;
             if (na + nb) {
                 hipLaunchKernelGGL(zero_two_kernel, dim3(2048), dim3(256), 0, ctx->stream, reinterpret_cast<float4*>(v_combined), na,
                                    reinterpret_cast<float4*>(v_transforms), nb);
@@ -1445,7 +1184,7 @@ static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_out
             if (n > 0) {
                 // dense outputs are zero-filled; the kernel scatters compact -> global (render_bwd.rs:123-138)
                 if (one_span) {
-                    BH_HIP(ctx, hipMemsetAsync(v_transforms, 0, ctx->ext_grad_floats * 4, ctx->stream));
+                    BH_HIP(ctx, hipMemsetAsync(v_transforms, 0, span_floats * 4, ctx->stream));
                 } else {
                     BH_HIP(ctx, hipMemsetAsync(v_transforms, 0, (size_t)n * 10 * 4, ctx->stream));
                     BH_HIP(ctx, hipMemsetAsync(v_sh_coeffs, 0, (size_t)n * C * 3 * 4, ctx->stream));
@@ -1460,7 +1199,7 @@ static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_out
         if (r.num_intersections > 0)
             BH_TRY(launch_rasterize_backward(ctx, fs.uniforms, fs.bg, fs.flags & BH_FLAG_SMOOTH_CUTOFF,
                                              r.compact_gid_from_isect, r.tile_offsets, r.projected, r.out_img, v_output, v_combined, fs.lpt,
-                                             r.tile_offsets_far, /*want_refine=*/!ctx->bwd_skip_refine, &fs.jobs));
+                                             r.tile_offsets_far, want_refine, &fs.jobs));
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
@@ -1491,7 +1230,7 @@ int bh_render_backward(bh_ctx* ctx, const float* v_output, const float* transfor
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
     return backward_impl(ctx, latest_forward(ctx), v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
-                         v_refine_weight);
+                         v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
 }
 
 // SplatBwdOps::{rasterize_bwd, project_bwd} take the forward's saved tensors explicitly (bwd/burn_glue.rs:62-92, 336-371): so does this.
@@ -1507,10 +1246,10 @@ int bh_render_backward_saved(bh_ctx* ctx, const BhRenderOut* saved, const float*
     for (const Retained& rt : ctx->retained)
         if (rt.fs.out.generation == saved->generation && rt.fs.out.out_img == saved->out_img)
             return backward_impl(ctx, rt.fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
-                                 v_refine_weight);
+                                 v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
     if (ctx->have_forward && saved->generation == ctx->last.generation && saved->out_img == ctx->last.out_img)
         return backward_impl(ctx, latest_forward(ctx), v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs,
-                             v_raw_opacities, v_refine_weight);
+                             v_raw_opacities, v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
     char msg[256];
     snprintf(msg, sizeof msg, "render_backward_saved: forward #%llu is stale (the context's buffers now hold forward #%llu); call bh_render_retain "
                               "on a forward that must outlive the next one", (unsigned long long)saved->generation, (unsigned long long)ctx->generation);
@@ -1746,21 +1485,10 @@ extern "C" int bh_train_step(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState
                              bh_grad_hook hook, void* hook_user, float grad_scale, BhTrainStats* stats) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     const int rc = train_step_impl(ctx, cfg, st, batch, hook, hook_user, grad_scale, stats);
-    if (rc != 0) {
-        // A step that fails behind its forward must not leave a deferred far-slice decision behind: the job holds the CALLER's
-        // parameter pointers (a per-tile-cut job replays the whole forward from them) and the caller is free to release or
-        // re-allocate them after a failed step (a refine changes n and every buffer).  Drop it; the frame it belonged to is
-        // incomplete, so nothing may be replayed from it either, and the view's next frame is rendered with complete lists.
-        if (ctx->far_job.pending) {
-            ctx->far_job.pending = false;
-            if (ctx->far_job.by_cut && ctx->far_job.view && ctx->far_job.view->exact_frames == 0u) ctx->far_job.view->exact_frames = 1u;
-        }
-        ctx->far_job.view = nullptr;
+    if (rc != 0) {   // (the frame is incomplete: nothing may be replayed or backpropagated from it)
+        drop_far_job(ctx);
         ctx->have_forward = false;
-        ctx->ext_visible = nullptr; ctx->ext_max_radius = nullptr; ctx->ext_visible_floats = 0;
-        ctx->ext_grad_begin = nullptr; ctx->ext_grad_floats = 0;
         ctx->clears.begin_forward();
-        ctx->defer_far = false;
     }
     return rc;
 }
@@ -1806,12 +1534,18 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
 
     // ---- forward (train.rs:211-215); `visible` lands directly in the exchange buffer
     BhRenderOut ro;
-    const uint32_t flags = BH_FLAG_BWD_INFO | (cfg->render_mip ? BH_FLAG_MIP : 0) | (cfg->exact_lists ? 0 : BH_FLAG_SLICED_LISTS);
-    ctx->ext_visible = s_visible;
-    ctx->ext_visible_floats = o_tr;  // the forward clears the section incl. its padding
-    ctx->ext_max_radius = s_radius;
-    ctx->ext_grad_begin = exch + o_tr;       // ... and the whole gradient span (padding included): K1 does both on its way
-    ctx->ext_grad_floats = exch_count - o_tr;
+    ForwardRequest fwd;
+    fwd.cam = batch->camera;
+    fwd.n = n; fwd.sh_degree = st->sh_degree;
+    fwd.flags = BH_FLAG_BWD_INFO | (cfg->render_mip ? BH_FLAG_MIP : 0) | (cfg->exact_lists ? 0 : BH_FLAG_SLICED_LISTS);
+    fwd.transforms = r_transforms; fwd.sh_coeffs = st->sh_coeffs; fwd.raw_opacities = r_raw_opac;
+    fwd.bg[0] = batch->background[0]; fwd.bg[1] = batch->background[1]; fwd.bg[2] = batch->background[2];
+    fwd.view_id = batch->view_id;
+    fwd.visible = s_visible;
+    fwd.visible_floats = o_tr;  // the forward clears the section incl. its padding
+    fwd.max_radius = s_radius;
+    fwd.grad_begin = exch + o_tr;       // ... and the whole gradient span (padding included): K1 does both on its way
+    fwd.grad_floats = exch_count - o_tr;
     // ... unless nobody but this step's own update reads the gradients (one GPU, no hook): then only the refine-weight vector
     // (N floats, the span's last section) is cleared.  K18 writes the rows of the splats that received a gradient and marks them in
     // that vector's sign bit, the update kernel takes every unmarked row as zero — at SH degree 3 the zero-fill was most of K1's
@@ -1833,24 +1567,14 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the LPIPS term needs the whole frame on this rank (no tile-row partition)");
     const bool masked_grads = !exchanging && !tile_mode && !ctx->knob_zero_grads && n > 0;
     if (masked_grads) {
-        ctx->ext_grad_begin = exch + o_ref;
-        ctx->ext_grad_floats = exch_count - o_ref;
+        fwd.grad_begin = exch + o_ref;
+        fwd.grad_floats = exch_count - o_ref;
     }
     // depth-sliced lists: whether the far slice has to run is known once the near slice's blend has; a single-GPU step does not
     // wait for that — the loss kernels are queued behind the near slice first (below) and the host reads the answer while they run
     // (a tile-partitioned frame hands the image to its hook right after the forward: there the forward waits itself)
-    ctx->defer_far = !tile_mode;
-    const uint32_t caller_view = ctx->view_id;
-    ctx->view_id = batch->view_id;
-    const int frc = bh_render_forward(ctx, &batch->camera, n, st->sh_degree, r_transforms, st->sh_coeffs, r_raw_opac,
-                                      batch->background, flags, &ro);
-    ctx->view_id = caller_view;
-    ctx->defer_far = false;
-    ctx->ext_visible = nullptr;
-    ctx->ext_max_radius = nullptr;
-    ctx->ext_grad_begin = nullptr;
-    ctx->ext_grad_floats = 0;
-    BH_TRY(frc);
+    fwd.defer_decision = !tile_mode;
+    BH_TRY(render_forward(ctx, fwd, &ro));
 
     // ---- tile-partitioned frame: fetch the other ranks' strips (not in the reference: SURVEY.md §8e)
     if (tile_mode) {
@@ -1903,10 +1627,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     if (ctx->knob_fail_loss_at && ++ctx->train_steps_seen == ctx->knob_fail_loss_at)   // (the forward is queued, a deferred far slice may be pending)
         return set_error(ctx, BH_ERR_OOM, "train_step: injected failure between the forward and the loss (BH_TEST_FAIL_LOSS_AT)");
 #endif
-    // A view whose forecast keeps missing (two of its last eight cut frames) decides FIRST — the host waits for the near pass's blend,
-    // ~15 us of bubble — instead of queueing loss kernels that a second attempt would make worthless (~120 us).  One isolated miss
-    // does not switch: eight bubbles cost more than the one wasted loss they would insure against at a 3 % miss rate.
-    if (ctx->far_job.pending && ctx->far_job.view && __builtin_popcount(ctx->far_job.view->penalty) >= 2) {
+    if (far_job_decides_first(ctx)) {   // (a view whose forecast keeps missing: lists.hip)
         BH_TRY(finish_far_slice(ctx, nullptr));
         ro = ctx->last;   // (a second attempt replaces the frame's outputs)
     }
@@ -1967,8 +1688,6 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     float* g_tr = exch + o_tr;
     float* g_sh = exch + o_sh;
     float* g_op = exch + o_op;
-    ctx->ext_grad_begin = g_tr;              // one zero-fill of the whole gradient span (padding included)
-    ctx->ext_grad_floats = exch_count - o_tr;
     // masked gradients rely on last step's row marks (sign bits of the refine-weight vector) being gone: K1 of the frame's (last)
     // forward clears the vector on its way when the span is float4-addressable (always, with the pad4 layout and hipMalloc's
     // alignment) - not an implicit invariant: if it could not, clear it here.  Decided HERE, behind every second attempt a failed
@@ -1978,13 +1697,11 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         ctx->clears.mark_rows();   // this step's backward runs K18 in marking mode and fills nothing
     }
     // the refine weight's one consumer stops reading it at growth_stop_iter (train.rs:589-614): from then on the blend backward
-    // runs without it (refine_weight_norm stays as refine() zeroed it)
-    ctx->bwd_skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
-    const int brc = bh_render_backward(ctx, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine);
-    ctx->bwd_skip_refine = false;
-    ctx->ext_grad_begin = nullptr;
-    ctx->ext_grad_floats = 0;
-    BH_TRY(brc);
+    // runs without it (refine_weight_norm stays as refine() zeroed it).  g_tr .. the end of the exchange buffer is one span
+    // (padding included): one zero-fill, if the forward's K1 did not clear it.
+    const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
+    BH_TRY(backward_impl(ctx, latest_forward(ctx), v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
+                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

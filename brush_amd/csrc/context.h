@@ -94,25 +94,21 @@ constexpr uint32_t COUNTER_SLOTS = 128;
 // one counter set on the device:
 //   [COUNTER_SLOTS][4] u64  visible, intersections, near intersections, near splats (K1's block totals; the last two only with
 //                           per-tile depth cuts: the pairs the near pass will list and the splats that own them, see ViewState)
-//   [COUNTER_SLOTS][3] u32  slicing feedback, written by the blend kernel of the forward BEFORE the one that accumulates into this
-//                           set (rasterize.hip SliceArgs::feedback): max exact-list slots a saturated tile needed | pairs listed
-//                           for tiles that never saturated | number of such tiles (empty ones included)
 //   [COUNTER_SLOTS][2] u32  max depth key, max ~key over the visible splats: the key range the depth sort splits on.
-// The first two parts are read back together (one copy), the third stays on the device.
+// The first part is read back, the second stays on the device.
 constexpr uint32_t COUNTER_K1_U64 = 4;                        // u64 words per slot of K1's block totals
-constexpr size_t COUNTER_SET_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64 + COUNTER_SLOTS * 12 + COUNTER_SLOTS * 8;
+constexpr size_t COUNTER_SET_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64 + COUNTER_SLOTS * 8;
 constexpr uint32_t COUNTER_SET_U64 = (uint32_t)(COUNTER_SET_BYTES / 8);
-constexpr uint32_t COUNTER_FB_WORD = COUNTER_SLOTS * 2 * COUNTER_K1_U64;   // u32 index of the feedback part inside a set: [COUNTER_SLOTS][3]
-constexpr uint32_t COUNTER_MINMAX_WORD = COUNTER_FB_WORD + COUNTER_SLOTS * 3;   // ... of the key-range part
+constexpr uint32_t COUNTER_MINMAX_WORD = COUNTER_SLOTS * 2 * COUNTER_K1_U64;   // u32 index of the key-range part inside a set
 // control words of SLOT_SLICE: [0] near-slice splats  [1] near pairs  [2] tiles the near pass left live  [3] far pairs
 // [4] live column bands  [5] live row bands (32 bands per axis; the far pass skips splats whose box misses them)  [6..7] spare
 constexpr uint32_t SLICE_CTRL_WORDS = 8;
 constexpr uint32_t FAR_GROUP_BLOCKS = 64;   // far slice: count-kernel blocks per group total (<= the projection workgroup size)
-constexpr size_t COUNTER_READ_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64 + COUNTER_SLOTS * 12;
-// ... or, when the depth sort's first kernel adds the slots up on the device: [COUNTER_K1_U64] u64 totals | [3] u32 feedback
-constexpr uint32_t HOST_SUM_WORDS = 2 * COUNTER_K1_U64 + 3 + 1;   // (+ the tag word the host polls)
-// pinned host block: [16] u32 scalars (refine control block / bounds picks / exchange rows) | the counter slots + feedback | the
-// loss word.  The loss has a word of its own BEHIND everything the refine / bounds / exchange readbacks overwrite.
+constexpr size_t COUNTER_READ_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64;
+// ... or, when the depth sort's first kernel adds the slots up on the device: [COUNTER_K1_U64] u64 totals
+constexpr uint32_t HOST_SUM_WORDS = 2 * COUNTER_K1_U64 + 1;   // (+ the tag word the host polls)
+// pinned host block: [16] u32 scalars (refine control block / bounds picks / exchange rows) | the counter slots | the loss word.
+// The loss has a word of its own BEHIND everything the refine / bounds / exchange readbacks overwrite.
 constexpr size_t HOST_LOSS_WORD = 16 + COUNTER_READ_BYTES / 4;
 constexpr size_t HOST_GATE_WORD = HOST_LOSS_WORD + 16;   // depth-sliced forward: tiles the near slice left unsaturated
 constexpr size_t HOST_GATE_TAG_WORD = HOST_GATE_WORD + 1;   // ... and the tag the kernel queued BEHIND the near blend stores when it starts (= the blend has finished)
@@ -134,7 +130,7 @@ struct Profiler {
     hipEvent_t ext_a = nullptr, ext_b = nullptr;
 };
 
-// Per-view state of the per-tile depth cut (BH_FLAG_SLICED_LISTS, automatic mode; api.hip has the whole story): for every tile the
+// Per-view state of the per-tile depth cut (BH_FLAG_SLICED_LISTS, automatic mode; api.hip has the whole story, lists.hip the policy): for every tile the
 // depth key behind which the tile needed no splat the last time THIS view was rendered (+ a margin), 0xFFFFFFFF = list everything.
 // Written in place by the blend kernel of every forward of the view, read by K1 / K5 / the far pass of its next one.
 // Bit 0 of an entry is not part of the cut: K1 sets it when it meets a pair BEHIND the cut ("this tile's near list is incomplete
@@ -148,12 +144,11 @@ struct ViewState {
     uint32_t tile_bw = 0, tile_bh = 0;
     bool seeded = false;            // a forward of this view has written the table
     uint32_t exact_frames = 0;      // frames to render with complete lists before the cut is trusted again (the forecast kept failing)
-    uint32_t penalty = 0;           // one bit per recent cut frame: its far pass had to run (api.hip view_outcome)
+    uint32_t penalty = 0;           // one bit per recent cut frame: its far pass had to run (lists.hip view_outcome)
     uint64_t last_used = 0;         // LRU stamp (the ctx's forward counter at the view's last frame)
     uint32_t gap = 0;               // forwards between the view's last two frames (a new view: the number of views the ctx knows) —
                                     // how stale the table will be when it is next read: the margin written into it grows with it
     uint32_t last_pairs = 0;        // num_intersections of the view's last frame
-    float last_share = 0.0f;        // share of its pairs the view's last CUT frame listed (0: none yet)
     uint32_t complete_frames = 0;   // frames to render with complete lists because cutting saved (almost) nothing last time; then one probe frame
     bool spl_written[2] = {false, false};   // the view's depth-sort splitter tables ([0] complete lists, [1] cut lists) have been written by a frame
     bool casual = false;            // created by a forward-only frame keyed by its camera (a viewer / eval render): these compete for CASUAL_VIEW_STATES tables only
@@ -213,15 +208,13 @@ constexpr size_t CASUAL_VIEW_STATES = 32;
 constexpr size_t SEEN_KEYS = 64;   // ring of camera hashes met once
 constexpr size_t VIEW_TABLE_BYTES = (size_t)256 << 20;   // ... and at most this much device memory in tables (8 B per tile and view: 64 KB at 1080p, 253 KB at 4K)
 
-// scratch of a depth-sliced forward (rasterize.hip SliceArgs); feedback alone may be set for the exact path (phase 0)
+// scratch of a depth-sliced forward (rasterize.hip SliceArgs)
 struct RasterSlice {
     uint32_t* done_bits = nullptr;
     uint32_t* unsat_count = nullptr;
     uint32_t* gate_host = nullptr;   // pinned host word: the near pass stores 1 there when it parks a tile (the host's copy of unsat_count != 0)
     float* state = nullptr;
     const uint32_t* offsets_near = nullptr;
-    const uint32_t* cum = nullptr;
-    uint32_t* feedback = nullptr;
     // per-tile depth cut: the view's table (read: is the tile's near list complete?  written: what the tile needed this time),
     // the depth keys in compact order and their number (to turn "last useful splat + margin" into a key); cut_active: the lists of
     // this frame were built against the table (else it is only written)
@@ -238,7 +231,26 @@ struct RasterSlice {
     BwdJobs jobs{};                   // BWD_INFO: file the backward's work as jobs with checkpoints (ckpt != NULL)
 };
 
-// The far slice of a depth-sliced forward, ready to be queued: everything launch_* needs (api.hip enqueue_far_slice).
+// One forward call: bh_render_forward's arguments, or the train step's, with where the train step wants its outputs and clears.
+// forward_impl reads the call's settings from here only (the ctx holds options and what outlives the call).
+struct ForwardRequest {
+    BhCamera cam{};
+    uint32_t n = 0, sh_degree = 0, flags = 0;
+    const float* transforms = nullptr;
+    const float* sh_coeffs = nullptr;
+    const float* raw_opacities = nullptr;
+    float bg[3] = {0, 0, 0};
+    uint32_t view_id = 0;              // keys the per-view table (lists.hip view_key; 0: the camera does)
+    float* visible = nullptr;          // train step: visible / max_radius land here (its stats buffer), else in the arena
+    float* max_radius = nullptr;
+    size_t visible_floats = 0;         // floats to clear at `visible` (its section of the exchange buffer incl. padding; 0: n)
+    float* grad_begin = nullptr;       // train step: a gradient span K1 zero-fills on its way (GradClears)
+    size_t grad_floats = 0;
+    bool defer_decision = false;       // return with far_job.pending instead of waiting for the near pass's gate word (bh_train_step)
+    bool allow_cut = true;             // false: complete lists whatever the view's table says (the second attempt, finish_far_slice)
+};
+
+// The far slice of a depth-sliced forward, ready to be queued: everything launch_* needs (lists.hip enqueue_far_slice).
 struct FarJob {
     bool pending = false;   // the near slice is queued and its gate word is on its way to the host; the far slice is undecided
     ViewUniforms u{};
@@ -265,27 +277,18 @@ struct FarJob {
     uint32_t* lpt = nullptr;
     float class_width = 8.0f;
     RasterSlice rs{};
-    // per-tile cut lists: only the splats with a pair in front of some cut were sorted and listed, so there is no far pass — if a
-    // tile is still live behind a cut list the forecast has failed and the whole forward is run again with complete lists
-    // (api.hip finish_far_slice).  Its arguments, and the train step's redirections that were in force:
     // how the host learns that the near blend has finished: an event behind it (recorded when the job is created, or late, by
     // finish_far_slice), or — bh_train_step — the tag word its loss kernel stores when it starts (no event: a barrier packet
     // costs ~6 us of bubble in front of the next kernel)
     bool gate_event_recorded = false;
     uint32_t gate_tag = 0;
+    // per-tile cut lists: only the splats with a pair in front of some cut were sorted and listed, so there is no far pass — if a
+    // tile is still live behind a cut list the forecast has failed and the whole forward is run again with complete lists
+    // (lists.hip finish_far_slice): the request to replay
     bool by_cut = false;
     ViewState* view = nullptr;      // whose prediction failed
     bool view_shared = false;       // ... and whether that is the table of view id 0 (shared by all frames without an id)
-    BhCamera cam{};
-    uint32_t n = 0, sh_degree = 0, flags = 0, view_id = 0;
-    const float* transforms = nullptr;
-    const float* sh_coeffs = nullptr;
-    const float* raw_opacities = nullptr;
-    float* ext_visible = nullptr;
-    float* ext_max_radius = nullptr;
-    size_t ext_visible_floats = 0;
-    float* ext_grad_begin = nullptr;
-    size_t ext_grad_floats = 0;
+    ForwardRequest req{};
 };
 
 // Clears done "on the way" by a forward's kernels, and how the train step wants its gradient span treated.
@@ -356,11 +359,6 @@ struct bh_ctx {
     uint64_t generation = 0;          // stamped into every BhRenderOut a forward of this ctx returns (bh_render_backward_saved checks it)
     std::vector<bh::Retained> retained;   // forwards detached by bh_render_retain, until bh_render_release
     std::vector<bh::Buffer> pool;     // blocks given back by bh_render_release: ensure() takes from here before it asks hipMalloc
-    float* ext_visible = nullptr;     // train step: the forward writes visible / max_radius here (stats buffer)
-    float* ext_max_radius = nullptr;
-    size_t ext_visible_floats = 0;    // floats to clear at ext_visible (its section of the exchange buffer incl. padding)
-    float* ext_grad_begin = nullptr;  // train step: v_transforms .. end of the exchange buffer is one span to zero-fill
-    size_t ext_grad_floats = 0;
     // What the forward's kernels cleared on their way, so that the backward can skip its fills (K1: the train step's gradient span;
     // K5: the backward's accumulator v_combined).  ONE record with explicit transitions (bh::GradClears below) instead of loose
     // flags: every fact is tied to the forward (generation) whose kernels established it and is consumed exactly once.
@@ -378,21 +376,15 @@ struct bh_ctx {
     hipEvent_t comm_ev = nullptr;
     int comm_rank = 0, comm_world = 1;
     uint32_t* lpt = nullptr;          // longest-first tile order of the last BWD_INFO forward (rasterize.hip), or NULL
-    // depth-sliced lists (BH_FLAG_SLICED_LISTS): share of the pair list the near slice takes.  <= 0: chosen per frame from the
-    // previous frame's feedback (bh_set_list_slicing)
+    // depth-sliced lists (BH_FLAG_SLICED_LISTS): share of the pair list the near slice takes.  <= 0: automatic, per-tile depth
+    // cuts from the view's last frame (bh_set_list_slicing)
     float slice_fraction = 0.0f;
-    bool had_forward = false;         // a forward ran on this ctx before (its feedback words are meaningful)
-    bool last_one_slice = true;       // ... and built one list per tile (exact path, or a sliced request that chose one slice)
-    uint32_t prev_intersections = 0;  // ... and listed this many pairs
-    float need_hint = 0.0f;           // fading maximum of the share of the pair list recent frames' slowest saturating tile needed
     float last_slice_share = 1.0f;    // what the last sliced forward used (1 = one slice = the exact lists); diagnostics
     // The far slice costs ~12 launches even when every one of them is a no-op (~4.5 us each on this chip), so whether to queue
     // it is decided on the HOST where possible: far_direct = the previous sliced frame needed it -> queue it right away
     // (device-gated, no host wait; the gate word is copied out to keep learning); otherwise the host reads the gate word —
     // bh_render_forward waits for it, bh_train_step queues the loss kernels first and waits behind them (far_job.pending).
     bool far_direct = false;
-    bool bwd_skip_refine = false;     // set by bh_train_step around its backward: step >= BhTrainConfig.growth_stop_iter, nobody reads the refine weight
-    bool defer_far = false;           // set by bh_train_step around its forward: return with far_job.pending instead of waiting
     uint32_t readback_tag = 0;        // tag of the last count readback the host polled for (depth_sort.hip counter_sums_to_host)
     uint32_t gate_tag = 0;            // tag of the last deferred far-slice decision
     bool gate_signal_queued = false;  // a kernel that stores far_job.gate_tag when it starts is queued behind the near blend
@@ -400,16 +392,15 @@ struct bh_ctx {
     uint32_t far_launches = 0;        // diagnostics: sliced forwards that queued a far slice / had to be run again with complete lists
     uint32_t last_listed_splats = 0;  // compact entries of the last forward (== num_visible unless per-tile cuts listed a subset)
     // per-tile depth cuts (automatic slicing): one table per view id (bh_set_view_id / BhTrainBatch.view_id; 0 = the ctx's own slot)
-    // keyed by the caller's view id, or — id 0 — by a hash of the camera (api.hip view_key): an unmodified SplatTrainer::step
+    // keyed by the caller's view id, or — id 0 — by a hash of the camera (lists.hip view_key): an unmodified SplatTrainer::step
     // (train.rs:176: a SceneBatch carries no view index, brush-dataset/src/scene.rs:138-147) gets the same tables
     std::unordered_map<uint64_t, bh::ViewState> views;
-    uint64_t seen_keys[bh::SEEN_KEYS] = {};   // camera hashes of forward-only frames that found no table (api.hip casual_view)
+    uint64_t seen_keys[bh::SEEN_KEYS] = {};   // camera hashes of forward-only frames that found no table (lists.hip view_state)
     uint32_t seen_pos = 0;
     uint32_t casual_views = 0;                // tables whose ViewState::casual is set
-    uint32_t view_id = 0;
+    uint32_t view_id = 0;             // bh_set_view_id: the view id of the caller's bh_render_forward calls
     uint64_t view_clock = 0;
-    bh::ViewState* gate_view = nullptr;   // the view whose far pass was queued unasked (gate_learn): penalised if it was needed
-    // The margin behind a tile's last useful splat adapts (api.hip cut_margin_pct): x (gap / 2)^(1/3) for a view that comes back
+    // The margin behind a tile's last useful splat adapts (lists.hip cut_margin_pct): x (gap / 2)^(1/3) for a view that comes back
     // after `gap` frames, x margin_scale — multiplied by 1.5 when a forecast fails, by 0.998 when one holds (about one second
     // attempt in 200 cut frames at equilibrium), within [0.5, 16].  A scene that still moves fast (early training, many views between
     // two visits) gets deep margins, a settled one tight ones.
@@ -465,8 +456,33 @@ struct bh_ctx {
 namespace bh {
 
 int set_error(bh_ctx* ctx, int code, const std::string& msg);
+// api.hip: the forward pipeline of one request (arguments already checked), and the host's wait for a tag word a kernel stores
+int forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
+int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what);
+
+// lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
+// The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view
+// id whose camera is new, or a failed allocation.  A second attempt (!req.allow_cut) leaves the view's gap and LRU stamp alone.
+ViewState* frame_view(bh_ctx* ctx, const ForwardRequest& req, uint32_t tile_bw, uint32_t tile_bh, bool casual);
+// whether this frame of `vs` lists against its cuts (else complete lists); counts down the view's complete-list frames
+bool cut_this_frame(const bh_ctx* ctx, ViewState* vs, bool allow_cut);
+// the view's device table: [T] depth cuts | [T] per-tile work of its last frame | [VIEW_SPL_WORDS] depth-sort splitter tables
+uint32_t* view_table(const ViewState* vs);
+// ... the splitter table a frame uses ([0] complete lists, [1] cut lists), and whether a frame has written it
+uint32_t* view_splitters(ViewState* vs, bool cut, bool** written);
+// margin (in % of a tile's depth rank) the blend kernel of this frame writes behind every tile's last useful splat
+uint32_t cut_margin_pct(const bh_ctx* ctx, const ViewState* vs);
+// the near slice's pair budget of a BH_FLAG_SLICED_LISTS frame with ni > 0 pairs (== ni: one slice, the complete lists).
+// cut_view: the view whose cuts this frame's lists end at (near_total pairs in front of them), or NULL
+uint32_t list_budget(bh_ctx* ctx, ViewState* cut_view, uint32_t near_total, uint32_t ni);
+// a frame of `vs` with ni pairs has been queued: its blend kernel leaves what every tile needed in the table
+void view_rendered(ViewState* vs, uint32_t ni);
 int enqueue_far_slice(bh_ctx* ctx, const FarJob& j);
 int finish_far_slice(bh_ctx* ctx, bool* launched);
+// bh_train_step: the pending job's view has missed at least twice lately — decide before the loss kernels are queued
+bool far_job_decides_first(const bh_ctx* ctx);
+// bh_train_step failed: forget the pending job (its view's next frame renders complete lists)
+void drop_far_job(bh_ctx* ctx);
 // after ANY host wait on the ctx stream: hand the last train step's loss (pinned staging word) to its BhTrainStats
 inline void deliver_pending_loss(bh_ctx* ctx) {
     if (ctx->pending_loss_dst) {

@@ -133,31 +133,23 @@ BH_DEV unsigned long long ds_match(uint32_t d) {
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// The mid-pipeline readback (render.rs:146-168) without a copy launch: K1's counter set (context.h: [COUNTER_SLOTS] block totals +
-// the previous frame's slicing feedback) is added up by one wave of the first kernel queued behind K1 and stored straight into
-// the pinned host block — [4] u64 totals | [3] u32 feedback (max need, unsaturated pairs, unsaturated tiles).  A blit kernel
-// between K1 and the sort cost 4.5 us of device time plus its two launch gaps in every frame.
+// The mid-pipeline readback (render.rs:146-168) without a copy launch: K1's counter set (context.h: [COUNTER_SLOTS] block totals)
+// is added up by one wave of the first kernel queued behind K1 and stored straight into the pinned host block — [4] u64 totals |
+// the tag word (HOST_SUM_WORDS).  A blit kernel between K1 and the sort cost 4.5 us of device time plus its two launch gaps in
+// every frame.
 BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __restrict__ host_sums, int lane, uint32_t tag, uint32_t* __restrict__ dev_sums) {
     const unsigned long long* c64 = reinterpret_cast<const unsigned long long*>(set);
     unsigned long long tot[COUNTER_K1_U64];
 #pragma unroll
     for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) tot[c] = 0ull;
-    uint32_t need = 0, pairs = 0, tiles = 0;
     for (uint32_t k = (uint32_t)lane; k < COUNTER_SLOTS; k += 64u) {
 #pragma unroll
         for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) tot[c] += c64[COUNTER_K1_U64 * k + c];
-        const uint32_t* fb = set + COUNTER_FB_WORD + 3u * k;
-        need = max(need, fb[0]);
-        pairs += fb[1];
-        tiles += fb[2];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
         for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) tot[c] += __shfl_down(tot[c], off);
-        need = max(need, (uint32_t)__shfl_down((int)need, off));
-        pairs += __shfl_down(pairs, off);
-        tiles += __shfl_down(tiles, off);
     }
     if (lane == 0) {
         // (a copy for the kernels queued behind the sort before the host has read anything: the list builder takes the number of
@@ -169,15 +161,11 @@ BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __r
         volatile unsigned long long* h64 = reinterpret_cast<volatile unsigned long long*>(host_sums);
 #pragma unroll
         for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) h64[c] = tot[c];
-        volatile uint32_t* h32 = host_sums + 2u * COUNTER_K1_U64;
-        h32[0] = need;
-        h32[1] = pairs;
-        h32[2] = tiles;
         // tag != 0: the host does not wait for an event behind this kernel (a barrier packet: ~6 us of bubble in front of the next
         // kernel) but polls this word — stored last, behind a system-scope fence, so the sums are there when it is
         if (tag) {
             __threadfence_system();
-            h32[3] = tag;
+            reinterpret_cast<volatile uint32_t*>(host_sums)[HOST_SUM_WORDS - 1u] = tag;
         }
     }
 }

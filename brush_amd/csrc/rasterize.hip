@@ -208,15 +208,13 @@ BH_DEV uint32_t stage_batch(const uint32_t* __restrict__ isect_gids, const float
 // bench workload that is every tile after a fifth of the pairs.  A tile with live pixels left parks its raw (rgb, T) state and
 // is counted in *unsat_count; the FAR slice is then listed for those tiles only and PHASE 2 resumes them.  The per-pixel
 // arithmetic is the same sequential fold over the same splats in the same order, so the image is bit-identical to PHASE 0 (the
-// exact path: one list per tile).  Every phase also leaves a two-word hint for the next frame's slicing in `feedback`.
+// exact path: one list per tile).
 struct SliceArgs {
     uint32_t* done_bits = nullptr;          // [ceil(T/32)] bit per tile: its pixels are final
     uint32_t* unsat_count = nullptr;        // tiles PHASE 1 left unsaturated (the gate of everything the far slice launches)
     uint32_t* gate_host = nullptr;          // pinned host word, zeroed by the host before the launch: a parked tile stores 1 (no copy launch for the host's decision)
     float* state = nullptr;                 // [H,W,4] raw rgb + signed T of those tiles
     const uint32_t* offsets_near = nullptr; // PHASE 2: the near slice's [T,2] table (shrunk ends: the tile's backward work so far)
-    const uint32_t* cum = nullptr;          // cum_tiles_hit [Nv]: the exact list's slot ranges (feedback)
-    uint32_t* feedback = nullptr;           // [COUNTER_SLOTS][3]: max slots a saturated tile needed | listed pairs of unsaturated tiles | their number
     // per-tile depth cuts (api.hip): zcut[tile] = the depth key behind which the tile's NEAR list was cut (ZCUT_ALL: complete).
     // Every phase that finishes a tile writes what it needed THIS time into the table (the view's next frame lists against it);
     // cut_active: this frame's lists were built against the table, so an unsaturated tile with a complete list is final in PHASE 1.
@@ -629,11 +627,9 @@ BH_DEV void blend_tile(const RasterUniforms& u, const uint32_t* __restrict__ ise
     if (lane == 0) {
         if (PHASE == 1) atomicOr(&sl.done_bits[tile >> 5], 1u << (tile & 31u));
         uint32_t work = (BWD_INFO ? last_useful : reached) - range_lo;
-        uint32_t listed = range_hi - range_lo;
-        if (PHASE == 2) {   // the tile's backward work / list = what both slices contributed
+        if (PHASE == 2) {   // the tile's backward work = what both slices contributed
             const uint32_t n_lo = sl.offsets_near[tile * 2], n_hi = sl.offsets_near[tile * 2 + 1];
             work += n_hi - n_lo;
-            listed += n_hi - n_lo;
         }
         if (sl.work) sl.work[tile] = work;   // the forecast of this tile's work at the view's next frame
         // rasterize.rs:183-189: shrink the tile's end to one past the last useful splat
@@ -667,13 +663,13 @@ BH_DEV void blend_tile(const RasterUniforms& u, const uint32_t* __restrict__ ise
             if (saturated && sl.nv) {
                 const uint32_t stop = BWD_INFO ? last_useful : reached;
                 // (the table is only kept in automatic mode, whose frames never run PHASE 2: a frame whose forecast failed is rendered
-                //  again with complete lists, api.hip finish_far_slice)
+                //  again with complete lists, lists.hip finish_far_slice)
                 uint32_t g = 0xFFFFFFFFu;
                 if (stop > range_lo) g = isect_gids[stop - 1u];
                 if (g != 0xFFFFFFFFu) {
                     // (how deep a tile has to go is set by its SLOWEST pixel — an extreme value that jumps when a few small splats
                     //  move, and the default step moves them on purpose: the margin is generous, the lists still a fraction.  The
-                    //  host scales it with how long the view will be away and with how forecasts have fared lately: api.hip cut_margin_pct)
+                    //  host scales it with how long the view will be away and with how forecasts have fared lately: lists.hip cut_margin_pct)
                     const unsigned long long mraw = (unsigned long long)g * sl.margin_pct / 100ull;
                     const uint32_t margin = mraw > 128ull ? (mraw < 0x7FFFFFFFull ? (uint32_t)mraw : 0x7FFFFFFFu) : 128u;
                     const uint32_t g2 = (unsigned long long)g + margin < sl.nv ? g + margin : sl.nv - 1u;
@@ -681,22 +677,6 @@ BH_DEV void blend_tile(const RasterUniforms& u, const uint32_t* __restrict__ ise
                 }
             }
             sl.zcut[tile] = newcut;
-        }
-        // hint for the next frame's slicing (read back with its counters): how many slots of the exact list a tile needed before
-        // it saturated (max over tiles), and how many pairs are listed for tiles that never saturate
-        if (sl.feedback) {
-            uint32_t* fb = sl.feedback + 3u * (blockIdx.x & (COUNTER_SLOTS - 1u));
-            const uint32_t stop = BWD_INFO ? last_useful : reached;
-            if (saturated) {
-                if (stop > range_lo) atomicMax(&fb[0], sl.cum[isect_gids[stop - 1u]]);
-                else if (PHASE == 2) {   // (saturated by the near slice's last splats, nothing blended here)
-                    const uint32_t n_lo = sl.offsets_near[tile * 2], n_hi = sl.offsets_near[tile * 2 + 1];
-                    if (n_hi > n_lo) atomicMax(&fb[0], sl.cum[isect_gids[n_hi - 1u]]);
-                }
-            } else {
-                if (listed) atomicAdd(&fb[1], listed);
-                atomicAdd(&fb[2], 1u);
-            }
         }
     }
 }
@@ -770,8 +750,6 @@ int launch_rasterize(bh_ctx* ctx, const ViewUniforms& vu, const float bg[3], boo
         sl.gate_host = phase == 1 ? slice->gate_host : nullptr;
         sl.state = slice->state;
         sl.offsets_near = slice->offsets_near;
-        sl.cum = slice->cum;
-        sl.feedback = slice->feedback;
         sl.zcut = slice->zcut;
         sl.depth_keys_sorted = slice->depth_keys_sorted;
         sl.nv = slice->nv;
@@ -788,7 +766,6 @@ int launch_rasterize(bh_ctx* ctx, const ViewUniforms& vu, const float bg[3], boo
     if (sl.zcut && (!sl.depth_keys_sorted && sl.nv)) sl.zcut = nullptr;
     if (phase != 0 && (!sl.done_bits || !sl.unsat_count || !sl.state || (phase == 2 && !sl.offsets_near)))
         return set_error(ctx, BH_ERR_INVALID_ARG, "launch_rasterize: sliced phase without its scratch");
-    if (sl.feedback && !sl.cum) sl.feedback = nullptr;
     uint32_t nblocks = band_slots(u.num_tiles) * 8u;
     if (sl.order && sl.order_mode == 2u) nblocks = ((band_slots(u.num_tiles) + 7u) / 8u) * 64u;   // 8 bands x 8 x seg ranks
     if (sl.split) nblocks += 8u * 3u * SPLIT_MAX;   // three more blocks for each tile a band may split (blocks behind the band's last rank leave at once)

@@ -776,7 +776,7 @@ def test_a_failed_step_drops_its_per_tile_cut_job_and_never_replays_freed_parame
 
 
 def test_the_cut_margin_adapts_to_how_long_a_view_is_away_and_to_failed_forecasts(dev):
-    """api.hip cut_margin_pct: a view that comes back after many other views gets a deeper margin than one that alternates with a
+    """lists.hip cut_margin_pct: a view that comes back after many other views gets a deeper margin than one that alternates with a
     single other view (same scene, same camera: a larger near share), and a failed forecast deepens the margins of the frames that
     follow (x 1.5 per miss).  Images stay the exact path's throughout."""
     import brush_amd as ba
