@@ -10,6 +10,8 @@ Names and argument meaning follow the reference (paths under
     render_splats     brush-render/src/gaussian_splats.rs:365-446 (forward / eval)
     render_splats_bwd brush-render/src/bwd/burn_glue.rs:223-311 (+ RenderBackwards::backward :121-182)
     render_splats_diff / RenderNode   the same as an autodiff node: forward now, backward later from its SAVED state (burn_glue.rs:336-371)
+    render_depth / RenderNode.depth   accumulated, expected or median depth map of a node; RenderNode.backward(v_depth=) differentiates it
+                                      (include/brush_hip_depth.h)
     radix_argsort     brush-sort/src/lib.rs:16
     tile_sort_offsets render.rs:228-243 + get_tile_offset.rs:11-58 (the forward's tile sort and offsets table, one operator)
     prefix_sum        brush-prefix-sum/src/lib.rs:11
@@ -37,6 +39,6 @@ from .host import (  # noqa: F401
     splat_to_ply, load_splat_from_ply, ply_parse_header, ParseMetadata, BatchUploader, SceneLoader, set_list_slicing, last_list_counts, set_view_id,
     render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
     knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
-    Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image,
+    Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
 )
 from ._ffi import BrushHipError  # noqa: F401

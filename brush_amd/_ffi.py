@@ -237,6 +237,13 @@ IMAGE_SYMBOLS = {
     "bh_uploader_commit_view": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BhViewLoad)]),
 }
 
+# every symbol include/brush_hip_depth.h declares (depth maps of a saved forward and their gradient, a header of its own on top of brush_hip.h)
+DEPTH_ACCUMULATED, DEPTH_EXPECTED, DEPTH_MEDIAN = 0, 1, 2   # BH_DEPTH_*
+DEPTH_SYMBOLS = {
+    "bh_render_depth": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_uint32, C.c_void_p]),
+    "bh_render_backward_depth_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 7),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -276,7 +283,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS))
     return _lib
 
 
@@ -285,5 +292,5 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **TEST_HOOK_SYMBOLS))
     return _lib_th

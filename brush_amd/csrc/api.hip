@@ -1149,9 +1149,10 @@ static ForwardState latest_forward(const bh_ctx* ctx) {
 // recorded in ctx->clears under that forward's generation: a backward of any other forward (a retained, older one) finds nothing
 // there and clears everything itself.  span_floats != 0 (the train step): the four gradient outputs are one span of that many
 // floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
-static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
-                         const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                         size_t span_floats, bool want_refine) {
+// depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
+int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
+                  const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
+                  size_t span_floats, bool want_refine, const DepthTerm* depth) {
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
@@ -1196,18 +1197,35 @@ static int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_out
     }
     {
         ProfScope ps(ctx, "RasterizeBackwards", /*dominant=*/true);
-        if (r.num_intersections > 0)
+        if (r.num_intersections > 0 && v_output)
             BH_TRY(launch_rasterize_backward(ctx, fs.uniforms, fs.bg, fs.flags & BH_FLAG_SMOOTH_CUTOFF,
                                              r.compact_gid_from_isect, r.tile_offsets, r.projected, r.out_img, v_output, v_combined, fs.lpt,
                                              r.tile_offsets_far, want_refine, &fs.jobs));
+        if (depth) BH_TRY(launch_depth_backward(ctx, fs, *depth, v_combined));
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
         BH_TRY(launch_project_backward(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs,
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
+        if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms));
     }
     return 0;
+}
+
+int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, ForwardState* latest, const ForwardState** fs) {
+    if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
+    for (const Retained& rt : ctx->retained)
+        if (rt.fs.out.generation == saved->generation && rt.fs.out.out_img == saved->out_img) { *fs = &rt.fs; return 0; }
+    if (ctx->have_forward && saved->generation == ctx->last.generation && saved->out_img == ctx->last.out_img) {
+        *latest = latest_forward(ctx);
+        *fs = latest;
+        return 0;
+    }
+    char msg[288];
+    snprintf(msg, sizeof msg, "%s: forward #%llu is stale (the context's buffers now hold forward #%llu); call bh_render_retain "
+                              "on a forward that must outlive the next one", who, (unsigned long long)saved->generation, (unsigned long long)ctx->generation);
+    return set_error(ctx, BH_ERR_STATE, msg);
 }
 
 // the arena slots a BhRenderOut points into (everything a retained forward must keep alive)
@@ -1242,18 +1260,11 @@ int bh_render_backward_saved(bh_ctx* ctx, const BhRenderOut* saved, const float*
         return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_saved: null argument");
     if (!(saved->flags & BH_FLAG_BWD_INFO)) return set_error(ctx, BH_ERR_STATE, "render_backward_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
     BH_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    for (const Retained& rt : ctx->retained)
-        if (rt.fs.out.generation == saved->generation && rt.fs.out.out_img == saved->out_img)
-            return backward_impl(ctx, rt.fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
-                                 v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
-    if (ctx->have_forward && saved->generation == ctx->last.generation && saved->out_img == ctx->last.out_img)
-        return backward_impl(ctx, latest_forward(ctx), v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs,
-                             v_raw_opacities, v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
-    char msg[256];
-    snprintf(msg, sizeof msg, "render_backward_saved: forward #%llu is stale (the context's buffers now hold forward #%llu); call bh_render_retain "
-                              "on a forward that must outlive the next one", (unsigned long long)saved->generation, (unsigned long long)ctx->generation);
-    return set_error(ctx, BH_ERR_STATE, msg);
+    ForwardState latest;
+    const ForwardState* fs = nullptr;
+    BH_TRY(find_saved_forward(ctx, saved, "render_backward_saved", &latest, &fs));
+    return backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
+                         /*span_floats=*/0, /*want_refine=*/true);
 }
 
 int bh_render_retain(bh_ctx* ctx, const BhRenderOut* out) {

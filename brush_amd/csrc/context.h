@@ -79,6 +79,7 @@ enum Slot : int {
     SLOT_LPIPS,              // bh_lpips_*: f64 partials | normalised inputs | scratch pair | activations of both images (lpips.hip)
     SLOT_PLY_COMPRESS,       // bh_splat_to_compressed_ply: box partials | box | Morton keys [N] | sorted keys [N] | row order [N] (ply_compress.hip)
     SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
+    SLOT_DEPTH,              // bh_render_backward_depth_saved: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip)
     SLOT_COUNT
 };
 
@@ -333,6 +334,12 @@ struct Retained {
     Buffer blocks[RETAIN_SLOTS];
 };
 
+// The depth term of a backward (depth.hip, brush_hip_depth.h): <v_depth, depth map `mode` of the forward>
+struct DepthTerm {
+    const float* v_depth = nullptr;   // [H,W]
+    uint32_t mode = 0;                // BH_DEPTH_ACCUMULATED or BH_DEPTH_EXPECTED
+};
+
 }  // namespace bh
 
 // The blend backward accumulates RAW per-splat sums into v_combined and the projection backward maps them to the reference's
@@ -459,6 +466,17 @@ int set_error(bh_ctx* ctx, int code, const std::string& msg);
 // api.hip: the forward pipeline of one request (arguments already checked), and the host's wait for a tag word a kernel stores
 int forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
 int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what);
+// api.hip: *fs = the saved state of the forward `saved` names — a retained one (the ctx's own entry, no copy) or the ctx's most
+// recent forward (assembled in *latest); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished first).
+// Valid until the next call that retains, releases or renders on the ctx.
+int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, ForwardState* latest, const ForwardState** fs);
+// api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth term (then K17 does not run)
+int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
+                  const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
+                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr);
+// depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
+int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
+int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms);
 
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view

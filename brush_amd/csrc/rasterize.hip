@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "context.h"
+#include "device_blend.h"
 
 namespace bh {
 
@@ -138,27 +139,8 @@ constexpr uint32_t JOB_TILE_MASK = 0x00FFFFFFu, JOB_SEG_SHIFT = 24u, JOB_SEG_MAS
 constexpr int SPLAT_STRIDE = 12;
 constexpr int BATCH = 64;
 constexpr uint32_t SPLIT_GROUP = 4;   // splats a quadrant wave of a split tile takes at a time (rasterize_kernel, NQ == 1)
-constexpr float SIGMA_CUT_MARGIN = 0.01f;  // >> the error of bh_logf/exp_blend (~1e-7)
 
-// exp(x) for the blend loops, x = -sigma <= 0 wherever the result is used (lanes that fail the
-// sigma pre-test compute a value nobody reads).  Base-2 form chosen for gfx950 issue rates: nine
-// full-rate VALU ops (fma, sub, fma, 5 fma, lshl_add) where the Cephes sequence of bh_expf
-// takes 14 with three half-rate ones (rndne, cvt, ldexp): k = rint(x*log2e) through the 1.5*2^23
-// magic add (fused into the product), 2^f from a degree-5 minimax polynomial on [-0.5, 0.5] (1.6e-7 max rel. error), and the
-// exponent spliced in by adding k << 23 to the bit pattern.  The CPU checker used by the tests
-// restates the same sequence, so images stay bit-identical to it.
-BH_DEV float exp_blend(float x) {
-    const float s = __builtin_fmaf(x, 1.44269504088896341f, 12582912.0f);
-    const float nkf = 12582912.0f - s;                               // -rint(x log2e), exact (as a subtraction: both fmas keep
-    const float f = __builtin_fmaf(x, 1.44269504088896341f, nkf);    //  their constant as a literal, no SGPR operand)
-    float p = 1.3274633092805743e-3f;
-    p = __builtin_fmaf(p, f, 9.671961888670921e-3f);
-    p = __builtin_fmaf(p, f, 5.5506784468889236e-2f);
-    p = __builtin_fmaf(p, f, 2.4022234976291656e-1f);
-    p = __builtin_fmaf(p, f, 6.931470632553101e-1f);
-    p = __builtin_fmaf(p, f, 1.0f);
-    return u2f(f2u(p) + (f2u(s) << 23));
-}
+// exp() in the blend loops, and a pixel's alpha / transmittance step: device_blend.h (shared with depth.hip)
 
 // 8 XCDs take workgroups round-robin; each XCD owns a band of tiles (context.h XCD BANDS).  (>= num_tiles: the slot names no tile)
 BH_DEV uint32_t tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode) {
@@ -183,8 +165,7 @@ BH_DEV uint32_t stage_batch(const uint32_t* __restrict__ isect_gids, const float
         float v[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) v[k] = p[k];
-        const float thr = SMOOTH ? (ALPHA_CUTOFF_MID - 0.5f * ALPHA_CUTOFF_BAND) : ALPHA_CUTOFF_MID;
-        const float cut = __builtin_fmaxf(bh_logf(v[5] / thr) + SIGMA_CUT_MARGIN, 0.0f);
+        const float cut = blend_sigma_cut<SMOOTH>(v[5]);
         const uint32_t gate = (v[6] >= 0.0f ? 1u : 0u) | (v[7] >= 0.0f ? 2u : 0u) | (v[8] >= 0.0f ? 4u : 0u);
         float4* d = reinterpret_cast<float4*>(s_splat + lane * SPLAT_STRIDE);
         const float diag = HALF_CONIC ? 0.5f : 1.0f;
@@ -325,11 +306,9 @@ BH_DEV void blend_tile(const RasterUniforms& u, const uint32_t* __restrict__ ise
             // live test on the state the first one left.  The pair is skipped when neither can reach its cutoff anywhere (the second
             // splat's test on the state BEFORE the first: conservative).
             auto apply = [&](const float4& s1, const float2& s2, const float alpha, const bool pre) {
-                const float w_cut = SMOOTH ? alpha_cutoff_weight(alpha) : (alpha >= ALPHA_CUTOFF_MID ? 1.0f : 0.0f);
-                const bool ok = pre && w_cut > 0.0f;
-                const float alpha_eff = SMOOTH ? alpha * w_cut : alpha;
-                const float next_t = tr[0] * (1.0f - alpha_eff);
-                const bool sat = next_t <= 1.0e-4f;
+                float alpha_eff, next_t;
+                bool sat;
+                const bool ok = blend_step<SMOOTH>(alpha, pre, tr[0], alpha_eff, next_t, sat);
                 const bool contrib = ok && !sat;
                 const float vis = contrib ? alpha_eff * tr[0] : 0.0f;
                 pr[0] = __builtin_fmaf(s1.z, vis, pr[0]);
@@ -475,12 +454,10 @@ BH_DEV void blend_tile(const RasterUniforms& u, const uint32_t* __restrict__ ise
                 // of a second half-rate v_cmp and a scalar and)
                 const bool pre = ((f2u(tr[q]) & sign_mask) | f2u(sigma)) <= cut_bits;
                 if (__ballot(pre) != 0ull) {
-                    const float alpha = __builtin_fminf(0.999f, s1.y * exp_blend(-sigma));
-                    const float w_cut = SMOOTH ? alpha_cutoff_weight(alpha) : (alpha >= ALPHA_CUTOFF_MID ? 1.0f : 0.0f);
-                    const bool ok = pre && w_cut > 0.0f;  // pre already implies sigma >= 0
-                    const float alpha_eff = SMOOTH ? alpha * w_cut : alpha;
-                    const float next_t = tr[q] * (1.0f - alpha_eff);
-                    const bool sat = next_t <= 1.0e-4f;
+                    const float alpha = blend_alpha(s1.y, sigma);
+                    float alpha_eff, next_t;
+                    bool sat;
+                    const bool ok = blend_step<SMOOTH>(alpha, pre, tr[q], alpha_eff, next_t, sat);
                     const bool contrib = ok && !sat;
                     const float vis = contrib ? alpha_eff * tr[q] : 0.0f;
                     pr[q] = __builtin_fmaf(s1.z, vis, pr[q]);   // (explicit fma: part of the numerical specification, as in the CPU checker)
@@ -809,29 +786,7 @@ int launch_rasterize(bh_ctx* ctx, const ViewUniforms& vu, const float bg[3], boo
 //     one splat later so nobody waits (446 us: the LDS pipe is not idle enough for 6.5 KB more per splat and wave), and the
 //     matrix core (v_mfma_f32_16x16x4_f32 with column selectors: exact, 542 us — the f32 MFMAs do not hide beside the VALU work).
 
-// Register butterfly: wave-wide sum of ten per-lane values in 28 VALU ops — v_permlane32_swap /
-// v_permlane16_swap fold two registers into one per step ("transpose-reduce"), then a DPP rotate-add finishes inside each
-// 16-lane row.  Afterwards every lane of row r of k[i] holds component comp(i, r): k0 -> g0 g2 g1 g3, k1 -> g4 g6 g5 g7,
-// k2 -> g8 - g9 -.
-BH_DEV float swap32_add(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(f2u(a), f2u(b), false, false);
-    return u2f(r[0]) + u2f(r[1]);
-}
-BH_DEV float swap16_add(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(f2u(a), f2u(b), false, false);
-    return u2f(r[0]) + u2f(r[1]);
-}
-template <int CTRL>
-BH_DEV float dpp_rot_add(float x) {
-    return x + u2f(__builtin_amdgcn_update_dpp(0u, f2u(x), CTRL, 0xF, 0xF, false));
-}
-BH_DEV float row_allreduce(float x) {
-    x = dpp_rot_add<0x128>(x);  // row_ror:8
-    x = dpp_rot_add<0x124>(x);  // row_ror:4
-    x = dpp_rot_add<0x122>(x);  // row_ror:2
-    x = dpp_rot_add<0x121>(x);  // row_ror:1
-    return x;
-}
+// (the register butterfly that sums the ten per-lane values over the wave: device_blend.h)
 
 // exp() of the backward's replay is the forward's exp_blend, bit for bit: the replay has to take the forward's decisions
 // (alpha >= 1/255, T' <= 1e-4) — with v_exp_f32 instead (BH_BWD_HW_EXP, measurement variant: 13 us faster) a pixel sitting

@@ -543,18 +543,33 @@ class RenderNode:
         w, h = img_size
         self.img = _view(out.out_img, (h, w, 4), torch.float32, splats.device)   # aliases ctx memory: valid while the node is (retained nodes: until release)
 
-    def backward(self, v_output):
+    def depth(self, mode="expected"):
+        """The node's depth map [H,W] f32 (bh_render_depth): "accumulated" sum of w z, "expected" = accumulated / alpha, or
+        "median" (z where the transmittance first falls to 1/2); a forward of a tile-row window writes its rows, the rest is 0."""
+        return render_depth(self, mode)
+
+    def backward(self, v_output, v_depth=None, depth_mode="expected"):
+        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>]; v_output may be None when v_depth is given."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
-        v_output = _f32c(v_output, dev).reshape(h, w, 4)
+        if v_output is None and v_depth is None:
+            raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
+        if v_output is not None:
+            v_output = _f32c(v_output, dev).reshape(h, w, 4)
         r_t, r_o = self._folded
         v_t = torch.empty((n, 10), dtype=torch.float32, device=dev)
         v_sh = torch.empty((n, c, 3), dtype=torch.float32, device=dev)
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
-        ctx.check(ctx.lib.bh_render_backward_saved(ctx._h, C.byref(self.out), _ptr(v_output), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                   _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+        if v_depth is not None:
+            v_depth = _f32c(v_depth, dev).reshape(h, w)
+            ctx.check(ctx.lib.bh_render_backward_depth_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
+                                                             _ptr(v_depth), _depth_mode(depth_mode), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
+                                                             _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+        else:
+            ctx.check(ctx.lib.bh_render_backward_saved(ctx._h, C.byref(self.out), _ptr(v_output), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
+                                                       _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
         if splats.min_scale is not None:
             ctx.check(ctx.lib.bh_fold_min_scale_backward(ctx._h, _ptr(splats.transforms), _ptr(splats.raw_opacities), _ptr(splats.min_scale), n,
                                                          _ptr(v_t), _ptr(v_op)))
@@ -566,12 +581,36 @@ class RenderNode:
             self.retained = False
 
 
+DEPTH_MODES = {"accumulated": _ffi.DEPTH_ACCUMULATED, "expected": _ffi.DEPTH_EXPECTED, "median": _ffi.DEPTH_MEDIAN}
+
+
+def _depth_mode(mode):
+    return int(DEPTH_MODES[mode]) if isinstance(mode, str) else int(mode)
+
+
+def render_depth(saved: "RenderNode", mode="expected", out=None):
+    """Depth map [H,W] f32 of a differentiable render's saved state (bh_render_depth; include/brush_hip_depth.h): the node must be
+    the ctx's most recent forward or a retained one.  `out`: a contiguous f32 [H,W] tensor to write into (rows outside a tile-row
+    window are left as they are); otherwise a zero-filled one is returned."""
+    ctx, dev = saved.ctx, saved.splats.device
+    w, h = saved.img_size
+    if out is None:
+        out = torch.zeros((h, w), dtype=torch.float32, device=dev)
+    if not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (h, w)
+            and out.device == torch.device(dev)):
+        raise BrushHipError("render_depth: `out` must be a contiguous float32 [%d, %d] tensor on %s" % (h, w, dev))
+    ctx.check(ctx.lib.bh_render_depth(ctx._h, C.byref(saved.out), _depth_mode(mode), _ptr(out)))
+    return out
+
+
 def render_splats_diff(splats: Splats, camera, img_size, background=(0.0, 0.0, 0.0), pass_: RasterPass = RasterPass.Backward,
-                       ctx: Optional[Context] = None, retain=False, sliced=False) -> RenderNode:
+                       ctx: Optional[Context] = None, retain=False, sliced=False, tile_rows=None) -> RenderNode:
     """Forward of a differentiable render; gradients later through RenderNode.backward (bwd/burn_glue.rs:223-311)."""
     assert pass_.bwd_info()
     ctx = ctx or get_context(splats.device)
     w, h = int(img_size[0]), int(img_size[1])
+    if tile_rows is not None and not isinstance(camera, _ffi.BhCamera):
+        camera = camera.uniforms((w, h), tile_rows)
     _, out, folded = _forward(ctx, splats, camera, (w, h), background, pass_, sliced)
     if retain:
         ctx.check(ctx.lib.bh_render_retain(ctx._h, C.byref(out)))

@@ -49,6 +49,7 @@
 #include "brush_hip_lpips.h"
 #include "brush_hip_compressed_ply.h"
 #include "brush_hip_image.h"
+#include "brush_hip_depth.h"
 
 namespace brush_hip {
 
@@ -404,6 +405,33 @@ class RenderNode {
         g.v_refine_weight.resize(n);
         ctx_.check(bh_render_backward_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(),
                                             g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
+        if (splats_.min_scale)
+            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
+                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
+        ctx_.sync();
+        return g;
+    }
+    // The node's depth map [H,W] f32 (brush_hip_depth.h): BH_DEPTH_ACCUMULATED, BH_DEPTH_EXPECTED or BH_DEPTH_MEDIAN.  Rows outside a
+    // tile-row window stay 0.
+    DeviceBuffer<float> depth(uint32_t mode = BH_DEPTH_EXPECTED) const {
+        DeviceBuffer<float> d;
+        d.resize((size_t)aux.img_w * aux.img_h);
+        d.zero();
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the fill is ordered before the ctx stream's kernel
+        ctx_.check(bh_render_depth(ctx_.get(), &aux.raw, mode, d.data()));
+        ctx_.sync();
+        return d;
+    }
+    // gradients of <v_output, image> + <v_depth, depth(mode)>; v_output may be nullptr (the depth term alone)
+    SplatGrads backward(const float* v_output, const float* v_depth, uint32_t mode = BH_DEPTH_EXPECTED) const {
+        const uint32_t n = splats_.num_splats();
+        SplatGrads g;
+        g.v_transforms.resize((size_t)n * 10);
+        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
+        g.v_raw_opacities.resize(n);
+        g.v_refine_weight.resize(n);
+        ctx_.check(bh_render_backward_depth_saved(ctx_.get(), &aux.raw, v_output, v_depth, mode, folded_.t, splats_.sh_coeffs.data(), folded_.o,
+                                                  g.v_transforms.data(), g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
         if (splats_.min_scale)
             ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
                                                   g.v_transforms.data(), g.v_raw_opacities.data()));
