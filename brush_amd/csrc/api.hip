@@ -14,12 +14,6 @@
 
 namespace bh {
 
-int launch_image_loss_forward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
-                                      uint32_t channels, uint32_t h, uint32_t w, const BhLossConfig& cfg, float* loss_map);
-int launch_image_loss_backward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
-                                       const float* dl_dmap, float dl_rgb, float dl_alpha, uint32_t channels, uint32_t h, uint32_t w,
-                                       const BhLossConfig& cfg, float* dl_dpred);
-
 int launch_image_loss_fused(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt, uint32_t h, uint32_t w, const BhLossConfig& cfg,
                             bool alpha_match, float dl_rgb, float dl_alpha, float* loss_out, float* v_output, float* loss_host = nullptr,
                             uint32_t* started_host = nullptr, uint32_t started_tag = 0);
@@ -343,40 +337,6 @@ int bh_profile_fetch(bh_ctx* ctx, const char** names, float* ms, uint32_t* calls
 // lists the keys).  Options select between paths that give the SAME results (A/B measurements, tests of the alternative paths);
 // they are host fields read when the next call is queued.
 namespace {
-struct OptionKey { const char* name; const char* help; };
-const OptionKey kOptionKeys[] = {
-    {"cut_min_pairs", "u32: a view whose last frame had fewer pairs keeps complete lists (= bh_set_list_cut_threshold)"},
-    {"cut_margin_pct", "0..10000: base margin behind a tile's last useful splat, % of its depth rank (default 150)"},
-    {"cut_margin_fixed", "0|1: the margin is cut_margin_pct for every frame instead of adaptive"},
-    {"cut_ctrl", "up:down:floor:gap_exp — the margin controller's constants (default 1.5:0.998:0.5:0.3333)"},
-    {"cut_sort_all", "0|1: with per-tile cuts, still depth-sort every visible splat"},
-    {"auto_exact_share", "0..1: a view whose last cut frame listed more than this share of its pairs renders complete lists (default 0.9; 0 = never)"},
-    {"no_view_hash", "0|1: frames without a view id share ONE table instead of being keyed by their camera"},
-    {"k16_order", "0 index order | 1 by the view's last per-tile work | 2 dealt: the forward blend's tile order"},
-    {"band_mode", "0|1: XCD bands of the blend kernels — contiguous eighths of the tile range, or dealt in chunks of 8 adjacent tiles (default 1)"},
-    {"k16_waves", "0..8: forward blend: resident one-wave tiles per SIMD (0 = 8 = all resident at once; fewer: the lighter tiles are dispatched as the heavier ones finish)"},
-    {"k16_split", "0..1000: forward blend: a tile whose forecast work is at least max(256, k16_split / 100 x its band's mean) is blended by four quadrant waves (default 250; 0: no tile is split)"},
-    {"k16_split_of_max", "0..100: ... and at least this many percent of its band's heaviest tile (default 45)"},
-    {"k16_split_min", "1..1023: a tile below this many blended splats (forecast) is never split (default 256)"},
-    {"k5_exact_spw", "16|32|64: splats per wave of the list builder for complete lists"},
-    {"bwd_jobs", "0|1: the blend backward works on checkpointed 128-entry segments of the tiles' lists (default 1) or on whole tiles"},
-    {"no_lpt", "0|1: the blend backward takes its tiles in index order"},
-    {"lpt_classes", "log|linear: work classes of the backward's longest-first tile order — two per octave of blended splats, or 1/64 of the mean list length wide"},
-    {"generic_depth_sort", "0|1: depth order by the generic radix sort + scan instead of the fused split sort"},
-    {"dsort_splitters", "0|1: the fused depth sort splits at the 254 depth quantiles of the view's previous frame (default 1) or always linearly over the frame's key range"},
-    {"tile_sort", "auto|bucket|lsd: the forward's tile sort (auto: bucket sort unless the view's pairs are concentrated in few tiles)"},
-    {"spec_k5", "0|1: queue the list builder before the host has read the frame's counts (default 1; 0: behind the count readback)"},
-    {"event_waits", "0|1: the host's mid-step waits use events behind the kernels instead of polled tag words"},
-    {"readback_copy", "0|1: counts and gate word reach the host through copy launches"},
-    {"force_exchange", "0|1: a one-rank communicator still walks the whole gradient-exchange path (overhead measurement)"},
-    {"zero_grads", "0|1: the single-GPU train step zero-fills its gradient span like the exchange path"},
-    {"loss_bands", "0|1: the fused loss's blocks take their tiles by XCD column bands (1) or row-major (0)"},
-    {"update_rows", "0|64|128|256: splats per block of the update kernel (0 = default)"},
-    {"update_early", "0|1: the update kernel's blocks issue all their loads up front"},
-    {"no_dormant", "0|1: the update kernel fetches and updates dormant splats like everyone else"},
-    {"sort_kpt", "0|4|8|16: keys per thread of the generic radix sort (0 = default)"},
-    {"grad_allreduce", "ring|direct: the dense gradient block's collective — ncclAllReduce, or reduce-scatter + all-gather over grouped send/recv"},
-};
 bool parse_u32(const char* v, uint32_t lo, uint32_t hi, uint32_t* out) {
     if (!v || !*v) return false;
     char* end = nullptr;
@@ -391,75 +351,99 @@ bool parse_flag(const char* v, bool* out) {
     *out = x != 0;
     return true;
 }
+// One row per key: bh_option_name / bh_option_help list it, bh_set_option finds it and calls apply, which parses the value and
+// stores it (false, and nothing stored: a bad value).  The row index is public (bh_option_name(i)): new keys go at the end.
+struct Option { const char* name; const char* help; bool (*apply)(bh_ctx* c, const char* v); };
+const Option kOptions[] = {
+    {"cut_min_pairs", "u32: a view whose last frame had fewer pairs keeps complete lists (= bh_set_list_cut_threshold)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 0xFFFFFFFFu, &c->cut_min_pairs); }},
+    {"cut_margin_pct", "0..10000: base margin behind a tile's last useful splat, % of its depth rank (default 150)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 10000, &c->knob_cut_margin_pct); }},
+    {"cut_margin_fixed", "0|1: the margin is cut_margin_pct for every frame instead of adaptive",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_fixed_margin); }},
+    {"cut_ctrl", "up:down:floor:gap_exp — the margin controller's constants (default 1.5:0.998:0.5:0.3333)", [](bh_ctx* c, const char* v) {
+        float a = 0, b = 0, d = 0, e = 0;
+        if (sscanf(v, "%f:%f:%f:%f", &a, &b, &d, &e) != 4 || !(a >= 1.0f && b > 0.0f && b <= 1.0f && d > 0.0f && e >= 0.0f && e <= 1.0f)) return false;
+        c->ctrl_up = a; c->ctrl_down = b; c->ctrl_floor = d; c->ctrl_gap_exp = e;
+        return true;
+    }},
+    {"cut_sort_all", "0|1: with per-tile cuts, still depth-sort every visible splat",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_cut_sort_all); }},
+    {"auto_exact_share", "0..1: a view whose last cut frame listed more than this share of its pairs renders complete lists (default 0.9; 0 = never)", [](bh_ctx* c, const char* v) {
+        char* end = nullptr;
+        const float x = strtof(v, &end);
+        if (end == v || *end != '\0' || !(x >= 0.0f && x <= 1.0f)) return false;
+        c->auto_exact_share = x;
+        return true;
+    }},
+    {"no_view_hash", "0|1: frames without a view id share ONE table instead of being keyed by their camera",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_no_view_hash); }},
+    {"k16_order", "0 index order | 1 by the view's last per-tile work | 2 dealt: the forward blend's tile order",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 2, &c->knob_k16_order); }},
+    {"band_mode", "0|1: XCD bands of the blend kernels — contiguous eighths of the tile range, or dealt in chunks of 8 adjacent tiles (default 1)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 1, &c->knob_band_mode); }},
+    {"k16_waves", "0..8: forward blend: resident one-wave tiles per SIMD (0 = 8 = all resident at once; fewer: the lighter tiles are dispatched as the heavier ones finish)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 8, &c->knob_k16_waves); }},
+    {"k16_split", "0..1000: forward blend: a tile whose forecast work is at least max(256, k16_split / 100 x its band's mean) is blended by four quadrant waves (default 250; 0: no tile is split)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 1000, &c->knob_k16_split); }},
+    {"k16_split_of_max", "0..100: ... and at least this many percent of its band's heaviest tile (default 45)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 100, &c->knob_k16_split_of_max); }},
+    {"k16_split_min", "1..1023: a tile below this many blended splats (forecast) is never split (default 256)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 1, 1023, &c->knob_k16_split_min); }},
+    {"k5_exact_spw", "16|32|64: splats per wave of the list builder for complete lists",
+     [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 16, 64, &u) || !(u == 16 || u == 32 || u == 64)) return false; c->knob_k5_exact_spw = u; return true; }},
+    {"bwd_jobs", "0|1: the blend backward works on checkpointed 128-entry segments of the tiles' lists (default 1) or on whole tiles",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_bwd_jobs); }},
+    {"no_lpt", "0|1: the blend backward takes its tiles in index order",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_no_lpt); }},
+    {"lpt_classes", "log|linear: work classes of the backward's longest-first tile order — two per octave of blended splats, or 1/64 of the mean list length wide",
+     [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "log") { c->knob_lpt_linear = false; return true; } if (w == "linear") { c->knob_lpt_linear = true; return true; } return false; }},
+    {"generic_depth_sort", "0|1: depth order by the generic radix sort + scan instead of the fused split sort",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_generic_depth_sort); }},
+    {"dsort_splitters", "0|1: the fused depth sort splits at the 254 depth quantiles of the view's previous frame (default 1) or always linearly over the frame's key range",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_dsort_splitters); }},
+    {"tile_sort", "auto|bucket|lsd: the forward's tile sort (auto: bucket sort unless the view's pairs are concentrated in few tiles)",
+     [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "auto") { c->knob_tile_sort = 0; return true; } if (w == "bucket") { c->knob_tile_sort = 1; return true; } if (w == "lsd") { c->knob_tile_sort = 2; return true; } return false; }},
+    {"spec_k5", "0|1: queue the list builder before the host has read the frame's counts (default 1; 0: behind the count readback)",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_spec_k5); }},
+    {"event_waits", "0|1: the host's mid-step waits use events behind the kernels instead of polled tag words",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_event_waits); }},
+    {"readback_copy", "0|1: counts and gate word reach the host through copy launches",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_readback_copy); }},
+    {"force_exchange", "0|1: a one-rank communicator still walks the whole gradient-exchange path (overhead measurement)",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_force_exchange); }},
+    {"zero_grads", "0|1: the single-GPU train step zero-fills its gradient span like the exchange path",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_zero_grads); }},
+    {"loss_bands", "0|1: the fused loss's blocks take their tiles by XCD column bands (1) or row-major (0)",
+     [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 1, &c->knob_loss_bands); }},
+    {"update_rows", "0|64|128|256: splats per block of the update kernel (0 = default)",
+     [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 256, &u) || !(u == 0 || u == 64 || u == 128 || u == 256)) return false; c->knob_update_rows = u; return true; }},
+    {"update_early", "0|1: the update kernel's blocks issue all their loads up front",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_update_early); }},
+    {"no_dormant", "0|1: the update kernel fetches and updates dormant splats like everyone else",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_no_dormant); }},
+    {"sort_kpt", "0|4|8|16: keys per thread of the generic radix sort (0 = default)",
+     [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 16, &u) || !(u == 0 || u == 4 || u == 8 || u == 16)) return false; c->knob_sort_kpt = u; return true; }},
+    {"grad_allreduce", "ring|direct: the dense gradient block's collective — ncclAllReduce, or reduce-scatter + all-gather over grouped send/recv",
+     [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "ring") { c->knob_direct_allreduce = false; return true; } if (w == "direct") { c->knob_direct_allreduce = true; return true; } return false; }},
+};
+constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
 }  // namespace
 
-extern "C" int bh_option_count(void) { return (int)(sizeof(kOptionKeys) / sizeof(kOptionKeys[0])); }
-extern "C" const char* bh_option_name(int i) { return i >= 0 && i < bh_option_count() ? kOptionKeys[i].name : nullptr; }
-extern "C" const char* bh_option_help(int i) { return i >= 0 && i < bh_option_count() ? kOptionKeys[i].help : nullptr; }
+extern "C" int bh_option_count(void) { return kOptionCount; }
+extern "C" const char* bh_option_name(int i) { return i >= 0 && i < kOptionCount ? kOptions[i].name : nullptr; }
+extern "C" const char* bh_option_help(int i) { return i >= 0 && i < kOptionCount ? kOptions[i].help : nullptr; }
 
 extern "C" int bh_set_option(bh_ctx* ctx, const char* key, const char* value) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!key || !value) return set_error(ctx, BH_ERR_INVALID_ARG, "set_option: null key or value");
     const std::string k(key);
-    bool ok = false;
-    uint32_t u = 0;
-    if (k == "cut_min_pairs") { if ((ok = parse_u32(value, 0, 0xFFFFFFFFu, &u))) ctx->cut_min_pairs = u; }
-    else if (k == "cut_margin_pct") { if ((ok = parse_u32(value, 0, 10000, &u))) ctx->knob_cut_margin_pct = u; }
-    else if (k == "cut_margin_fixed") ok = parse_flag(value, &ctx->knob_fixed_margin);
-    else if (k == "cut_ctrl") {
-        float a = 0, b = 0, c = 0, d = 0;
-        if (sscanf(value, "%f:%f:%f:%f", &a, &b, &c, &d) == 4 && a >= 1.0f && b > 0.0f && b <= 1.0f && c > 0.0f && d >= 0.0f && d <= 1.0f) {
-            ctx->ctrl_up = a; ctx->ctrl_down = b; ctx->ctrl_floor = c; ctx->ctrl_gap_exp = d;
-            ok = true;
-        }
+    for (const Option& o : kOptions) {
+        if (k != o.name) continue;
+        if (!o.apply(ctx, value)) return set_error(ctx, BH_ERR_INVALID_ARG, "set_option: bad value '" + std::string(value) + "' for '" + k + "'");
+        return 0;
     }
-    else if (k == "cut_sort_all") ok = parse_flag(value, &ctx->knob_cut_sort_all);
-    else if (k == "auto_exact_share") {
-        char* end = nullptr;
-        const float f = strtof(value, &end);
-        if (end != value && *end == '\0' && f >= 0.0f && f <= 1.0f) { ctx->auto_exact_share = f; ok = true; }
-    }
-    else if (k == "no_view_hash") ok = parse_flag(value, &ctx->knob_no_view_hash);
-    else if (k == "k16_order") { if ((ok = parse_u32(value, 0, 2, &u))) ctx->knob_k16_order = u; }
-    else if (k == "band_mode") { if ((ok = parse_u32(value, 0, 1, &u))) ctx->knob_band_mode = u; }
-    else if (k == "k16_waves") { if ((ok = parse_u32(value, 0, 8, &u))) ctx->knob_k16_waves = u; }
-    else if (k == "k16_split") { if ((ok = parse_u32(value, 0, 1000, &u))) ctx->knob_k16_split = u; }
-    else if (k == "k16_split_of_max") { if ((ok = parse_u32(value, 0, 100, &u))) ctx->knob_k16_split_of_max = u; }
-    else if (k == "k16_split_min") { if ((ok = parse_u32(value, 1, 1023, &u))) ctx->knob_k16_split_min = u; }
-    else if (k == "k5_exact_spw") { if ((ok = parse_u32(value, 16, 64, &u) && (u == 16 || u == 32 || u == 64))) ctx->knob_k5_exact_spw = u; }
-    else if (k == "bwd_jobs") ok = parse_flag(value, &ctx->knob_bwd_jobs);
-    else if (k == "no_lpt") ok = parse_flag(value, &ctx->knob_no_lpt);
-    else if (k == "lpt_classes") {
-        const std::string v(value);
-        if (v == "log") { ctx->knob_lpt_linear = false; ok = true; }
-        else if (v == "linear") { ctx->knob_lpt_linear = true; ok = true; }
-    }
-    else if (k == "generic_depth_sort") ok = parse_flag(value, &ctx->knob_generic_depth_sort);
-    else if (k == "dsort_splitters") ok = parse_flag(value, &ctx->knob_dsort_splitters);
-    else if (k == "tile_sort") {
-        const std::string v(value);
-        if (v == "auto") { ctx->knob_tile_sort = 0; ok = true; }
-        else if (v == "bucket") { ctx->knob_tile_sort = 1; ok = true; }
-        else if (v == "lsd") { ctx->knob_tile_sort = 2; ok = true; }
-    }
-    else if (k == "spec_k5") ok = parse_flag(value, &ctx->knob_spec_k5);
-    else if (k == "event_waits") ok = parse_flag(value, &ctx->knob_event_waits);
-    else if (k == "readback_copy") ok = parse_flag(value, &ctx->knob_readback_copy);
-    else if (k == "force_exchange") ok = parse_flag(value, &ctx->knob_force_exchange);
-    else if (k == "zero_grads") ok = parse_flag(value, &ctx->knob_zero_grads);
-    else if (k == "loss_bands") { if ((ok = parse_u32(value, 0, 1, &u))) ctx->knob_loss_bands = u; }
-    else if (k == "update_rows") { if ((ok = parse_u32(value, 0, 256, &u) && (u == 0 || u == 64 || u == 128 || u == 256))) ctx->knob_update_rows = u; }
-    else if (k == "update_early") ok = parse_flag(value, &ctx->knob_update_early);
-    else if (k == "no_dormant") ok = parse_flag(value, &ctx->knob_no_dormant);
-    else if (k == "sort_kpt") { if ((ok = parse_u32(value, 0, 16, &u) && (u == 0 || u == 4 || u == 8 || u == 16))) ctx->knob_sort_kpt = u; }
-    else if (k == "grad_allreduce") {
-        const std::string v(value);
-        if (v == "ring") { ctx->knob_direct_allreduce = false; ok = true; }
-        else if (v == "direct") { ctx->knob_direct_allreduce = true; ok = true; }
-    }
-    else return set_error(ctx, BH_ERR_INVALID_ARG, "set_option: unknown key '" + k + "' (bh_option_name lists the keys)");
-    if (!ok) return set_error(ctx, BH_ERR_INVALID_ARG, "set_option: bad value '" + std::string(value) + "' for '" + k + "'");
-    return 0;
+    return set_error(ctx, BH_ERR_INVALID_ARG, "set_option: unknown key '" + k + "' (bh_option_name lists the keys)");
 }
 
 // ---- lens laws in f64 (brush-render/src/camera.rs:85-198) ------------------------------------
@@ -649,13 +633,15 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     const float* transforms = req.transforms;
     const float* sh_coeffs = req.sh_coeffs;
     const float* raw_opacities = req.raw_opacities;
-    const float* background = req.bg;
     ctx->have_forward = false;
     ctx->clears.begin_forward();   // (filled in below only by the kernels of THIS forward)
-    const bool mip = flags & BH_FLAG_MIP, bwd_info = flags & BH_FLAG_BWD_INFO, smooth = flags & BH_FLAG_SMOOTH_CUTOFF;
-    const ViewUniforms u = make_uniforms(req.cam);
-    if (u.tile_y0 >= u.tile_y1 || u.tile_y1 > u.tile_bh) return set_error(ctx, BH_ERR_INVALID_ARG, "tile_row window must satisfy begin < end <= ceil(img_h / 16)");
-    const uint32_t num_tiles = u.tile_bw * u.tile_bh;
+    const bool mip = flags & BH_FLAG_MIP;
+    Frame f;
+    f.bwd_info = flags & BH_FLAG_BWD_INFO; f.smooth = flags & BH_FLAG_SMOOTH_CUTOFF;
+    f.bg[0] = req.bg[0]; f.bg[1] = req.bg[1]; f.bg[2] = req.bg[2];
+    f.u = make_uniforms(req.cam);
+    if (f.u.tile_y0 >= f.u.tile_y1 || f.u.tile_y1 > f.u.tile_bh) return set_error(ctx, BH_ERR_INVALID_ARG, "tile_row window must satisfy begin < end <= ceil(img_h / 16)");
+    f.num_tiles = f.u.tile_bw * f.u.tile_bh;
     const size_t npad = n ? n : 1;
 
     // two counter pairs: K1 accumulates into one and clears the other for the next forward (no fill launch)
@@ -666,26 +652,26 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     auto* depth_keys = (uint32_t*)ensure(ctx, SLOT_DEPTH_KEYS, npad * 4);
     auto* isect_counts = (uint32_t*)ensure(ctx, SLOT_ISECT_COUNTS, npad * 4);
     auto* max_radius = req.max_radius ? req.max_radius : (float*)ensure(ctx, SLOT_MAX_RADIUS, npad * 4);
-    auto* proj_by_gid = (float*)ensure(ctx, SLOT_PROJECTED_BY_GID, npad * 9 * 4);
-    if (!counters || !depth_keys || !isect_counts || !max_radius || !proj_by_gid) return BH_ERR_OOM;
+    f.proj_by_gid = (float*)ensure(ctx, SLOT_PROJECTED_BY_GID, npad * 9 * 4);
+    if (!counters || !depth_keys || !isect_counts || !max_radius || !f.proj_by_gid) return BH_ERR_OOM;
 
-    auto* gfc = (uint32_t*)ensure(ctx, SLOT_GLOBAL_FROM_COMPACT, npad * 4);
+    f.gfc = (uint32_t*)ensure(ctx, SLOT_GLOBAL_FROM_COMPACT, npad * 4);
     auto* depths_sorted = (uint32_t*)ensure(ctx, SLOT_DEPTHS_SORTED, npad * 4);
-    if (!gfc || !depths_sorted) return BH_ERR_OOM;
+    if (!f.gfc || !depths_sorted) return BH_ERR_OOM;
     // [T,2] offsets | 8 x LPT_CLASSES work-class counters | [8][LPT_CLASSES][ceil(T/8)] class lists (longest-first tile order of the backward)
     // backward jobs (rasterize.hip): the blend backward works on checkpointed segments of the tiles' lists
-    const bool bwd_jobs = bwd_info && ctx->knob_bwd_jobs && !ctx->knob_no_lpt && !((flags & BH_FLAG_SLICED_LISTS) && ctx->slice_fraction > 0.0f);
-    const size_t lpt_words = LPT_HEADER_WORDS + (size_t)8 * LPT_CLASSES * band_slots(num_tiles);
-    auto* tile_offsets = (uint32_t*)ensure(ctx, SLOT_TILE_OFFSETS, ((size_t)num_tiles * 2 + lpt_words) * 4);
-    auto* visible = (bwd_info && req.visible) ? req.visible : (float*)ensure(ctx, SLOT_VISIBLE, (bwd_info ? npad : 1) * 4);
-    if (!tile_offsets || !visible) return BH_ERR_OOM;
-    const size_t visible_words = bwd_info ? ((req.visible && req.visible_floats) ? req.visible_floats : npad) : 0;
+    const bool bwd_jobs = f.bwd_info && ctx->knob_bwd_jobs && !ctx->knob_no_lpt && !((flags & BH_FLAG_SLICED_LISTS) && ctx->slice_fraction > 0.0f);
+    const size_t lpt_words = LPT_HEADER_WORDS + (size_t)8 * LPT_CLASSES * band_slots(f.num_tiles);
+    auto* tile_offsets = (uint32_t*)ensure(ctx, SLOT_TILE_OFFSETS, ((size_t)f.num_tiles * 2 + lpt_words) * 4);
+    f.visible = (f.bwd_info && req.visible) ? req.visible : (float*)ensure(ctx, SLOT_VISIBLE, (f.bwd_info ? npad : 1) * 4);
+    if (!tile_offsets || !f.visible) return BH_ERR_OOM;
+    const size_t visible_words = f.bwd_info ? ((req.visible && req.visible_floats) ? req.visible_floats : npad) : 0;
     // depth-sliced lists: [0] near-slice splats  [1] near-slice pairs  [2] tiles the near slice left unsaturated  [3] far-slice pairs |
     // done bits | far tile offsets [T,2] | far pairs per block group.  Cleared by K1 with the tile table, whether or not this frame ends up slicing.
     const bool want_sliced = (flags & BH_FLAG_SLICED_LISTS) != 0;
-    const size_t slice_bit_words = ((size_t)num_tiles + 31) / 32;
+    const size_t slice_bit_words = ((size_t)f.num_tiles + 31) / 32;
     const size_t slice_group_words = (size_t)n / (256 * FAR_GROUP_BLOCKS) + 2;   // far pairs per group of count-kernel blocks
-    const size_t slice_words = want_sliced ? SLICE_CTRL_WORDS + slice_bit_words + (size_t)num_tiles * 2 + slice_group_words : 0;
+    const size_t slice_words = want_sliced ? SLICE_CTRL_WORDS + slice_bit_words + (size_t)f.num_tiles * 2 + slice_group_words : 0;
     uint32_t* slice_tab = nullptr;
     if (want_sliced) {
         slice_tab = (uint32_t*)ensure(ctx, SLOT_SLICE, slice_words * 4);
@@ -710,7 +696,7 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     // work they had at the same camera's last frame (K16 193 -> ~150 us at 1 M splats / 1080p), and it refreshes the table.
     const bool order_only = !want_sliced && ctx->knob_k16_order != 0u && n >= 8u * 256u;
     if (n > 0 && (auto_cuts || order_only)) {
-        view = frame_view(ctx, req, u.tile_bw, u.tile_bh, /*casual=*/order_only && !bwd_info);
+        view = frame_view(ctx, req, f.u.tile_bw, f.u.tile_bh, /*casual=*/order_only && !f.bwd_info);
         if (!view && auto_cuts) return set_error(ctx, BH_ERR_OOM, "hipMalloc for the per-view tile table failed");
         if (!view) (void)hipGetLastError();   // (ordering is optional: carry on in index order)
         cut_active = auto_cuts && view && cut_this_frame(ctx, view, req.allow_cut);
@@ -724,7 +710,7 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
         if (!near_counts) return BH_ERR_OOM;
     }
 
-    uint32_t nv = 0, ni = 0, near_total = 0, nv_true = 0;
+    uint32_t near_total = 0, nv_true = 0;
     bool fused_scan = false;
     uint32_t* cum_early = nullptr;
     bool k5_queued = false;   // K5 was queued before the counts were read (below): valid unless the pairs overflowed its buffers
@@ -739,21 +725,21 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
             ctx->counters_ready = false;
             ForwardPrep prep;
             prep.next_counters = reinterpret_cast<unsigned long long*>(counter_pairs + counter_set_words * ((ctx->counter_phase & 1u) ^ 1u));
-            prep.visible = visible_words ? reinterpret_cast<uint32_t*>(visible) : nullptr;
+            prep.visible = visible_words ? reinterpret_cast<uint32_t*>(f.visible) : nullptr;
             prep.visible_words = (uint32_t)visible_words;
             prep.tile_table = tile_offsets;
-            prep.tile_words = num_tiles * 2 + LPT_HEADER_WORDS;
+            prep.tile_words = f.num_tiles * 2 + LPT_HEADER_WORDS;
             prep.slice_table = slice_tab;
             prep.slice_words = (uint32_t)slice_words;
             prep.list_all_visible = ctx->knob_cut_sort_all;
             if (view && ctx->knob_k16_order && n >= 8u * 256u) {   // the forward blend's tile order from the view's last per-tile work (K1's blocks 0..7 sort it: the grid must have them)
-                const uint32_t win_t = u.tile_bw * (u.tile_y1 - u.tile_y0);
+                const uint32_t win_t = f.u.tile_bw * (f.u.tile_y1 - f.u.tile_y0);
                 tile_order = (uint32_t*)ensure(ctx, SLOT_TILE_ORDER, ((size_t)8 * band_slots(win_t) + SPLIT_TAIL_WORDS) * 4);
                 if (!tile_order) return BH_ERR_OOM;
-                prep.order_work = vtab + (size_t)num_tiles;
+                prep.order_work = vtab + (size_t)f.num_tiles;
                 prep.order_out = tile_order;
                 prep.order_tiles = win_t;
-                prep.order_tile_begin = u.tile_bw * u.tile_y0;
+                prep.order_tile_begin = f.u.tile_bw * f.u.tile_y0;
                 prep.order_mode = ctx->knob_k16_order;
                 prep.band_mode = ctx->knob_band_mode;
                 if (ctx->knob_k16_split && ctx->knob_k16_order == 1u) {   // split tiles (context.h SPLIT_MAX): K1's order blocks pick them
@@ -764,14 +750,14 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                     prep.split_of_max = (float)ctx->knob_k16_split_of_max * 0.01f;
                 }
             }
-            if (bwd_info && req.grad_begin && req.grad_floats && (req.grad_floats & 3u) == 0 &&
+            if (f.bwd_info && req.grad_begin && req.grad_floats && (req.grad_floats & 3u) == 0 &&
                 (reinterpret_cast<uintptr_t>(req.grad_begin) & 15u) == 0 && req.grad_floats / 4 <= 0xFFFFFFFFull) {
                 prep.span = reinterpret_cast<float4*>(req.grad_begin);   // the train step's gradient span
                 prep.span_f4 = (uint32_t)(req.grad_floats / 4);
                 ctx->clears.k1_cleared_span();
             }
-            BH_TRY(launch_project_forward(ctx, u, n, mip, sh_degree, transforms, sh_coeffs, raw_opacities, depth_keys, isect_counts, max_radius,
-                                          proj_by_gid, counters, prep, cut_active ? vtab : nullptr, near_counts));
+            BH_TRY(launch_project_forward(ctx, f.u, n, mip, sh_degree, transforms, sh_coeffs, raw_opacities, depth_keys, isect_counts, max_radius,
+                                          f.proj_by_gid, counters, prep, cut_active ? vtab : nullptr, near_counts));
             ctx->counter_phase ^= 1u;
             ctx->counters_ready = true;
         }
@@ -802,11 +788,11 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                 if (poll_tag && ++ctx->readback_tag == 0u) ctx->readback_tag = 1u;
                 bool* spl_written = nullptr;
                 uint32_t* spl = view_splitters(view, cut_active, &spl_written);
-                BH_TRY(depth_sort_scan(ctx, depth_keys, counters + COUNTER_MINMAX_WORD, cut_active ? near_counts : isect_counts, n, depths_sorted, gfc, cum_early,
+                BH_TRY(depth_sort_scan(ctx, depth_keys, counters + COUNTER_MINMAX_WORD, cut_active ? near_counts : isect_counts, n, depths_sorted, f.gfc, cum_early,
                                        sums_on_device ? counters : nullptr, ctx->host_counters + 16, ctx->readback_ev, poll_tag ? ctx->readback_tag : 0u,
                                        sums_on_device ? dev_sums : nullptr, spl, spl_written));
             } else {
-                BH_TRY(radix_argsort(ctx, depth_keys, nullptr, n, 32, depths_sorted, gfc));
+                BH_TRY(radix_argsort(ctx, depth_keys, nullptr, n, 32, depths_sorted, f.gfc));
             }
         }
         // ---- speculative K5: the list builder is queued BEFORE the host has read the counts.  Between the depth sort's last kernel and
@@ -820,13 +806,13 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
             const size_t cap_pairs = std::min(ctx->slots[SLOT_TILE_IDS].cap, ctx->slots[SLOT_ISECT_GIDS].cap) / 4;
             if (cap_pairs >= 4096) {
                 spec_projected = (float*)ensure(ctx, SLOT_PROJECTED, npad * 9 * 4);   // (rows for up to n listed splats)
-                spec_vc = bwd_info ? (float4*)ensure(ctx, SLOT_V_COMBINED, npad * 10 * 4 + 16) : nullptr;
-                if (!spec_projected || (bwd_info && !spec_vc)) return BH_ERR_OOM;
+                spec_vc = f.bwd_info ? (float4*)ensure(ctx, SLOT_V_COMBINED, npad * 10 * 4 + 16) : nullptr;
+                if (!spec_projected || (f.bwd_info && !spec_vc)) return BH_ERR_OOM;
                 spec_tile_ids = (uint32_t*)ctx->slots[SLOT_TILE_IDS].ptr;
                 spec_isect_gids = (uint32_t*)ctx->slots[SLOT_ISECT_GIDS].ptr;
                 spec_pair_cap = (uint32_t)std::min<size_t>(cap_pairs, 0xFFFFFFFEull);
                 ProfScope ps(ctx, "MapGaussiansToIntersect");
-                BH_TRY(launch_map_gaussians(ctx, n, u, proj_by_gid, gfc, spec_projected, cum_early, spec_tile_ids, spec_isect_gids, spec_vc,
+                BH_TRY(launch_map_gaussians(ctx, n, f.u, f.proj_by_gid, f.gfc, spec_projected, cum_early, spec_tile_ids, spec_isect_gids, spec_vc,
                                             spec_vc ? (uint32_t)(((size_t)n * 10 + 3) / 4) : 0u, 0xFFFFFFFFu, cut_active ? slice_tab : nullptr,
                                             cut_active ? vtab : nullptr, cut_active ? depths_sorted : nullptr, dev_sums + (cut_active ? 3 : 0), spec_pair_cap));
                 k5_queued = true;
@@ -848,29 +834,29 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
         }
         if (hc[1] > 0xFFFFFFFFull) return set_error(ctx, BH_ERR_UNSUPPORTED, "more than 2^32-1 tile intersections");
         nv_true = (uint32_t)hc[0];
-        ni = (uint32_t)hc[1];
-        near_total = cut_active ? (uint32_t)hc[2] : ni;
+        f.ni = (uint32_t)hc[1];
+        near_total = cut_active ? (uint32_t)hc[2] : f.ni;
         // per-tile cuts: only the splats that own a pair in front of some cut were given a real depth key (K1): the compact
         // arrays, K5's grid, the backward's accumulator and K18 are sized for THEM; num_visible stays the reference's count
-        nv = cut_active ? (uint32_t)hc[3] : nv_true;   // (BH_CUT_SORT_ALL: K1 then listed every visible splat, hc[3] == hc[0])
+        f.nv = cut_active ? (uint32_t)hc[3] : nv_true;   // (BH_CUT_SORT_ALL: K1 then listed every visible splat, hc[3] == hc[0])
     } else {   // no K1 to clear them on the way
-        BH_HIP(ctx, hipMemsetAsync(tile_offsets, 0, ((size_t)num_tiles * 2 + LPT_HEADER_WORDS) * 4, ctx->stream));
-        if (visible_words) BH_HIP(ctx, hipMemsetAsync(visible, 0, visible_words * 4, ctx->stream));
+        BH_HIP(ctx, hipMemsetAsync(tile_offsets, 0, ((size_t)f.num_tiles * 2 + LPT_HEADER_WORDS) * 4, ctx->stream));
+        if (visible_words) BH_HIP(ctx, hipMemsetAsync(f.visible, 0, visible_words * 4, ctx->stream));
     }
 
-    const size_t nvpad = nv ? nv : 1, nipad = ni ? ni : 1;
-    auto* cum = fused_scan ? cum_early : (uint32_t*)ensure(ctx, SLOT_CUM_TILES_HIT, nvpad * 4);
-    auto* projected = (float*)ensure(ctx, SLOT_PROJECTED, nvpad * 9 * 4);
-    auto* tile_ids = (uint32_t*)ensure(ctx, SLOT_TILE_IDS, nipad * 4);
-    auto* isect_gids = (uint32_t*)ensure(ctx, SLOT_ISECT_GIDS, nipad * 4);
-    auto* tile_ids_sorted = (uint32_t*)ensure(ctx, SLOT_TILE_IDS_SORTED, nipad * 4);
-    auto* isect_gids_sorted = (uint32_t*)ensure(ctx, SLOT_ISECT_GIDS_SORTED, nipad * 4);
-    const size_t pixels = (size_t)u.img_w * u.img_h;
-    void* out_img = ensure(ctx, SLOT_OUT_IMG, pixels * (bwd_info ? 16 : 4));
-    if (!cum || !projected || !tile_ids || !isect_gids || !tile_ids_sorted || !isect_gids_sorted || !out_img)
+    const size_t nvpad = f.nv ? f.nv : 1, nipad = f.ni ? f.ni : 1;
+    f.cum = fused_scan ? cum_early : (uint32_t*)ensure(ctx, SLOT_CUM_TILES_HIT, nvpad * 4);
+    f.projected = (float*)ensure(ctx, SLOT_PROJECTED, nvpad * 9 * 4);
+    f.tile_ids = (uint32_t*)ensure(ctx, SLOT_TILE_IDS, nipad * 4);
+    f.isect_gids = (uint32_t*)ensure(ctx, SLOT_ISECT_GIDS, nipad * 4);
+    f.tile_ids_sorted = (uint32_t*)ensure(ctx, SLOT_TILE_IDS_SORTED, nipad * 4);
+    f.isect_gids_sorted = (uint32_t*)ensure(ctx, SLOT_ISECT_GIDS_SORTED, nipad * 4);
+    const size_t pixels = (size_t)f.u.img_w * f.u.img_h;
+    void* out_img = ensure(ctx, SLOT_OUT_IMG, pixels * (f.bwd_info ? 16 : 4));
+    if (!f.cum || !f.projected || !f.tile_ids || !f.isect_gids || !f.tile_ids_sorted || !f.isect_gids_sorted || !out_img)
         return BH_ERR_OOM;
     // the speculative K5 stands if its pairs fitted and none of its buffers has moved since
-    if (k5_queued && ((cut_active ? near_total : ni) > spec_pair_cap || projected != spec_projected || tile_ids != spec_tile_ids || isect_gids != spec_isect_gids))
+    if (k5_queued && ((cut_active ? near_total : f.ni) > spec_pair_cap || f.projected != spec_projected || f.tile_ids != spec_tile_ids || f.isect_gids != spec_isect_gids))
         k5_queued = false;
 
     // ---- depth-sliced lists (BH_FLAG_SLICED_LISTS) --------------------------------------------------------------------------
@@ -884,78 +870,74 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     // same splats are folded in the same order: out_img, visible[], the blended part of every list and the gradients are those
     // of the exact path.  The near slice's size comes from the per-tile cuts of the view's last frame (lists.hip list_budget), or
     // from bh_set_list_slicing.
-    const uint32_t budget = want_sliced && ni > 0 ? list_budget(ctx, cut_active ? view : nullptr, near_total, ni) : ni;   // == ni: one slice, the exact lists
-    const bool sliced = budget < ni;
+    f.budget = want_sliced && f.ni > 0 ? list_budget(ctx, cut_active ? view : nullptr, near_total, f.ni) : f.ni;   // == ni: one slice, the exact lists
+    const bool sliced = f.budget < f.ni;
     const bool by_cut = cut_active && sliced;           // this frame's lists end at the per-tile cuts
     const uint32_t* zcut_lists = cut_active ? vtab : nullptr;   // (cut_active but not sliced: the cut removed nothing — K5 still filters, and keeps everything)
-    uint32_t* slice_info = slice_tab;
-    uint32_t* done_bits = slice_tab ? slice_tab + SLICE_CTRL_WORDS : nullptr;
-    uint32_t* tile_offsets_far = slice_tab ? slice_tab + SLICE_CTRL_WORDS + slice_bit_words : nullptr;
-    uint32_t* far_group_totals = slice_tab ? slice_tab + SLICE_CTRL_WORDS + slice_bit_words + (size_t)num_tiles * 2 : nullptr;
-    uint32_t tile_bits = 0;
-    while (tile_bits < 32 && (num_tiles >> tile_bits) != 0) tile_bits++;  // render.rs:228
-    RasterSlice rs;
-    ctx->jobs = BwdJobs{};
+    f.slice_info = slice_tab;
+    f.done_bits = slice_tab ? slice_tab + SLICE_CTRL_WORDS : nullptr;
+    f.tile_offsets_far = slice_tab ? slice_tab + SLICE_CTRL_WORDS + slice_bit_words : nullptr;
+    f.far_group_totals = slice_tab ? slice_tab + SLICE_CTRL_WORDS + slice_bit_words + (size_t)f.num_tiles * 2 : nullptr;
+    while (f.tile_bits < 32 && (f.num_tiles >> f.tile_bits) != 0) f.tile_bits++;  // render.rs:228
     if (bwd_jobs) {
         // checkpoint slots are addressed by list position (context.h BwdJobs): listed pairs / BWD_SEG + tiles of them
-        const uint32_t listed = cut_active ? near_total : ni;
-        const uint32_t ckpt_cap = (uint32_t)std::min<uint64_t>((uint64_t)listed / BWD_SEG + num_tiles + 1u, BWD_CKPT_MAX_SLOTS);
-        rs.jobs.ckpt = (float4*)ensure(ctx, SLOT_BWD_CKPT, (size_t)ckpt_cap * 256 * sizeof(float4));
-        rs.jobs.ckpt_cap = ckpt_cap;
-        rs.jobs.top_cap = band_slots(num_tiles) + ckpt_cap;   // (a band's full segments: at most one per checkpoint + one per tile)
-        rs.jobs.top_list = (uint32_t*)ensure(ctx, SLOT_BWD_TOPLIST, (size_t)8 * rs.jobs.top_cap * 4);
-        if (!rs.jobs.ckpt || !rs.jobs.top_list) return BH_ERR_OOM;
-        ctx->jobs = rs.jobs;
+        const uint32_t listed = cut_active ? near_total : f.ni;
+        const uint32_t ckpt_cap = (uint32_t)std::min<uint64_t>((uint64_t)listed / BWD_SEG + f.num_tiles + 1u, BWD_CKPT_MAX_SLOTS);
+        f.rs.jobs.ckpt = (float4*)ensure(ctx, SLOT_BWD_CKPT, (size_t)ckpt_cap * 256 * sizeof(float4));
+        f.rs.jobs.ckpt_cap = ckpt_cap;
+        f.rs.jobs.top_cap = band_slots(f.num_tiles) + ckpt_cap;   // (a band's full segments: at most one per checkpoint + one per tile)
+        f.rs.jobs.top_list = (uint32_t*)ensure(ctx, SLOT_BWD_TOPLIST, (size_t)8 * f.rs.jobs.top_cap * 4);
+        if (!f.rs.jobs.ckpt || !f.rs.jobs.top_list) return BH_ERR_OOM;
     }
     if (view) {   // every forward of a view refreshes its table
-        rs.zcut = vtab;
-        rs.depth_keys_sorted = depths_sorted;
-        rs.nv = nv;
-        rs.cut_active = by_cut;
-        rs.margin_pct = cut_margin_pct(ctx, view);
-        rs.work = vtab + (size_t)num_tiles;
-        rs.order = tile_order;
-        rs.order_mode = ctx->knob_k16_order;
-        rs.split = tile_split;
+        f.rs.zcut = vtab;
+        f.rs.depth_keys_sorted = depths_sorted;
+        f.rs.nv = f.nv;
+        f.rs.cut_active = by_cut;
+        f.rs.margin_pct = cut_margin_pct(ctx, view);
+        f.rs.work = vtab + (size_t)f.num_tiles;
+        f.rs.order = tile_order;
+        f.rs.order_mode = ctx->knob_k16_order;
+        f.rs.split = tile_split;
 #ifdef BH_TEST_HOOKS
         ctx->last_split = tile_split;
 #endif
     }
     // work classes ~1/64 of the mean list length wide (a tile typically blends ~10 % of its list before it saturates)
-    const uint32_t win_tiles = u.tile_bw * (u.tile_y1 - u.tile_y0);
-    const float class_width_raw = (float)ni / (float)(win_tiles ? win_tiles : 1u) / 64.0f;
-    const float class_width = ctx->knob_lpt_linear ? (class_width_raw < 8.0f ? 8.0f : class_width_raw) : 0.0f;   // (0: logarithmic classes, rasterize.hip)
-    ctx->lpt = (bwd_info && !ctx->knob_no_lpt) ? tile_offsets + (size_t)num_tiles * 2 : nullptr;
-    float* out_f32 = bwd_info ? (float*)out_img : nullptr;
-    uint32_t* out_u8 = bwd_info ? nullptr : (uint32_t*)out_img;
+    const uint32_t win_tiles = f.u.tile_bw * (f.u.tile_y1 - f.u.tile_y0);
+    const float class_width_raw = (float)f.ni / (float)(win_tiles ? win_tiles : 1u) / 64.0f;
+    f.class_width = ctx->knob_lpt_linear ? (class_width_raw < 8.0f ? 8.0f : class_width_raw) : 0.0f;   // (0: logarithmic classes, rasterize.hip)
+    f.lpt = (f.bwd_info && !ctx->knob_no_lpt) ? tile_offsets + (size_t)f.num_tiles * 2 : nullptr;
+    f.out_f32 = f.bwd_info ? (float*)out_img : nullptr;
+    f.out_u8 = f.bwd_info ? nullptr : (uint32_t*)out_img;
 
     bool offsets_done = false;   // the tile sort wrote the offsets table on its way
-    if (nv > 0) {
+    if (f.nv > 0) {
         if (!fused_scan) {
             ProfScope ps(ctx, "PrefixSumGaussHits");
-            BH_TRY(prefix_sum(ctx, cut_active ? near_counts : isect_counts, gfc, nv, cum, false));
+            BH_TRY(prefix_sum(ctx, cut_active ? near_counts : isect_counts, f.gfc, f.nv, f.cum, false));
         }
-        if (ni == 0) {   // nothing to map: only the record gather is left (K5 does it on its way otherwise)
+        if (f.ni == 0) {   // nothing to map: only the record gather is left (K5 does it on its way otherwise)
             ProfScope ps(ctx, "ProjectVisible");
-            BH_TRY(launch_project_visible(ctx, nv, proj_by_gid, gfc, projected));
+            BH_TRY(launch_project_visible(ctx, f.nv, f.proj_by_gid, f.gfc, f.projected));
         }
-        if (ni > 0) {
+        if (f.ni > 0) {
             {
                 ProfScope ps(ctx, "MapGaussiansToIntersect");
                 // the backward's accumulator [nv,10] is cleared by K5 on its way (whole float4s: + 16 B of room)
                 float4* vc = nullptr;
-                if (bwd_info) {
-                    vc = (float4*)ensure(ctx, SLOT_V_COMBINED, (size_t)nv * 10 * 4 + 16);
+                if (f.bwd_info) {
+                    vc = (float4*)ensure(ctx, SLOT_V_COMBINED, (size_t)f.nv * 10 * 4 + 16);
                     if (!vc) return BH_ERR_OOM;
                 }
                 if (zcut_lists && near_total == 0u) {
                     // no pair in front of any cut: nothing to emit (and K5 does not run to clear v_combined)
-                } else if (k5_queued && (!bwd_info || vc == spec_vc)) {
+                } else if (k5_queued && (!f.bwd_info || vc == spec_vc)) {
                     ctx->clears.k5_cleared_accum(vc != nullptr);   // (it ran in front of the count readback)
                 } else {
                     ctx->clears.k5_cleared_accum(vc != nullptr);
-                    BH_TRY(launch_map_gaussians(ctx, nv, u, proj_by_gid, gfc, projected, cum, tile_ids, isect_gids, vc, vc ? (uint32_t)(((size_t)nv * 10 + 3) / 4) : 0u,
-                                                (sliced && !by_cut) ? budget : 0xFFFFFFFFu, (sliced || zcut_lists) ? slice_info : nullptr, zcut_lists,
+                    BH_TRY(launch_map_gaussians(ctx, f.nv, f.u, f.proj_by_gid, f.gfc, f.projected, f.cum, f.tile_ids, f.isect_gids, vc, vc ? (uint32_t)(((size_t)f.nv * 10 + 3) / 4) : 0u,
+                                                (sliced && !by_cut) ? f.budget : 0xFFFFFFFFu, (sliced || zcut_lists) ? f.slice_info : nullptr, zcut_lists,
                                                 zcut_lists ? depths_sorted : nullptr));
                 }
             }
@@ -963,65 +945,57 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                 ProfScope ps(ctx, "TileSort");
                 // (scratch sized for the whole list: the near list's length moves from frame to frame)
                 // host-known lengths: the sort that also writes the offsets table, four launches instead of seven (sort.hip)
-                if ((zcut_lists || !sliced) && tile_sort_supported(tile_bits, zcut_lists ? near_total : ni) && !(ctx->knob_tile_sort == 2u)) {
-                    BH_TRY(tile_sort_offsets(ctx, tile_ids, isect_gids, zcut_lists ? near_total : ni, tile_bits, num_tiles, tile_ids_sorted, isect_gids_sorted,
-                                             tile_offsets, ni));
+                if ((zcut_lists || !sliced) && tile_sort_supported(f.tile_bits, zcut_lists ? near_total : f.ni) && !(ctx->knob_tile_sort == 2u)) {
+                    BH_TRY(tile_sort_offsets(ctx, f.tile_ids, f.isect_gids, zcut_lists ? near_total : f.ni, f.tile_bits, f.num_tiles, f.tile_ids_sorted, f.isect_gids_sorted,
+                                             tile_offsets, f.ni));
                     offsets_done = true;
                 } else
-                if (zcut_lists) BH_TRY(radix_argsort_dev(ctx, tile_ids, isect_gids, near_total, nullptr, nullptr, nullptr, tile_bits, tile_ids_sorted, isect_gids_sorted, ni));
-                else if (sliced) BH_TRY(radix_argsort_dev(ctx, tile_ids, isect_gids, budget, slice_info + 1, nullptr, nullptr, tile_bits, tile_ids_sorted, isect_gids_sorted, ni));
-                else BH_TRY(radix_argsort(ctx, tile_ids, isect_gids, ni, tile_bits, tile_ids_sorted, isect_gids_sorted));
+                if (zcut_lists) BH_TRY(radix_argsort_dev(ctx, f.tile_ids, f.isect_gids, near_total, nullptr, nullptr, nullptr, f.tile_bits, f.tile_ids_sorted, f.isect_gids_sorted, f.ni));
+                else if (sliced) BH_TRY(radix_argsort_dev(ctx, f.tile_ids, f.isect_gids, f.budget, f.slice_info + 1, nullptr, nullptr, f.tile_bits, f.tile_ids_sorted, f.isect_gids_sorted, f.ni));
+                else BH_TRY(radix_argsort(ctx, f.tile_ids, f.isect_gids, f.ni, f.tile_bits, f.tile_ids_sorted, f.isect_gids_sorted));
             }
         }
     }
     if (!offsets_done) {
         ProfScope ps(ctx, "GetTileOffsets");   // K1 cleared the table (or a fill did, for n == 0)
-        if (zcut_lists) BH_TRY(launch_tile_offsets(ctx, tile_ids_sorted, near_total, num_tiles, tile_offsets, /*pre_zeroed=*/true));
-        else if (sliced) BH_TRY(launch_tile_offsets_dev(ctx, tile_ids_sorted, budget, slice_info + 1, nullptr, nullptr, num_tiles, tile_offsets));
-        else BH_TRY(launch_tile_offsets(ctx, tile_ids_sorted, ni, num_tiles, tile_offsets, /*pre_zeroed=*/true));
+        if (zcut_lists) BH_TRY(launch_tile_offsets(ctx, f.tile_ids_sorted, near_total, f.num_tiles, tile_offsets, /*pre_zeroed=*/true));
+        else if (sliced) BH_TRY(launch_tile_offsets_dev(ctx, f.tile_ids_sorted, f.budget, f.slice_info + 1, nullptr, nullptr, f.num_tiles, tile_offsets));
+        else BH_TRY(launch_tile_offsets(ctx, f.tile_ids_sorted, f.ni, f.num_tiles, tile_offsets, /*pre_zeroed=*/true));
     }
     if (!sliced) {
         ProfScope ps(ctx, "Rasterize");   // `visible` was cleared by K1 as well
-        BH_TRY(launch_rasterize(ctx, u, background, bwd_info, smooth, isect_gids_sorted, tile_offsets, projected, gfc, out_f32, out_u8, visible, ctx->lpt,
-                                class_width, /*phase=*/0, &rs));
+        BH_TRY(launch_rasterize(ctx, f.u, f.bg, f.bwd_info, f.smooth, f.isect_gids_sorted, tile_offsets, f.projected, f.gfc, f.out_f32, f.out_u8, f.visible, f.lpt,
+                                f.class_width, /*phase=*/0, &f.rs));
     } else {
         auto* state = (float*)ensure(ctx, SLOT_SLICE_STATE, pixels * 16);
-        auto* far_counts = (uint32_t*)ensure(ctx, SLOT_SLICE_COUNTS, nvpad * 4);
-        auto* far_block_totals = (uint32_t*)ensure(ctx, SLOT_SLICE_CUM, (nvpad / 256 + 2) * 4);
-        if (!state || !far_counts || !far_block_totals) return BH_ERR_OOM;
-        rs.done_bits = done_bits;
-        rs.unsat_count = slice_info + 2;
+        f.far_counts = (uint32_t*)ensure(ctx, SLOT_SLICE_COUNTS, nvpad * 4);
+        f.far_block_totals = (uint32_t*)ensure(ctx, SLOT_SLICE_CUM, (nvpad / 256 + 2) * 4);
+        if (!state || !f.far_counts || !f.far_block_totals) return BH_ERR_OOM;
+        f.rs.done_bits = f.done_bits;
+        f.rs.unsat_count = f.slice_info + 2;
         if (!ctx->knob_readback_copy) {
             // how many tiles are left, for the host (to decide now, or to learn for the next frame: context.h far_direct): the
             // blend kernel stores into the pinned word itself.  Nothing of an earlier frame can still write it — every frame's
             // count readback waited behind the previous frame's blend.
-            rs.gate_host = ctx->host_counters + HOST_GATE_WORD;
-            *reinterpret_cast<volatile uint32_t*>(rs.gate_host) = 0u;
+            f.rs.gate_host = ctx->host_counters + HOST_GATE_WORD;
+            *reinterpret_cast<volatile uint32_t*>(f.rs.gate_host) = 0u;
         }
-        rs.state = state;
-        rs.offsets_near = tile_offsets;
-        rs.live_bands = slice_info + 4;
+        f.rs.state = state;
+        f.rs.offsets_near = tile_offsets;
+        f.rs.live_bands = f.slice_info + 4;
         {
             ProfScope ps(ctx, "Rasterize");
-            BH_TRY(launch_rasterize(ctx, u, background, bwd_info, smooth, isect_gids_sorted, tile_offsets, projected, gfc, out_f32, out_u8, visible, ctx->lpt,
-                                    class_width, /*phase=*/1, &rs));
+            BH_TRY(launch_rasterize(ctx, f.u, f.bg, f.bwd_info, f.smooth, f.isect_gids_sorted, tile_offsets, f.projected, f.gfc, f.out_f32, f.out_u8, f.visible, f.lpt,
+                                    f.class_width, /*phase=*/1, &f.rs));
         }
         FarJob& j = ctx->far_job;
-        j.u = u;
-        j.bg[0] = background[0]; j.bg[1] = background[1]; j.bg[2] = background[2];
-        j.bwd_info = bwd_info; j.smooth = smooth;
-        j.nv = nv; j.ni = ni; j.budget = budget; j.num_tiles = num_tiles; j.tile_bits = tile_bits;
-        j.proj_by_gid = proj_by_gid; j.gfc = gfc; j.projected = projected; j.cum = cum;
-        j.slice_info = slice_info; j.done_bits = done_bits; j.tile_offsets_far = tile_offsets_far;
-        j.far_counts = far_counts; j.far_block_totals = far_block_totals; j.far_group_totals = far_group_totals;
-        j.tile_ids = tile_ids; j.isect_gids = isect_gids; j.tile_ids_sorted = tile_ids_sorted; j.isect_gids_sorted = isect_gids_sorted;
-        j.out_f32 = out_f32; j.out_u8 = out_u8; j.visible = visible; j.lpt = ctx->lpt; j.class_width = class_width; j.rs = rs;
+        j.frame = f;
         j.by_cut = by_cut;
         j.view = by_cut ? view : nullptr;
         j.view_shared = req.view_id == 0u && ctx->knob_no_view_hash;   // (one table shared by every frame without an id: the A/B knob only)
         if (by_cut) j.req = req;   // what a second attempt with complete lists needs (finish_far_slice)
         if (ctx->knob_readback_copy)
-            BH_HIP(ctx, hipMemcpyAsync(ctx->host_counters + HOST_GATE_WORD, slice_info + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+            BH_HIP(ctx, hipMemcpyAsync(ctx->host_counters + HOST_GATE_WORD, f.slice_info + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
         // (per-tile cuts: the forecast is expected to hold — the host decides every time, bh_train_step hides the wait behind its
         //  loss kernels)
         if (ctx->far_direct && !by_cut) {
@@ -1040,7 +1014,7 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                 bool again = false;
                 BH_TRY(finish_far_slice(ctx, &again));
                 if (by_cut && again) {   // the forecast failed and the frame was rendered a second time, with complete lists: that is the result
-                    *out = ctx->last;
+                    *out = ctx->latest.out;
                     return 0;
                 }
             }
@@ -1049,39 +1023,38 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
 
     BhRenderOut r{};
     r.num_visible = nv_true;
-    r.num_listed_splats = nv;
-    r.num_intersections = ni;
-    r.num_tiles = num_tiles;
-    r.tile_bw = u.tile_bw;
-    r.tile_bh = u.tile_bh;
+    r.num_listed_splats = f.nv;
+    r.num_intersections = f.ni;
+    r.num_tiles = f.num_tiles;
+    r.tile_bw = f.u.tile_bw;
+    r.tile_bh = f.u.tile_bh;
     r.flags = flags;
-    r.out_img = bwd_info ? (float*)out_img : nullptr;
-    r.out_img_packed = bwd_info ? nullptr : (uint32_t*)out_img;
-    r.visible = bwd_info ? visible : nullptr;
+    r.out_img = f.bwd_info ? (float*)out_img : nullptr;
+    r.out_img_packed = f.bwd_info ? nullptr : (uint32_t*)out_img;
+    r.visible = f.bwd_info ? f.visible : nullptr;
     r.max_radius = max_radius;
     r.tile_offsets = tile_offsets;
-    r.projected = projected;
-    r.compact_gid_from_isect = isect_gids_sorted;
-    r.tile_id_from_isect = tile_ids_sorted;
-    r.global_from_compact_gid = gfc;
-    r.cum_tiles_hit = cum;
+    r.projected = f.projected;
+    r.compact_gid_from_isect = f.isect_gids_sorted;
+    r.tile_id_from_isect = f.tile_ids_sorted;
+    r.global_from_compact_gid = f.gfc;
+    r.cum_tiles_hit = f.cum;
     r.intersect_counts = isect_counts;
     r.depths_sorted = (float*)depths_sorted;
-    r.tile_offsets_far = sliced ? tile_offsets_far : nullptr;
-    r.list_budget = budget;   // (per-tile cuts: the pairs the near pass listed)
+    r.tile_offsets_far = sliced ? f.tile_offsets_far : nullptr;
+    r.list_budget = f.budget;   // (per-tile cuts: the pairs the near pass listed)
     r.generation = ++ctx->generation;
     ctx->clears.stamp(r.generation);
     *out = r;
-    ctx->last = r;
-    ctx->last_listed_splats = nv;
-    ctx->cam = req.cam;
-    ctx->uniforms = u;
-    ctx->n = n;
-    ctx->sh_degree = sh_degree;
-    ctx->flags = flags;
-    ctx->bg[0] = background[0]; ctx->bg[1] = background[1]; ctx->bg[2] = background[2];
+    ForwardState& latest = ctx->latest;
+    latest.out = r;
+    latest.uniforms = f.u;
+    latest.n = n; latest.sh_degree = sh_degree; latest.flags = flags;
+    latest.bg[0] = f.bg[0]; latest.bg[1] = f.bg[1]; latest.bg[2] = f.bg[2];
+    latest.lpt = f.lpt;
+    latest.jobs = f.rs.jobs;
     ctx->have_forward = true;
-    if (view) view_rendered(view, ni);   // this frame's blend kernel leaves what every tile needed
+    if (view) view_rendered(view, f.ni);   // this frame's blend kernel leaves what every tile needed
     return 0;
 }
 
@@ -1133,17 +1106,6 @@ uint32_t bh_view_table_count(bh_ctx* ctx) { return ctx ? (uint32_t)ctx->views.si
 }  // extern "C"
 
 namespace bh {
-
-static ForwardState latest_forward(const bh_ctx* ctx) {
-    ForwardState fs;
-    fs.out = ctx->last;
-    fs.uniforms = ctx->uniforms;
-    fs.n = ctx->n; fs.sh_degree = ctx->sh_degree; fs.flags = ctx->flags;
-    fs.bg[0] = ctx->bg[0]; fs.bg[1] = ctx->bg[1]; fs.bg[2] = ctx->bg[2];
-    fs.lpt = ctx->lpt;
-    fs.jobs = ctx->jobs;
-    return fs;
-}
 
 // The two backward kernels on the saved state `fs` (bwd/render_bwd.rs:21-171).  What the forward's kernels cleared on their way is
 // recorded in ctx->clears under that forward's generation: a backward of any other forward (a retained, older one) finds nothing
@@ -1213,15 +1175,11 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
     return 0;
 }
 
-int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, ForwardState* latest, const ForwardState** fs) {
+int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, const ForwardState** fs) {
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
     for (const Retained& rt : ctx->retained)
         if (rt.fs.out.generation == saved->generation && rt.fs.out.out_img == saved->out_img) { *fs = &rt.fs; return 0; }
-    if (ctx->have_forward && saved->generation == ctx->last.generation && saved->out_img == ctx->last.out_img) {
-        *latest = latest_forward(ctx);
-        *fs = latest;
-        return 0;
-    }
+    if (ctx->have_forward && saved->generation == ctx->latest.out.generation && saved->out_img == ctx->latest.out.out_img) { *fs = &ctx->latest; return 0; }
     char msg[288];
     snprintf(msg, sizeof msg, "%s: forward #%llu is stale (the context's buffers now hold forward #%llu); call bh_render_retain "
                               "on a forward that must outlive the next one", who, (unsigned long long)saved->generation, (unsigned long long)ctx->generation);
@@ -1241,13 +1199,13 @@ int bh_render_backward(bh_ctx* ctx, const float* v_output, const float* transfor
                        const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities,
                        float* v_refine_weight) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!ctx->have_forward || !(ctx->flags & BH_FLAG_BWD_INFO))
+    if (!ctx->have_forward || !(ctx->latest.flags & BH_FLAG_BWD_INFO))
         return set_error(ctx, BH_ERR_STATE, "render_backward needs a preceding BH_FLAG_BWD_INFO forward on this context");
     if (!v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
         return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward: null argument");
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    return backward_impl(ctx, latest_forward(ctx), v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
+    return backward_impl(ctx, ctx->latest, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
                          v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
 }
 
@@ -1260,9 +1218,8 @@ int bh_render_backward_saved(bh_ctx* ctx, const BhRenderOut* saved, const float*
         return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_saved: null argument");
     if (!(saved->flags & BH_FLAG_BWD_INFO)) return set_error(ctx, BH_ERR_STATE, "render_backward_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
     BH_HIP(ctx, hipSetDevice(ctx->device));
-    ForwardState latest;
     const ForwardState* fs = nullptr;
-    BH_TRY(find_saved_forward(ctx, saved, "render_backward_saved", &latest, &fs));
+    BH_TRY(find_saved_forward(ctx, saved, "render_backward_saved", &fs));
     return backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
                          /*span_floats=*/0, /*want_refine=*/true);
 }
@@ -1271,17 +1228,17 @@ int bh_render_retain(bh_ctx* ctx, const BhRenderOut* out) {
     if (!ctx || !out) return BH_ERR_INVALID_ARG;
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    if (!ctx->have_forward || out->generation != ctx->last.generation || out->out_img != ctx->last.out_img || out->out_img_packed != ctx->last.out_img_packed)
+    if (!ctx->have_forward || out->generation != ctx->latest.out.generation || out->out_img != ctx->latest.out.out_img || out->out_img_packed != ctx->latest.out.out_img_packed)
         return set_error(ctx, BH_ERR_STATE, "render_retain: only the context's most recent forward can be retained (and only once)");
     Retained rt;
-    rt.fs = latest_forward(ctx);
+    rt.fs = ctx->latest;
     for (int i = 0; i < RETAIN_SLOTS; ++i) {   // the blocks leave the arena: the next forward gets its own (from the pool, or hipMalloc)
         rt.blocks[i] = ctx->slots[kRetainSlots[i]];
         ctx->slots[kRetainSlots[i]] = Buffer{};
     }
     ctx->retained.push_back(rt);
     ctx->have_forward = false;    // bh_render_backward ("the last forward") has nothing to refer to until the next forward
-    ctx->lpt = nullptr;
+    ctx->latest.lpt = nullptr;
     return 0;
 }
 
@@ -1310,7 +1267,7 @@ int bh_last_render_out(bh_ctx* ctx, BhRenderOut* out) {
     if (!ctx->have_forward) return set_error(ctx, BH_ERR_STATE, "no forward render on this context yet");
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    *out = ctx->last;
+    *out = ctx->latest.out;
     return 0;
 }
 
@@ -1319,9 +1276,9 @@ int bh_last_list_counts(bh_ctx* ctx, uint32_t* near_pairs, uint32_t* far_pairs) 
     if (!ctx->have_forward) return set_error(ctx, BH_ERR_STATE, "no forward render on this context yet");
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    *near_pairs = ctx->last.num_intersections;
+    *near_pairs = ctx->latest.out.num_intersections;
     *far_pairs = 0u;
-    if (!ctx->last.tile_offsets_far) return 0;   // one slice: the exact lists
+    if (!ctx->latest.out.tile_offsets_far) return 0;   // one slice: the exact lists
     // slice_info (SLOT_SLICE): [0] near splats  [1] near pairs  [2] tiles the near slice left unsaturated  [3] far pairs
     uint32_t info[4] = {0u, 0u, 0u, 0u};
     BH_HIP(ctx, hipMemcpyAsync(info, ctx->slots[SLOT_SLICE].ptr, sizeof info, hipMemcpyDeviceToHost, ctx->stream));
@@ -1640,7 +1597,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
 #endif
     if (far_job_decides_first(ctx)) {   // (a view whose forecast keeps missing: lists.hip)
         BH_TRY(finish_far_slice(ctx, nullptr));
-        ro = ctx->last;   // (a second attempt replaces the frame's outputs)
+        ro = ctx->latest.out;   // (a second attempt replaces the frame's outputs)
     }
     BH_TRY(queue_loss());
     if (ctx->far_job.pending) {
@@ -1650,7 +1607,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         bool far_ran = false;
         BH_TRY(finish_far_slice(ctx, &far_ran));
         if (far_ran) {
-            ro = ctx->last;
+            ro = ctx->latest.out;
             BH_TRY(queue_loss());
         }
     }
@@ -1711,7 +1668,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // runs without it (refine_weight_norm stays as refine() zeroed it).  g_tr .. the end of the exchange buffer is one span
     // (padding included): one zero-fill, if the forward's K1 did not clear it.
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
-    BH_TRY(backward_impl(ctx, latest_forward(ctx), v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
+    BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
                          /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");

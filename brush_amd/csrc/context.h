@@ -46,14 +46,11 @@ enum Slot : int {
     SLOT_OUT_IMG,
     SLOT_VISIBLE,
     SLOT_V_COMBINED,
-    SLOT_LOSS_PRED,          // train step: pred in CHW
     SLOT_LOSS_MAP,
-    SLOT_LOSS_GRAD,          // dL/dpred CHW
     SLOT_V_OUTPUT,           // [H,W,4]
     SLOT_GRADS,              // exchange buffer: visible | v_transforms | v_sh | v_raw_opac | v_refine
     SLOT_STATS,              // screen radius of the last train-step forward
     SLOT_LOSS_SCALAR,
-    SLOT_COL_SCALE,          // per-column lr tables
     SLOT_MISC,
     SLOT_REFINE,             // refine plan: control block + 10 x [N] u32
     SLOT_REFINE_BOUNDS,      // percentile bounds: keys / sorted keys / indices
@@ -251,17 +248,17 @@ struct ForwardRequest {
     bool allow_cut = true;             // false: complete lists whatever the view's table says (the second attempt, finish_far_slice)
 };
 
-// The far slice of a depth-sliced forward, ready to be queued: everything launch_* needs (lists.hip enqueue_far_slice).
-struct FarJob {
-    bool pending = false;   // the near slice is queued and its gate word is on its way to the host; the far slice is undecided
+// The working set of one forward: what forward_impl computes once per call and its later stages read — its own list build and
+// blend, and the far slice if the frame needs one (a FarJob holds a copy).
+struct Frame {
     ViewUniforms u{};
     float bg[3] = {0, 0, 0};
     bool bwd_info = false, smooth = false;
     uint32_t nv = 0, ni = 0, budget = 0, num_tiles = 0, tile_bits = 0;
-    const float* proj_by_gid = nullptr;
-    const uint32_t* gfc = nullptr;
+    float* proj_by_gid = nullptr;
+    uint32_t* gfc = nullptr;
     float* projected = nullptr;
-    const uint32_t* cum = nullptr;
+    uint32_t* cum = nullptr;
     uint32_t* slice_info = nullptr;
     uint32_t* done_bits = nullptr;
     uint32_t* tile_offsets_far = nullptr;
@@ -275,9 +272,15 @@ struct FarJob {
     float* out_f32 = nullptr;
     uint32_t* out_u8 = nullptr;
     float* visible = nullptr;
-    uint32_t* lpt = nullptr;
+    uint32_t* lpt = nullptr;   // longest-first tile order of a BWD_INFO forward (rasterize.hip), or NULL
     float class_width = 8.0f;
     RasterSlice rs{};
+};
+
+// The far slice of a depth-sliced forward, ready to be queued: everything launch_* needs (lists.hip enqueue_far_slice).
+struct FarJob {
+    bool pending = false;   // the near slice is queued and its gate word is on its way to the host; the far slice is undecided
+    Frame frame{};
     // how the host learns that the near blend has finished: an event behind it (recorded when the job is created, or late, by
     // finish_far_slice), or — bh_train_step — the tag word its loss kernel stores when it starts (no event: a barrier packet
     // costs ~6 us of bubble in front of the next kernel)
@@ -358,11 +361,7 @@ struct bh_ctx {
     uint32_t counter_phase = 0;         // which half of SLOT_COUNTERS that is
     // state of the last forward (what RenderBackwards saves, bwd/burn_glue.rs:336-371)
     bool have_forward = false;
-    BhCamera cam{};
-    bh::ViewUniforms uniforms{};
-    uint32_t n = 0, sh_degree = 0, flags = 0;
-    float bg[3] = {0, 0, 0};
-    BhRenderOut last{};
+    bh::ForwardState latest;          // complete only while have_forward (forward_impl fills it at its end)
     uint64_t generation = 0;          // stamped into every BhRenderOut a forward of this ctx returns (bh_render_backward_saved checks it)
     std::vector<bh::Retained> retained;   // forwards detached by bh_render_retain, until bh_render_release
     std::vector<bh::Buffer> pool;     // blocks given back by bh_render_release: ensure() takes from here before it asks hipMalloc
@@ -382,7 +381,6 @@ struct bh_ctx {
     hipStream_t comm_stream = nullptr;
     hipEvent_t comm_ev = nullptr;
     int comm_rank = 0, comm_world = 1;
-    uint32_t* lpt = nullptr;          // longest-first tile order of the last BWD_INFO forward (rasterize.hip), or NULL
     // depth-sliced lists (BH_FLAG_SLICED_LISTS): share of the pair list the near slice takes.  <= 0: automatic, per-tile depth
     // cuts from the view's last frame (bh_set_list_slicing)
     float slice_fraction = 0.0f;
@@ -397,7 +395,6 @@ struct bh_ctx {
     bool gate_signal_queued = false;  // a kernel that stores far_job.gate_tag when it starts is queued behind the near blend
     bool gate_learn = false;          // a gate word copied out by a far_direct frame has not been looked at yet
     uint32_t far_launches = 0;        // diagnostics: sliced forwards that queued a far slice / had to be run again with complete lists
-    uint32_t last_listed_splats = 0;  // compact entries of the last forward (== num_visible unless per-tile cuts listed a subset)
     // per-tile depth cuts (automatic slicing): one table per view id (bh_set_view_id / BhTrainBatch.view_id; 0 = the ctx's own slot)
     // keyed by the caller's view id, or — id 0 — by a hash of the camera (lists.hip view_key): an unmodified SplatTrainer::step
     // (train.rs:176: a SceneBatch carries no view index, brush-dataset/src/scene.rs:138-147) gets the same tables
@@ -438,7 +435,6 @@ struct bh_ctx {
     // developer knobs (A/B measurements): bh_set_option
     bool knob_no_lpt = false;         // option no_lpt: backward tiles in index order
     bool knob_bwd_jobs = true;        // option bwd_jobs: the blend backward works on checkpointed segments of the tiles' lists (rasterize.hip)
-    bh::BwdJobs jobs{};                   // of the last BWD_INFO forward (with ctx->lpt)
     bool knob_lpt_linear = false;     // option lpt_classes=linear: the work classes of rounds 2-5 (rasterize.hip)
     bool knob_force_exchange = false;       // BH_FORCE_PG: run the gradient-exchange path with a one-rank communicator too (overhead measurement)
     bool knob_break_allreduce = false;      // BH_BREAK_ALLREDUCE: corrupt the library's all-reduce (the bench self-check must notice)
@@ -466,10 +462,10 @@ int set_error(bh_ctx* ctx, int code, const std::string& msg);
 // api.hip: the forward pipeline of one request (arguments already checked), and the host's wait for a tag word a kernel stores
 int forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
 int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what);
-// api.hip: *fs = the saved state of the forward `saved` names — a retained one (the ctx's own entry, no copy) or the ctx's most
-// recent forward (assembled in *latest); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished first).
+// api.hip: *fs = the saved state of the forward `saved` names — a retained one or the ctx's most recent forward (the ctx's own
+// record either way, no copy); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished first).
 // Valid until the next call that retains, releases or renders on the ctx.
-int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, ForwardState* latest, const ForwardState** fs);
+int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, const ForwardState** fs);
 // api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth term (then K17 does not run)
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
@@ -645,10 +641,6 @@ int launch_image_loss_forward(bh_ctx* ctx, const float* pred, const uint32_t* gt
 int launch_image_loss_backward(bh_ctx* ctx, const float* pred, const uint32_t* gt, const float* dl_dmap,
                                float dl_const, uint32_t channels, uint32_t h, uint32_t w, const BhLossConfig& cfg,
                                float* dl_dpred);
-// layout helpers used by the train step
-int launch_hwc4_to_chw(bh_ctx* ctx, const float* img_hwc4, uint32_t channels, uint32_t h, uint32_t w, float* chw);
-int launch_chw_to_hwc4(bh_ctx* ctx, const float* chw, uint32_t channels, uint32_t h, uint32_t w, float* hwc4);
-int launch_sum(bh_ctx* ctx, const float* x, uint64_t n, float scale, float* out_scalar, bool accumulate);
 // optim.hip
 int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
                 const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps);

@@ -382,9 +382,8 @@ int bh_render_depth(bh_ctx* ctx, const BhRenderOut* saved, uint32_t mode, float*
     if (mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_depth: unknown depth mode");
     if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_depth: the saved forward was not a BH_FLAG_BWD_INFO forward");
     BH_HIP(ctx, hipSetDevice(ctx->device));
-    bh::ForwardState latest;
     const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_forward(ctx, saved, "render_depth", &latest, &found));
+    BH_TRY(bh::find_saved_forward(ctx, saved, "render_depth", &found));
     const bh::ForwardState& fs = *found;
     if (fs.out.num_intersections == 0) {   // nothing listed: every mode is 0 over the rendered window
         const bh::ViewUniforms& vu = fs.uniforms;
@@ -406,9 +405,8 @@ int bh_render_backward_depth_saved(bh_ctx* ctx, const BhRenderOut* saved, const 
     if (mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_depth_saved: unknown depth mode");
     if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_depth_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
     BH_HIP(ctx, hipSetDevice(ctx->device));
-    bh::ForwardState latest;
     const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_forward(ctx, saved, "render_backward_depth_saved", &latest, &found));
+    BH_TRY(bh::find_saved_forward(ctx, saved, "render_backward_depth_saved", &found));
     const bh::ForwardState& fs = *found;
     bh::DepthTerm term;
     term.v_depth = v_depth;

@@ -201,26 +201,27 @@ static void view_outcome(bh_ctx* ctx, ViewState* vs, bool missed, bool shared_ta
 // offsets: one array for the backward), blend from the parked state.  Every kernel is gated on the device by the number of
 // unsaturated tiles, so queueing it for a frame that does not need it is correct, just ~50 us of empty launches.
 int enqueue_far_slice(bh_ctx* ctx, const FarJob& j) {
-    const uint32_t* gate = j.slice_info + 2;
-    const uint32_t far_max = j.ni;   // the host's bound; the live count is slice_info[3] on the device (the emit kernel's last block)
+    const Frame& f = j.frame;
+    const uint32_t* gate = f.slice_info + 2;
+    const uint32_t far_max = f.ni;   // the host's bound; the live count is slice_info[3] on the device (the emit kernel's last block)
     {
         ProfScope ps(ctx, "MapGaussiansToIntersect");
-        BH_TRY(launch_map_gaussians_far(ctx, j.nv, j.u, j.proj_by_gid, j.gfc, j.projected, j.cum, j.budget, j.done_bits, gate, j.far_counts, j.far_block_totals,
-                                        j.far_group_totals, j.slice_info, j.tile_ids, j.isect_gids));
+        BH_TRY(launch_map_gaussians_far(ctx, f.nv, f.u, f.proj_by_gid, f.gfc, f.projected, f.cum, f.budget, f.done_bits, gate, f.far_counts, f.far_block_totals,
+                                        f.far_group_totals, f.slice_info, f.tile_ids, f.isect_gids));
     }
     {
         ProfScope ps(ctx, "TileSort");
-        BH_TRY(radix_argsort_dev(ctx, j.tile_ids, j.isect_gids, far_max, j.slice_info + 3, gate, j.slice_info + 1, j.tile_bits, j.tile_ids_sorted,
-                                 j.isect_gids_sorted));
+        BH_TRY(radix_argsort_dev(ctx, f.tile_ids, f.isect_gids, far_max, f.slice_info + 3, gate, f.slice_info + 1, f.tile_bits, f.tile_ids_sorted,
+                                 f.isect_gids_sorted));
     }
     {
         ProfScope ps(ctx, "GetTileOffsets");
-        BH_TRY(launch_tile_offsets_dev(ctx, j.tile_ids_sorted, far_max, j.slice_info + 3, gate, j.slice_info + 1, j.num_tiles, j.tile_offsets_far));
+        BH_TRY(launch_tile_offsets_dev(ctx, f.tile_ids_sorted, far_max, f.slice_info + 3, gate, f.slice_info + 1, f.num_tiles, f.tile_offsets_far));
     }
     {
         ProfScope ps(ctx, "Rasterize");
-        BH_TRY(launch_rasterize(ctx, j.u, j.bg, j.bwd_info, j.smooth, j.isect_gids_sorted, j.tile_offsets_far, j.projected, j.gfc, j.out_f32, j.out_u8, j.visible,
-                                j.lpt, j.class_width, /*phase=*/2, &j.rs));
+        BH_TRY(launch_rasterize(ctx, f.u, f.bg, f.bwd_info, f.smooth, f.isect_gids_sorted, f.tile_offsets_far, f.projected, f.gfc, f.out_f32, f.out_u8, f.visible,
+                                f.lpt, f.class_width, /*phase=*/2, &f.rs));
     }
     ctx->far_launches++;
     return 0;

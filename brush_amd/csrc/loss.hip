@@ -190,7 +190,7 @@ static LossArgs make_args(uint32_t h, uint32_t w, const BhLossConfig& cfg, uint3
     return a;
 }
 
-int launch_image_loss_forward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
+static int launch_image_loss_forward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
                                       uint32_t channels, uint32_t h, uint32_t w, const BhLossConfig& cfg, float* loss_map) {
     if (channels != 3 && channels != 4) return set_error(ctx, BH_ERR_INVALID_ARG, "image loss: channels must be 3 or 4");
     const LossArgs a = make_args(h, w, cfg, pix_stride, ch_stride);
@@ -200,7 +200,7 @@ int launch_image_loss_forward_strided(bh_ctx* ctx, const float* pred, uint32_t p
     return 0;
 }
 
-int launch_image_loss_backward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
+static int launch_image_loss_backward_strided(bh_ctx* ctx, const float* pred, uint32_t pix_stride, uint32_t ch_stride, const uint32_t* gt,
                                        const float* dl_dmap, float dl_rgb, float dl_alpha, uint32_t channels, uint32_t h, uint32_t w,
                                        const BhLossConfig& cfg, float* dl_dpred) {
     if (channels != 3 && channels != 4) return set_error(ctx, BH_ERR_INVALID_ARG, "image loss: channels must be 3 or 4");
@@ -219,88 +219,6 @@ int launch_image_loss_forward(bh_ctx* ctx, const float* pred, const uint32_t* gt
 int launch_image_loss_backward(bh_ctx* ctx, const float* pred, const uint32_t* gt, const float* dl_dmap, float dl_const,
                                uint32_t channels, uint32_t h, uint32_t w, const BhLossConfig& cfg, float* dl_dpred) {
     return launch_image_loss_backward_strided(ctx, pred, 1, h * w, gt, dl_dmap, dl_const, dl_const, channels, h, w, cfg, dl_dpred);
-}
-
-// ---------------------------------------------------------------------------
-// deterministic sum: out = (accumulate ? out : 0) + scale * sum(x)
-// ---------------------------------------------------------------------------
-constexpr int SUM_WG = 256;
-constexpr int SUM_BLOCKS = 1024;
-
-__global__ __launch_bounds__(SUM_WG) void sum_partial_kernel(const float* __restrict__ x, uint64_t n, float* __restrict__ partial) {
-    __shared__ float s_w[SUM_WG / 64];
-    float acc = 0.0f;
-    for (uint64_t i = (uint64_t)blockIdx.x * SUM_WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SUM_WG) acc += x[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < SUM_WG / 64; ++w) t += s_w[w];
-        partial[blockIdx.x] = t;
-    }
-}
-
-__global__ __launch_bounds__(SUM_WG) void sum_final_kernel(const float* __restrict__ partial, int nb, float scale, float* __restrict__ out, int accumulate) {
-    __shared__ float s_w[SUM_WG / 64];
-    float acc = 0.0f;
-    for (int i = threadIdx.x; i < nb; i += SUM_WG) acc += partial[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < SUM_WG / 64; ++w) t += s_w[w];
-        out[0] = (accumulate ? out[0] : 0.0f) + scale * t;
-    }
-}
-
-int launch_sum(bh_ctx* ctx, const float* x, uint64_t n, float scale, float* out_scalar, bool accumulate) {
-    float* partial = (float*)ensure(ctx, SLOT_MISC, SUM_BLOCKS * sizeof(float));
-    if (!partial) return BH_ERR_OOM;
-    const int nb = (int)std::min<uint64_t>(SUM_BLOCKS, (n + SUM_WG - 1) / SUM_WG > 0 ? (n + SUM_WG - 1) / SUM_WG : 1);
-    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(SUM_WG), 0, ctx->stream, x, n, partial);
-    BH_LAUNCH_CHECK(ctx, "sum_partial_kernel");
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(SUM_WG), 0, ctx->stream, partial, nb, scale, out_scalar, accumulate ? 1 : 0);
-    BH_LAUNCH_CHECK(ctx, "sum_final_kernel");
-    return 0;
-}
-
-// layout helpers for the stand-alone (CHW) loss API
-__global__ void hwc4_to_chw_kernel(const float* __restrict__ src, uint32_t channels, uint64_t hw, float* __restrict__ dst) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= hw) return;
-    const float4 v = *reinterpret_cast<const float4*>(&src[p * 4]);
-    dst[p] = v.x;
-    dst[hw + p] = v.y;
-    dst[2 * hw + p] = v.z;
-    if (channels == 4) dst[3 * hw + p] = v.w;
-}
-__global__ void chw_to_hwc4_kernel(const float* __restrict__ src, uint32_t channels, uint64_t hw, float* __restrict__ dst) {
-    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= hw) return;
-    float4 v;
-    v.x = src[p];
-    v.y = src[hw + p];
-    v.z = src[2 * hw + p];
-    v.w = channels == 4 ? src[3 * hw + p] : 0.0f;
-    *reinterpret_cast<float4*>(&dst[p * 4]) = v;
-}
-int launch_hwc4_to_chw(bh_ctx* ctx, const float* img_hwc4, uint32_t channels, uint32_t h, uint32_t w, float* chw) {
-    const uint64_t hw = (uint64_t)h * w;
-    hipLaunchKernelGGL(hwc4_to_chw_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, ctx->stream, img_hwc4, channels, hw, chw);
-    BH_LAUNCH_CHECK(ctx, "hwc4_to_chw_kernel");
-    return 0;
-}
-int launch_chw_to_hwc4(bh_ctx* ctx, const float* chw, uint32_t channels, uint32_t h, uint32_t w, float* hwc4) {
-    const uint64_t hw = (uint64_t)h * w;
-    hipLaunchKernelGGL(chw_to_hwc4_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, ctx->stream, chw, channels, hw, hwc4);
-    BH_LAUNCH_CHECK(ctx, "chw_to_hwc4_kernel");
-    return 0;
 }
 
 }  // namespace bh

@@ -35,6 +35,20 @@ def test_set_option_validates_keys_and_values(dev):
     ctx.close()
 
 
+def test_every_listed_option_key_is_accepted_by_the_setter(dev):
+    """Every key bh_option_name lists is one bh_set_option knows: the empty string is a bad VALUE for each of them, never an
+    unknown key.  (A rejected value changes nothing, so the context needs no clean-up.)"""
+    import brush_amd as ba
+    ctx = ba.Context(dev)
+    names = [ctx.lib.bh_option_name(i).decode() for i in range(ctx.lib.bh_option_count())]
+    assert len(names) == len(set(names)) and names
+    for name in names:
+        with pytest.raises(ba.BrushHipError) as e:
+            ctx.set_option(name, "")
+        assert "bad value" in str(e.value) and "unknown key" not in str(e.value), (name, str(e.value))
+    ctx.close()
+
+
 def test_environment_translation_is_the_harness_not_the_library():
     """The Python mirror turns BH_OPTIONS / the legacy variable names into bh_set_option calls; nothing else reads them."""
     from brush_amd import host
