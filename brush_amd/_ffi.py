@@ -244,6 +244,15 @@ DEPTH_SYMBOLS = {
     "bh_render_backward_depth_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 7),
 }
 
+# every symbol include/brush_hip_pose.h declares (the pose gradient of a saved forward and the host arithmetic of a pose update)
+dp = C.POINTER(C.c_double)
+POSE_SYMBOLS = {
+    "bh_render_backward_pose_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut)] + [C.c_void_p] * 9),
+    "bh_train_set_pose_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bh_pose_twist": (C.c_int, [fp, fp, dp]),
+    "bh_camera_apply_twist": (C.c_int, [C.POINTER(BhCamera), dp]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -283,7 +292,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS))
     return _lib
 
 
@@ -292,5 +301,5 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -1112,9 +1112,10 @@ namespace bh {
 // there and clears everything itself.  span_floats != 0 (the train step): the four gradient outputs are one span of that many
 // floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
 // depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
+// v_viewmat (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined.
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth) {
+                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat) {
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
@@ -1171,6 +1172,11 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
         if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms));
+    }
+    if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
+        ProfScope ps(ctx, "PoseGrad");
+        BH_TRY(launch_pose_grad(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs, r.global_from_compact_gid,
+                                v_combined, v_viewmat));
     }
     return 0;
 }
@@ -1669,7 +1675,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // (padding included): one zero-fill, if the forward's K1 did not clear it.
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
     BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
-                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine));
+                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, /*depth=*/nullptr, ctx->pose_grad));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

@@ -77,6 +77,7 @@ enum Slot : int {
     SLOT_PLY_COMPRESS,       // bh_splat_to_compressed_ply: box partials | box | Morton keys [N] | sorted keys [N] | row order [N] (ply_compress.hip)
     SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
     SLOT_DEPTH,              // bh_render_backward_depth_saved: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip)
+    SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
     SLOT_COUNT
 };
 
@@ -375,6 +376,7 @@ struct bh_ctx {
     hipEvent_t image_tab_ev = nullptr; // ... free again once this event (behind their copy) has completed
     const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
     float lpips_weight = 0.0f;
+    float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
@@ -469,10 +471,13 @@ int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, c
 // api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth term (then K17 does not run)
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr);
+                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
 int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
 int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms);
+// project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
+int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
+                     const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);
 
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view

@@ -1061,4 +1061,161 @@ int launch_project_backward(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, boo
                : launch_pb_deg<false, false>(ctx, u, nv, sh_degree, transforms, sh, raw_opac, gid, v_combined, v_transforms, v_sh, v_raw_opac, v_refine, row_mask, projected);
 }
 
+// ---- pose gradient (brush_hip_pose.h) -------------------------------------------------------------------------
+// K18's per-splat chain once more, ending in the camera instead of the splat: with W = view_rotation, t = view_translation and
+// the SH view direction taken from p = -W^T t, a splat contributes
+//   to v_t:  v_mean_c + W v_mean_from_sh          to v_W:  v_mean_c (x) mean + 2 vcc W Sigma + t (x) v_mean_from_sh
+// (the last terms are -W v_p and -t (x) v_p with v_p = -v_mean_from_sh, folded per splat: both are linear in the sum).
+// The rows of v_combined are RasterizeGrads here (K18 has run); a row whose geometry and colour entries are all zero gives zero.
+// The twelve f32 contributions are widened to f64 and summed in a fixed order: a lane-exchange butterfly inside the wave, the
+// block's waves in wave order through LDS, one f64 row per block; pose_grad_final_kernel adds the rows in index order.
+constexpr int POSE_WAVES = PROJ_WG / 64;
+// pose_grad_final_kernel: 85 runs of consecutive rows x 12 entries = 1020 lanes.  The pass waits on memory, one dependent f64
+// add per row: at 1 M splats / 1080p (3400 rows) 16 runs took 64 us, five times K18
+constexpr int POSE_FINAL_CHUNKS = 85;
+
+BH_DEV double wave_sum_f64(double x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);   // every lane adds the same pairs in the same order
+    return x;
+}
+
+template <int DEG, bool PINHOLE>
+__global__ __launch_bounds__(PROJ_WG) void pose_grad_kernel(
+    ViewUniforms u, uint32_t nv, bool mip, const float* __restrict__ transforms, const float* __restrict__ sh_coeffs,
+    const uint32_t* __restrict__ global_from_compact_gid, const float* __restrict__ v_combined, double* __restrict__ partials) {
+    __shared__ double wave_rows[POSE_WAVES][12];
+    const uint32_t cg = blockIdx.x * PROJ_WG + threadIdx.x;
+    float c[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = 0.0f;
+    float g[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool any = false;
+    if (cg < nv) {
+        const float* rg = v_combined + (size_t)cg * 10;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { g[k] = rg[k]; any = any || (g[k] != 0.0f); }
+    }
+    if (any) {
+        constexpr int C = (DEG + 1) * (DEG + 1);
+        const uint32_t gid = global_from_compact_gid[cg];
+        float tr[10];
+        {
+            const float* trp = transforms + (size_t)gid * 10;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) tr[k] = trp[k];
+        }
+        const Vec3A mean = v3(tr[0], tr[1], tr[2]);
+        const Vec3A scl = v3(bh_expf(tr[7]), bh_expf(tr[8]), bh_expf(tr[9]));
+        const Quat q = qnormalize(Quat{tr[3], tr[4], tr[5], tr[6]});
+        const Vec3A u_world = sub(mean, camera_pos(u));
+        const float u_len = length(u_world);
+        const Vec3A v = scale(u_world, 1.0f / u_len);
+        const Vec3A v_color = v3(g[5], g[6], g[7]);
+        const Vec3A v_v_sh = sh_color_viewdir_vjp<DEG>(sh_coeffs + (size_t)gid * C * 3, v, v_color);
+        const float v_dot_vv = dot(v, v_v_sh);
+        const Vec3A v_mean_from_sh = scale(sub(v_v_sh, scale(v, v_dot_vv)), 1.0f / u_len);
+        const Vec3A mean_c = world_to_cam(mean, u);
+        const Mat3 m = mul_diag(quat_to_mat3(q), scl);
+        const Sym2 raw_cov = calc_cov2d<PINHOLE>(scl, q, mean_c, u);
+        float filter_comp;
+        const Sym2 cov = mip ? compensate_cov2d<true>(raw_cov, filter_comp) : compensate_cov2d<false>(raw_cov, filter_comp);
+        const Sym2 conic_inv = sym2_inverse(cov);
+        const Sym2 v_cov2d = inverse2x2_vjp(conic_inv, Sym2{g[2], g[3] * 0.5f, g[4]});
+        const Sym3 covar = outer_product_self(m);
+        const Mat3 view_rot = view_rotation(u);
+        const Sym3 cov_c = congruence(covar, view_rot);
+        const Mat2x3 jac = project_jacobian<PINHOLE>(mean_c, u);
+        const Vec2 v_xy = Vec2{g[0], g[1]};
+        Vec3A v_mean_c;
+        if (PINHOLE) v_mean_c = projection_vjp_pinhole(jac, mean_c, cov_c, u, v_cov2d, v_xy);
+        else if (u.model == CAM_KB4) v_mean_c = projection_vjp_kb4(jac, mean_c, cov_c, u, v_cov2d, v_xy, u.dist);
+        else if (u.model == CAM_RT8) v_mean_c = projection_vjp_rt8(mean_c, cov_c, u, v_cov2d, v_xy, u.dist);
+        else v_mean_c = projection_vjp_tpf(jac, mean_c, cov_c, u, v_cov2d, v_xy, u.dist);
+        const Sym3 vcc = transpose_congruence_sym2(jac, v_cov2d);
+        // 2 vcc W Sigma, column j = (vcc W) (row j of Sigma)
+        const Mat3 vw = sym3_mul_mat3(sym3_scale(vcc, 2.0f), view_rot);
+        const Vec3A t = view_translation(u);
+        const Vec3A w0 = add(add(scale(v_mean_c, mean.x), mul_vec3(vw, s3row0(covar))), scale(t, v_mean_from_sh.x));
+        const Vec3A w1 = add(add(scale(v_mean_c, mean.y), mul_vec3(vw, s3row1(covar))), scale(t, v_mean_from_sh.y));
+        const Vec3A w2 = add(add(scale(v_mean_c, mean.z), mul_vec3(vw, s3row2(covar))), scale(t, v_mean_from_sh.z));
+        const Vec3A vt = add(v_mean_c, mul_vec3(view_rot, v_mean_from_sh));
+        c[0] = w0.x; c[1] = w0.y; c[2] = w0.z;
+        c[3] = w1.x; c[4] = w1.y; c[5] = w1.z;
+        c[6] = w2.x; c[7] = w2.y; c[8] = w2.z;
+        c[9] = vt.x; c[10] = vt.y; c[11] = vt.z;
+    }
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const double s = wave_sum_f64((double)c[k]);
+        if (lane == 0) wave_rows[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double s = wave_rows[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < POSE_WAVES; ++w) s += wave_rows[w][threadIdx.x];
+        partials[(size_t)blockIdx.x * 12 + threadIdx.x] = s;
+    }
+}
+
+// one block: lane (chunk, k) adds entry k of its run of consecutive rows in index order, lane k then adds the runs in order
+__global__ __launch_bounds__(POSE_FINAL_CHUNKS * 12) void pose_grad_final_kernel(uint32_t rows, const double* __restrict__ partials,
+                                                                                 float* __restrict__ v_viewmat) {
+    __shared__ double runs[POSE_FINAL_CHUNKS][12];
+    const uint32_t chunk = threadIdx.x / 12u, k = threadIdx.x % 12u;
+    const uint32_t per = (rows + POSE_FINAL_CHUNKS - 1) / POSE_FINAL_CHUNKS;
+    const uint32_t r0 = chunk * per < rows ? chunk * per : rows;
+    const uint32_t r1 = r0 + per < rows ? r0 + per : rows;
+    double s = 0.0;
+    uint32_t r = r0;
+    for (; r + 4 <= r1; r += 4) {   // four loads in flight, the adds in index order
+        const double a0 = partials[(size_t)r * 12 + k], a1 = partials[(size_t)(r + 1) * 12 + k];
+        const double a2 = partials[(size_t)(r + 2) * 12 + k], a3 = partials[(size_t)(r + 3) * 12 + k];
+        s += a0; s += a1; s += a2; s += a3;
+    }
+    for (; r < r1; ++r) s += partials[(size_t)r * 12 + k];
+    runs[chunk][k] = s;
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double total = runs[0][threadIdx.x];
+#pragma unroll
+        for (int i = 1; i < POSE_FINAL_CHUNKS; ++i) total += runs[i][threadIdx.x];
+        v_viewmat[threadIdx.x] = (float)total;
+    }
+}
+
+template <bool PINHOLE>
+static int launch_pose_deg(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t deg, const float* t, const float* sh,
+                           const uint32_t* gid, const float* vc, double* partials) {
+    const dim3 grid((nv + PROJ_WG - 1) / PROJ_WG), block(PROJ_WG);
+    switch (deg) {
+        case 0: hipLaunchKernelGGL((pose_grad_kernel<0, PINHOLE>), grid, block, 0, ctx->stream, u, nv, mip, t, sh, gid, vc, partials); break;
+        case 1: hipLaunchKernelGGL((pose_grad_kernel<1, PINHOLE>), grid, block, 0, ctx->stream, u, nv, mip, t, sh, gid, vc, partials); break;
+        case 2: hipLaunchKernelGGL((pose_grad_kernel<2, PINHOLE>), grid, block, 0, ctx->stream, u, nv, mip, t, sh, gid, vc, partials); break;
+        case 3: hipLaunchKernelGGL((pose_grad_kernel<3, PINHOLE>), grid, block, 0, ctx->stream, u, nv, mip, t, sh, gid, vc, partials); break;
+        case 4: hipLaunchKernelGGL((pose_grad_kernel<4, PINHOLE>), grid, block, 0, ctx->stream, u, nv, mip, t, sh, gid, vc, partials); break;
+        default: return set_error(ctx, BH_ERR_INVALID_ARG, "sh_degree must be 0..4");
+    }
+    BH_LAUNCH_CHECK(ctx, "pose_grad_kernel");
+    return 0;
+}
+
+int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
+                     const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat) {
+    if (nv == 0) {   // an empty view: twelve zeros
+        BH_HIP(ctx, hipMemsetAsync(v_viewmat, 0, 12 * 4, ctx->stream));
+        return 0;
+    }
+    const uint32_t rows = (nv + PROJ_WG - 1) / PROJ_WG;
+    auto* partials = (double*)ensure(ctx, SLOT_POSE, (size_t)rows * 12 * 8);
+    if (!partials) return BH_ERR_OOM;
+    if (u.model == CAM_PINHOLE) BH_TRY(launch_pose_deg<true>(ctx, u, nv, mip, sh_degree, transforms, sh, gid, v_combined, partials));
+    else BH_TRY(launch_pose_deg<false>(ctx, u, nv, mip, sh_degree, transforms, sh, gid, v_combined, partials));
+    hipLaunchKernelGGL(pose_grad_final_kernel, dim3(1), dim3(POSE_FINAL_CHUNKS * 12), 0, ctx->stream, rows, partials, v_viewmat);
+    BH_LAUNCH_CHECK(ctx, "pose_grad_final_kernel");
+    return 0;
+}
+
 }  // namespace bh

@@ -281,6 +281,26 @@ class Camera:
             cam.tile_row_begin, cam.tile_row_end = int(tile_rows[0]), int(tile_rows[1])
         return cam
 
+    def apply_twist(self, twist) -> "Camera":
+        """The camera moved by the twist (omega, tau): W <- exp([omega]x) W, t <- exp([omega]x) t + tau on its world-to-camera
+        pose, by bh_camera_apply_twist on its uniforms (include/brush_hip_pose.h); position and rotation are read back from the
+        moved view matrix.  Returns a new Camera."""
+        import dataclasses
+        cam = _uniforms_apply_twist(self.uniforms((16, 16)), twist)   # (vm and cam_pos do not depend on the image size)
+        r = [[float(cam.vm[3 * i + j]) for j in range(3)] for i in range(3)]   # camera-to-world = W^T: r[i][j] = W[j][i] = vm[3 i + j]
+        q = [1 + r[0][0] - r[1][1] - r[2][2], 1 - r[0][0] + r[1][1] - r[2][2], 1 - r[0][0] - r[1][1] + r[2][2], 1 + r[0][0] + r[1][1] + r[2][2]]
+        k = q.index(max(q))   # the best-conditioned of the four quaternion extractions
+        if k == 3:
+            quat = (r[2][1] - r[1][2], r[0][2] - r[2][0], r[1][0] - r[0][1], q[3])
+        elif k == 0:
+            quat = (q[0], r[1][0] + r[0][1], r[0][2] + r[2][0], r[2][1] - r[1][2])
+        elif k == 1:
+            quat = (r[1][0] + r[0][1], q[1], r[2][1] + r[1][2], r[0][2] - r[2][0])
+        else:
+            quat = (r[0][2] + r[2][0], r[2][1] + r[1][2], q[2], r[1][0] - r[0][1])
+        n = math.sqrt(sum(v * v for v in quat))
+        return dataclasses.replace(self, position=tuple(float(v) for v in cam.cam_pos), rotation=tuple(v / n for v in quat))
+
 
 # ---------------------------------------------------------------------------
 # Splats (brush-render/src/gaussian_splats.rs:62-74)
@@ -548,8 +568,10 @@ class RenderNode:
         "median" (z where the transmittance first falls to 1/2); a forward of a tile-row window writes its rows, the rest is 0."""
         return render_depth(self, mode)
 
-    def backward(self, v_output, v_depth=None, depth_mode="expected"):
-        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>]; v_output may be None when v_depth is given."""
+    def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False):
+        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>]; v_output may be None when v_depth is given.
+        pose=True (bh_render_backward_pose_saved): also "v_viewmat", the twelve f32 of the gradient with respect to the camera's
+        view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
@@ -562,7 +584,14 @@ class RenderNode:
         v_sh = torch.empty((n, c, 3), dtype=torch.float32, device=dev)
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
-        if v_depth is not None:
+        v_vm = None
+        if pose:
+            if v_depth is not None or v_output is None:
+                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_depth)")
+            v_vm = torch.empty((12,), dtype=torch.float32, device=dev)
+            ctx.check(ctx.lib.bh_render_backward_pose_saved(ctx._h, C.byref(self.out), _ptr(v_output), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
+                                                            _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf), _ptr(v_vm)))
+        elif v_depth is not None:
             v_depth = _f32c(v_depth, dev).reshape(h, w)
             ctx.check(ctx.lib.bh_render_backward_depth_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
                                                              _ptr(v_depth), _depth_mode(depth_mode), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
@@ -573,7 +602,10 @@ class RenderNode:
         if splats.min_scale is not None:
             ctx.check(ctx.lib.bh_fold_min_scale_backward(ctx._h, _ptr(splats.transforms), _ptr(splats.raw_opacities), _ptr(splats.min_scale), n,
                                                          _ptr(v_t), _ptr(v_op)))
-        return dict(v_transforms=v_t, v_sh_coeffs=v_sh, v_raw_opacities=v_op, v_refine_weight=v_rf)
+        res = dict(v_transforms=v_t, v_sh_coeffs=v_sh, v_raw_opacities=v_op, v_refine_weight=v_rf)
+        if v_vm is not None:
+            res["v_viewmat"] = v_vm
+        return res
 
     def release(self):
         if self.retained:
@@ -615,6 +647,93 @@ def render_splats_diff(splats: Splats, camera, img_size, background=(0.0, 0.0, 0
     if retain:
         ctx.check(ctx.lib.bh_render_retain(ctx._h, C.byref(out)))
     return RenderNode(ctx, splats, out, folded, (w, h), bool(retain))
+
+
+# ---------------------------------------------------------------------------
+# Camera pose refinement (include/brush_hip_pose.h)
+# ---------------------------------------------------------------------------
+def pose_twist(vm, v_viewmat):
+    """(v_omega, v_tau) [6] f64 of a view-matrix gradient (bh_pose_twist): the derivative of the loss along
+    W <- exp([omega]x) W, t <- exp([omega]x) t + tau at zero.  `vm`, `v_viewmat`: twelve floats, column-major 3x4."""
+    import numpy as np
+    a = (C.c_float * 12)(*[float(v) for v in vm])
+    b = (C.c_float * 12)(*[float(v) for v in v_viewmat])
+    out = (C.c_double * 6)()
+    if _ffi.load().bh_pose_twist(a, b, out) != 0:
+        raise BrushHipError("bh_pose_twist failed")
+    return np.array(list(out), np.float64)
+
+
+def _uniforms_apply_twist(cam: "_ffi.BhCamera", twist) -> "_ffi.BhCamera":
+    """A copy of the uniforms `cam` moved by the twist (bh_camera_apply_twist rewrites vm and cam_pos together)."""
+    out = _ffi.BhCamera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(out))
+    tw = (C.c_double * 6)(*[float(v) for v in twist])
+    if _ffi.load().bh_camera_apply_twist(C.byref(out), tw) != 0:
+        raise BrushHipError("bh_camera_apply_twist failed")
+    return out
+
+
+class PoseOptimizer:
+    """Adam on a 6-vector (omega, tau) per view id, on the host in f64: the view's camera is its dataset camera moved by that
+    twist (Camera.apply_twist / bh_camera_apply_twist).  The gradient is the twist of v_viewmat at the current pose (pose_twist),
+    which is the gradient with respect to the 6-vector to first order in it.
+
+    One step of a view: `camera(view_id, base, img_size)` gives the uniforms to render, `update(view_id, vm, v_viewmat)` takes the
+    twelve floats read back after the backward (48 bytes, one synchronisation of the stream the backward ran on: `step` does it).  A camera
+    that moves every step must not key the per-view tile-cut tables by its hash, which would mint a table per step: `bind`
+    names the view with bh_set_view_id, and SplatTrainer passes the batch's view_id."""
+
+    def __init__(self, lr_rotation=1e-3, lr_translation=1e-3, beta1=0.9, beta2=0.999, eps=1e-12):
+        self.lr_rotation, self.lr_translation = float(lr_rotation), float(lr_translation)
+        self.beta1, self.beta2, self.eps = float(beta1), float(beta2), float(eps)
+        self.views = {}   # view id -> dict(twist [6], m1 [6], m2 [6], t)
+
+    def _state(self, view_id):
+        import numpy as np
+        view_id = int(view_id)
+        if view_id <= 0:
+            raise ValueError("PoseOptimizer: a view id > 0 names the view (0 = unknown)")
+        if view_id not in self.views:
+            self.views[view_id] = dict(twist=np.zeros(6), m1=np.zeros(6), m2=np.zeros(6), t=0)
+        return self.views[view_id]
+
+    def twist(self, view_id):
+        return self._state(view_id)["twist"].copy()
+
+    def camera(self, view_id, base, img_size=None) -> "_ffi.BhCamera":
+        """The uniforms of view `view_id` at its current correction; `base`: its dataset Camera (with img_size) or BhCamera."""
+        if not isinstance(base, _ffi.BhCamera):
+            base = base.uniforms(img_size)
+        return _uniforms_apply_twist(base, self._state(view_id)["twist"])
+
+    def bind(self, ctx, view_id, base, img_size=None) -> "_ffi.BhCamera":
+        """camera(), and names the view on `ctx` for the forwards that follow (bh_set_view_id)."""
+        ctx.check(ctx.lib.bh_set_view_id(ctx._h, int(view_id)))
+        return self.camera(view_id, base, img_size)
+
+    def update(self, view_id, vm, v_viewmat):
+        """One Adam step of the view's 6-vector on the twist of `v_viewmat` [12] at the rendered pose `vm` [12]."""
+        import numpy as np
+        s = self._state(view_id)
+        g = pose_twist(vm, v_viewmat)
+        s["t"] += 1
+        s["m1"] = self.beta1 * s["m1"] + (1.0 - self.beta1) * g
+        s["m2"] = self.beta2 * s["m2"] + (1.0 - self.beta2) * g * g
+        m1 = s["m1"] / (1.0 - self.beta1 ** s["t"])
+        m2 = s["m2"] / (1.0 - self.beta2 ** s["t"])
+        lr = np.array([self.lr_rotation] * 3 + [self.lr_translation] * 3)
+        s["twist"] = s["twist"] - lr * m1 / (np.sqrt(m2) + self.eps)
+        return g
+
+    def step(self, view_id, vm, v_viewmat_dev, ctx: Optional["Context"] = None):
+        """update() on a device tensor of twelve floats the backward on `ctx` wrote: the 48-byte readback waits for the stream that
+        wrote them — torch's current stream, which the copy synchronises, or the ctx's own (Context(use_torch_stream=False)),
+        which is synchronised first.  Pass the ctx the backward ran on (None = the device's default context)."""
+        ctx = ctx or get_context(v_viewmat_dev.device)
+        if not ctx.uses_torch_stream:
+            ctx.sync()
+        return self.update(view_id, vm, v_viewmat_dev.detach().cpu().numpy().astype("float64"))
 
 
 # ---------------------------------------------------------------------------
@@ -1185,7 +1304,7 @@ class SplatTrainer:
 
     def __init__(self, config: TrainConfig, median_scene_scale: float = 1.0, process_group=None, ctx: Optional[Context] = None,
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
-                 allreduce: str = "ring", lpips: Optional["Lpips"] = None):
+                 allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -1197,9 +1316,18 @@ class SplatTrainer:
         all-gathered before the loss and the partial gradients summed.
 
         lpips: the LpipsModel the step uses when config.lpips_loss_weight > 0 (train.rs:153, 265-273; bh_train_set_lpips).
-        Not with partition "tiles"."""
+        Not with partition "tiles".
+
+        pose_optimizer: a PoseOptimizer that refines the batches' cameras beside the splats (bh_train_set_pose_grad): every step
+        renders the batch's view at its current correction, reads the step's twelve pose-gradient floats back (48 bytes, one
+        synchronisation per step) and updates that view's 6-vector.  Batches must carry a view_id > 0.  Not with partition
+        "tiles"."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
+        if pose_optimizer is not None and partition == "tiles":
+            raise ValueError("pose_optimizer is not available with partition 'tiles'")
+        self.pose_optimizer = pose_optimizer
+        self._pose_buf = None
         if allreduce not in ("ring", "direct"):
             raise ValueError("allreduce must be 'ring' (all_reduce / ncclAllReduce) or 'direct' (reduce-scatter + all-gather over point-to-point messages)")
         # how long messages of the gradient exchange are summed: the collective library's all-reduce, or the direct algorithm for a
@@ -1401,6 +1529,13 @@ class SplatTrainer:
         stats = _ffi.BhTrainStats()
         b.exchange_mode = 1 if (self.sparse_exchange and (self.pg is not None or self.native_comm)) else 0
         b.view_id = int(getattr(batch, "view_id", 0)) & 0xFFFFFFFF
+        po = self.pose_optimizer
+        if po is not None:   # the view at its current correction, named by its id (a moving camera's hash would mint a view table per step)
+            b.camera = po.camera(b.view_id, b.camera)
+            if self._pose_buf is None:
+                self._pose_buf = torch.zeros((12,), dtype=torch.float32, device=dev)
+                if not ctx.uses_torch_stream:
+                    torch.cuda.current_stream(dev).synchronize()   # the zero-fill ran on torch's stream, the step runs on the ctx's own
         hook, scale = None, 1.0
         if self.native_comm:
             scale = 1.0 if tiles else 1.0 / ctx.comm_world()
@@ -1415,8 +1550,16 @@ class SplatTrainer:
             raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
         # the term is ctx state (bh_train_set_lpips): set it for THIS trainer's step, whatever another trainer on the ctx left
         ctx.check(ctx.lib.bh_train_set_lpips(ctx._h, self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0))
-        ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
-                                        float(scale), C.byref(stats)))
+        if po is not None:
+            ctx.check(ctx.lib.bh_train_set_pose_grad(ctx._h, _ptr(self._pose_buf)))
+        try:
+            ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
+                                            float(scale), C.byref(stats)))
+        finally:
+            if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
+                ctx.lib.bh_train_set_pose_grad(ctx._h, None)
+        if po is not None:
+            po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
         self.step_count = st.step_count
         self._last_stats = stats
         self._keep = (gt, ns)

@@ -24,6 +24,8 @@
 //   brush_hip::knn_log_scales / to_init_splats / load_init_splats   brush-train/src/splat_init.rs:179-242, train_stream.rs:100-123
 //   brush_hip::eval_metrics / eval_stats / run_eval   brush-train/src/eval.rs:23-63, train_stream.rs:506-566 (held-out PSNR / SSIM)
 //   brush_hip::Lpips / lpips / lpips_value_and_grad / train_set_lpips   crates/lpips/src/lib.rs, train.rs:265-273 (lpips_loss_weight)
+//   RenderNode::backward_pose / train_set_pose_grad / pose_twist / camera_apply_twist   not in the reference: camera pose
+//                                                   gradients (gsplat's v_viewmats) and the host arithmetic of a pose update
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -50,6 +52,7 @@
 #include "brush_hip_compressed_ply.h"
 #include "brush_hip_image.h"
 #include "brush_hip_depth.h"
+#include "brush_hip_pose.h"
 
 namespace brush_hip {
 
@@ -432,6 +435,23 @@ class RenderNode {
         g.v_refine_weight.resize(n);
         ctx_.check(bh_render_backward_depth_saved(ctx_.get(), &aux.raw, v_output, v_depth, mode, folded_.t, splats_.sh_coeffs.data(), folded_.o,
                                                   g.v_transforms.data(), g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
+        if (splats_.min_scale)
+            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
+                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
+        ctx_.sync();
+        return g;
+    }
+    // gradients of <v_output, image> and, into v_viewmat (device, 12 floats in the layout of BhCamera.vm), its gradient with respect
+    // to the camera's view matrix (brush_hip_pose.h); the four splat outputs are backward(v_output)'s
+    SplatGrads backward_pose(const float* v_output, float* v_viewmat) const {
+        const uint32_t n = splats_.num_splats();
+        SplatGrads g;
+        g.v_transforms.resize((size_t)n * 10);
+        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
+        g.v_raw_opacities.resize(n);
+        g.v_refine_weight.resize(n);
+        ctx_.check(bh_render_backward_pose_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(),
+                                                 g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data(), v_viewmat));
         if (splats_.min_scale)
             ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
                                                   g.v_transforms.data(), g.v_raw_opacities.data()));
@@ -1093,6 +1113,20 @@ inline void lpips_value_and_grad(const Context& ctx, const Lpips& model, const f
 // bh_train_step on this ctx adds weight * LPIPS (model == nullptr or weight 0: detached)
 inline void train_set_lpips(const Context& ctx, const Lpips* model, float weight) {
     ctx.check(bh_train_set_lpips(ctx.get(), model ? model->get() : nullptr, weight));
+}
+
+// ---- camera pose gradients (brush_hip_pose.h; not in the reference) ---------------------------------------------------------------
+// bh_train_step on this ctx writes the step's pose gradient into v_viewmat (device, 12 floats); nullptr detaches
+inline void train_set_pose_grad(const Context& ctx, float* v_viewmat) { ctx.check(bh_train_set_pose_grad(ctx.get(), v_viewmat)); }
+// (v_omega, v_tau) of a view-matrix gradient at the pose vm, in f64 on the host
+inline std::array<double, 6> pose_twist(const float vm[12], const float v_viewmat[12]) {
+    std::array<double, 6> t{};
+    if (bh_pose_twist(vm, v_viewmat, t.data()) != 0) throw Error(BH_ERR_INVALID_ARG, "pose_twist: null argument");
+    return t;
+}
+// W <- exp([omega]x) W, t <- exp([omega]x) t + tau on the uniforms, vm and cam_pos together
+inline void camera_apply_twist(BhCamera& cam, const std::array<double, 6>& twist) {
+    if (bh_camera_apply_twist(&cam, twist.data()) != 0) throw Error(BH_ERR_INVALID_ARG, "camera_apply_twist: null argument, a degenerate view matrix or a twist that is not finite");
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
