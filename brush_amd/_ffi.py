@@ -253,6 +253,21 @@ POSE_SYMBOLS = {
     "bh_camera_apply_twist": (C.c_int, [C.POINTER(BhCamera), dp]),
 }
 
+# every symbol include/brush_hip_exposure.h declares (per-view exposure compensation: a device table of affine colour transforms)
+EXPOSURE_SYMBOLS = {
+    "bh_exposure_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_exposure_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bh_exposure_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_exposure_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_exposure_get_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_exposure_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, dp, dp, u32p]),
+    "bh_exposure_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, dp, dp, C.c_uint32]),
+    "bh_exposure_set_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bh_exposure_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_exposure_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "bh_train_set_exposure": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -292,7 +307,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS))
     return _lib
 
 
@@ -301,5 +316,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **TEST_HOOK_SYMBOLS))
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS,
+                                                   **TEST_HOOK_SYMBOLS))
     return _lib_th

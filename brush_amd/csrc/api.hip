@@ -294,6 +294,7 @@ void bh_destroy(bh_ctx* ctx) {
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
     if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);
     if (ctx->image_tab_ev) (void)hipEventDestroy(ctx->image_tab_ev);
+    bh::exposure_free_all(ctx);
     if (ctx->comm) (void)bh_comm_destroy(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1474,6 +1475,15 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         !st->m2_sh || !st->m1_opac || !st->m2_opac || !st->refine_weight_norm || !st->vis_weight || !st->max_screen_size ||
         !batch->gt_packed)
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null state tensor");
+    // an exposure table (brush_hip_exposure.h): the batch's view names the row, and the term needs the whole frame on this rank
+    bh_exposure* const exposure = ctx->exposure;
+    if (exposure) {
+        if (batch->view_id == 0u || batch->view_id > exposure_views(exposure))
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with an exposure table the batch's view_id must be 1 .. n_views");
+        const ViewUniforms eu = make_uniforms(batch->camera);
+        if (batch->image_hook || eu.tile_y0 != 0u || eu.tile_y1 != eu.tile_bh)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the exposure term needs the whole frame on this rank (no tile-row partition)");
+    }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
     const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
@@ -1573,6 +1583,9 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     auto* v_output = (float*)ensure(ctx, SLOT_V_OUTPUT, hw * 16);
     auto* loss_dev = (float*)ensure(ctx, SLOT_LOSS_SCALAR, 16);
     if (!v_output || !loss_dev) return BH_ERR_OOM;
+    // with an exposure table the loss reads the exposed frame from a slot of its own: out_img is what K17 replays from
+    float* exposed = nullptr;
+    if (exposure && !(exposed = (float*)ensure(ctx, SLOT_EXPOSED, hw * 16))) return BH_ERR_OOM;
     // the loss scalar goes straight into pinned host memory (bh_sync hands it to stats->loss): no copy launch
     float* loss_host = reinterpret_cast<float*>(ctx->host_counters) + HOST_LOSS_WORD;
     const float dl_rgb = 1.0f / (float)(hw * 3);
@@ -1594,7 +1607,11 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
             return launch_image_loss_fused_window(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, wu.tile_y0, wu.tile_y1,
                                                   loss_dev, v_output, loss_host, started_host, started_tag);
         }
-        return launch_image_loss_fused(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
+        if (exposed) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
+            ProfScope ps(ctx, "Exposure");
+            BH_TRY(launch_exposure_apply(ctx, exposure, batch->view_id, ro.out_img, H, W, exposed));
+        }
+        return launch_image_loss_fused(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
                                        started_tag);
     };
 #ifdef BH_TEST_HOOKS
@@ -1619,7 +1636,12 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     }
     // ---- LPIPS (train.rs:265-273): on the frame's final image, GT composited as the loss above does it; loss and dL/dimg grow
     // in place on the device (no host wait)
-    if (lpips_on) BH_TRY(lpips_train_term(ctx, ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
+    if (lpips_on) BH_TRY(lpips_train_term(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
+    // ---- exposure backward: v_output becomes A^T v' in place (x = the frame as rendered), the view's row takes its Adam step
+    if (exposed) {
+        ProfScope ps(ctx, "Exposure");
+        BH_TRY(launch_exposure_backward(ctx, exposure, batch->view_id, ro.out_img, v_output, H, W, v_output, /*update=*/true));
+    }
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
     // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling

@@ -12,6 +12,7 @@
 #include "../../include/brush_hip.h"
 #include "../../include/brush_hip_lpips.h"
 #include "../../include/brush_hip_image.h"
+#include "../../include/brush_hip_exposure.h"
 #include "device_math.h"
 
 namespace bh {
@@ -78,6 +79,8 @@ enum Slot : int {
     SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
     SLOT_DEPTH,              // bh_render_backward_depth_saved: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip)
     SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
+    SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
+    SLOT_EXPOSED,            // bh_train_step with an exposure table: [H,W,4] the exposed frame the loss reads (out_img stays as rendered)
     SLOT_COUNT
 };
 
@@ -377,6 +380,8 @@ struct bh_ctx {
     const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
     float lpips_weight = 0.0f;
     float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
+    bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
+    std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
@@ -478,6 +483,13 @@ int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transf
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
                      const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);
+// exposure.hip: y = A x + b with the row of `view` (1 .. exposure_views), and its backward: v_img = A^T v_exposed (in place
+// allowed), grad[view] = v_m, and one Adam step of the row when `update` (brush_hip_exposure.h).  The view is already checked.
+uint32_t exposure_views(const bh_exposure* tab);
+int launch_exposure_apply(bh_ctx* ctx, const bh_exposure* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out);
+int launch_exposure_backward(bh_ctx* ctx, bh_exposure* tab, uint32_t view, const float* img, const float* v_exposed, uint32_t h, uint32_t w,
+                             float* v_img, bool update);
+void exposure_free_all(bh_ctx* ctx);   // bh_destroy
 
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view

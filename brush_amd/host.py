@@ -737,6 +737,113 @@ class PoseOptimizer:
 
 
 # ---------------------------------------------------------------------------
+# Per-view exposure compensation (include/brush_hip_exposure.h)
+# ---------------------------------------------------------------------------
+class ExposureTable:
+    """A device table of one affine colour transform m[12] (row-major 3x4, column 3 the offset) per training view, with its Adam
+    moments and update on the device (bh_exposure_*): y = A x + b on the rasterizer's image before the loss.  Views are numbered
+    from 1 (row i is view id i + 1, as SceneLoader numbers them).  Nothing here reads back except the getters (`params`, `grads`,
+    `state`).  SplatTrainer(exposure=table) attaches it to the train step.  Data parallel over cameras: the table is per process,
+    nothing is all-reduced, a view must stay with one rank."""
+
+    def __init__(self, n_views, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, ctx: Optional[Context] = None):
+        ctx = ctx or get_context()
+        self.ctx, self.lib, self.n_views = ctx, ctx.lib, int(n_views)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.bh_exposure_create(ctx._h, self.n_views, C.byref(h)))
+        self._h = h
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
+        self.set_lr(lr)
+
+    def set_lr(self, lr):
+        """The learning rate of every following update (bh_exposure_set_adam); 0 freezes the rows while their moments still move."""
+        self.ctx.check(self.lib.bh_exposure_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
+        self.lr = float(lr)
+
+    def _get(self, fn):
+        import numpy as np
+        out = np.empty((self.n_views, 12), np.float32)
+        self.ctx.check(fn(self.ctx._h, self._h, 1, self.n_views, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    @property
+    def params(self):
+        """[V,12] f32 numpy copy of every row (one synchronisation); assign an array of the same shape to set them."""
+        return self._get(self.lib.bh_exposure_get_params)
+
+    @params.setter
+    def params(self, value):
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(value, np.float32))
+        if a.shape != (self.n_views, 12):
+            raise ValueError("params must be [%d, 12]" % self.n_views)
+        self.ctx.check(self.lib.bh_exposure_set_params(self.ctx._h, self._h, 1, self.n_views, a.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_view(self, view, m):
+        """Row `view` (from 1) = the twelve floats m."""
+        a = (C.c_float * 12)(*[float(v) for v in m])
+        self.ctx.check(self.lib.bh_exposure_set_params(self.ctx._h, self._h, int(view), 1, a))
+
+    @property
+    def grads(self):
+        """[V,12] f32: the last v_m written for each row (zeros for a row no backward has touched)."""
+        return self._get(self.lib.bh_exposure_get_grad)
+
+    def state(self, view):
+        """(m1 [12] f64, m2 [12] f64, t) of row `view`: its Adam moments and step count."""
+        import numpy as np
+        m1, m2, t = np.empty(12, np.float64), np.empty(12, np.float64), C.c_uint32()
+        dp = C.POINTER(C.c_double)
+        self.ctx.check(self.lib.bh_exposure_get_state(self.ctx._h, self._h, int(view), m1.ctypes.data_as(dp), m2.ctypes.data_as(dp), C.byref(t)))
+        return m1, m2, int(t.value)
+
+    def set_state(self, view, m1, m2, t):
+        """Puts a row's Adam state back (resuming from a checkpoint)."""
+        import numpy as np
+        a, b = np.ascontiguousarray(m1, np.float64).reshape(12), np.ascontiguousarray(m2, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        self.ctx.check(self.lib.bh_exposure_set_state(self.ctx._h, self._h, int(view), a.ctypes.data_as(dp), b.ctypes.data_as(dp), int(t)))
+
+    def apply(self, view, img, out=None):
+        """y = A x + b of `img` [H,W,4] f32 with row `view`; `out` may be `img` (in place)."""
+        img = _aligned_hwc4(img, img.device)
+        if out is None:
+            out = torch.empty_like(img)
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        self.ctx.check(self.lib.bh_exposure_apply(self.ctx._h, self._h, int(view), _ptr(img), h, w, _ptr(out)))
+        return out
+
+    def backward(self, view, img, v_exposed, update=False, out=None):
+        """v_img = A^T v_exposed (`out` may be `v_exposed`), grads[view] = v_m of (img, v_exposed), and with `update` one Adam
+        step of row `view` on it."""
+        img = _aligned_hwc4(img, img.device)
+        v = _aligned_hwc4(v_exposed, img.device)
+        if v.shape != img.shape:
+            raise ValueError("v_exposed must have the shape of img")
+        if out is None:
+            out = torch.empty_like(v)
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        self.ctx.check(self.lib.bh_exposure_backward(self.ctx._h, self._h, int(view), _ptr(img), _ptr(v), h, w, _ptr(out), 1 if update else 0))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):   # (a closed context has freed its tables)
+                self.lib.bh_exposure_destroy(self.ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------
 # PLY at the edges (brush-serde)
 # ---------------------------------------------------------------------------
 def splat_to_ply(splats: Splats, up_axis=None, ctx: Optional[Context] = None) -> bytes:
@@ -1304,7 +1411,8 @@ class SplatTrainer:
 
     def __init__(self, config: TrainConfig, median_scene_scale: float = 1.0, process_group=None, ctx: Optional[Context] = None,
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
-                 allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None):
+                 allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None,
+                 exposure: Optional["ExposureTable"] = None, exposure_lr=None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -1321,13 +1429,21 @@ class SplatTrainer:
         pose_optimizer: a PoseOptimizer that refines the batches' cameras beside the splats (bh_train_set_pose_grad): every step
         renders the batch's view at its current correction, reads the step's twelve pose-gradient floats back (48 bytes, one
         synchronisation per step) and updates that view's 6-vector.  Batches must carry a view_id > 0.  Not with partition
+        "tiles".
+
+        exposure: an ExposureTable (bh_train_set_exposure): every step exposes its frame with the row of the batch's view_id
+        (1 .. n_views) before the loss and updates that row on the device: no readback, no synchronisation.  exposure_lr: an
+        optional callable of the step number (from 1) giving the table's learning rate for that step.  Not with partition
         "tiles"."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if pose_optimizer is not None and partition == "tiles":
             raise ValueError("pose_optimizer is not available with partition 'tiles'")
+        if exposure is not None and partition == "tiles":
+            raise ValueError("exposure is not available with partition 'tiles'")
         self.pose_optimizer = pose_optimizer
         self._pose_buf = None
+        self.exposure, self.exposure_lr = exposure, exposure_lr
         if allreduce not in ("ring", "direct"):
             raise ValueError("allreduce must be 'ring' (all_reduce / ncclAllReduce) or 'direct' (reduce-scatter + all-gather over point-to-point messages)")
         # how long messages of the gradient exchange are summed: the collective library's all-reduce, or the direct algorithm for a
@@ -1552,12 +1668,19 @@ class SplatTrainer:
         ctx.check(ctx.lib.bh_train_set_lpips(ctx._h, self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0))
         if po is not None:
             ctx.check(ctx.lib.bh_train_set_pose_grad(ctx._h, _ptr(self._pose_buf)))
+        ex = self.exposure
+        if ex is not None:
+            if self.exposure_lr is not None:
+                ex.set_lr(self.exposure_lr(self.step_count + 1))
+            ctx.check(ctx.lib.bh_train_set_exposure(ctx._h, ex._h))
         try:
             ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                             float(scale), C.byref(stats)))
         finally:
             if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
+            if ex is not None:
+                ctx.lib.bh_train_set_exposure(ctx._h, None)
         if po is not None:
             po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
         self.step_count = st.step_count

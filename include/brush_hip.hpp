@@ -26,6 +26,8 @@
 //   brush_hip::Lpips / lpips / lpips_value_and_grad / train_set_lpips   crates/lpips/src/lib.rs, train.rs:265-273 (lpips_loss_weight)
 //   RenderNode::backward_pose / train_set_pose_grad / pose_twist / camera_apply_twist   not in the reference: camera pose
 //                                                   gradients (gsplat's v_viewmats) and the host arithmetic of a pose update
+//   brush_hip::ExposureTable / train_set_exposure   not in the reference: per-view exposure compensation (an affine colour
+//                                                   transform per training view, Adam on the device; brush_hip_exposure.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -53,6 +55,7 @@
 #include "brush_hip_image.h"
 #include "brush_hip_depth.h"
 #include "brush_hip_pose.h"
+#include "brush_hip_exposure.h"
 
 namespace brush_hip {
 
@@ -1127,6 +1130,65 @@ inline std::array<double, 6> pose_twist(const float vm[12], const float v_viewma
 // W <- exp([omega]x) W, t <- exp([omega]x) t + tau on the uniforms, vm and cam_pos together
 inline void camera_apply_twist(BhCamera& cam, const std::array<double, 6>& twist) {
     if (bh_camera_apply_twist(&cam, twist.data()) != 0) throw Error(BH_ERR_INVALID_ARG, "camera_apply_twist: null argument, a degenerate view matrix or a twist that is not finite");
+}
+
+// ---- per-view exposure compensation (brush_hip_exposure.h; not in the reference) ---------------------------------------------------
+// A device table of one affine colour transform m[12] (row-major 3x4, column 3 the offset) per training view, with Adam on the
+// device (bh_exposure_*).  Views are numbered from 1.  Move-only; destroy it before its Context (a Context that dies first frees
+// the table itself, and this handle must then not be used).  Only the getters read back.
+class ExposureTable {
+public:
+    ExposureTable(const Context& ctx, uint32_t n_views, double lr = 1e-3, double beta1 = 0.9, double beta2 = 0.999, double eps = 1e-8)
+        : ctx_(&ctx), n_(n_views), beta1_(beta1), beta2_(beta2), eps_(eps) {
+        ctx.check(bh_exposure_create(ctx.get(), n_views, &h_));
+        set_lr(lr);
+    }
+    ExposureTable(const ExposureTable&) = delete;
+    ExposureTable& operator=(const ExposureTable&) = delete;
+    ExposureTable(ExposureTable&& o) noexcept : ctx_(o.ctx_), h_(o.h_), n_(o.n_), beta1_(o.beta1_), beta2_(o.beta2_), eps_(o.eps_) { o.h_ = nullptr; }
+    ~ExposureTable() { if (h_) (void)bh_exposure_destroy(ctx_->get(), h_); }
+    bh_exposure* get() const { return h_; }
+    uint32_t n_views() const { return n_; }
+    void set_lr(double lr) { ctx_->check(bh_exposure_set_adam(ctx_->get(), h_, lr, beta1_, beta2_, eps_)); }
+    // every row, [V,12] on the host (one synchronisation each)
+    std::vector<float> params() const {
+        std::vector<float> out((size_t)n_ * 12);
+        ctx_->check(bh_exposure_get_params(ctx_->get(), h_, 1, n_, out.data()));
+        return out;
+    }
+    std::vector<float> grads() const {
+        std::vector<float> out((size_t)n_ * 12);
+        ctx_->check(bh_exposure_get_grad(ctx_->get(), h_, 1, n_, out.data()));
+        return out;
+    }
+    void set_params(const std::vector<float>& rows, uint32_t first_view = 1) {
+        ctx_->check(bh_exposure_set_params(ctx_->get(), h_, first_view, (uint32_t)(rows.size() / 12), rows.data()));
+    }
+    struct State { std::array<double, 12> m1, m2; uint32_t t; };
+    State state(uint32_t view) const {
+        State s{};
+        ctx_->check(bh_exposure_get_state(ctx_->get(), h_, view, s.m1.data(), s.m2.data(), &s.t));
+        return s;
+    }
+    void set_state(uint32_t view, const State& s) { ctx_->check(bh_exposure_set_state(ctx_->get(), h_, view, s.m1.data(), s.m2.data(), s.t)); }
+    // out = A x + b of img [h,w,4] (device) with the row of `view`; out may be img
+    void apply(uint32_t view, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) const {
+        ctx_->check(bh_exposure_apply(ctx_->get(), h_, view, img_hwc4, h, w, out_hwc4));
+    }
+    // v_img = A^T v_exposed (may be in place), grads[view] = v_m, and with `update` one Adam step of the row
+    void backward(uint32_t view, const float* img_hwc4, const float* v_exposed, uint32_t h, uint32_t w, float* v_img, bool update = false) {
+        ctx_->check(bh_exposure_backward(ctx_->get(), h_, view, img_hwc4, v_exposed, h, w, v_img, update ? 1 : 0));
+    }
+
+private:
+    const Context* ctx_;
+    bh_exposure* h_ = nullptr;
+    uint32_t n_;
+    double beta1_, beta2_, eps_;
+};
+// bh_train_step on this ctx exposes its frame with the row of the batch's view_id and updates that row; nullptr detaches
+inline void train_set_exposure(const Context& ctx, const ExposureTable* table) {
+    ctx.check(bh_train_set_exposure(ctx.get(), table ? table->get() : nullptr));
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
