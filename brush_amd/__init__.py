@@ -32,6 +32,9 @@ Names and argument meaning follow the reference (paths under
                                          optimizer (not in the reference; gsplat's v_viewmats)
     ExposureTable / SplatTrainer(exposure=)   per-view exposure compensation: an affine colour transform per training view with
                                          Adam on the device (not in the reference; the INRIA trainer's exposure)
+    depth_loss_value_and_grad / eval_depth_metrics / SceneBatch(depth=) / TrainConfig.depth_loss_weight   depth supervision: a fused
+                                         depth loss, a depth term in the step, held-out depth metrics (not in the reference; the INRIA
+                                         trainer's depth regularisation, gsplat's depth_loss)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -44,6 +47,6 @@ from .host import (  # noqa: F401
     render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
     knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
     Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
-    PoseOptimizer, pose_twist, ExposureTable,
+    PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -268,6 +268,21 @@ EXPOSURE_SYMBOLS = {
     "bh_train_set_exposure": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/brush_hip_depth_loss.h declares (depth supervision: the fused depth loss, the step's depth term, depth metrics)
+DEPTH_LOSS_L1, DEPTH_LOSS_DISPARITY = 0, 1   # BH_DEPTH_LOSS_*
+
+
+class BhDepthTarget(C.Structure):
+    _fields_ = [("gt", C.c_void_p), ("h", C.c_uint32), ("w", C.c_uint32), ("kind", C.c_uint32), ("weight", C.c_float),
+                ("scale", C.c_float), ("offset", C.c_float)]
+
+
+DEPTH_LOSS_SYMBOLS = {
+    "bh_depth_loss_value_and_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhDepthTarget), C.c_void_p, C.c_void_p]),
+    "bh_train_set_depth": (C.c_int, [C.c_void_p, C.POINTER(BhDepthTarget)]),
+    "bh_eval_depth_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhDepthTarget), C.c_void_p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -307,7 +322,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS))
     return _lib
 
 
@@ -316,6 +331,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -1172,7 +1172,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         BH_TRY(launch_project_backward(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs,
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
-        if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms));
+        if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
     }
     if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
         ProfScope ps(ctx, "PoseGrad");
@@ -1484,6 +1484,19 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (batch->image_hook || eu.tile_y0 != 0u || eu.tile_y1 != eu.tile_bh)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the exposure term needs the whole frame on this rank (no tile-row partition)");
     }
+    // a depth target (brush_hip_depth_loss.h): refused before anything is queued; weight <= 0 is no term at all
+    const BhDepthTarget* const depth_target = (ctx->depth_attached && ctx->depth_target.weight > 0.0f) ? &ctx->depth_target : nullptr;
+    if (depth_target) {
+        if (!depth_target->gt) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth target has no depth map");
+        if (depth_target->h != batch->camera.img_h || depth_target->w != batch->camera.img_w)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth target's size differs from the camera's");
+        if (depth_target->kind > BH_DEPTH_LOSS_DISPARITY) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: unknown depth loss kind");
+        const ViewUniforms du = make_uniforms(batch->camera);
+        if (batch->image_hook || du.tile_y0 != 0u || du.tile_y1 != du.tile_bh)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth term needs the whole frame on this rank (no tile-row partition)");
+        if (ctx->pose_grad)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a depth target and a pose-gradient buffer cannot be attached together (the pose pass does not carry the depth term's gradient)");
+    }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
     const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
@@ -1643,6 +1656,22 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         BH_TRY(launch_exposure_backward(ctx, exposure, batch->view_id, ro.out_img, v_output, H, W, v_output, /*update=*/true));
     }
 
+    // ---- depth term (brush_hip_depth_loss.h): the frame is final here — a second attempt with complete lists has replaced it, if
+    // there was one — so the expected depth is that of the state the backward replays.  E and v_depth live in a slot of their own
+    // until the backward (SLOT_DEPTH is the depth backward's scratch and may move).  loss += the term's, in f32, behind LPIPS.
+    DepthTerm depth_term;
+    const bool depth_on = depth_target != nullptr && ctx->latest.out.num_intersections > 0 && n > 0;   // (an empty frame has no valid pixel)
+    if (depth_on) {
+        ProfScope ps(ctx, "DepthTerm");
+        auto* e_map = (float*)ensure(ctx, SLOT_DEPTH_TERM, (hw * 2 + 4) * 4);
+        if (!e_map) return BH_ERR_OOM;
+        float* v_depth = e_map + hw;
+        BH_TRY(launch_depth_forward(ctx, ctx->latest, BH_DEPTH_EXPECTED, e_map));
+        BH_TRY(launch_depth_loss(ctx, e_map, *depth_target, v_depth + hw, v_depth, loss_dev, loss_host));
+        depth_term.v_depth = v_depth;
+        depth_term.mode = BH_DEPTH_EXPECTED;
+    }
+
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
     // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling
     // to the host NOW — the backward hides the collective's latency and the readback, and the host finds the count ready
@@ -1697,7 +1726,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // (padding included): one zero-fill, if the forward's K1 did not clear it.
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
     BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
-                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, /*depth=*/nullptr, ctx->pose_grad));
+                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, depth_on ? &depth_term : nullptr, ctx->pose_grad));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

@@ -13,6 +13,7 @@
 #include "../../include/brush_hip_lpips.h"
 #include "../../include/brush_hip_image.h"
 #include "../../include/brush_hip_exposure.h"
+#include "../../include/brush_hip_depth_loss.h"
 #include "device_math.h"
 
 namespace bh {
@@ -81,6 +82,8 @@ enum Slot : int {
     SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
     SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
     SLOT_EXPOSED,            // bh_train_step with an exposure table: [H,W,4] the exposed frame the loss reads (out_img stays as rendered)
+    SLOT_DEPTH_LOSS,         // bh_depth_loss_value_and_grad / bh_eval_depth_metrics: one f64 row of 4 per block (depth_loss.hip)
+    SLOT_DEPTH_TERM,         // bh_train_step with a depth target: expected depth [H,W] | v_depth [H,W] | the term's loss pair (4 floats)
     SLOT_COUNT
 };
 
@@ -380,6 +383,8 @@ struct bh_ctx {
     const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
     float lpips_weight = 0.0f;
     float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
+    bool depth_attached = false;      // bh_train_set_depth: the step adds the depth term of depth_target (brush_hip_depth_loss.h); weight <= 0 = off
+    BhDepthTarget depth_target{};
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
@@ -479,7 +484,13 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                   size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
 int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
-int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms);
+// mark_rows (the single-GPU train step's ROW_MARKS span): a row K18 did not write is stored whole (zeros but the mean) and marked
+int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows = false, float* v_sh_coeffs = nullptr,
+                            float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
+int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, float* out_depth);
+// depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
+// accum[0] += loss[0], and the sum is stored to accum_host too
+int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
                      const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);

@@ -303,6 +303,39 @@ __global__ __launch_bounds__(256) void depth_vz_scatter_kernel(uint32_t nv, floa
     vt[2] = __builtin_fmaf(r2, vz, vt[2]);
 }
 
+// The same behind a K18 in marking mode (the single-GPU train step: only the refine-weight vector was cleared, K18 marked the rows
+// it wrote in that vector's sign bits and the update reads marked rows only).  K18 skips a splat whose ten sums are all zero — one
+// whose every pair sat at the alpha clamp still has a v_z — so a row that receives v_z may hold last step's bytes and carry no
+// mark: such a row is STORED whole (what a zero-filled row would hold after the accumulate above, bit for bit) and marked.  The
+// mark is the sign of a zero: the refine weight itself is not touched.
+__global__ __launch_bounds__(256) void depth_vz_scatter_marking_kernel(uint32_t nv, float r0, float r1, float r2, uint32_t sh_floats,
+                                                                       const uint32_t* __restrict__ global_from_compact, const float* __restrict__ v_z,
+                                                                       float* __restrict__ v_transforms, float* __restrict__ v_sh, float* __restrict__ v_raw_opac,
+                                                                       float* __restrict__ v_refine) {
+    const uint32_t cg = blockIdx.x * 256u + threadIdx.x;
+    if (cg >= nv) return;
+    const float vz = v_z[cg];
+    if (vz == 0.0f) return;
+    const uint32_t gid = global_from_compact[cg];
+    float* vt = v_transforms + (size_t)gid * 10;
+    const uint32_t mark = f2u(v_refine[gid]);
+    if (mark >> 31) {
+        vt[0] = __builtin_fmaf(r0, vz, vt[0]);
+        vt[1] = __builtin_fmaf(r1, vz, vt[1]);
+        vt[2] = __builtin_fmaf(r2, vz, vt[2]);
+        return;
+    }
+    vt[0] = __builtin_fmaf(r0, vz, 0.0f);
+    vt[1] = __builtin_fmaf(r1, vz, 0.0f);
+    vt[2] = __builtin_fmaf(r2, vz, 0.0f);
+#pragma unroll
+    for (int k = 3; k < 10; ++k) vt[k] = 0.0f;
+    float* sh = v_sh + (size_t)gid * sh_floats;
+    for (uint32_t k = 0; k < sh_floats; ++k) sh[k] = 0.0f;
+    v_raw_opac[gid] = 0.0f;
+    v_refine[gid] = u2f(mark | 0x80000000u);
+}
+
 DepthUniforms depth_uniforms(const bh_ctx* ctx, const ViewUniforms& vu) {
     DepthUniforms u;
     u.tile_bw = vu.tile_bw;
@@ -360,12 +393,20 @@ int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& 
     return 0;
 }
 
-int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms) {
+int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows, float* v_sh_coeffs, float* v_raw_opacities,
+                            float* v_refine_weight) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     if (nv == 0 || r.num_intersections == 0) return 0;
     const float* v_z = (const float*)ctx->slots[SLOT_DEPTH].ptr;
     const float* vm = fs.uniforms.vm;   // column-major rotation: row 2 = (vm[2], vm[5], vm[8])
+    if (mark_rows) {
+        const uint32_t sh_floats = (fs.sh_degree + 1) * (fs.sh_degree + 1) * 3;
+        hipLaunchKernelGGL(depth_vz_scatter_marking_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, vm[2], vm[5], vm[8], sh_floats,
+                           r.global_from_compact_gid, v_z, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight);
+        BH_LAUNCH_CHECK(ctx, "depth_vz_scatter_marking_kernel");
+        return 0;
+    }
     hipLaunchKernelGGL(depth_vz_scatter_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, vm[2], vm[5], vm[8], r.global_from_compact_gid, v_z,
                        v_transforms);
     BH_LAUNCH_CHECK(ctx, "depth_vz_scatter_kernel");

@@ -635,6 +635,47 @@ def render_depth(saved: "RenderNode", mode="expected", out=None):
     return out
 
 
+DEPTH_LOSS_KINDS = {"l1": _ffi.DEPTH_LOSS_L1, "disparity": _ffi.DEPTH_LOSS_DISPARITY}
+
+
+def _depth_target(gt, dev, kind="l1", weight=1.0, scale=1.0, offset=0.0, shape=None):
+    """(BhDepthTarget, the tensor its gt points into).  `kind`: "l1" (gt holds depth) or "disparity" (gt holds inverse depth)."""
+    gt = _f32c(gt, dev)
+    if gt.dim() != 2 or (shape is not None and tuple(gt.shape) != tuple(shape)):
+        raise ValueError("the depth target must be [H, W]%s" % ("" if shape is None else " = %s" % (tuple(shape),)))
+    t = _ffi.BhDepthTarget()
+    t.gt, t.h, t.w = gt.data_ptr(), int(gt.shape[0]), int(gt.shape[1])
+    t.kind = int(DEPTH_LOSS_KINDS[kind]) if isinstance(kind, str) else int(kind)
+    t.weight, t.scale, t.offset = float(weight), float(scale), float(offset)
+    return t, gt
+
+
+def depth_loss_value_and_grad(depth, gt, kind="l1", weight=1.0, scale=1.0, offset=0.0, ctx: Optional[Context] = None, want_grad=True):
+    """The fused depth loss (bh_depth_loss_value_and_grad; include/brush_hip_depth_loss.h) of an expected-depth map [H,W] against
+    the target t = fma(scale, gt, offset): -> (loss [2] device f32 = (weight * sum |.| / (H W), valid pixels), v_depth [H,W] or
+    None).  A pixel counts when gt is finite, t > 0 and depth > 0.  Queued on the ctx stream: nothing is read back."""
+    dev = depth.device
+    ctx = ctx or get_context(dev)
+    depth = _f32c(depth, dev)
+    t, keep = _depth_target(gt, dev, kind, weight, scale, offset, shape=depth.shape)
+    loss = torch.empty((2,), dtype=torch.float32, device=dev)
+    v_depth = torch.empty_like(depth) if want_grad else None
+    ctx.check(ctx.lib.bh_depth_loss_value_and_grad(ctx._h, _ptr(depth), C.byref(t), _ptr(loss), _ptr(v_depth) if want_grad else None))
+    return loss, v_depth
+
+
+def eval_depth_metrics(depth, gt, kind="l1", scale=1.0, offset=0.0, ctx: Optional[Context] = None, out=None):
+    """Held-out depth metrics (bh_eval_depth_metrics) of an expected-depth map against a target: -> device f32 [4] = (abs-rel, RMSE,
+    share of pixels with max(E / z, z / E) < 1.25, valid pixels); validity as in depth_loss_value_and_grad.  Nothing is read back."""
+    dev = depth.device
+    ctx = ctx or get_context(dev)
+    depth = _f32c(depth, dev)
+    t, keep = _depth_target(gt, dev, kind, 1.0, scale, offset, shape=depth.shape)
+    metrics = out if out is not None else torch.empty((4,), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_eval_depth_metrics(ctx._h, _ptr(depth), C.byref(t), _ptr(metrics)))
+    return metrics
+
+
 def render_splats_diff(splats: Splats, camera, img_size, background=(0.0, 0.0, 0.0), pass_: RasterPass = RasterPass.Backward,
                        ctx: Optional[Context] = None, retain=False, sliced=False, tile_rows=None) -> RenderNode:
     """Forward of a differentiable render; gradients later through RenderNode.backward (bwd/burn_glue.rs:223-311)."""
@@ -1089,6 +1130,19 @@ class TrainConfig:
     opac_decay: float = 0.004
     # config.rs:92: > 0 adds lpips_loss_weight * LPIPS(pred, GT) to the loss; needs SplatTrainer(..., lpips=Lpips)
     lpips_loss_weight: float = 0.0
+    # not in the reference: > 0 adds the depth term (brush_hip_depth_loss.h) for batches that carry a depth map; the weight goes
+    # from depth_loss_weight to depth_loss_weight_end (None: constant) over total_train_iters on lr_mean's exponential curve
+    depth_loss_weight: float = 0.0
+    depth_loss_weight_end: Optional[float] = None
+    depth_loss_kind: str = "l1"   # "l1": SceneBatch.depth holds depth; "disparity": it holds inverse depth
+
+    def depth_weight_at(self, step: int) -> float:
+        """The depth term's weight at step `step` (from 1): w0 * (w1 / w0) ** ((step - 1) / total_train_iters)."""
+        w0 = float(self.depth_loss_weight)
+        w1 = w0 if self.depth_loss_weight_end is None else float(self.depth_loss_weight_end)
+        if w0 <= 0.0 or w1 <= 0.0 or w1 == w0:
+            return w0
+        return w0 * (w1 / w0) ** ((int(step) - 1) / float(self.total_train_iters))
 
 
 @dataclass
@@ -1128,6 +1182,11 @@ class SceneBatch:
     has_alpha: bool = False
     alpha_is_mask: bool = False
     view_id: int = 0   # which view of the dataset this is (index + 1; 0 = unknown): keys the per-tile depth cuts (BhTrainBatch.view_id)
+    # depth supervision (TrainConfig.depth_loss_weight): the view's depth (or inverse depth) map [H,W] f32, and the per-view
+    # alignment t = depth_scale * depth + depth_offset of a monocular prior (1, 0 for metric depth).  None: no depth term this step
+    depth: Optional[torch.Tensor] = None
+    depth_scale: float = 1.0
+    depth_offset: float = 0.0
 
     def img_size(self):
         return tuple(self.img_packed.shape)  # (h, w)
@@ -1659,6 +1718,15 @@ class SplatTrainer:
             if self._hook is None:
                 self._hook = self._make_hook(dev)
             hook, scale = self._hook, (1.0 if tiles else 1.0 / self._world)
+        # the depth term is ctx state (bh_train_set_depth): attached for a batch that has a depth map — at this step's weight, and a
+        # weight of 0 is no term — and detached for one that has none; detached again behind the step, like the pose buffer
+        dgt = None
+        if getattr(batch, "depth", None) is not None:
+            dt, dgt = _depth_target(batch.depth, dev, getattr(c, "depth_loss_kind", "l1"), c.depth_weight_at(self.step_count + 1),
+                                    batch.depth_scale, batch.depth_offset, shape=(h, w))
+            ctx.check(ctx.lib.bh_train_set_depth(ctx._h, C.byref(dt)))
+        else:
+            ctx.check(ctx.lib.bh_train_set_depth(ctx._h, None))
         if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
             self.batch_patch(b)
         lw = float(getattr(c, "lpips_loss_weight", 0.0))
@@ -1677,6 +1745,7 @@ class SplatTrainer:
             ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                             float(scale), C.byref(stats)))
         finally:
+            ctx.lib.bh_train_set_depth(ctx._h, None)
             if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
             if ex is not None:
@@ -1685,7 +1754,7 @@ class SplatTrainer:
             po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
         self.step_count = st.step_count
         self._last_stats = stats
-        self._keep = (gt, ns)
+        self._keep = (gt, ns, dgt)
         if tiles and self.rebalance_every > 0:
             if self.step_count % self.rebalance_every == 0:
                 self._measure_row_weights(ctx, (h + 15) // 16, (w + 15) // 16, dev)
@@ -1972,6 +2041,10 @@ class EvalResult:
     avg_ssim: float
     per_view: torch.Tensor
     images: Optional[list] = None
+    # views that carry depth (run_eval): [V, 4] (abs-rel, RMSE, share within 1.25, valid pixels) on the host, NaN rows for views
+    # without depth, and the mean abs-rel over the views that have one; None when no view carries depth
+    depth_per_view: Optional[torch.Tensor] = None
+    avg_depth_abs_rel: Optional[float] = None
 
 
 def _aligned_hwc4(img_hwc4, dev):
@@ -2025,12 +2098,15 @@ def eval_stats(splats: "Splats", camera, gt_packed, ctx: Optional[Context] = Non
 def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images=False) -> EvalResult:
     """run_eval (train_stream.rs:506-566): eval_stats of every held-out view, the per-view PSNR and SSIM averaged in f32 (not the
     PSNR of a mean MSE).  `views` has compute_pup_scores' shape: (image uint8 [H,W,3|4] or a callable returning one, Camera[,
-    alpha_is_mask]), packed through a BatchUploader.  Every view's metrics go to its row of one device table; one readback at the end."""
+    alpha_is_mask[, depth]]), packed through a BatchUploader.  Every view's metrics go to its row of one device table; one readback at
+    the end.  `depth`: the view's depth map [H,W] f32, or a dict(depth=, kind="l1", scale=1.0, offset=0.0): such a view is also
+    rendered differentiably for its expected depth and scored by eval_depth_metrics (EvalResult.depth_per_view)."""
     import numpy as np
     dev = splats.device
     ctx = ctx or get_context(dev)
     views = list(views)
     table = torch.empty((len(views), 3), dtype=torch.float32, device=dev)
+    depth_table = None
     images = [] if keep_images else None
     up = None
     try:
@@ -2051,6 +2127,16 @@ def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images
             up.release(slot)
             if keep_images:
                 images.append(rgb8)
+            dv = view[3] if len(view) > 3 else None
+            if dv is not None:
+                dv = dv if isinstance(dv, dict) else dict(depth=dv)
+                if depth_table is None:
+                    depth_table = torch.full((len(views), 4), float("nan"), dtype=torch.float32, device=dev)
+                    if not ctx.uses_torch_stream:
+                        torch.cuda.current_stream(dev).synchronize()   # the fill ran on torch's stream, the metrics on the ctx's own
+                node = render_splats_diff(splats, view[1], (img.shape[1], img.shape[0]), ctx=ctx)
+                eval_depth_metrics(node.depth("expected"), torch.as_tensor(dv["depth"]).to(dev), dv.get("kind", "l1"), dv.get("scale", 1.0),
+                                   dv.get("offset", 0.0), ctx=ctx, out=depth_table[i])
     finally:
         if up is not None:
             ctx.sync()
@@ -2063,7 +2149,12 @@ def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images
     with np.errstate(invalid="ignore", divide="ignore"):
         psnr = np.float32(psnr / np.float32(len(views)))   # :559-560 (no views: 0 / 0 = NaN, as in the reference)
         ssim = np.float32(ssim / np.float32(len(views)))
-    return EvalResult(avg_psnr=float(psnr), avg_ssim=float(ssim), per_view=per_view, images=images)
+    res = EvalResult(avg_psnr=float(psnr), avg_ssim=float(ssim), per_view=per_view, images=images)
+    if depth_table is not None:
+        res.depth_per_view = depth_table.cpu()
+        rows = res.depth_per_view.numpy()
+        res.avg_depth_abs_rel = float(np.mean(rows[~np.isnan(rows[:, 0]), 0], dtype=np.float64))
+    return res
 
 
 # ---------------------------------------------------------------------------

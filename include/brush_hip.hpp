@@ -28,6 +28,8 @@
 //                                                   gradients (gsplat's v_viewmats) and the host arithmetic of a pose update
 //   brush_hip::ExposureTable / train_set_exposure   not in the reference: per-view exposure compensation (an affine colour
 //                                                   transform per training view, Adam on the device; brush_hip_exposure.h)
+//   brush_hip::depth_loss_value_and_grad / eval_depth_metrics / train_set_depth   not in the reference: depth supervision (a fused
+//                                                   depth loss, the step's depth term, held-out depth metrics; brush_hip_depth_loss.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -56,6 +58,7 @@
 #include "brush_hip_depth.h"
 #include "brush_hip_pose.h"
 #include "brush_hip_exposure.h"
+#include "brush_hip_depth_loss.h"
 
 namespace brush_hip {
 
@@ -1190,6 +1193,26 @@ private:
 inline void train_set_exposure(const Context& ctx, const ExposureTable* table) {
     ctx.check(bh_train_set_exposure(ctx.get(), table ? table->get() : nullptr));
 }
+
+// ---- depth supervision (brush_hip_depth_loss.h; not in the reference) --------------------------------------------------------------
+// A target: gt [H,W] f32 on the device holds depth (BH_DEPTH_LOSS_L1) or inverse depth (BH_DEPTH_LOSS_DISPARITY); t = fma(scale, gt, offset).
+inline BhDepthTarget depth_target(const float* gt, uint32_t h, uint32_t w, uint32_t kind = BH_DEPTH_LOSS_L1, float weight = 1.0f, float scale = 1.0f,
+                                  float offset = 0.0f) {
+    static_assert(BH_DEPTH_LOSS_L1 == 0u && BH_DEPTH_LOSS_DISPARITY == 1u, "depth loss kinds");
+    BhDepthTarget t{};
+    t.gt = gt; t.h = h; t.w = w; t.kind = kind; t.weight = weight; t.scale = scale; t.offset = offset;
+    return t;
+}
+// loss [2] (device) = (weight * sum |.| / (H W), valid pixels), v_depth [H,W] or nullptr = dloss / d depth; nothing is read back
+inline void depth_loss_value_and_grad(const Context& ctx, const float* depth, const BhDepthTarget& target, float* loss, float* v_depth) {
+    ctx.check(bh_depth_loss_value_and_grad(ctx.get(), depth, &target, loss, v_depth));
+}
+// metrics [4] (device) = (abs-rel, RMSE, share of valid pixels within a ratio of 1.25, valid pixels)
+inline void eval_depth_metrics(const Context& ctx, const float* depth, const BhDepthTarget& target, float* metrics) {
+    ctx.check(bh_eval_depth_metrics(ctx.get(), depth, &target, metrics));
+}
+// bh_train_step on this ctx adds the depth term of `target` (copied; its gt must outlive the steps); nullptr detaches
+inline void train_set_depth(const Context& ctx, const BhDepthTarget* target) { ctx.check(bh_train_set_depth(ctx.get(), target)); }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
 // compute_knn_scales in place: columns 7..9 of splats.transforms = ln(clamp((d1 + d2) / 4, 1e-3, 0.1 median_size)) (bh_knn_log_scales).

@@ -1,0 +1,35 @@
+"""Depth supervision through the C++ host mirror (include/brush_hip.hpp depth_loss_value_and_grad / eval_depth_metrics /
+train_set_depth): tests/cpp/test_depth_loss.cpp, compiled with the g++ line of tests/cpp/Makefile into a temporary directory.
+CPU: it compiles and links; GPU: the operators against the header's definitions restated in the program, and one train step with a
+target (its loss is the plain step's plus the hand-composed term, a target of the wrong size is refused)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _build(tmp_path):
+    import __graft_entry__ as g
+    g.build()
+    exe = str(tmp_path / "test_depth_loss")
+    inc, lib = os.path.join(ROOT, "include"), os.path.join(ROOT, "brush_amd")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I/opt/rocm/include",
+                           os.path.join(ROOT, "tests", "cpp", "test_depth_loss.cpp"), "-o", exe, "-L" + lib, "-lbrush_hip", "-L/opt/rocm/lib", "-lamdhip64",
+                           "-ldl", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_cpp_depth_loss_program_compiles_and_links(tmp_path):
+    assert os.path.exists(_build(tmp_path))
+
+
+@pytest.mark.gpu
+def test_cpp_depth_loss_program_passes_on_the_gpu(tmp_path):
+    exe = _build(tmp_path)
+    r = subprocess.run([exe], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "ok depth loss kind 0" in r.stdout and "ok depth loss kind 1" in r.stdout and "ok depth loss arguments" in r.stdout
+    assert "ok train step with a depth target" in r.stdout and "all C++ depth loss checks passed" in r.stdout
