@@ -290,6 +290,7 @@ void bh_destroy(bh_ctx* ctx) {
         if (b.ptr) (void)hipFree(b.ptr);
     if (ctx->host_counters) (void)hipHostFree(ctx->host_counters);
     if (ctx->dsort_spl) (void)hipFree(ctx->dsort_spl);
+    if (ctx->sort_groups) (void)hipFree(ctx->sort_groups);
     if (ctx->readback_ev) (void)hipEventDestroy(ctx->readback_ev);
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
     if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);

@@ -30,7 +30,7 @@ enum Slot : int {
     SLOT_SORT_KEYS_B,
     SLOT_SORT_VALS_A,
     SLOT_SORT_VALS_B,
-    SLOT_SORT_HIST,          // [256 * nblocks] u32
+    SLOT_SORT_HIST,          // digit totals | [nblocks][256] u32 block histograms (| the depth sort's digit bytes)
     SLOT_COMM_SCRATCH,       // direct all-reduce: the other ranks' versions of this rank's chunk (comm.hip)
     SLOT_BWD_CKPT,           // backward jobs: the forward blend's pixel-state checkpoints (rasterize.hip)
     SLOT_BWD_TOPLIST,        // ... and the bands' top-class job lists
@@ -108,6 +108,9 @@ constexpr uint32_t COUNTER_MINMAX_WORD = COUNTER_SLOTS * 2 * COUNTER_K1_U64;   /
 // control words of SLOT_SLICE: [0] near-slice splats  [1] near pairs  [2] tiles the near pass left live  [3] far pairs
 // [4] live column bands  [5] live row bands (32 bands per axis; the far pass skips splats whose box misses them)  [6..7] spare
 constexpr uint32_t SLICE_CTRL_WORDS = 8;
+// Both radix sorts (sort.hip, depth_sort.hip): histogram blocks per group total.  A scatter block adds up the totals of the groups in
+// front of its own and the histograms of the earlier blocks of its own group: no scan launch between histogram and scatter.
+constexpr uint32_t SORT_GROUP_BLOCKS = 32;
 constexpr uint32_t FAR_GROUP_BLOCKS = 64;   // far slice: count-kernel blocks per group total (<= the projection workgroup size)
 constexpr size_t COUNTER_READ_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64;
 // ... or, when the depth sort's first kernel adds the slots up on the device: [COUNTER_K1_U64] u64 totals
@@ -440,6 +443,11 @@ struct bh_ctx {
     bh::FarJob far_job;
     uint32_t refine_n = 0, refine_new_n = 0;  // a bh_refine_plan awaiting its bh_refine_apply
     bool dsort_lds_raised = false;    // likewise dsort_bucket_kernel (depth_sort.hip)
+    // the sorts' group tables (sort.hip SortGroups): two sets of sort_groups_cap words; set sort_groups_cur is all zero, the other one
+    // holds the last sort's sums in its first sort_groups_dirty words
+    uint32_t* sort_groups = nullptr;
+    size_t sort_groups_cap = 0, sort_groups_dirty = 0;
+    uint32_t sort_groups_cur = 0;
     uint32_t* dsort_spl = nullptr;    // [DSORT_SPL_STRIDE] device: the depth sort's splitter table (depth_sort.hip SPLITTERS) of frames without a view
     bool dsort_spl_written = false;   // a frame has written it (until then a frame sorts a sample first)
     bool knob_dsort_splitters = true; // option dsort_splitters: the split digit from the previous frame's quantiles (0: always the linear split)
@@ -625,19 +633,42 @@ int launch_project_backward(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, boo
                             float* v_combined, float* v_transforms, float* v_sh, float* v_raw_opac,
                             float* v_refine, bool mark_written = false, const float* projected = nullptr);
 // sort.hip
+// Group tables of one histogram -> scatter pair (SORT_GROUP_BLOCKS).  The histogram blocks ADD into `sums`, which therefore has to be
+// zero, and nothing in front of them on the stream is there to clear it: the ctx keeps two sets, the histogram kernel of every sort
+// clears the set the sort BEFORE it used (`stale`, plain stores spread over its grid) and the sets change roles.
+struct SortGroups {
+    uint32_t* sums = nullptr;    // [words] zero on entry
+    uint32_t* stale = nullptr;   // [stale_words] to be cleared by the kernel that adds into `sums`
+    uint32_t stale_words = 0;
+};
+inline uint32_t sort_group_count(uint32_t nblocks) { return (nblocks + SORT_GROUP_BLOCKS - 1u) / SORT_GROUP_BLOCKS; }
+// Every call is followed by exactly ONE histogram launch on ctx->stream that takes `out`: that launch clears the stale set, and the
+// roles of the two sets have changed when this returns.
+int sort_groups_next(bh_ctx* ctx, size_t words, SortGroups* out);
+// Up to SORT_DIRECT_GROUPS groups (1024 blocks) a scatter block adds up the group rows in front of it itself.  That is nblocks x
+// ngroups KB of table reads, quadratic in the key count: 16 MB at 512 blocks, 360 MB at 2930 (6 M splats: measured, +50 us per step
+// over the two sorts).  Longer sorts therefore keep ONE small launch between histogram and scatter (5.6 us): sort_groups_scan turns
+// the group table into exclusive prefixes over the groups in place and stores the digit totals, and a scatter block reads one group
+// row and the totals whatever the length.  Measured on both sides of the threshold against the row-scan version (EXPERIMENTS.md):
+// 2 M splats (977 depth-sort blocks, direct) -1.6 % of the step, 3 M (1465, scanned) -1.1 %, 6 M / 4K (2930, scanned) -0.4 %.
+constexpr uint32_t SORT_DIRECT_GROUPS = 32;
+inline bool sort_groups_scanned(uint32_t ngroups) { return ngroups > SORT_DIRECT_GROUPS; }
+// sums: `tables` tables of [ngroups][256] -> exclusive prefixes over the groups, in place; totals[tables][256] <- the column sums
+int sort_groups_scan(bh_ctx* ctx, uint32_t* sums, uint32_t ngroups, uint32_t tables, uint32_t* totals);
+// (the device side — a scatter block's offsets, the clearing of the stale set — is sort_groups.h, for sort.hip and depth_sort.hip)
 int radix_argsort(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t bits,
                   uint32_t* out_keys, uint32_t* out_vals);
 // the same with the number of pairs in device memory (host: only the bound n_max): n = min(*n_dev, n_max), 0 if *gate == 0
 // (gate may be NULL); the result is written *out_base elements into out_keys / out_vals (out_base may be NULL).  Not in place.
 int radix_argsort_dev(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint32_t n_max, const uint32_t* n_dev, const uint32_t* gate,
                       const uint32_t* out_base, uint32_t bits, uint32_t* out_keys, uint32_t* out_vals, uint32_t alloc_n = 0);
-// sort.hip — the forward's tile sort AND its offsets table in four launches (high digit first, one block per bucket finishes);
+// sort.hip — the forward's tile sort AND its offsets table in four launches (high digit first, parts of 4096 pairs finish);
 // bits in 9..16 and n <= 16 M (tile_sort_supported), the table zero on entry
 bool tile_sort_supported(uint32_t bits, uint32_t n);
 int tile_sort_offsets(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t bits, uint32_t num_tiles,
                       uint32_t* out_keys, uint32_t* out_vals, uint32_t* tile_offsets, uint32_t alloc_n = 0);
 // depth_sort.hip — the forward's depth ordering: stable argsort of the depth keys + inclusive scan of the tile counts in that
-// order, four launches.  minmax: the second part of a counter set (K1).  cum == NULL: no scan.  rb_*: the first launch also adds
+// order, three launches.  minmax: the second part of a counter set (K1).  cum == NULL: no scan.  rb_*: the first launch also adds
 // up counter set rb_set into the pinned host words rb_host (HOST_SUM_WORDS) and rb_done is recorded behind it.
 bool depth_sort_supported(uint32_t n);
 int depth_sort_scan(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys,

@@ -1,5 +1,5 @@
 // depth_sort.hip — the forward's depth ordering: stable argsort of the per-splat depth keys AND the prefix sum of the
-// per-splat tile counts in that order, in FOUR launches.
+// per-splat tile counts in that order, in THREE launches (four beyond 2 M splats).
 //
 // Reference: render.rs:177-187 — radix_argsort(depths, 32 bits) (brush-sort: 8 four-bit passes, 40 launches), then
 // int_gather + prefix_sum (brush-prefix-sum: 5 launches).  Round 1 ran this as a generic 8-bit LSD sort (4 passes x 3
@@ -9,8 +9,10 @@
 // 0xFFFFFFFF), and the visible keys of a frame span a narrow range of it [kmin, kmax], which K1 leaves behind (per-block
 // maxima of key and ~key in 128 slots).  So:
 //   1. ONE most-significant-digit split: digit = (key - kmin) >> shift with shift the smallest that keeps the visible range
-//      inside digits 0..254 (culled -> 255): histogram, row scan of the [digit][block] table, stable scatter — the three
-//      kernels of a radix pass.  The histogram kernel also adds up the tile counts per digit.
+//      inside digits 0..254 (culled -> 255): histogram and stable scatter — the two kernels of a radix pass (sort.hip: the
+//      scatter blocks add up group totals and the earlier blocks of their own group themselves; until this a row scan of a
+//      [digit][block] table was a launch of its own between the two, 7 us; beyond 1024 blocks a scan of the group table is).  The histogram kernel also adds up the tile counts
+//      per digit and group; block 0 of the scatter leaves both kinds of digit totals for step 2.
 //   2. ONE kernel with a block per digit bucket finishes the job: the keys of a bucket agree in everything above `shift`,
 //      so the block sorts them on the low `shift` bits (stable LSD passes through LDS, 4096 keys at a time, running digit
 //      bases carried from chunk to chunk: a bucket of any size works, typical ones are one or two chunks) and, knowing
@@ -21,6 +23,7 @@
 #include <cstddef>
 
 #include "context.h"
+#include "sort_groups.h"
 
 namespace bh {
 
@@ -56,7 +59,7 @@ constexpr uint32_t SPL_WORDS = 258;
 static_assert(SPL_WORDS <= DSORT_SPL_STRIDE, "context.h reserves the table");
 constexpr uint32_t SPL_MIN_KEYS = 16384;   // frames with fewer visible keys leave no table (the linear split serves them)
 // A frame that finds NO table (a view's first frame in this list mode; the host knows) does not fall back to the linear split blindly:
-// every SPL_SAMPLE_STRIDE-th key is sorted first — the same four kernels on 1/64 of the keys, linear split (a crowded sample is a few
+// every SPL_SAMPLE_STRIDE-th key is sorted first — the same three kernels on 1/64 of the keys, linear split (a crowded sample is a few
 // thousand keys in one bucket: nothing) — and the bucket kernel of THAT run leaves the sample's quantiles as the frame's table.  ~30 us,
 // once per view and list mode; without it the first frame of a scene whose depths crowd into a thin shell took 2.4 ms instead of 0.44.
 constexpr uint32_t SPL_SAMPLE_STRIDE = 64;
@@ -170,11 +173,12 @@ BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __r
     }
 }
 
-// ---- 1a: histogram of the split digit per block + tile-count sums per (digit, block) ------------------------------------
+// ---- 1a: histogram of the split digit per block; the same and the tile-count sums per (digit, group of blocks) ------------------
+// grp.sums: [ngroups][256] keys | [ngroups][256] tile counts (context.h SortGroups)
 // (block `nblocks`, present when rb_set is given, carries the counter readback instead of a chunk of keys)
 __global__ __launch_bounds__(DS_WG) void dsort_hist_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ counts,
                                                           uint32_t n, uint32_t nblocks, const uint32_t* __restrict__ minmax,
-                                                          uint32_t* __restrict__ hist, uint32_t* __restrict__ csum,
+                                                          uint32_t* __restrict__ hist /*[nblocks][256]*/, SortGroups grp, uint32_t ngroups,
                                                           const uint32_t* __restrict__ rb_set, uint32_t* __restrict__ rb_host, uint32_t rb_tag, uint32_t* __restrict__ rb_dev,
                                                           const uint32_t* __restrict__ spl_in, uint8_t* __restrict__ digits /*[n]: every key's split digit, for the split kernel*/) {
     __shared__ uint32_t s_hist[DS_WAVES][DS_RADIX];
@@ -182,6 +186,7 @@ __global__ __launch_bounds__(DS_WG) void dsort_hist_kernel(const uint32_t* __res
     __shared__ uint32_t s_red[2 * DS_WAVES];
     __shared__ uint32_t s_spl[SPL_WORDS];
     const int tid = threadIdx.x, wave = tid >> 6;
+    sort_groups_clear(grp.stale, grp.stale_words);
     if (blockIdx.x == nblocks) {   // (block-uniform: taken before the first barrier)
         if (wave == 0) counter_sums_to_host(rb_set, rb_host, tid, rb_tag, rb_dev);
         return;
@@ -227,61 +232,11 @@ __global__ __launch_bounds__(DS_WG) void dsort_hist_kernel(const uint32_t* __res
     uint32_t t = 0, c = 0;
 #pragma unroll
     for (int w = 0; w < DS_WAVES; ++w) { t += s_hist[w][tid]; c += s_csum[w][tid]; }
-    hist[(size_t)tid * nblocks + blockIdx.x] = t;
-    csum[(size_t)tid * nblocks + blockIdx.x] = c;
-}
-
-// ---- 1b: per digit row: exclusive scan of the block histogram (-> scatter offsets), row totals of both tables ----------
-constexpr int DS_ROW_EPT = 16;   // rows of up to 4096 blocks (16.7 M splats); dsort_supported() guards it
-__global__ __launch_bounds__(DS_WG) void dsort_rowscan_kernel(uint32_t* __restrict__ hist, const uint32_t* __restrict__ csum, uint32_t nblocks,
-                                                             uint32_t* __restrict__ digit_totals /*[256] keys | [256] tile counts*/) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t d = blockIdx.x;
-    uint32_t* row = hist + (size_t)d * nblocks;
-    const uint32_t* crow = csum + (size_t)d * nblocks;
-    uint32_t v[DS_ROW_EPT], incl[DS_ROW_EPT];
-    __shared__ uint32_t s_chunk[DS_ROW_EPT][DS_WAVES];
-    __shared__ uint32_t s_c[DS_WAVES];
-    uint32_t cacc = 0;
-#pragma unroll
-    for (int k = 0; k < DS_ROW_EPT; ++k) {
-        const uint32_t i = (uint32_t)k * DS_WG + tid;
-        v[k] = i < nblocks ? row[i] : 0u;
-        cacc += i < nblocks ? crow[i] : 0u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cacc += __shfl_down(cacc, off);
-    if (lane == 0) s_c[wave] = cacc;
-#pragma unroll
-    for (int k = 0; k < DS_ROW_EPT; ++k) {
-        uint32_t x = v[k];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(x, off);
-            if (lane >= off) x += t;
-        }
-        incl[k] = x;
-        if (lane == 63) s_chunk[k][wave] = x;
-    }
-    __syncthreads();
-    uint32_t run = 0;
-#pragma unroll
-    for (int k = 0; k < DS_ROW_EPT; ++k) {
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < DS_WAVES; ++w) {
-            const uint32_t c = s_chunk[k][w];
-            before += w < wave ? c : 0u;
-            total += c;
-        }
-        const uint32_t i = (uint32_t)k * DS_WG + tid;
-        if (i < nblocks) row[i] = run + before + incl[k] - v[k];
-        run += total;
-    }
-    if (tid == 0) {
-        digit_totals[d] = run;
-        digit_totals[DS_RADIX + d] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
-    }
+    hist[(size_t)blockIdx.x * DS_RADIX + tid] = t;
+    // one returnless atomic per thread and table on consecutive words, 32 adders per word: the rate global atomics run at anyway
+    const size_t gw = (size_t)(blockIdx.x / SORT_GROUP_BLOCKS) * DS_RADIX + tid;
+    if (t != 0u) atomicAdd(&grp.sums[gw], t);
+    if (c != 0u) atomicAdd(&grp.sums[(size_t)ngroups * DS_RADIX + gw], c);
 }
 
 // One chunk (<= 4096 elements, in index order) of a stable scatter by digit: element e goes to dst[s_base[digit] + (number of
@@ -406,8 +361,9 @@ BH_DEV void scatter_chunk(ChunkLds<WG>& L, uint32_t* __restrict__ s_base /*[256]
 
 // ---- 1c: the split itself: stable scatter of (key, splat id) by split digit --------------------------------------------------
 __global__ __launch_bounds__(DS_WG) void dsort_split_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t nblocks,
-                                                           const uint32_t* __restrict__ offsets /*row-scanned hist*/,
-                                                           const uint32_t* __restrict__ digit_totals, uint32_t* __restrict__ out_keys,
+                                                           const uint32_t* __restrict__ hist /*[nblocks][256]*/, const uint32_t* __restrict__ gsum, uint32_t ngroups, uint32_t scanned,
+                                                           uint32_t* digit_totals /*[256] keys | [256] tile counts for the bucket kernel: block 0 leaves them, or (scanned) the group scan has*/,
+                                                           uint32_t* __restrict__ out_keys,
                                                            uint32_t* __restrict__ out_vals, uint32_t* __restrict__ fin_keys, uint32_t* __restrict__ fin_vals,
                                                            const uint8_t* __restrict__ digits /*[n] the histogram kernel's*/) {
     __shared__ ChunkLds<DS_WG> L;
@@ -416,7 +372,14 @@ __global__ __launch_bounds__(DS_WG) void dsort_split_kernel(const uint32_t* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // destination of this block's first element of digit `tid`: keys with a smaller digit + this digit's keys in earlier blocks
     {
-        const uint32_t gt = digit_totals[tid];
+        uint32_t before, gt;
+        sort_group_offset(hist, gsum, digit_totals, ngroups, scanned != 0u, blockIdx.x, (uint32_t)tid, before, gt);
+        if (!scanned && blockIdx.x == 0u) {   // (block-uniform)
+            uint32_t ct = 0;
+            for (uint32_t g = 0; g < ngroups; ++g) ct += gsum[(size_t)(ngroups + g) * DS_RADIX + tid];
+            digit_totals[tid] = gt;
+            digit_totals[DS_RADIX + tid] = ct;
+        }
         uint32_t gincl = gt;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -428,7 +391,7 @@ __global__ __launch_bounds__(DS_WG) void dsort_split_kernel(const uint32_t* __re
         uint32_t gofs = 0;
 #pragma unroll
         for (int w = 0; w < DS_WAVES; ++w) gofs += (w < wave) ? s_red[w] : 0u;
-        s_base[tid] = gincl - gt + gofs + offsets[(size_t)tid * nblocks + blockIdx.x];
+        s_base[tid] = gincl - gt + gofs + before;
     }
     __syncthreads();
     const uint32_t first = blockIdx.x * DS_TILE;
@@ -749,12 +712,13 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
     if (cum != nullptr) bk_scan_counts(out_vals + start, size, counts, tiles_before, cum + start, &L.keys[0], s_red);
 }
 
-// Up to the row scan's reach (4096 chunks of DS_TILE keys: 8.4 M splats); beyond it the generic sort + scan run.  (Until round 4 the limit was 4 M:
+// Up to 4096 chunks of DS_TILE keys (8.4 M splats: the reach of the row scan this path had until the group sums); beyond it the generic sort + scan run.  (Until round 4 the limit was 4 M:
 // "the fused path pays off while launches, not bytes, are the cost".  With per-tile cuts only the listed sixth of the 6 M / 4K
 // scene's splats is moved at all: depth order + scan 255 -> 97 us there; with complete lists 306 -> 302.)
 #define BH_DSORT_MAX_N (16u << 20)
 constexpr uint32_t DSORT_MAX_N = BH_DSORT_MAX_N;
-bool depth_sort_supported(uint32_t n) { return n > 0 && n <= DSORT_MAX_N && (n + DS_TILE - 1) / DS_TILE <= (uint32_t)DS_ROW_EPT * DS_WG; }
+constexpr uint32_t DS_MAX_BLOCKS = 4096;
+bool depth_sort_supported(uint32_t n) { return n > 0 && n <= DSORT_MAX_N && (n + DS_TILE - 1) / DS_TILE <= DS_MAX_BLOCKS; }
 
 // keys: [n] depth keys (culled = 0xFFFFFFFF); minmax: K1's [COUNTER_SLOTS][2] (max key, max ~key over visible splats);
 // counts: [n] tiles hit per splat.  -> out_keys / out_vals: the stable argsort; cum: inclusive scan of counts[out_vals[i]]
@@ -769,21 +733,25 @@ __global__ __launch_bounds__(256) void dsort_sample_kernel(const uint32_t* __res
     if (i < m) out[i] = keys[(size_t)i * stride];
 }
 
-// the four launches; scratch sized by the caller
+// the three (or four) launches; scratch sized by the caller
 static int dsort_launches(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys, uint32_t* out_vals,
                           uint32_t* cum, const uint32_t* rb_set, uint32_t* rb_host, hipEvent_t rb_done, uint32_t rb_tag, uint32_t* rb_dev, uint32_t* totals,
                           uint32_t* a_keys, uint32_t* a_vals, const uint32_t* spl_in, uint32_t* spl_out, uint32_t spl_min_keys) {
     const uint32_t nblocks = (n + DS_TILE - 1) / DS_TILE;
     uint32_t* hist = totals + 2 * DS_RADIX;
-    uint32_t* csum = hist + (size_t)DS_RADIX * nblocks;
-    uint8_t* digits = reinterpret_cast<uint8_t*>(csum + (size_t)DS_RADIX * nblocks);   // [nblocks * DS_TILE] every key's split digit (hist -> split)
-    hipLaunchKernelGGL(dsort_hist_kernel, dim3(nblocks + (rb_set ? 1u : 0u)), dim3(DS_WG), 0, ctx->stream, keys, counts, n, nblocks, minmax, hist, csum,
+    uint8_t* digits = reinterpret_cast<uint8_t*>(hist + (size_t)DS_RADIX * nblocks);   // [nblocks * DS_TILE] every key's split digit (hist -> split)
+    const uint32_t ngroups = sort_group_count(nblocks);
+    SortGroups grp;
+    BH_TRY(sort_groups_next(ctx, (size_t)2 * ngroups * DS_RADIX, &grp));
+    hipLaunchKernelGGL(dsort_hist_kernel, dim3(nblocks + (rb_set ? 1u : 0u)), dim3(DS_WG), 0, ctx->stream, keys, counts, n, nblocks, minmax, hist, grp, ngroups,
                        rb_set, rb_host, rb_tag, rb_dev, spl_in, digits);
     BH_LAUNCH_CHECK(ctx, "dsort_hist_kernel");
     if (rb_set && !rb_tag) BH_HIP(ctx, hipEventRecord(rb_done, ctx->stream));   // (rb_tag: the host polls the tag word instead)
-    hipLaunchKernelGGL(dsort_rowscan_kernel, dim3(DS_RADIX), dim3(DS_WG), 0, ctx->stream, hist, csum, nblocks, totals);
-    BH_LAUNCH_CHECK(ctx, "dsort_rowscan_kernel");
-    hipLaunchKernelGGL(dsort_split_kernel, dim3(nblocks), dim3(DS_WG), 0, ctx->stream, keys, n, nblocks, hist, totals, a_keys, a_vals, out_keys, out_vals, digits);
+    // more than 2 M keys: the group tables (keys | tile counts) are scanned by a launch of their own (context.h SORT_DIRECT_GROUPS)
+    const uint32_t scanned = sort_groups_scanned(ngroups) ? 1u : 0u;
+    if (scanned) BH_TRY(sort_groups_scan(ctx, grp.sums, ngroups, 2u, totals));
+    hipLaunchKernelGGL(dsort_split_kernel, dim3(nblocks), dim3(DS_WG), 0, ctx->stream, keys, n, nblocks, hist, grp.sums, ngroups, scanned, totals, a_keys, a_vals, out_keys, out_vals,
+                       digits);
     BH_LAUNCH_CHECK(ctx, "dsort_split_kernel");
     // buckets 0..254; the culled splats (digit 255: all keys 0xFFFFFFFF, already in splat-id order) went straight to the output
     if (!ctx->dsort_lds_raised) {   // 146 KB of dynamic LDS: above the 64 KB default, opt in once per ctx (the attribute is per device)
@@ -812,8 +780,8 @@ int depth_sort_scan(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, c
         spl = ctx->dsort_spl;
         spl_written = &ctx->dsort_spl_written;
     }
-    // [512] digit totals (keys | tile counts), then the two [256][nblocks] tables, then the keys' digits (bytes)
-    uint32_t* totals = (uint32_t*)ensure(ctx, SLOT_SORT_HIST, ((size_t)2 * DS_RADIX * nblocks + 2 * DS_RADIX) * 4 + (size_t)nblocks * DS_TILE);
+    // [512] digit totals (keys | tile counts), then the [nblocks][256] table, then the keys' digits (bytes)
+    uint32_t* totals = (uint32_t*)ensure(ctx, SLOT_SORT_HIST, ((size_t)DS_RADIX * nblocks + 2 * DS_RADIX) * 4 + (size_t)nblocks * DS_TILE);
     uint32_t* a_keys = (uint32_t*)ensure(ctx, SLOT_SORT_KEYS_A, (size_t)n * 4);
     uint32_t* a_vals = (uint32_t*)ensure(ctx, SLOT_SORT_VALS_A, (size_t)n * 4);
     if (!totals || !a_keys || !a_vals) return BH_ERR_OOM;

@@ -5,9 +5,16 @@
 // reference's 4-bit FidelityFX-style passes (5 kernels per pass, kernels.rs:29-401)
 // are replaced by a wave64 design:
 //   * 8-bit digits: half the passes (4 for depth keys, 2 for <=16-bit tile ids);
-//   * per pass: histogram (+ digit totals) -> one-launch row scan of the [digit][block]
-//     table -> scatter  (3 launches; a chained-scan "onesweep" was measured SLOWER on
-//     MI355X: every look-back hop is a cross-XCD fabric round trip);
+//   * per pass: histogram -> scatter (2 launches).  A scatter block needs, per digit, the keys of that digit in the
+//     blocks in front of it.  The histogram kernel writes a [block][digit] table and adds every block's 256 counts
+//     into the totals of its group of SORT_GROUP_BLOCKS blocks (one returnless atomic per thread on consecutive
+//     words); thread d of a scatter block adds up the totals of the groups in front and the counts of the earlier
+//     blocks of its own group — coalesced rows, independent loads, no waiting for another block.  (Until this a
+//     one-launch row scan of a [digit][block] table sat between the two: ~7 us of launch and dependent boundary for
+//     a few hundred KB.  A chained-scan "onesweep" was measured SLOWER on MI355X: every look-back hop is a
+//     cross-XCD fabric round trip.)  Block 0 stores the digit totals it has added up anyway.  Sorts of more than
+//     SORT_DIRECT_GROUPS groups (1024 blocks) keep one launch in between, a one-block scan of the GROUP table
+//     (context.h sort_groups_scan): every scatter block reading every group row is quadratic in the key count.
 //   * ranking inside a block uses wave-wide digit matching (8 ballots) so each wave
 //     ranks 64 keys per step without LDS atomics; waves own contiguous chunks so
 //     the block order is the input order (stability);
@@ -16,6 +23,7 @@
 // HBM traffic per pass: 4 (hist read) + 8 (scatter read) + 8 (write) = 20 B/pair —
 // the algorithmic figure of SURVEY.md §8d.
 #include "context.h"
+#include "sort_groups.h"
 
 namespace bh {
 
@@ -44,7 +52,7 @@ BH_DEV unsigned long long match_digit(uint32_t d) {
 
 // Device-side length (the depth-sliced forward, api.hip): the host knows only an upper bound `n` of the number of pairs; the
 // exact count sits in device memory (`n_dev`), `gate` == 0 switches the whole sort off (every block leaves at once), and the
-// last pass writes its output `*out_base` elements into the destination.  The grid and the [digit][block] table are sized for
+// last pass writes its output `*out_base` elements into the destination.  The grid and the [block][digit] table are sized for
 // the bound; blocks past the live count return before touching anything.  All three NULL: the plain sort.
 struct SortDyn {
     const uint32_t* n_dev = nullptr;
@@ -60,12 +68,13 @@ BH_DEV uint32_t sort_live_n(uint32_t n, const SortDyn& dyn) {
     return n;
 }
 
-// hist[digit * nblocks + block]
+// hist[block * 256 + digit], and the same counts added into gsum[(block / SORT_GROUP_BLOCKS) * 256 + digit] (context.h SortGroups)
 // (electing one leader per digit group with 8 ballots instead of the LDS atomic was measured: tile sort 132 -> 155 us)
 template <int SORT_KPT>
 __global__ __launch_bounds__(SORT_WG) void radix_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift,
-                                                            uint32_t mask, uint32_t nblocks, uint32_t* __restrict__ hist, SortDyn dyn) {
+                                                            uint32_t mask, uint32_t* __restrict__ hist, SortGroups grp, SortDyn dyn) {
     __shared__ uint32_t s_hist[SORT_WAVES][RADIX];
+    sort_groups_clear(grp.stale, grp.stale_words);   // (by every block of the grid, a gated-off sort's included)
     n = sort_live_n(n, dyn);
     if (blockIdx.x * (uint32_t)(SORT_WG * SORT_KPT) >= n) return;   // (only with a device-side length)
     const int tid = threadIdx.x, wave = tid >> 6;
@@ -97,67 +106,17 @@ __global__ __launch_bounds__(SORT_WG) void radix_hist_kernel(const uint32_t* __r
     uint32_t total = 0;
 #pragma unroll
     for (int w = 0; w < SORT_WAVES; ++w) total += s_hist[w][tid];
-    hist[(size_t)tid * nblocks + blockIdx.x] = total;
-}
-
-// Row-wise exclusive scan of the [digit][block] table in ONE launch (block d owns digit
-// row d and also emits the row total); the scatter kernel adds the 256-entry prefix over
-// the digit totals itself.  3 launches per pass instead of the 5 of a generic
-// reduce/spine/apply scan over the whole table.
-constexpr int ROWSCAN_MAX_EPT = 16;  // rows of up to 4096 blocks (16.7 M keys) in one trip; longer rows loop with a carry
-__global__ __launch_bounds__(SORT_WG) void radix_rowscan_kernel(uint32_t* __restrict__ hist, uint32_t nblocks, uint32_t n, uint32_t tile,
-                                                               uint32_t* __restrict__ digit_totals, SortDyn dyn) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t d = blockIdx.x;
-    const uint32_t live_n = sort_live_n(n, dyn);
-    if (live_n == 0u) return;
-    const uint32_t live = (live_n + tile - 1u) / tile;   // blocks that wrote their column (== nblocks for the plain sort)
-    uint32_t* row = hist + (size_t)d * nblocks;
-    __shared__ uint32_t s_chunk[ROWSCAN_MAX_EPT][SORT_WAVES];
-    uint32_t run = 0;
-    for (uint32_t c0 = 0; c0 < live; c0 += (uint32_t)ROWSCAN_MAX_EPT * SORT_WG) {
-        // the row segment stays in registers: entry c0 + k*256 + tid (coalesced), ROWSCAN_MAX_EPT chunks
-        uint32_t v[ROWSCAN_MAX_EPT], incl[ROWSCAN_MAX_EPT];
-#pragma unroll
-        for (int k = 0; k < ROWSCAN_MAX_EPT; ++k) {
-            const uint32_t i = c0 + (uint32_t)k * SORT_WG + tid;
-            v[k] = i < live ? row[i] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < ROWSCAN_MAX_EPT; ++k) {
-            uint32_t x = v[k];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t t = __shfl_up(x, off);
-                if (lane >= off) x += t;
-            }
-            incl[k] = x;
-            if (lane == 63) s_chunk[k][wave] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < ROWSCAN_MAX_EPT; ++k) {
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < SORT_WAVES; ++w) {
-                const uint32_t c = s_chunk[k][w];
-                before += w < wave ? c : 0u;
-                total += c;
-            }
-            const uint32_t i = c0 + (uint32_t)k * SORT_WG + tid;
-            if (i < live) row[i] = run + before + incl[k] - v[k];
-            run += total;
-        }
-        __syncthreads();   // s_chunk is rewritten by the next trip
-    }
-    if (tid == 0) digit_totals[d] = run;
+    hist[(size_t)blockIdx.x * RADIX + tid] = total;
+    // (blocks past a device-side length have left: the sums hold the live blocks only, a gated-off sort leaves them zero)
+    if (total != 0u) atomicAdd(&grp.sums[(size_t)(blockIdx.x / SORT_GROUP_BLOCKS) * RADIX + tid], total);
 }
 
 template <bool HAS_VALS, int SORT_KPT>
 __global__ __launch_bounds__(SORT_WG) void radix_scatter_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                               uint32_t n, uint32_t shift, uint32_t mask, uint32_t nblocks,
-                                                               const uint32_t* __restrict__ offsets,  // exclusive scan of hist
-                                                               const uint32_t* __restrict__ digit_totals,  // row-scan mode: offsets are per-row, add the digit prefix
+                                                               uint32_t n, uint32_t shift, uint32_t mask, uint32_t ngroups, uint32_t scanned,
+                                                               const uint32_t* __restrict__ hist,   // [block][digit], the histogram kernel's
+                                                               const uint32_t* __restrict__ gsum,   // [group][digit]; scanned: exclusive prefixes over the groups
+                                                               uint32_t* digit_totals,              // [256] scanned: in.  Else out (block 0), or NULL: nobody reads them
                                                                uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_vals, SortDyn dyn) {
     constexpr int SORT_TILE = SORT_WG * SORT_KPT;
     n = sort_live_n(n, dyn);
@@ -180,10 +139,10 @@ __global__ __launch_bounds__(SORT_WG) void radix_scatter_kernel(const uint32_t* 
     const uint32_t wave_base = block_base + wave * (64 * SORT_KPT);
     uint32_t key[SORT_KPT], val[SORT_KPT], rank[SORT_KPT];
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    // this thread's two table entries are needed only after the ranking: issue their loads first so the (strided, L2)
-    // round trip runs under it
-    const uint32_t my_offset = offsets[(size_t)tid * nblocks + blockIdx.x];
-    const uint32_t my_gtotal = digit_totals ? digit_totals[tid] : 0u;
+    // this thread's digit: its keys in the blocks in front of this one and in all blocks
+    uint32_t my_offset, my_gtotal;
+    sort_group_offset(hist, gsum, digit_totals, ngroups, scanned != 0u, blockIdx.x, (uint32_t)tid, my_offset, my_gtotal);
+    if (!scanned && digit_totals != nullptr && blockIdx.x == 0u) digit_totals[tid] = my_gtotal;
     if (block_base + (uint32_t)SORT_TILE <= n) {   // every block but the last: no bounds tests around the loads
 #pragma unroll
         for (int k = 0; k < SORT_KPT; ++k) {
@@ -242,7 +201,7 @@ __global__ __launch_bounds__(SORT_WG) void radix_scatter_kernel(const uint32_t* 
 #pragma unroll
         for (int w = 0; w < SORT_WAVES; ++w) { wofs += (w < wave) ? s_wsum[0][w] : 0u; gofs += (w < wave) ? s_wsum[1][w] : 0u; }
         const uint32_t excl = incl - total + wofs;
-        const uint32_t below = gincl - gt + gofs;  // keys with a smaller digit (0 when offsets already hold the full scan)
+        const uint32_t below = gincl - gt + gofs;  // keys with a smaller digit
         s_dbase[tid] = excl;
         s_gofs[tid] = below + my_offset - excl;
     }
@@ -270,6 +229,57 @@ __global__ __launch_bounds__(SORT_WG) void radix_scatter_kernel(const uint32_t* 
     }
 }
 
+// One block per table of [ngroups][256] group sums: exclusive prefixes over the groups in place, the column sums -> totals
+// (context.h SORT_DIRECT_GROUPS: only sorts of more than 1024 blocks).  16 rows in flight per trip.
+__global__ __launch_bounds__(RADIX) void sort_groups_scan_kernel(uint32_t* __restrict__ sums, uint32_t ngroups, uint32_t* __restrict__ totals) {
+    constexpr uint32_t B = 16;
+    uint32_t* col = sums + (size_t)blockIdx.x * ngroups * RADIX + threadIdx.x;
+    uint32_t run = 0;
+    for (uint32_t g0 = 0; g0 < ngroups; g0 += B) {
+        uint32_t v[B];
+#pragma unroll
+        for (uint32_t j = 0; j < B; ++j) v[j] = g0 + j < ngroups ? col[(size_t)(g0 + j) * RADIX] : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < B; ++j) {
+            if (g0 + j < ngroups) col[(size_t)(g0 + j) * RADIX] = run;
+            run += v[j];
+        }
+    }
+    totals[blockIdx.x * RADIX + threadIdx.x] = run;
+}
+int sort_groups_scan(bh_ctx* ctx, uint32_t* sums, uint32_t ngroups, uint32_t tables, uint32_t* totals) {
+    hipLaunchKernelGGL(sort_groups_scan_kernel, dim3(tables), dim3(RADIX), 0, ctx->stream, sums, ngroups, totals);
+    BH_LAUNCH_CHECK(ctx, "sort_groups_scan_kernel");
+    return 0;
+}
+
+// The next zeroed set of group tables (context.h SortGroups: exactly one histogram launch follows every call).  Growing (rare: the tables only grow) allocates both sets anew and
+// clears them with the one fill launch of their lifetime.
+int sort_groups_next(bh_ctx* ctx, size_t words, SortGroups* out) {
+    if (words > 0xFFFFFFFFull) return set_error(ctx, BH_ERR_INVALID_ARG, "sort: group tables beyond 2^32 words");
+    if (words > ctx->sort_groups_cap) {
+        if (ctx->sort_groups) {
+            BH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // queued kernels may still use the old tables
+            (void)hipFree(ctx->sort_groups);
+            ctx->sort_groups = nullptr;
+            ctx->sort_groups_cap = 0;
+        }
+        size_t cap = 16384;   // 64 blocks' groups: most sorts never grow it
+        while (cap < words) cap *= 2;
+        if (hipMalloc((void**)&ctx->sort_groups, 2 * cap * 4) != hipSuccess) { (void)hipGetLastError(); ctx->sort_groups = nullptr; return set_error(ctx, BH_ERR_OOM, "sort: group tables"); }
+        BH_HIP(ctx, hipMemsetAsync(ctx->sort_groups, 0, 2 * cap * 4, ctx->stream));
+        ctx->sort_groups_cap = cap;
+        ctx->sort_groups_dirty = 0;
+        ctx->sort_groups_cur = 0;
+    }
+    out->sums = ctx->sort_groups + (size_t)ctx->sort_groups_cur * ctx->sort_groups_cap;
+    out->stale = ctx->sort_groups + (size_t)(ctx->sort_groups_cur ^ 1u) * ctx->sort_groups_cap;
+    out->stale_words = (uint32_t)ctx->sort_groups_dirty;
+    ctx->sort_groups_dirty = words;
+    ctx->sort_groups_cur ^= 1u;
+    return 0;
+}
+
 // alloc_n >= n: what the scratch slots are sized for (a caller whose bound n moves from frame to frame passes its largest: the
 // arena only grows, and growing waits for the stream)
 static int radix_argsort_impl(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t bits,
@@ -292,12 +302,12 @@ static int radix_argsort_impl(bh_ctx* ctx, const uint32_t* keys, const uint32_t*
     if (alloc_n < n) alloc_n = n;
     const size_t alloc_bytes = (size_t)alloc_n * 4;
     const uint32_t alloc_blocks = (alloc_n + tile - 1) / tile;
-    // [256] digit totals followed by the [256][nblocks] table
+    // [256] digit totals (the tile sort's) followed by the [nblocks][256] table
     uint32_t* totals = (uint32_t*)ensure(ctx, SLOT_SORT_HIST, ((size_t)RADIX * alloc_blocks + RADIX) * 4);
     if (!totals) return BH_ERR_OOM;
     uint32_t* hist = totals + RADIX;
-    // (a device-side length always takes the row scan: it walks only the live part of each row, however long the table)
-    const bool rowscan = dynamic || nblocks <= (uint32_t)ROWSCAN_MAX_EPT * SORT_WG;
+    const uint32_t ngroups = sort_group_count(nblocks);
+    const uint32_t scanned = sort_groups_scanned(ngroups) ? 1u : 0u;
     // Ping-pong through two scratch pairs; pass 0 reads the caller's input (never
     // written), the last pass lands in out_* unless that would alias its source
     // (single-pass in-place call), in which case it is staged and copied.
@@ -330,27 +340,24 @@ static int radix_argsort_impl(bh_ctx* ctx, const uint32_t* keys, const uint32_t*
         const uint32_t width = base_w + (p < wide ? 1u : 0u);
         const uint32_t shift = p * base_w + (p < wide ? p : wide);
         const uint32_t mask = (1u << width) - 1u;
-        if (kpt == 4u) hipLaunchKernelGGL(radix_hist_kernel<4>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, nblocks, hist, pd);
-        else if (kpt == 8u) hipLaunchKernelGGL(radix_hist_kernel<8>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, nblocks, hist, pd);
-        else hipLaunchKernelGGL(radix_hist_kernel<16>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, nblocks, hist, pd);
+        SortGroups grp;   // (every pass its own zeroed set: the pass behind it clears this one)
+        BH_TRY(sort_groups_next(ctx, (size_t)ngroups * RADIX, &grp));
+        if (kpt == 4u) hipLaunchKernelGGL(radix_hist_kernel<4>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, hist, grp, pd);
+        else if (kpt == 8u) hipLaunchKernelGGL(radix_hist_kernel<8>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, hist, grp, pd);
+        else hipLaunchKernelGGL(radix_hist_kernel<16>, dim3(nblocks), dim3(SORT_WG), 0, ctx->stream, src_k, n, shift, mask, hist, grp, pd);
         BH_LAUNCH_CHECK(ctx, "radix_hist_kernel");
-        if (rowscan) {
-            hipLaunchKernelGGL(radix_rowscan_kernel, dim3(RADIX), dim3(SORT_WG), 0, ctx->stream, hist, nblocks, n, tile, totals, pd);
-            BH_LAUNCH_CHECK(ctx, "radix_rowscan_kernel");
-        } else {
-            BH_TRY(prefix_sum(ctx, hist, nullptr, RADIX * nblocks, hist, /*exclusive=*/true));
-        }
-        const uint32_t* tot = rowscan ? totals : nullptr;
+        if (scanned) BH_TRY(sort_groups_scan(ctx, grp.sums, ngroups, 1u, totals));
+        uint32_t* const no_totals = scanned ? totals : nullptr;   // (nobody reads the digit totals behind a generic pass)
         const dim3 grid(nblocks), block(SORT_WG);
         if (kpt == 4u) {
-            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 4>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
-            else hipLaunchKernelGGL((radix_scatter_kernel<false, 4>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
+            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 4>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
+            else hipLaunchKernelGGL((radix_scatter_kernel<false, 4>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
         } else if (kpt == 8u) {
-            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 8>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
-            else hipLaunchKernelGGL((radix_scatter_kernel<false, 8>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
+            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 8>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
+            else hipLaunchKernelGGL((radix_scatter_kernel<false, 8>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
         } else {
-            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 16>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
-            else hipLaunchKernelGGL((radix_scatter_kernel<false, 16>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, nblocks, hist, tot, dst_k, dst_v, pd);
+            if (src_v) hipLaunchKernelGGL((radix_scatter_kernel<true, 16>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
+            else hipLaunchKernelGGL((radix_scatter_kernel<false, 16>), grid, block, 0, ctx->stream, src_k, src_v, n, shift, mask, ngroups, scanned, hist, grp.sums, no_totals, dst_k, dst_v, pd);
         }
         BH_LAUNCH_CHECK(ctx, "radix_scatter_kernel");
         src_k = dst_k;
@@ -362,15 +369,15 @@ static int radix_argsort_impl(bh_ctx* ctx, const uint32_t* keys, const uint32_t*
 }
 
 // ---------------------------------------------------------------------------
-// The forward's tile sort + get_tile_offsets (render.rs:228-243, get_tile_offset.rs) in FIVE launches instead of seven.
+// The forward's tile sort + get_tile_offsets (render.rs:228-243, get_tile_offset.rs) in FOUR launches instead of seven (five beyond 4 M pairs).
 //
 // The (tile id, compact splat id) pairs arrive in depth order and leave grouped by tile, depth order kept.  As two LSD passes
-// plus the offsets kernel that is hist / row scan / scatter twice and one more launch: seven dependent launches of 5-18 us
-// for 20 MB.  Here the FIRST pass takes the HIGH digit (the three kernels above, stable): the pairs of one digit — a bucket of
-// 2^low_bits consecutive tiles — then sit together, still in depth order, and ONE block per bucket finishes the job without any
-// global table: it counts the bucket's pairs per tile and wave (a wave owns a contiguous part of the bucket), scans, writes the
-// tiles' [begin, end) rows of the offsets table — it knows them — and places every pair at
-//     bucket start + pairs of lower tiles + pairs of the same tile owned by earlier waves + rank inside the wave's part,
+// plus the offsets kernel that was hist / row scan / scatter twice and one more launch: seven dependent launches of 5-18 us
+// for 20 MB.  Here the FIRST pass takes the HIGH digit (the two kernels above, stable): the pairs of one digit — a bucket of
+// 2^low_bits consecutive tiles — then sit together, still in depth order, and blocks that each take a PART of a bucket (below)
+// finish the job: they count the part's pairs per tile and wave (a wave owns a contiguous piece of the part), add up the bucket's
+// part tables, write the tiles' [begin, end) rows of the offsets table and place every pair at
+//     bucket start + pairs of lower tiles + pairs of the same tile in earlier parts and earlier waves + rank inside the wave's piece,
 // which is the stable order.  Ranking is the scatter kernel's (wave-wide digit matching, no LDS atomics).
 // ---------------------------------------------------------------------------
 // Work is dealt in PARTS, not in buckets: a bucket of `size` pairs is ceil(size / TP_CHUNK) parts and ONE block handles one part,
@@ -579,13 +586,16 @@ int tile_sort_offsets(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, u
     uint32_t* hist = totals + RADIX;
     const SortDyn none{};
     const dim3 grid(nblocks), block(SORT_WG);
-    if (kpt == 8u) hipLaunchKernelGGL(radix_hist_kernel<8>, grid, block, 0, ctx->stream, keys, n, shift, mask, nblocks, hist, none);
-    else hipLaunchKernelGGL(radix_hist_kernel<16>, grid, block, 0, ctx->stream, keys, n, shift, mask, nblocks, hist, none);
+    const uint32_t ngroups = sort_group_count(nblocks);
+    const uint32_t scanned = sort_groups_scanned(ngroups) ? 1u : 0u;
+    SortGroups grp;
+    BH_TRY(sort_groups_next(ctx, (size_t)ngroups * RADIX, &grp));
+    if (kpt == 8u) hipLaunchKernelGGL(radix_hist_kernel<8>, grid, block, 0, ctx->stream, keys, n, shift, mask, hist, grp, none);
+    else hipLaunchKernelGGL(radix_hist_kernel<16>, grid, block, 0, ctx->stream, keys, n, shift, mask, hist, grp, none);
     BH_LAUNCH_CHECK(ctx, "radix_hist_kernel");
-    hipLaunchKernelGGL(radix_rowscan_kernel, dim3(RADIX), dim3(SORT_WG), 0, ctx->stream, hist, nblocks, n, tile, totals, none);
-    BH_LAUNCH_CHECK(ctx, "radix_rowscan_kernel");
-    if (kpt == 8u) hipLaunchKernelGGL((radix_scatter_kernel<true, 8>), grid, block, 0, ctx->stream, keys, vals, n, shift, mask, nblocks, hist, totals, mid_k, mid_v, none);
-    else hipLaunchKernelGGL((radix_scatter_kernel<true, 16>), grid, block, 0, ctx->stream, keys, vals, n, shift, mask, nblocks, hist, totals, mid_k, mid_v, none);
+    if (scanned) BH_TRY(sort_groups_scan(ctx, grp.sums, ngroups, 1u, totals));
+    if (kpt == 8u) hipLaunchKernelGGL((radix_scatter_kernel<true, 8>), grid, block, 0, ctx->stream, keys, vals, n, shift, mask, ngroups, scanned, hist, grp.sums, totals, mid_k, mid_v, none);
+    else hipLaunchKernelGGL((radix_scatter_kernel<true, 16>), grid, block, 0, ctx->stream, keys, vals, n, shift, mask, ngroups, scanned, hist, grp.sums, totals, mid_k, mid_v, none);
     BH_LAUNCH_CHECK(ctx, "radix_scatter_kernel");
     // parts of at most TP_CHUNK pairs, numbered bucket by bucket: at most n / TP_CHUNK + one partial part per bucket
     const uint32_t max_parts = n / TP_CHUNK + RADIX, alloc_parts = alloc_n / TP_CHUNK + RADIX;
