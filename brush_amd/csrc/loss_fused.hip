@@ -22,7 +22,14 @@
 // the XCD's own L2 instead of over the fabric — FETCH_SIZE per launch 95 -> 43 MB (pass A), 333 -> 123 MB (pass B), the pair
 // 114 -> 108 us.  (Round 2 had measured a banded order "neutral" in time and left it out: the Infinity Cache served the
 // repeated fetches; what they cost is fabric bandwidth the step's other kernels do not need at that moment.)
+// Operands: the eleven Gaussian taps are literals of the blurs' FMAs (TAP_TABLE below), and the few other values the hot blocks
+// multiply by (l1 / SSIM weights, the tap of an accumulator's first term) are copied into VGPRs once per block — a VALU op
+// with an SGPR source, which every tap FMA was while the taps travelled in the kernel arguments, issues at half rate
+// (DESIGN.md §4).  Pass B's row blur takes its items as column pairs of the 126 (plane, row) lines, without index arithmetic.
+// scripts/valu_operand_audit.py counts what is left (profiles/valu_operand_audit.txt); measurements in profiles/EXPERIMENTS.md.
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 
 #include "context.h"
 
@@ -53,6 +60,36 @@ Taps gauss_taps() {  // lib.rs:55-68
     return g;
 }
 
+// The same eleven taps as literals, for the kernels: a tap that arrives in FusedArgs sits in an SGPR, and a VALU op with an SGPR
+// source issues at half rate — every multiply-accumulate of both blurs did.  As literals / inline constants of the
+// FMAs they cost no register either.  gauss_taps() stays the definition: the launcher compares the two bit for bit
+// (taps_mismatch) and refuses to run on a host whose expf gives anything else.
+#define BH_TAP_0 0x1.0d957p-10f   /* w[0] = w[10] */
+#define BH_TAP_1 0x1.f1fe04p-8f   /* w[1] = w[9] */
+#define BH_TAP_2 0x1.26eb18p-5f   /* w[2] = w[8] */
+#define BH_TAP_3 0x1.bff1p-4f     /* w[3] = w[7] */
+#define BH_TAP_4 0x1.b43c4p-3f    /* w[4] = w[6] */
+#define BH_TAP_5 0x1.106562p-2f   /* w[5] */
+constexpr float TAP_TABLE[11] = {BH_TAP_0, BH_TAP_1, BH_TAP_2, BH_TAP_3, BH_TAP_4, BH_TAP_5, BH_TAP_4, BH_TAP_3, BH_TAP_2, BH_TAP_1, BH_TAP_0};
+// tap i of the table; every caller's index is a constant after unrolling, so this folds to the literal
+BH_DEV constexpr float tap(int i) { return TAP_TABLE[i]; }
+// A value the hot blocks use as a VALU operand, copied from its SGPR (a kernel argument) or literal into a VGPR once per block.
+// Tap 4 needs it although it is a literal: it weighs an accumulator's first term, fma(x, w, 0), which only exists as VOP3,
+// VOP3 takes no literal on gfx9, and the compiler then parks the literal in an SGPR.  (x * w instead would flip the sign of a
+// zero product; the results are to stay the parent's bit for bit.)
+BH_DEV float in_vgpr(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// index of the first tap at which gauss_taps() and the table differ in a bit, or -1
+int taps_mismatch() {
+    const Taps g = gauss_taps();
+    for (int i = 0; i < 11; ++i)
+        if (memcmp(&g.w[i], &TAP_TABLE[i], sizeof(float)) != 0) return i;
+    return -1;
+}
+
 struct FusedArgs {
     uint32_t h, w;
     float l1_w, ssim_w;
@@ -75,7 +112,6 @@ struct FusedArgs {
     // belongs to XCD b & 7 (the dispatcher deals consecutive workgroups to the eight XCDs in turn) and takes the (b >> 3)-th
     // tile, row-major, of column band b & 7 (band_w tile columns wide) — see loss_tile()
     uint32_t gx, gy_blocks, band_w;
-    Taps taps;
 };
 
 // Which 16 x 32 tile a block works on.  Row-major (band_w == 0), or by XCD column bands: a pass re-reads the 5-pixel apron of
@@ -207,6 +243,7 @@ __global__ __launch_bounds__(256) void loss_fused_forward_kernel(const float* __
         }
     }
     float acc_rgb = 0.0f;
+    const float tap4 = in_vgpr(tap(4)), l1_w = in_vgpr(a.l1_w), ssim_w = in_vgpr(a.ssim_w);
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
         __syncthreads();   // the tile is loaded (c == 0) / the previous plane's column pass is done with s_h
@@ -229,14 +266,14 @@ __global__ __launch_bounds__(256) void loss_fused_forward_kernel(const float* __
                 float sx = 0, sx2 = 0, sy = 0, sy2 = 0, sxy = 0;
 #pragma unroll
                 for (int d = 1; d < 6; ++d) {
-                    const float wd = a.taps.w[5 - d];
+                    const float wd = d == 1 ? tap4 : tap(5 - d);
                     sx += (x[cc - d] + x[cc + d]) * wd;
                     sx2 += (xx[cc - d] + xx[cc + d]) * wd;
                     sy += (y[cc - d] + y[cc + d]) * wd;
                     sy2 += (yy[cc - d] + yy[cc + d]) * wd;
                     sxy += (xy[cc - d] + xy[cc + d]) * wd;
                 }
-                const float wc = a.taps.w[5];
+                const float wc = tap(5);
                 sx += x[cc] * wc;
                 sx2 += xx[cc] * wc;
                 sy += y[cc] * wc;
@@ -260,12 +297,12 @@ __global__ __launch_bounds__(256) void loss_fused_forward_kernel(const float* __
             float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int d = 1; d < 6; ++d) {
-                const float wd = a.taps.w[5 - d];
+                const float wd = d == 1 ? tap4 : tap(5 - d);
 #pragma unroll
                 for (int k = 0; k < 5; ++k) m[k] += (v[o + 5 - d][k] + v[o + 5 + d][k]) * wd;
             }
 #pragma unroll
-            for (int k = 0; k < 5; ++k) m[k] += v[o + 5][k] * a.taps.w[5];
+            for (int k = 0; k < 5; ++k) m[k] += v[o + 5][k] * tap(5);
             if (!inside[o]) continue;
             const float mu1 = m[0], mu2 = m[2];
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2;
@@ -281,7 +318,9 @@ __global__ __launch_bounds__(256) void loss_fused_forward_kernel(const float* __
             const float cd = c_top * d_top * inv_ab;
             const float ssim = clampf(cd, -1.0f, 1.0f);
             const float2 pg = s_tile[c][(2 * ly + o + HALO) * SW + lx + HALO];
-            float lv = a.l1_w * __builtin_fabsf(pg.x - pg.y) + a.ssim_w * ssim;
+            // (spelled out: under fp contract(fast) WHICH of the two products is fused is the compiler's choice, and it changed
+            //  with the operands' register class — the loss moved by an ulp.  This is the form the kernel has always had.)
+            float lv = __builtin_fmaf(l1_w, __builtin_fabsf(pg.x - pg.y), ssim_w * ssim);
             if (a.mask) lv = lv * ga[o];
             acc_rgb += lv;
             // SSIM partials for the backward (lib.rs:455-520)
@@ -329,8 +368,9 @@ __global__ __launch_bounds__(256) void loss_fused_forward_kernel(const float* __
 __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kernel(const float* __restrict__ img, const uint32_t* __restrict__ gt,
                                                                  const float* __restrict__ partials /*[3][3][H][W]*/,
                                                                  float* __restrict__ v_output /*[H,W,4]*/, FusedArgs a) {
-    __shared__ float s_part[3][SR * SW];       // chain * (dmu1, dsigma1, dsigma12) of ONE colour plane
-    __shared__ float s_h2[3][SR * H2P];
+    // (8-byte aligned, SW and H2P even: the row blur reads and writes column pairs)
+    __shared__ __align__(8) float s_part[3][SR * SW];       // chain * (dmu1, dsigma1, dsigma12) of ONE colour plane
+    __shared__ __align__(8) float s_h2[3][SR * H2P];
     // strip-wise loss: the launch covers pixel rows [row0, row1) (whole 16-row tile rows); blocks are 32 rows tall
     const int lx = threadIdx.x, ly = threadIdx.y;
     const int rank = ly * TW + lx;
@@ -373,7 +413,8 @@ __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kerne
     // A tile row is 26 floats from column tx0 - 5: fetched as the 8 aligned float4s from tx0 - 8 (128 contiguous bytes; W % 4 == 0,
     // so a float4 lies entirely inside or outside the image) — 3 x 336 16-byte loads per colour instead of 3 x 1092 4-byte ones,
     // four per thread, and they are issued one colour AHEAD into registers: a block is a chain of nine barrier-separated phases
-    // and only six blocks fit a CU, so a global round trip per colour standing in front of its blur passes was most of the
+    // and only four blocks fit a CU (the kernel's 126-128 VGPRs allow four waves per SIMD; its 24.6 KB of LDS would allow six),
+    // so a global round trip per colour standing in front of its blur passes was most of the
     // block's life (probe builds: the plane loads cost 12-16 us, the two blur passes 11, the rest of the 65-us kernel was waiting).
     constexpr int ROW_ITEMS = 3 * SR * 8;
     auto fetch_rows = [&](const int c, float4 (&dst)[4]) {
@@ -410,6 +451,7 @@ __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kerne
     };
     float4 pre[4];
     if (wide_rows) fetch_rows(0, pre);
+    const float tap4 = in_vgpr(tap(4)), l1_w = in_vgpr(a.l1_w), ssim_w = in_vgpr(a.ssim_w);
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
         __syncthreads();   // the previous plane's column pass is done with the buffers
@@ -429,16 +471,37 @@ __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kerne
             }
         }
         __syncthreads();
-        const int probe_items = 3 * SR * TW;
-        for (int i = rank; i < probe_items; i += 256) {
-            const int j = i / (SR * TW), rem = i - j * (SR * TW);
-            const int r = rem / TW, col = (rem - r * TW) + HALO;
-            const float* row = &s_part[j][r * SW];
-            float acc = 0.0f;
+        // Row blur.  The three planes' 42 rows lie one behind the other in s_part and in s_h2 alike: "line" L = 42 j + r starts at
+        // float L * SW there and L * H2P here, so an item needs no (plane, row, column) at all — as a loop over i = rank + 256 n
+        // with i / (SR * TW), / TW and the two address builds, 15 of an item's 31 VALU instructions were that arithmetic.  An
+        // item is a PAIR of adjacent outputs of one line, 126 x 8 of them: its 12 inputs are six aligned 8-byte LDS reads (22
+        // 4-byte ones for two single outputs) and its two results one 8-byte store; thread -> (line rank / 8 + 32 n, pair rank & 7)
+        // for n = 0..3, every offset between trips an immediate.  Each output's accumulation order is what it was.
+        {
+            const float* src = &s_part[0][0] + (rank >> 3) * SW + 2 * (rank & 7);
+            float* dst = &s_h2[0][0] + (rank >> 3) * H2P + 2 * (rank & 7);
 #pragma unroll
-            for (int d = 1; d < 6; ++d) acc += (row[col - d] + row[col + d]) * a.taps.w[5 - d];
-            acc += row[col] * a.taps.w[5];
-            s_h2[j][r * H2P + (col - HALO)] = acc;
+            for (int n = 0; n < 4; ++n) {
+                if (n == 3 && rank >= 8 * (3 * SR - 96)) break;   // lines 126 and 127 do not exist
+                const float2* row = reinterpret_cast<const float2*>(src + 32 * n * SW);   // row[k] = tile columns 2 pair + 2 k, + 1
+                float x[12];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const float2 t = row[k];
+                    x[2 * k] = t.x; x[2 * k + 1] = t.y;
+                }
+                float res[2];
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    const int cc = HALO + o;
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int d = 1; d < 6; ++d) acc += (x[cc - d] + x[cc + d]) * (d == 1 ? tap4 : tap(5 - d));
+                    acc += x[cc] * tap(5);
+                    res[o] = acc;
+                }
+                *reinterpret_cast<float2*>(dst + 32 * n * H2P) = make_float2(res[0], res[1]);
+            }
         }
         __syncthreads();
         float v[3][12];
@@ -453,8 +516,8 @@ __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kerne
             for (int j = 0; j < 3; ++j) {
                 float acc = 0.0f;
 #pragma unroll
-                for (int d = 1; d < 6; ++d) acc += (v[j][o + 5 - d] + v[j][o + 5 + d]) * a.taps.w[5 - d];
-                acc += v[j][o + 5] * a.taps.w[5];
+                for (int d = 1; d < 6; ++d) acc += (v[j][o + 5 - d] + v[j][o + 5 + d]) * (d == 1 ? tap4 : tap(5 - d));
+                acc += v[j][o + 5] * tap(5);
                 sres[j] = acc;
             }
             const float ga = gt_ch(val[o], 3);
@@ -466,7 +529,7 @@ __global__ __launch_bounds__(256, BH_LOSSB_WAVES) void loss_fused_backward_kerne
             const float ssim_grad = sres[0] + (2.0f * p1) * sres[1] + ge * sres[2];
             const float diff = p1 - ge;
             const float l1_sign = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f);
-            out[o][c] = a.ssim_w * ssim_grad + a.l1_w * l1_sign * chain_c;
+            out[o][c] = __builtin_fmaf(ssim_w, ssim_grad, l1_w * l1_sign * chain_c);   // spelled out, as in pass A
         }
     }
 #pragma unroll
@@ -497,6 +560,13 @@ int launch_image_loss_fused_window(bh_ctx* ctx, const float* img_hwc4, const uin
     const uint32_t gx = (w + LB - 1) / LB, gy = (h + LB - 1) / LB;
     if (tile_y1 > gy) tile_y1 = gy;
     if (tile_y0 >= tile_y1) return set_error(ctx, BH_ERR_INVALID_ARG, "image loss: empty tile-row window");
+    static const int bad_tap = taps_mismatch();   // the host's libm does not change under a running process
+    if (bad_tap >= 0) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "image loss: Gaussian tap %d is %a on this host, the kernels' table holds %a", bad_tap, (double)gauss_taps().w[bad_tap],
+                 (double)TAP_TABLE[bad_tap]);
+        return set_error(ctx, BH_ERR_UNSUPPORTED, msg);
+    }
     const uint32_t a0 = tile_y0 > 0 ? tile_y0 - 1 : 0, a1 = tile_y1 < gy ? tile_y1 + 1 : gy;  // pass A window
     const dim3 block(TW, 16);
     const bool banded = ctx->knob_loss_bands != 0u && gx >= 16u;
@@ -510,7 +580,6 @@ int launch_image_loss_fused_window(bh_ctx* ctx, const float* img_hwc4, const uin
     a.bg[0] = cfg.bg[0]; a.bg[1] = cfg.bg[1]; a.bg[2] = cfg.bg[2];
     a.composite = cfg.composite_bg; a.mask = cfg.mask; a.alpha_match = alpha_match ? 1 : 0;
     a.dl_rgb = dl_rgb; a.dl_alpha = dl_alpha;
-    a.taps = gauss_taps();
     {
         ProfScope ps(ctx, "ImageLoss");
         a.ty_base = a0;
