@@ -396,6 +396,8 @@ const Option kOptions[] = {
      [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 16, 64, &u) || !(u == 16 || u == 32 || u == 64)) return false; c->knob_k5_exact_spw = u; return true; }},
     {"bwd_jobs", "0|1: the blend backward works on checkpointed 128-entry segments of the tiles' lists (default 1) or on whole tiles",
      [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_bwd_jobs); }},
+    {"bwd_wide_rows", "0|1: the blend backward addresses the gradient accumulator in 64 bits, as it does by itself from 2^32 bytes of accumulator on (default 0)",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_bwd_wide_rows); }},
     {"no_lpt", "0|1: the blend backward takes its tiles in index order",
      [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_no_lpt); }},
     {"lpt_classes", "log|linear: work classes of the backward's longest-first tile order — two per octave of blended splats, or 1/64 of the mean list length wide",
@@ -1165,7 +1167,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         if (r.num_intersections > 0 && v_output)
             BH_TRY(launch_rasterize_backward(ctx, fs.uniforms, fs.bg, fs.flags & BH_FLAG_SMOOTH_CUTOFF,
                                              r.compact_gid_from_isect, r.tile_offsets, r.projected, r.out_img, v_output, v_combined, fs.lpt,
-                                             r.tile_offsets_far, want_refine, &fs.jobs));
+                                             r.tile_offsets_far, want_refine, &fs.jobs, nv));
         if (depth) BH_TRY(launch_depth_backward(ctx, fs, *depth, v_combined));
     }
     {

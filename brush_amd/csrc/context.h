@@ -454,6 +454,7 @@ struct bh_ctx {
     bool adam_lds_raised = false;     // adam_rowreduced_kernel's > 64 KB dynamic-LDS opt-in was made on this ctx's device
     // developer knobs (A/B measurements): bh_set_option
     bool knob_no_lpt = false;         // option no_lpt: backward tiles in index order
+    bool knob_bwd_wide_rows = false;  // option bwd_wide_rows: the blend backward forms the accumulator's addresses in 64 bits whatever its size (rasterize.hip)
     bool knob_bwd_jobs = true;        // option bwd_jobs: the blend backward works on checkpointed segments of the tiles' lists (rasterize.hip)
     bool knob_lpt_linear = false;     // option lpt_classes=linear: the work classes of rounds 2-5 (rasterize.hip)
     bool knob_force_exchange = false;       // BH_FORCE_PG: run the gradient-exchange path with a one-rank communicator too (overhead measurement)
@@ -693,7 +694,8 @@ int launch_rasterize(bh_ctx* ctx, const ViewUniforms& u, const float bg[3], bool
 int launch_rasterize_backward(bh_ctx* ctx, const ViewUniforms& u, const float bg[3], bool smooth,
                               const uint32_t* isect_gids, const uint32_t* tile_offsets, const float* projected,
                               const float* out_img, const float* v_output, float* v_combined, const uint32_t* lpt,
-                              const uint32_t* tile_offsets_far = nullptr, bool want_refine = true, const BwdJobs* jobs = nullptr);
+                              const uint32_t* tile_offsets_far = nullptr, bool want_refine = true, const BwdJobs* jobs = nullptr,
+                              uint32_t accum_rows = 0u);   // rows of v_combined (0: not known)
 // loss.hip
 int launch_image_loss_forward(bh_ctx* ctx, const float* pred, const uint32_t* gt, uint32_t channels, uint32_t h,
                               uint32_t w, const BhLossConfig& cfg, float* loss_map);

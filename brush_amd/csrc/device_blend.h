@@ -75,5 +75,32 @@ BH_DEV float row_allreduce(float x) {
     x = dpp_rot_add<0x121>(x);  // row_ror:1
     return x;
 }
+// The same three row sums, FOLDED into one register while they are reduced (seven DPP adds instead of twelve): a DPP add with a
+// partial bank_mask writes only some 4-lane banks of its destination, so b's row_ror:8 sums go into banks 2-3 of a's, the
+// merged row_ror:4 step is kept where it is right (row_ror:4 feeds bank n from bank n-1: banks 1 and 3), c's row_ror:4 sums take
+// the two banks that step left stale (0 and 2), and the last two steps run inside the quads of the ONE register.  Afterwards
+// row r holds, in every lane of the bank, bank 1: a's row sum, bank 3: b's, banks 0 and 2: c's — each the same 16 values in a
+// pairwise tree of the same depth as row_allreduce's.
+// The compiler does not fuse a masked update_dpp with the add, hence the assembly, and it pads no hazard inside it: a VALU write
+// of a VGPR needs 2 wait states before a DPP op reads it (what the compiler's own recognizer enforces: GCNHazardRecognizer,
+// DppVgprWaitStates).  The opening s_nop covers the adds in front; below, every DPP read has two instructions or one + s_nop 0,
+// or s_nop 1, between it and the write of its source.  Needs all 64 lanes active (DPP reads return 0 from lanes that are not).
+BH_DEV float row_allreduce3_folded(float a, float b, float c) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %[a], %[a], %[a] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[c], %[c], %[c] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[a], %[b], %[b] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %[a], %[a], %[a] row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %[a], %[c], %[c] row_ror:4 row_mask:0xf bank_mask:0x5\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %[a], %[a], %[a] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %[a], %[a], %[a] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+        : [a] "+v"(a), [c] "+v"(c)
+        : [b] "v"(b));
+    return a;
+}
 
 }  // namespace bh

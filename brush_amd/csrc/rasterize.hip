@@ -155,7 +155,7 @@ BH_DEV uint32_t tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode
 // and the conservative sigma bound used for the wave-uniform quadrant skip.
 // HALF_CONIC (the forward): c00 and c11 are staged halved — sigma = 1/2 (c00 dx^2 + c11 dy^2) + c01 dx dy then needs no
 // multiply by 1/2 per pixel, and scaling by a power of two commutes with every rounding on the way: bit-identical.
-template <bool SMOOTH, bool HALF_CONIC>
+template <bool SMOOTH, bool HALF_CONIC, uint32_t GID_SCALE = 1u>
 BH_DEV uint32_t stage_batch(const uint32_t* __restrict__ isect_gids, const float* __restrict__ projected,
                             uint32_t batch_start, uint32_t cnt, int lane, float* s_splat) {
     uint32_t cg = 0;
@@ -171,7 +171,7 @@ BH_DEV uint32_t stage_batch(const uint32_t* __restrict__ isect_gids, const float
         const float diag = HALF_CONIC ? 0.5f : 1.0f;
         d[0] = make_float4(v[0], v[1], diag * v[2], v[3]);
         d[1] = make_float4(diag * v[4], v[5], __builtin_fmaxf(v[6], 0.0f), __builtin_fmaxf(v[7], 0.0f));
-        d[2] = make_float4(__builtin_fmaxf(v[8], 0.0f), cut, u2f(gate), u2f(cg));
+        d[2] = make_float4(__builtin_fmaxf(v[8], 0.0f), cut, u2f(gate), u2f(cg * GID_SCALE));
     }
     return cg;
 }
@@ -781,7 +781,9 @@ int launch_rasterize(bh_ctx* ctx, const ViewUniforms& vu, const float bg[3], boo
 //   * the ten per-splat sums over the tile's 256 pixels leave the wave through a register butterfly (below) and ONE 10-lane
 //     global_atomic_add_f32.  It is the single most expensive piece left: a build without any reduction (wrong results) runs
 //     232 us instead of 325 — 28 % of the kernel for ~45 instructions, because v_permlane*_swap and DPP adds are slow AND
-//     form a dependent chain.  Three replacements were built, verified against the CPU checker, measured and dropped
+//     form a dependent chain.  (Since then the row stage folds its three registers into one while it reduces them — seven DPP
+//     adds instead of twelve, no per-lane select of the result — and the atomic's address is a 32-bit add of a staged byte
+//     offset on the kernel argument: 319 -> 298 us, profiles/EXPERIMENTS.md.)  Three replacements were built, verified against the CPU checker, measured and dropped
 //     (DESIGN.md §8): partials parked in LDS and summed by lane pairs behind a barrier (384 us), the same with the reads issued
 //     one splat later so nobody waits (446 us: the LDS pipe is not idle enough for 6.5 KB more per splat and wave), and the
 //     matrix core (v_mfma_f32_16x16x4_f32 with column selectors: exact, 542 us — the f32 MFMAs do not hide beside the VALU work).
@@ -810,7 +812,7 @@ constexpr int BWD_WAVES = 5;   // waves per SIMD the default variant (hard cutof
 // accumulator like those of different tiles.  Why: one wave per TILE made the launch last as long as its heaviest tile (a lone
 // wave retires an op every ~5 cycles, one of five on a SIMD every ~13): 409 us for a frame whose heaviest tile blends 879 splats
 // while the mean tile blends 58 (an object in front of an empty background), and 1.6 rounds of whole tiles on the uniform frame.
-template <bool SMOOTH, bool REFINE, bool JOBS>
+template <bool SMOOTH, bool REFINE, bool JOBS, bool WIDE>
 __global__ __launch_bounds__(64, (BWD_WAVES - (SMOOTH ? 1 : 0) + (REFINE ? 0 : 1))) void rasterize_backward_kernel(RasterUniforms u, const uint32_t* __restrict__ isect_gids,
                                                                const uint32_t* __restrict__ tile_offsets,
                                                                const float* __restrict__ projected,
@@ -936,6 +938,16 @@ __global__ __launch_bounds__(64, (BWD_WAVES - (SMOOTH ? 1 : 0) + (REFINE ? 0 : 1
     // and are cleared only after a reduction: a splat that touches no pixel leaves them at zero, so the common "no contribution" path
     // carries no re-initialisation at all.
     float aP = 0.f, aQ = 0.f, aR2 = 0.f, aR3 = 0.f, aR4 = 0.f, aCr = 0.f, aCg = 0.f, aCb = 0.f, aVs = 0.f, aRf = 0.f;
+    // Which component of a reduced splat this lane sends (byte offset inside the accumulator row), and whether it sends at all:
+    // functions of the lane alone, fixed per job.  ri: lane inside its 16-lane row; rsel: rows 0..3 of a swap16_add result hold
+    // components 0 2 1 3 of its four.
+    const uint32_t ri = (uint32_t)lane & 15u, rrow = (uint32_t)lane >> 4;
+    const uint32_t rsel = ((rrow & 1u) << 1) | (rrow >> 1);
+    // folded register (device_blend.h row_allreduce3_folded): bank 1 of row r holds g[rsel], bank 3 g[4 + rsel], banks 0 and 2
+    // g8 (row 0) / g9 (row 2).  Senders: lanes 4 and 12 of every row, lane 0 of rows 0 and 2.
+    const uint32_t in_k2 = 0u - (((ri >> 2) & 1u) ^ 1u);   // all ones in bank 0 (and 2), branch-free on purpose
+    const uint32_t comp4 = ((in_k2 & (8u + (rrow >> 1))) | (~in_k2 & ((ri >> 3) * 4u + rsel))) * 4u;
+    const bool sends = ((ri & 3u) == 0u) & (ri != 8u) & ((ri != 0u) | ((rrow & 1u) == 0u));
     // One staged batch.  CLAMP = false: every alpha0 of the batch is <= 0.999, so min(0.999, alpha0 * G) is the identity and
     // the "below the clamp" gate of the geometry gradients (…:332) is always open — one v_min, one v_cmp and one v_cndmask
     // (all half-rate) less per pixel-quadrant.  Which variant runs is decided per BATCH (a ballot at staging time), not per
@@ -1028,14 +1040,14 @@ __global__ __launch_bounds__(64, (BWD_WAVES - (SMOOTH ? 1 : 0) + (REFINE ? 0 : 1
                 // tiles, so K18 applies them ONCE per splat to the accumulated row instead of this kernel once per (splat, tile).
                 const float h0 = swap32_add(aP, aQ), h1 = swap32_add(aR2, aR3), h2 = swap32_add(aR4, aCr);
                 const float h3 = swap32_add(aCg, aCb), h4 = swap32_add(aVs, REFINE ? aRf : 0.0f);
-                const float k0 = row_allreduce(swap16_add(h0, h1));
-                const float k1 = row_allreduce(swap16_add(h2, h3));
-                const float k2 = row_allreduce(swap16_add(h4, 0.0f));
-                const int ri = lane & 15, rrow = lane >> 4;
-                const int comp = ri * 4 + (((rrow & 1) << 1) | (rrow >> 1));
-                const float mine = ri == 0 ? k0 : (ri == 1 ? k1 : k2);
-                const uint32_t cg = f2u(s_splat[t * SPLAT_STRIDE + 11]);
-                if (ri < 3 && comp < 10) unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + comp], mine);
+                const float mine = row_allreduce3_folded(swap16_add(h0, h1), swap16_add(h2, h3), swap16_add(h4, 0.0f));
+                // the accumulator row was staged in word 11 as a BYTE offset (row * 40): the address is a 32-bit add on a
+                // loop-invariant base.  WIDE (2^32 bytes of accumulator or more: the launch decides): the row index, 64 bits.
+                const uint32_t row = f2u(s_splat[t * SPLAT_STRIDE + 11]);
+                if (sends) {
+                    if (!WIDE) unsafeAtomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(v_combined) + (size_t)(uint32_t)(row + comp4)), mine);
+                    else unsafeAtomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(v_combined) + ((size_t)row * 40u + comp4)), mine);
+                }
                 aP = aQ = aR2 = aR3 = aR4 = aCr = aCg = aCb = aVs = aRf = 0.0f;
             }
         }
@@ -1047,7 +1059,7 @@ __global__ __launch_bounds__(64, (BWD_WAVES - (SMOOTH ? 1 : 0) + (REFINE ? 0 : 1
         for (uint32_t batch_start = range_lo; batch_start < range_hi; batch_start += BATCH) {
             const uint32_t cnt = min((uint32_t)BATCH, range_hi - batch_start);
             __syncthreads();
-            stage_batch<SMOOTH, true>(isect_gids, projected, batch_start, cnt, lane, s_splat);
+            stage_batch<SMOOTH, true, WIDE ? 1u : 40u>(isect_gids, projected, batch_start, cnt, lane, s_splat);
             __syncthreads();
             const bool mine_clamps = (uint32_t)lane < cnt && s_splat[lane * SPLAT_STRIDE + 5] > 0.999f;
             if (__ballot(mine_clamps) != 0ull) run_batch(std::true_type{}, cnt);
@@ -1058,21 +1070,21 @@ __global__ __launch_bounds__(64, (BWD_WAVES - (SMOOTH ? 1 : 0) + (REFINE ? 0 : 1
   }
 }
 
-template <bool SMOOTH, bool REFINE, bool JOBS>
+template <bool SMOOTH, bool REFINE, bool JOBS, bool WIDE>
 static void launch_rasterize_backward_t(hipStream_t stream, dim3 grid, hipEvent_t ea, hipEvent_t eb, const RasterUniforms& u, const uint32_t* isect_gids,
                                         const uint32_t* tile_offsets, const float* projected, const float* out_img, const float* v_output, float* v_combined,
                                         const uint32_t* lpt, const uint32_t* tile_offsets_far, const BwdJobs& jb) {
     const dim3 block(64);
     if (ea)   // profiling level 2 (bench.py's timed region): the launch carries its own start / stop events (context.h)
-        hipExtLaunchKernelGGL((rasterize_backward_kernel<SMOOTH, REFINE, JOBS>), grid, block, 0, stream, ea, eb, 0, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb);
+        hipExtLaunchKernelGGL((rasterize_backward_kernel<SMOOTH, REFINE, JOBS, WIDE>), grid, block, 0, stream, ea, eb, 0, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb);
     else
-        hipLaunchKernelGGL((rasterize_backward_kernel<SMOOTH, REFINE, JOBS>), grid, block, 0, stream, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb);
+        hipLaunchKernelGGL((rasterize_backward_kernel<SMOOTH, REFINE, JOBS, WIDE>), grid, block, 0, stream, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb);
 }
 
 int launch_rasterize_backward(bh_ctx* ctx, const ViewUniforms& vu, const float bg[3], bool smooth,
                               const uint32_t* isect_gids, const uint32_t* tile_offsets, const float* projected,
                               const float* out_img, const float* v_output, float* v_combined, const uint32_t* lpt,
-                              const uint32_t* tile_offsets_far, bool want_refine, const BwdJobs* jobs) {
+                              const uint32_t* tile_offsets_far, bool want_refine, const BwdJobs* jobs, uint32_t accum_rows) {
     RasterUniforms u;
     u.band_mode = ctx->knob_band_mode;
     u.rcp_class_width = 1.0f;
@@ -1091,9 +1103,15 @@ int launch_rasterize_backward(bh_ctx* ctx, const ViewUniforms& vu, const float b
     const uint32_t per = band_slots(u.num_tiles);
     const uint32_t nblocks = (by_jobs ? 2u : 1u) * per * 8u;
     const dim3 grid(nblocks);
+    // K17 stages a splat's accumulator row as a BYTE offset (row * 40) and adds it to the base in 32 bits: that holds while the
+    // whole accumulator is below 2^32 bytes (accum_rows * 40 <= 2^32: 107 M listed splats).  Beyond that, or when the caller does
+    // not say how many rows there are, the WIDE variants stage the row index and form the address in 64 bits.
+    // (option bwd_wide_rows = 1 selects them at any size: what the tests run them by)
+    const bool wide = ctx->knob_bwd_wide_rows || accum_rows == 0u || (uint64_t)accum_rows * 40ull > (1ull << 32);
     hipEvent_t ea = ctx->prof.ext_a, eb = ctx->prof.ext_b;
     ctx->prof.ext_a = ctx->prof.ext_b = nullptr;
-#define BH_K17(S, R, J) launch_rasterize_backward_t<S, R, J>(ctx->stream, grid, ea, eb, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb)
+#define BH_K17_W(S, R, J, W) launch_rasterize_backward_t<S, R, J, W>(ctx->stream, grid, ea, eb, u, isect_gids, tile_offsets, projected, out_img, v_output, v_combined, lpt, tile_offsets_far, jb)
+#define BH_K17(S, R, J) do { if (wide) BH_K17_W(S, R, J, true); else BH_K17_W(S, R, J, false); } while (0)
     if (by_jobs) {
         if (smooth && want_refine) BH_K17(true, true, true);
         else if (smooth) BH_K17(true, false, true);
@@ -1106,6 +1124,7 @@ int launch_rasterize_backward(bh_ctx* ctx, const ViewUniforms& vu, const float b
         else BH_K17(false, false, false);
     }
 #undef BH_K17
+#undef BH_K17_W
     BH_LAUNCH_CHECK(ctx, "rasterize_backward_kernel");
     return 0;
 }
