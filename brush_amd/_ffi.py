@@ -283,6 +283,17 @@ DEPTH_LOSS_SYMBOLS = {
     "bh_eval_depth_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhDepthTarget), C.c_void_p]),
 }
 
+# every symbol include/brush_hip_normal.h declares (normal maps of a saved forward, normals from a depth map, and their gradients)
+NORMAL_ACCUMULATED, NORMAL_UNIT = 0, 1   # BH_NORMAL_*
+NORMAL_SYMBOLS = {
+    "bh_splat_normals": (C.c_int, [C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bh_render_normal": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bh_render_backward_normal_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+                                        + [C.c_void_p] * 7),
+    "bh_depth_to_normal": (C.c_int, [C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_depth_to_normal_backward": (C.c_int, [C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -322,7 +333,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS))
     return _lib
 
 
@@ -331,6 +342,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

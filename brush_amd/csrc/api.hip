@@ -1117,9 +1117,10 @@ namespace bh {
 // floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
 // depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
 // v_viewmat (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined.
+// normal (normal.hip): a normal term's raw sums join the accumulator like depth's; only with dense, zero-filled outputs.
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat) {
+                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat, const NormalTerm* normal) {
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
@@ -1137,6 +1138,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         row_marks = span == GradClears::ROW_MARKS;
         // (ROW_MARKS: the single-GPU train step reads only the rows K18 writes and marks — its forward cleared the marks)
         if (row_marks && !one_span) return set_error(ctx, BH_ERR_STATE, "internal: row-marked gradients without the train step's gradient span");
+        if (row_marks && normal) return set_error(ctx, BH_ERR_STATE, "internal: a normal term with row-marked gradients");
         const bool span_done = one_span && span != GradClears::NONE;
         if (one_span && (span_floats & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_transforms) & 15u) == 0) {
             // v_combined and the exchange buffer's gradient span cleared by ONE launch (hipMemsetAsync spends two or
@@ -1169,6 +1171,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                              r.compact_gid_from_isect, r.tile_offsets, r.projected, r.out_img, v_output, v_combined, fs.lpt,
                                              r.tile_offsets_far, want_refine, &fs.jobs, nv));
         if (depth) BH_TRY(launch_depth_backward(ctx, fs, *depth, v_combined));
+        if (normal) BH_TRY(launch_normal_backward(ctx, fs, *normal, transforms, v_combined));
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
@@ -1176,6 +1179,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
         if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
+        if (normal) BH_TRY(launch_normal_vn_scatter(ctx, fs, transforms, v_transforms));
     }
     if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
         ProfScope ps(ctx, "PoseGrad");

@@ -84,6 +84,7 @@ enum Slot : int {
     SLOT_EXPOSED,            // bh_train_step with an exposure table: [H,W,4] the exposed frame the loss reads (out_img stays as rendered)
     SLOT_DEPTH_LOSS,         // bh_depth_loss_value_and_grad / bh_eval_depth_metrics: one f64 row of 4 per block (depth_loss.hip)
     SLOT_DEPTH_TERM,         // bh_train_step with a depth target: expected depth [H,W] | v_depth [H,W] | the term's loss pair (4 floats)
+    SLOT_NORMAL,             // bh_render_normal / bh_render_backward_normal_saved: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip)
     SLOT_COUNT
 };
 
@@ -353,6 +354,12 @@ struct DepthTerm {
     uint32_t mode = 0;                // BH_DEPTH_ACCUMULATED or BH_DEPTH_EXPECTED
 };
 
+// The normal term of a backward (normal.hip, brush_hip_normal.h): <v_normal, normal map `mode` of the forward>
+struct NormalTerm {
+    const float* v_normal = nullptr;   // [H,W,3]
+    uint32_t mode = 0;                 // BH_NORMAL_ACCUMULATED or BH_NORMAL_UNIT
+};
+
 }  // namespace bh
 
 // The blend backward accumulates RAW per-splat sums into v_combined and the projection backward maps them to the reference's
@@ -487,16 +494,22 @@ int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, con
 // record either way, no copy); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished first).
 // Valid until the next call that retains, releases or renders on the ctx.
 int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, const ForwardState** fs);
-// api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth term (then K17 does not run)
+// api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth or a normal term (then K17
+// does not run)
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr);
+                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr,
+                  const NormalTerm* normal = nullptr);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
 int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
 // mark_rows (the single-GPU train step's ROW_MARKS span): a row K18 did not write is stored whole (zeros but the mean) and marked
 int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows = false, float* v_sh_coeffs = nullptr,
                             float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
 int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, float* out_depth);
+// normal.hip: the normal term between K17 and K18 (raw sums into v_combined, Vn into SLOT_NORMAL), and Vn -> v_quat behind a K18
+// that wrote dense, zero-filled outputs (never the row-marked train-step path)
+int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined);
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms);
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);

@@ -1,0 +1,684 @@
+// normal.hip — normal maps of a rendered frame, normals from a depth map, and their gradients (include/brush_hip_normal.h,
+// DESIGN.md §6m).
+//
+// A normal map is one more blend over the lists a BH_FLAG_BWD_INFO forward saved, as a depth map is (depth.hip): the same splats in
+// the same order with the same alpha, cut-off, clamp and saturation rule as the colour blend (device_blend.h holds the one copy of
+// that arithmetic), folding a per-splat 3-vector where depth folds z.  K16 / K17 / K18 and the depth kernels are not touched.
+//
+//   * splat normals: one thread per splat, dense [N,3] (bh_splat_normals) or compact [Nv,3] over global_from_compact_gid (what
+//     the two blends stage);
+//   * forward: the shape of depth_forward_kernel.  A staged splat is 12 floats (x y c00/2 c01 | c11/2 alpha0 sigma_cut nx | ny nz - -),
+//     three uniform ds_read_b128 per splat, three fmas per contributing pair;
+//   * backward: one wave per tile, forward-order replay as depth_backward_kernel with a 3-vector cotangent g per pixel: the "colour"
+//     of splat i is g . n_i, the remaining sum S starts at g . N (an accumulated-normal forward into scratch precedes the replay).
+//     UNIT mode turns v into g = (v - (v . u) u) / |N| in the prologue, so both modes are one replay.  P Q R2 R3 R4 Vs join the
+//     [Nv,10] accumulator between K17 and K18 in the columns depth uses; Vn = sum of vis * g goes to a compact [Nv,3] vector that a
+//     small kernel behind K18 carries to the quaternions;
+//   * depth -> normal and its backward: streaming kernels, one thread per pixel; the backward is a gather without atomics.
+#include <algorithm>
+
+#include "context.h"
+#include "device_blend.h"
+#include "../../include/brush_hip_depth.h"
+#include "../../include/brush_hip_normal.h"
+
+namespace bh {
+
+namespace {
+
+constexpr int NORMAL_STRIDE = 12;   // floats per staged splat
+constexpr int NORMAL_BATCH = 64;
+
+struct NormalUniforms {
+    uint32_t tile_bw, num_tiles, tile_begin, img_w, img_h, band_mode;
+};
+
+// block -> tile of the window (depth.hip depth_tile_of_block's band map)
+BH_DEV uint32_t normal_tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode) {
+    const uint32_t per = band_slots(num_tiles);
+    const uint32_t i = b >> 3;
+    return i < per ? band_tile(b & 7u, i, per, band_mode) : 0xFFFFFFFFu;
+}
+
+// the view a splat normal needs: rotation (column-major) and translation of the view matrix
+struct NormalView {
+    float vm[12];
+};
+
+// ---------------------------------------------------------------------------
+// the normal of a splat
+// ---------------------------------------------------------------------------
+// k: the smallest log-scale (lowest index on a tie); qn: the normalised quaternion; sign: -1 where R_view col_k(qn) looks away from the camera
+struct SplatFrame {
+    Quat q, qn;
+    float inv_len, sign;
+    int k;
+    Vec3A n;   // the oriented camera-space normal
+};
+
+BH_DEV SplatFrame splat_frame(const float* __restrict__ t, const NormalView& v) {
+    SplatFrame f;
+    const Vec3A mean = v3(t[0], t[1], t[2]);
+    f.q = Quat{t[3], t[4], t[5], t[6]};
+    const float s0 = t[7], s1 = t[8], s2 = t[9];
+    f.k = 0;
+    float best = s0;
+    if (s1 < best) { best = s1; f.k = 1; }
+    if (s2 < best) { best = s2; f.k = 2; }
+    f.inv_len = 1.0f / __builtin_sqrtf(qdot(f.q, f.q));
+    f.qn = qscale(f.q, f.inv_len);
+    const Mat3 r = quat_to_mat3(f.qn);
+    const Vec3A nw = f.k == 0 ? col0(r) : (f.k == 1 ? col1(r) : col2(r));
+    const Mat3 rv = Mat3{v.vm[0], v.vm[1], v.vm[2], v.vm[3], v.vm[4], v.vm[5], v.vm[6], v.vm[7], v.vm[8]};
+    const Vec3A nc = mul_vec3(rv, nw);
+    const Vec3A mean_c = add(mul_vec3(rv, mean), v3(v.vm[9], v.vm[10], v.vm[11]));
+    f.sign = dot(nc, mean_c) > 0.0f ? -1.0f : 1.0f;
+    f.n = scale(nc, f.sign);
+    return f;
+}
+
+// gid == NULL: the dense form (row i of transforms -> row i of out); else row gid[i] -> row i (the compact form)
+__global__ __launch_bounds__(256) void splat_normals_kernel(uint64_t n, NormalView v, const uint32_t* __restrict__ gid,
+                                                            const float* __restrict__ transforms, float* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t row = gid ? (uint64_t)gid[i] : i;
+    const SplatFrame f = splat_frame(transforms + row * 10, v);
+    float* o = out + i * 3;
+    o[0] = f.n.x;
+    o[1] = f.n.y;
+    o[2] = f.n.z;
+}
+
+// lane i stages splat i of the batch; the diagonal of the conic halved as in K16 (bit-identical sigma, rasterize.hip stage_batch)
+template <bool SMOOTH>
+BH_DEV uint32_t stage_normal_batch(const uint32_t* __restrict__ isect_gids, const float* __restrict__ projected, const float* __restrict__ normals,
+                                   uint32_t batch_start, uint32_t cnt, int lane, float* s_splat) {
+    uint32_t cg = 0;
+    if ((uint32_t)lane < cnt) {
+        cg = isect_gids[batch_start + lane];
+        const float* p = projected + (size_t)cg * 9;
+        float v[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] = p[k];
+        const float* nn = normals + (size_t)cg * 3;
+        const float nx = nn[0], ny = nn[1], nz = nn[2];
+        float4* d = reinterpret_cast<float4*>(s_splat + lane * NORMAL_STRIDE);
+        d[0] = make_float4(v[0], v[1], 0.5f * v[2], v[3]);
+        d[1] = make_float4(0.5f * v[4], v[5], blend_sigma_cut<SMOOTH>(v[5]), nx);
+        d[2] = make_float4(ny, nz, 0.0f, 0.0f);
+    }
+    return cg;
+}
+
+// ---------------------------------------------------------------------------
+// forward
+// ---------------------------------------------------------------------------
+// MODE: BH_NORMAL_ACCUMULATED / UNIT.  A finished pixel keeps a negative T (K16's convention).
+template <bool SMOOTH, uint32_t MODE>
+__global__ __launch_bounds__(64, 8) void normal_forward_kernel(NormalUniforms u, const uint32_t* __restrict__ isect_gids,
+                                                               const uint32_t* __restrict__ tile_offsets, const uint32_t* __restrict__ tile_offsets_far,
+                                                               const float* __restrict__ projected, const float* __restrict__ normals,
+                                                               float* __restrict__ out_normal) {
+    __shared__ __attribute__((aligned(16))) float s_splat[NORMAL_BATCH * NORMAL_STRIDE];
+    const uint32_t local_tile = normal_tile_of_block(blockIdx.x, u.num_tiles, u.band_mode);
+    if (local_tile >= u.num_tiles) return;
+    const uint32_t tile = u.tile_begin + local_tile;
+    const int lane = threadIdx.x;
+    const uint32_t px0 = (tile % u.tile_bw) * TILE_WIDTH + (lane & 7), py0 = (tile / u.tile_bw) * TILE_WIDTH + (lane >> 3);
+    const float pcx[2] = {(float)px0 + 0.5f, (float)(px0 + 8) + 0.5f};
+    const float pcy[2] = {(float)py0 + 0.5f, (float)(py0 + 8) + 0.5f};
+    float tr[4], ax[4], ay[4], az[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
+        tr[q] = (px < u.img_w && py < u.img_h) ? 1.0f : -1.0f;
+        ax[q] = ay[q] = az[q] = 0.0f;
+    }
+    auto any_live = [&]() {
+        bool l = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) l = l || tr[q] > 0.0f;
+        return l;
+    };
+    uint32_t sign_mask = 0x80000000u;   // kept in a VGPR: an SGPR operand halves a VALU op's issue rate
+    asm volatile("" : "+v"(sign_mask));
+    // the tile's blended splats, front to back: the near list, then the far slice's (all zero for a tile the near slice finished)
+    const uint32_t lo0 = tile_offsets[tile * 2], hi0 = tile_offsets[tile * 2 + 1];
+    uint32_t lo1 = 0u, hi1 = 0u;
+    if (tile_offsets_far) { lo1 = tile_offsets_far[tile * 2]; hi1 = tile_offsets_far[tile * 2 + 1]; }
+    bool done = false;
+#pragma nounroll
+    for (int part = 0; part < 2 && !done; ++part) {
+        const uint32_t range_lo = part ? lo1 : lo0, range_hi = part ? hi1 : hi0;
+        for (uint32_t batch_start = range_lo; batch_start < range_hi && !done; batch_start += NORMAL_BATCH) {
+            if (__ballot(any_live()) == 0ull) { done = true; break; }
+            const uint32_t cnt = min((uint32_t)NORMAL_BATCH, range_hi - batch_start);
+            __syncthreads();  // previous batch fully consumed (single wave: cheap)
+            stage_normal_batch<SMOOTH>(isect_gids, projected, normals, batch_start, cnt, lane, s_splat);
+            __syncthreads();
+            for (uint32_t t = 0; t < cnt; ++t) {
+                const float4 s0 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE]);      // x y c00/2 c01
+                const float4 s1 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 4]);  // c11/2 a sigma_cut nx
+                const float4 s2 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 8]);  // ny nz - -
+                const uint32_t cut_bits = f2u(s1.z);
+                float a_xx[2], b_x[2], c_y[2], dy[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const float dx = pcx[k] - s0.x;
+                    a_xx[k] = (s0.z * dx) * dx;
+                    b_x[k] = s0.w * dx;
+                    dy[k] = pcy[k] - s0.y;
+                    c_y[k] = s1.x * dy[k];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int k = q & 1, m = q >> 1;
+                    const float half_qv = __builtin_fmaf(c_y[m], dy[m], a_xx[k]);
+                    const float sigma = __builtin_fmaf(b_x[k], dy[m], half_qv);
+                    const bool pre = ((f2u(tr[q]) & sign_mask) | f2u(sigma)) <= cut_bits;
+                    if (__ballot(pre) != 0ull) {
+                        const float alpha = blend_alpha(s1.y, sigma);
+                        float alpha_eff, next_t;
+                        bool sat;
+                        const bool ok = blend_step<SMOOTH>(alpha, pre, tr[q], alpha_eff, next_t, sat);
+                        const bool contrib = ok && !sat;
+                        const float vis = contrib ? alpha_eff * tr[q] : 0.0f;
+                        ax[q] = __builtin_fmaf(s1.w, vis, ax[q]);   // (one explicit fma per channel and term, as the colour channels)
+                        ay[q] = __builtin_fmaf(s2.x, vis, ay[q]);
+                        az[q] = __builtin_fmaf(s2.y, vis, az[q]);
+                        tr[q] = ok ? (sat ? -tr[q] : next_t) : tr[q];
+                    }
+                }
+                // every pixel of the tile is done: the rest of the batch cannot contribute (checked every 8th splat, as K16 does)
+                if ((t & 7u) == 7u && __ballot(any_live()) == 0ull) { done = true; break; }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
+        if (px < u.img_w && py < u.img_h) {
+            float x = ax[q], y = ay[q], z = az[q];
+            if (MODE == BH_NORMAL_UNIT) {
+                const float len = __builtin_sqrtf(__builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
+                const float inv = len == 0.0f ? 0.0f : 1.0f / len;
+                x *= inv; y *= inv; z *= inv;
+            }
+            float* o = out_normal + ((size_t)px + (size_t)py * u.img_w) * 3;
+            o[0] = x; o[1] = y; o[2] = z;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// backward
+// ---------------------------------------------------------------------------
+// Unit normals U = N / |N|: dU = (dN - (dN . u) u) / |N|, so both modes are ONE replay with a per-pixel cotangent g (accumulated:
+// g = v; unit: g = (v - (v . u) u) / |N|, 0 where |N| == 0).  The "colour" of splat i at the pixel is cv = g . n_i and
+// S = the remaining sum of w_j (g . n_j), including the splat in flight, as in K17: it starts at g . N.
+template <bool SMOOTH>
+__global__ __launch_bounds__(64, 6) void normal_backward_kernel(NormalUniforms u, const uint32_t unit, const uint32_t* __restrict__ isect_gids,
+                                                                const uint32_t* __restrict__ tile_offsets, const uint32_t* __restrict__ tile_offsets_far,
+                                                                const float* __restrict__ projected, const float* __restrict__ normals,
+                                                                const float* __restrict__ normal_acc, const float* __restrict__ v_normal,
+                                                                float* __restrict__ v_combined, float* __restrict__ v_n) {
+    __shared__ __attribute__((aligned(16))) float s_splat[NORMAL_BATCH * NORMAL_STRIDE];
+    __shared__ uint32_t s_cg[NORMAL_BATCH];
+    const uint32_t local_tile = normal_tile_of_block(blockIdx.x, u.num_tiles, u.band_mode);
+    if (local_tile >= u.num_tiles) return;
+    const uint32_t tile = u.tile_begin + local_tile;
+    const uint32_t lo0 = tile_offsets[tile * 2], hi0 = tile_offsets[tile * 2 + 1];
+    uint32_t lo1 = 0u, hi1 = 0u;
+    if (tile_offsets_far) { lo1 = tile_offsets_far[tile * 2]; hi1 = tile_offsets_far[tile * 2 + 1]; }
+    if (hi0 <= lo0 && hi1 <= lo1) return;
+    const int lane = threadIdx.x;
+    const uint32_t px0 = (tile % u.tile_bw) * TILE_WIDTH + (lane & 7), py0 = (tile / u.tile_bw) * TILE_WIDTH + (lane >> 3);
+    const float pcx[2] = {(float)px0 + 0.5f, (float)(px0 + 8) + 0.5f};
+    const float pcy[2] = {(float)py0 + 0.5f, (float)(py0 + 8) + 0.5f};
+    float sS[4], sw[4], gx[4], gy[4], gz[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
+        sS[q] = sw[q] = gx[q] = gy[q] = gz[q] = 0.0f;
+        if (px < u.img_w && py < u.img_h) {
+            const size_t pix = ((size_t)px + (size_t)py * u.img_w) * 3;
+            const float nx = normal_acc[pix], ny = normal_acc[pix + 1], nz = normal_acc[pix + 2];
+            float vx = v_normal[pix], vy = v_normal[pix + 1], vz = v_normal[pix + 2];
+            if (unit) {
+                const float len = __builtin_sqrtf(__builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx)));
+                const float inv = len == 0.0f ? 0.0f : 1.0f / len;
+                const float ux = nx * inv, uy = ny * inv, uz = nz * inv;
+                const float vu = __builtin_fmaf(vz, uz, __builtin_fmaf(vy, uy, vx * ux));
+                vx = __builtin_fmaf(-vu, ux, vx) * inv;
+                vy = __builtin_fmaf(-vu, uy, vy) * inv;
+                vz = __builtin_fmaf(-vu, uz, vz) * inv;
+            }
+            gx[q] = vx; gy[q] = vy; gz[q] = vz;
+            sS[q] = __builtin_fmaf(vz, nz, __builtin_fmaf(vy, ny, vx * nx));
+            sw[q] = 1.0f;
+        }
+    }
+    float aP = 0.f, aQ = 0.f, aR2 = 0.f, aR3 = 0.f, aR4 = 0.f, aVs = 0.f, aNx = 0.f, aNy = 0.f, aNz = 0.f;
+#pragma nounroll
+    for (int part = 0; part < 2; ++part) {
+        const uint32_t range_lo = part ? lo1 : lo0, range_hi = part ? hi1 : hi0;
+        for (uint32_t batch_start = range_lo; batch_start < range_hi; batch_start += NORMAL_BATCH) {
+            const uint32_t cnt = min((uint32_t)NORMAL_BATCH, range_hi - batch_start);
+            __syncthreads();
+            const uint32_t my_cg = stage_normal_batch<SMOOTH>(isect_gids, projected, normals, batch_start, cnt, lane, s_splat);
+            s_cg[lane] = my_cg;
+            __syncthreads();
+            for (uint32_t t = 0; t < cnt; ++t) {
+                const float4 s0 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE]);      // x y c00/2 c01
+                const float4 s1 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 4]);  // c11/2 a sigma_cut nx
+                const float4 s2 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 8]);  // ny nz - -
+                const uint32_t cut_bits = f2u(s1.z);
+                float dxp[2], dyp[2], a_xx[2], b_x[2], c_y[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    dxp[k] = pcx[k] - s0.x;
+                    a_xx[k] = (s0.z * dxp[k]) * dxp[k];
+                    b_x[k] = s0.w * dxp[k];
+                    dyp[k] = pcy[k] - s0.y;
+                    c_y[k] = s1.x * dyp[k];
+                }
+                bool any = false;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int k = q & 1, m = q >> 1;
+                    // --- replay: the forward's arithmetic, instruction for instruction ---
+                    const float half_qv = __builtin_fmaf(c_y[m], dyp[m], a_xx[k]);
+                    const float sigma = __builtin_fmaf(b_x[k], dyp[m], half_qv);
+                    const bool pre = sw[q] > 0.0f && f2u(sigma) <= cut_bits;
+                    if (__ballot(pre) != 0ull) {
+                        const float alpha_raw = s1.y * exp_blend(-sigma);
+                        const float alpha = __builtin_fminf(0.999f, alpha_raw);
+                        const float T = sw[q];
+                        float alpha_eff, next_t;
+                        bool sat;
+                        const bool ok = blend_step<SMOOTH>(alpha, pre, T, alpha_eff, next_t, sat);
+                        sw[q] = (ok && sat) ? 0.0f : T;   // the pixel is done WITHOUT this splat
+                        if (ok && !sat) {
+                            // --- gradients (tolerance-checked) ---
+                            const float vis = alpha_eff * T;
+                            aNx = __builtin_fmaf(vis, gx[q], aNx);
+                            aNy = __builtin_fmaf(vis, gy[q], aNy);
+                            aNz = __builtin_fmaf(vis, gz[q], aNz);
+                            const float cv = __builtin_fmaf(gz[q], s2.y, __builtin_fmaf(gy[q], s2.x, gx[q] * s1.w));
+                            const float v_alpha_eff = __builtin_fmaf(T, cv, -sS[q]) * __builtin_amdgcn_rcpf(1.0f - alpha_eff);
+                            const float v_alpha = SMOOTH ? v_alpha_eff * (alpha_cutoff_weight(alpha) + alpha * alpha_cutoff_weight_deriv(alpha)) : v_alpha_eff;
+                            // geometry / opacity gradients only below the alpha clamp
+                            const float v_sigma = alpha_raw <= 0.999f ? -alpha * v_alpha : 0.0f;
+                            const float ux = v_sigma * dxp[k], uy = v_sigma * dyp[m];
+                            aP += ux;
+                            aQ += uy;
+                            aR2 = __builtin_fmaf(ux, dxp[k], aR2);
+                            aR3 = __builtin_fmaf(ux, dyp[m], aR3);
+                            aR4 = __builtin_fmaf(uy, dyp[m], aR4);
+                            aVs += v_sigma;
+                            sS[q] = __builtin_fmaf(-vis, cv, sS[q]);
+                            sw[q] = next_t;
+                            any = true;
+                        }
+                    }
+                }
+                if (__ballot(any) != 0ull) {
+                    // the nine RAW sums leave through K17's register butterfly, three registers where depth needs two:
+                    // k0 holds P R2 Q R3 in rows 0..3, k1 R4 Nx Vs Ny, k2 Nz - - -
+                    const float h0 = swap32_add(aP, aQ), h1 = swap32_add(aR2, aR3), h2 = swap32_add(aR4, aVs), h3 = swap32_add(aNx, aNy);
+                    const float h4 = swap32_add(aNz, 0.0f);
+                    const float k0 = row_allreduce(swap16_add(h0, h1));
+                    const float k1 = row_allreduce(swap16_add(h2, h3));
+                    const float k2 = row_allreduce(swap16_add(h4, 0.0f));
+                    const int ri = lane & 15, rrow = lane >> 4;
+                    const int c = ((rrow & 1) << 1) | (rrow >> 1);   // which of the register's four components this row holds
+                    const uint32_t cg = s_cg[t];
+                    if (ri == 0) {
+                        unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + c], k0);               // P Q R2 R3: columns 0..3
+                    } else if (ri == 1) {
+                        if (c == 0) unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + 4], k1);   // R4
+                        else if (c == 1) unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + 8], k1);   // Vs
+                        else unsafeAtomicAdd(&v_n[(size_t)cg * 3 + (c - 2)], k1);            // Vn x, y
+                    } else if (ri == 2) {
+                        if (c == 0) unsafeAtomicAdd(&v_n[(size_t)cg * 3 + 2], k2);           // Vn z
+                    }
+                    aP = aQ = aR2 = aR3 = aR4 = aVs = aNx = aNy = aNz = 0.0f;
+                }
+            }
+        }
+    }
+}
+
+// v_quat += the chain of Vn through the sign, R_view^T, column k of the rotation matrix and the quaternion's normalisation, behind
+// K18 in its dense mode: a row K18 skipped (its ten sums are zero) is zero in the zero-filled dense output, so a splat that
+// received only Vn is still written
+__global__ __launch_bounds__(256) void normal_vn_scatter_kernel(uint32_t nv, NormalView v, const uint32_t* __restrict__ global_from_compact,
+                                                                const float* __restrict__ transforms, const float* __restrict__ v_n,
+                                                                float* __restrict__ v_transforms) {
+    const uint32_t cg = blockIdx.x * 256u + threadIdx.x;
+    if (cg >= nv) return;
+    const float vx = v_n[(size_t)cg * 3], vy = v_n[(size_t)cg * 3 + 1], vz = v_n[(size_t)cg * 3 + 2];
+    if (vx == 0.0f && vy == 0.0f && vz == 0.0f) return;
+    const uint32_t gid = global_from_compact[cg];
+    const SplatFrame f = splat_frame(transforms + (size_t)gid * 10, v);
+    const Mat3 rv = Mat3{v.vm[0], v.vm[1], v.vm[2], v.vm[3], v.vm[4], v.vm[5], v.vm[6], v.vm[7], v.vm[8]};
+    const Vec3A a = transpose_mul_vec3(rv, scale(v3(vx, vy, vz), f.sign));   // d / d n_w
+    const float w = f.qn.w, x = f.qn.x, y = f.qn.y, z = f.qn.z;
+    Quat d;   // d / d (normalised quaternion): a . (d column k / d component)
+    if (f.k == 0) {          // (1 - 2 (y2 + z2), 2 (xy + wz), 2 (xz - wy))
+        d.w = 2.0f * (z * a.y - y * a.z);
+        d.x = 2.0f * (y * a.y + z * a.z);
+        d.y = 2.0f * ((x * a.y - w * a.z) - 2.0f * y * a.x);
+        d.z = 2.0f * ((w * a.y + x * a.z) - 2.0f * z * a.x);
+    } else if (f.k == 1) {   // (2 (xy - wz), 1 - 2 (x2 + z2), 2 (yz + wx))
+        d.w = 2.0f * (x * a.z - z * a.x);
+        d.x = 2.0f * ((y * a.x + w * a.z) - 2.0f * x * a.y);
+        d.y = 2.0f * (x * a.x + z * a.z);
+        d.z = 2.0f * ((y * a.z - w * a.x) - 2.0f * z * a.y);
+    } else {                 // (2 (xz + wy), 2 (yz - wx), 1 - 2 (x2 + y2))
+        d.w = 2.0f * (y * a.x - x * a.y);
+        d.x = 2.0f * ((z * a.x - w * a.y) - 2.0f * x * a.z);
+        d.y = 2.0f * ((w * a.x + z * a.y) - 2.0f * y * a.z);
+        d.z = 2.0f * (x * a.x + y * a.y);
+    }
+    // qn = q / |q|: v_q = (d - qn (qn . d)) / |q|
+    const float along = qdot(f.qn, d);
+    float* vt = v_transforms + (size_t)gid * 10;
+    vt[3] += (d.w - w * along) * f.inv_len;
+    vt[4] += (d.x - x * along) * f.inv_len;
+    vt[5] += (d.y - y * along) * f.inv_len;
+    vt[6] += (d.z - z * along) * f.inv_len;
+}
+
+// ---------------------------------------------------------------------------
+// depth -> normal
+// ---------------------------------------------------------------------------
+struct PinholeK {
+    float fx, fy, cx, cy;
+    uint32_t w, h;
+};
+
+BH_DEV bool depth_ok(float d) { return is_finite_f32(d) && d > 0.0f; }
+
+// The stencil centred at (x, y): valid, the cross product c = gy x gx and the pieces its backward needs.
+struct Stencil {
+    bool valid;
+    float kxl, kxr, kx, kyu, kyd, ky;
+    Vec3A gx, gy, c;
+};
+
+BH_DEV Stencil depth_stencil(const PinholeK& k, const float* __restrict__ depth, uint32_t x, uint32_t y) {
+    Stencil s;
+    s.valid = false;
+    if (x < 1u || y < 1u || x + 2u > k.w || y + 2u > k.h) return s;   // 1 <= x <= W-2, 1 <= y <= H-2
+    const size_t p = (size_t)x + (size_t)y * k.w;
+    const float dc = depth[p], dl = depth[p - 1], dr = depth[p + 1], du = depth[p - k.w], dd = depth[p + k.w];
+    if (!(depth_ok(dc) && depth_ok(dl) && depth_ok(dr) && depth_ok(du) && depth_ok(dd))) return s;
+    s.valid = true;
+    const float fxc = ((float)x + 0.5f) - k.cx, fyc = ((float)y + 0.5f) - k.cy;
+    s.kx = fxc / k.fx; s.kxl = (fxc - 1.0f) / k.fx; s.kxr = (fxc + 1.0f) / k.fx;
+    s.ky = fyc / k.fy; s.kyu = (fyc - 1.0f) / k.fy; s.kyd = (fyc + 1.0f) / k.fy;
+    s.gx = v3(s.kxr * dr - s.kxl * dl, s.ky * dr - s.ky * dl, dr - dl);
+    s.gy = v3(s.kx * dd - s.kx * du, s.kyd * dd - s.kyu * du, dd - du);
+    // c = gy x gx
+    s.c = v3(s.gy.y * s.gx.z - s.gy.z * s.gx.y, s.gy.z * s.gx.x - s.gy.x * s.gx.z, s.gy.x * s.gx.y - s.gy.y * s.gx.x);
+    return s;
+}
+
+__global__ __launch_bounds__(256) void depth_to_normal_kernel(PinholeK k, const float* __restrict__ depth, float* __restrict__ out) {
+    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= (size_t)k.w * k.h) return;
+    const uint32_t x = (uint32_t)(p % k.w), y = (uint32_t)(p / k.w);
+    const Stencil s = depth_stencil(k, depth, x, y);
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+    if (s.valid) {
+        const float len = length(s.c);
+        const float inv = len == 0.0f ? 0.0f : 1.0f / len;
+        ox = s.c.x * inv; oy = s.c.y * inv; oz = s.c.z * inv;
+    }
+    out[p * 3] = ox;
+    out[p * 3 + 1] = oy;
+    out[p * 3 + 2] = oz;
+}
+
+// d <v, c / |c|> / d (the depth of neighbour `which` of the stencil at (x, y)): 0 left, 1 right, 2 up, 3 down; 0 for an invalid stencil
+BH_DEV float stencil_grad(const PinholeK& k, const float* __restrict__ depth, const float* __restrict__ v_normal, uint32_t x, uint32_t y, int which) {
+    const Stencil s = depth_stencil(k, depth, x, y);
+    if (!s.valid) return 0.0f;
+    const float len = length(s.c);
+    if (len == 0.0f) return 0.0f;
+    const float inv = 1.0f / len;
+    const Vec3A u = scale(s.c, inv);
+    const size_t p = ((size_t)x + (size_t)y * k.w) * 3;
+    const Vec3A v = v3(v_normal[p], v_normal[p + 1], v_normal[p + 2]);
+    const Vec3A vc = scale(sub(v, scale(u, dot(v, u))), inv);
+    if (which < 2) {
+        // c = gy x gx: v_gx = vc x gy
+        const Vec3A vg = v3(vc.y * s.gy.z - vc.z * s.gy.y, vc.z * s.gy.x - vc.x * s.gy.z, vc.x * s.gy.y - vc.y * s.gy.x);
+        return which == 0 ? -dot(vg, v3(s.kxl, s.ky, 1.0f)) : dot(vg, v3(s.kxr, s.ky, 1.0f));
+    }
+    // v_gy = gx x vc
+    const Vec3A vg = v3(s.gx.y * vc.z - s.gx.z * vc.y, s.gx.z * vc.x - s.gx.x * vc.z, s.gx.x * vc.y - s.gx.y * vc.x);
+    return which == 2 ? -dot(vg, v3(s.kx, s.kyu, 1.0f)) : dot(vg, v3(s.kx, s.kyd, 1.0f));
+}
+
+// a gather in a fixed order (no atomics): pixel (x, y) is the right neighbour of the stencil at x-1, the left one of x+1, the lower
+// one of y-1 and the upper one of y+1; its own stencil does not read its own depth
+__global__ __launch_bounds__(256) void depth_to_normal_backward_kernel(PinholeK k, const float* __restrict__ depth, const float* __restrict__ v_normal,
+                                                                       float* __restrict__ v_depth) {
+    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= (size_t)k.w * k.h) return;
+    const uint32_t x = (uint32_t)(p % k.w), y = (uint32_t)(p / k.w);
+    float g = 0.0f;
+    if (x >= 1u) g += stencil_grad(k, depth, v_normal, x - 1u, y, 1);
+    if (x + 1u < k.w) g += stencil_grad(k, depth, v_normal, x + 1u, y, 0);
+    if (y >= 1u) g += stencil_grad(k, depth, v_normal, x, y - 1u, 3);
+    if (y + 1u < k.h) g += stencil_grad(k, depth, v_normal, x, y + 1u, 2);
+    v_depth[p] = g;
+}
+
+NormalUniforms normal_uniforms(const bh_ctx* ctx, const ViewUniforms& vu) {
+    NormalUniforms u;
+    u.tile_bw = vu.tile_bw;
+    u.num_tiles = vu.tile_bw * (vu.tile_y1 - vu.tile_y0);
+    u.tile_begin = vu.tile_bw * vu.tile_y0;
+    u.img_w = vu.img_w;
+    u.img_h = vu.img_h;
+    u.band_mode = ctx->knob_band_mode;
+    return u;
+}
+
+NormalView normal_view(const float* vm) {
+    NormalView v;
+    for (int i = 0; i < 12; ++i) v.vm[i] = vm[i];
+    return v;
+}
+
+// SLOT_NORMAL: compact splat normals [Nv,3] | Vn [Nv,3] (each padded to a multiple of 64 floats) | the accumulated map [H,W,3]
+struct NormalScratch {
+    float* normals = nullptr;
+    float* v_n = nullptr;
+    float* acc = nullptr;
+    size_t vec_floats = 0;
+};
+
+int normal_scratch(bh_ctx* ctx, uint32_t nv, size_t pixels, bool backward, NormalScratch* s) {
+    s->vec_floats = ((size_t)(nv ? nv : 1u) * 3u + 63u) & ~(size_t)63u;
+    const size_t floats = backward ? 2 * s->vec_floats + pixels * 3 : s->vec_floats;
+    auto* base = (float*)ensure(ctx, SLOT_NORMAL, floats * 4);
+    if (!base) return BH_ERR_OOM;
+    s->normals = base;
+    s->v_n = base + s->vec_floats;
+    s->acc = base + 2 * s->vec_floats;
+    return 0;
+}
+
+int launch_compact_normals(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* normals) {
+    const uint32_t nv = fs.out.num_listed_splats;
+    if (nv == 0) return 0;
+    hipLaunchKernelGGL(splat_normals_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, (uint64_t)nv, normal_view(fs.uniforms.vm),
+                       fs.out.global_from_compact_gid, transforms, normals);
+    BH_LAUNCH_CHECK(ctx, "splat_normals_kernel");
+    return 0;
+}
+
+// the blend over the saved lists (num_intersections > 0, num_listed_splats > 0, compact normals already queued)
+int launch_normal_forward(bh_ctx* ctx, const ForwardState& fs, const float* normals, uint32_t mode, float* out_normal) {
+    const BhRenderOut& r = fs.out;
+    const NormalUniforms u = normal_uniforms(ctx, fs.uniforms);
+    if (u.num_tiles == 0) return 0;
+    const dim3 grid(band_slots(u.num_tiles) * 8u), block(64);
+    const bool smooth = fs.flags & BH_FLAG_SMOOTH_CUTOFF;
+#define BH_NORMAL_FWD(S, M) hipLaunchKernelGGL((normal_forward_kernel<S, M>), grid, block, 0, ctx->stream, u, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far, r.projected, normals, out_normal)
+    switch (mode) {
+        case BH_NORMAL_ACCUMULATED: if (smooth) BH_NORMAL_FWD(true, BH_NORMAL_ACCUMULATED); else BH_NORMAL_FWD(false, BH_NORMAL_ACCUMULATED); break;
+        case BH_NORMAL_UNIT: if (smooth) BH_NORMAL_FWD(true, BH_NORMAL_UNIT); else BH_NORMAL_FWD(false, BH_NORMAL_UNIT); break;
+        default: return set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: unknown normal mode");
+    }
+#undef BH_NORMAL_FWD
+    BH_LAUNCH_CHECK(ctx, "normal_forward_kernel");
+    return 0;
+}
+
+PinholeK pinhole_of(const BhCamera* cam, uint32_t h, uint32_t w) {
+    PinholeK k;
+    k.fx = cam->fx; k.fy = cam->fy; k.cx = cam->cx; k.cy = cam->cy;
+    k.w = w; k.h = h;
+    return k;
+}
+
+}  // namespace
+
+// The normal term of a backward, between K17 and K18: v_combined += its raw sums, Vn (SLOT_NORMAL) = sum of vis * g.
+int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined) {
+    const BhRenderOut& r = fs.out;
+    const uint32_t nv = r.num_listed_splats;
+    const NormalUniforms u = normal_uniforms(ctx, fs.uniforms);
+    NormalScratch s;
+    BH_TRY(normal_scratch(ctx, nv, (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
+    BH_HIP(ctx, hipMemsetAsync(s.v_n, 0, s.vec_floats * 4, ctx->stream));
+    if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
+    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
+    BH_TRY(launch_normal_forward(ctx, fs, s.normals, BH_NORMAL_ACCUMULATED, s.acc));
+    const dim3 grid(band_slots(u.num_tiles) * 8u), block(64);
+    const uint32_t unit = term.mode == BH_NORMAL_UNIT ? 1u : 0u;
+    if (fs.flags & BH_FLAG_SMOOTH_CUTOFF)
+        hipLaunchKernelGGL((normal_backward_kernel<true>), grid, block, 0, ctx->stream, u, unit, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far,
+                           r.projected, s.normals, s.acc, term.v_normal, v_combined, s.v_n);
+    else
+        hipLaunchKernelGGL((normal_backward_kernel<false>), grid, block, 0, ctx->stream, u, unit, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far,
+                           r.projected, s.normals, s.acc, term.v_normal, v_combined, s.v_n);
+    BH_LAUNCH_CHECK(ctx, "normal_backward_kernel");
+    return 0;
+}
+
+// Vn -> the quaternion columns of the dense, zero-filled v_transforms, behind K18 (never the row-marked train-step path)
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms) {
+    const BhRenderOut& r = fs.out;
+    const uint32_t nv = r.num_listed_splats;
+    if (nv == 0 || r.num_intersections == 0) return 0;
+    const size_t vec_floats = ((size_t)nv * 3u + 63u) & ~(size_t)63u;
+    const float* v_n = (const float*)ctx->slots[SLOT_NORMAL].ptr + vec_floats;
+    hipLaunchKernelGGL(normal_vn_scatter_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, normal_view(fs.uniforms.vm),
+                       r.global_from_compact_gid, transforms, v_n, v_transforms);
+    BH_LAUNCH_CHECK(ctx, "normal_vn_scatter_kernel");
+    return 0;
+}
+
+}  // namespace bh
+
+extern "C" {
+
+int bh_splat_normals(bh_ctx* ctx, const BhCamera* cam, const float* transforms, uint64_t n, float* out) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!cam) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "splat_normals: null camera");
+    if (n == 0) return 0;
+    if (!transforms || !out) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "splat_normals: null argument");
+    if (n > 0xFFFFFFFFull) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "splat_normals: more than 2^32 - 1 splats");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(bh::splat_normals_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, n, bh::normal_view(cam->vm),
+                       (const uint32_t*)nullptr, transforms, out);
+    BH_LAUNCH_CHECK(ctx, "splat_normals_kernel");
+    return 0;
+}
+
+int bh_render_normal(bh_ctx* ctx, const BhRenderOut* saved, const float* transforms, uint32_t mode, float* out) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!saved || !out) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: null argument");
+    if (mode > BH_NORMAL_UNIT) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: unknown normal mode");
+    if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: the saved forward was not a BH_FLAG_BWD_INFO forward");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    const bh::ForwardState* found = nullptr;
+    BH_TRY(bh::find_saved_forward(ctx, saved, "render_normal", &found));
+    const bh::ForwardState& fs = *found;
+    if (fs.out.num_intersections == 0 || fs.out.num_listed_splats == 0) {   // nothing listed: both modes are 0 over the rendered window
+        const bh::ViewUniforms& vu = fs.uniforms;
+        const size_t row0 = (size_t)vu.tile_y0 * bh::TILE_WIDTH, row1 = std::min<size_t>((size_t)vu.tile_y1 * bh::TILE_WIDTH, vu.img_h);
+        if (row1 > row0) BH_HIP(ctx, hipMemsetAsync(out + row0 * vu.img_w * 3, 0, (row1 - row0) * vu.img_w * 3 * 4, ctx->stream));
+        return 0;
+    }
+    if (!transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: null transforms");
+    bh::ProfScope ps(ctx, "RenderNormal");
+    bh::NormalScratch s;
+    BH_TRY(bh::normal_scratch(ctx, fs.out.num_listed_splats, 0, /*backward=*/false, &s));
+    BH_TRY(bh::launch_compact_normals(ctx, fs, transforms, s.normals));
+    return bh::launch_normal_forward(ctx, fs, s.normals, mode, out);
+}
+
+int bh_render_backward_normal_saved(bh_ctx* ctx, const BhRenderOut* saved, const float* v_output, const float* v_depth, uint32_t depth_mode,
+                                    const float* v_normal, uint32_t normal_mode, const float* transforms, const float* sh_coeffs,
+                                    const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities,
+                                    float* v_refine_weight) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!saved || !v_normal || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
+        return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: null argument");
+    if (normal_mode > BH_NORMAL_UNIT) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown normal mode");
+    if (v_depth && depth_mode == BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: median depth has no gradient");
+    if (v_depth && depth_mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown depth mode");
+    if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    const bh::ForwardState* found = nullptr;
+    BH_TRY(bh::find_saved_forward(ctx, saved, "render_backward_normal_saved", &found));
+    const bh::ForwardState& fs = *found;
+    if (fs.n > 0 && !transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: null transforms");
+    bh::DepthTerm depth;
+    depth.v_depth = v_depth;
+    depth.mode = depth_mode;
+    bh::NormalTerm normal;
+    normal.v_normal = v_normal;
+    normal.mode = normal_mode;
+    return bh::backward_impl(ctx, fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
+                             /*span_floats=*/0, /*want_refine=*/true, v_depth ? &depth : nullptr, /*v_viewmat=*/nullptr, &normal);
+}
+
+int bh_depth_to_normal(bh_ctx* ctx, const BhCamera* cam, const float* depth, uint32_t h, uint32_t w, float* out) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!cam) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal: null camera");
+    if (cam->model != BH_CAMERA_PINHOLE) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal: pinhole cameras only");
+    const size_t pixels = (size_t)h * w;
+    if (pixels == 0) return 0;
+    if (!depth || !out) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal: null argument");
+    if (pixels > 0x7FFFFFFFull) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal: more than 2^31 - 1 pixels");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(bh::depth_to_normal_kernel, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), 0, ctx->stream, bh::pinhole_of(cam, h, w), depth, out);
+    BH_LAUNCH_CHECK(ctx, "depth_to_normal_kernel");
+    return 0;
+}
+
+int bh_depth_to_normal_backward(bh_ctx* ctx, const BhCamera* cam, const float* depth, const float* v_normal, uint32_t h, uint32_t w, float* v_depth) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!cam) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal_backward: null camera");
+    if (cam->model != BH_CAMERA_PINHOLE) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal_backward: pinhole cameras only");
+    const size_t pixels = (size_t)h * w;
+    if (pixels == 0) return 0;
+    if (!depth || !v_normal || !v_depth) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal_backward: null argument");
+    if (pixels > 0x7FFFFFFFull) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "depth_to_normal_backward: more than 2^31 - 1 pixels");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(bh::depth_to_normal_backward_kernel, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), 0, ctx->stream, bh::pinhole_of(cam, h, w), depth,
+                       v_normal, v_depth);
+    BH_LAUNCH_CHECK(ctx, "depth_to_normal_backward_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -568,14 +568,20 @@ class RenderNode:
         "median" (z where the transmittance first falls to 1/2); a forward of a tile-row window writes its rows, the rest is 0."""
         return render_depth(self, mode)
 
-    def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False):
-        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>]; v_output may be None when v_depth is given.
+    def normal(self, mode="accumulated"):
+        """The node's normal map [H,W,3] f32 in camera space (bh_render_normal): "accumulated" sum of w n, or "unit" = accumulated /
+        its length (0 where that is 0); a forward of a tile-row window writes its rows, the rest is 0."""
+        return render_normal(self, mode)
+
+    def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False, v_normal=None, normal_mode="accumulated"):
+        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>] [+ <v_normal, normal(normal_mode)>]; v_output may be None
+        when v_depth or v_normal is given.
         pose=True (bh_render_backward_pose_saved): also "v_viewmat", the twelve f32 of the gradient with respect to the camera's
         view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
-        if v_output is None and v_depth is None:
+        if v_output is None and v_depth is None and v_normal is None:
             raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
         if v_output is not None:
             v_output = _f32c(v_output, dev).reshape(h, w, 4)
@@ -585,7 +591,17 @@ class RenderNode:
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
         v_vm = None
-        if pose:
+        if v_normal is not None:
+            if pose:
+                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_normal)")
+            v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
+            if v_depth is not None:
+                v_depth = _f32c(v_depth, dev).reshape(h, w)
+            ctx.check(ctx.lib.bh_render_backward_normal_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
+                                                              _ptr(v_depth) if v_depth is not None else None, _depth_mode(depth_mode),
+                                                              _ptr(v_normal), _normal_mode(normal_mode), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
+                                                              _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+        elif pose:
             if v_depth is not None or v_output is None:
                 raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_depth)")
             v_vm = torch.empty((12,), dtype=torch.float32, device=dev)
@@ -632,6 +648,78 @@ def render_depth(saved: "RenderNode", mode="expected", out=None):
             and out.device == torch.device(dev)):
         raise BrushHipError("render_depth: `out` must be a contiguous float32 [%d, %d] tensor on %s" % (h, w, dev))
     ctx.check(ctx.lib.bh_render_depth(ctx._h, C.byref(saved.out), _depth_mode(mode), _ptr(out)))
+    return out
+
+
+NORMAL_MODES = {"accumulated": _ffi.NORMAL_ACCUMULATED, "unit": _ffi.NORMAL_UNIT}
+
+
+def _normal_mode(mode):
+    return int(NORMAL_MODES[mode]) if isinstance(mode, str) else int(mode)
+
+
+def _camera_of(camera, shape_hw):
+    h, w = shape_hw
+    return camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((int(w), int(h)))
+
+
+def splat_normals(splats: Splats, camera, ctx: Optional[Context] = None):
+    """The camera-space normal [N,3] f32 of every splat (bh_splat_normals; include/brush_hip_normal.h): the axis of the smallest
+    scale of the rendered (folded) transforms, turned to face the camera.  `camera`: a BhCamera, or a Camera (any image size)."""
+    ctx = ctx or get_context(splats.device)
+    cam = camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((16, 16))
+    n = splats.num_splats()
+    r_t, _ = splats.folded(ctx)
+    out = torch.empty((n, 3), dtype=torch.float32, device=splats.device)
+    ctx.check(ctx.lib.bh_splat_normals(ctx._h, C.byref(cam), _ptr(r_t), n, _ptr(out)))
+    if splats.min_scale is not None:
+        ctx.sync()   # the folded temporary dies with this scope
+    return out
+
+
+def render_normal(saved: "RenderNode", mode="accumulated", out=None):
+    """Normal map [H,W,3] f32 of a differentiable render's saved state (bh_render_normal; include/brush_hip_normal.h): the node must
+    be the ctx's most recent forward or a retained one.  `out`: a contiguous f32 [H,W,3] tensor to write into (rows outside a
+    tile-row window are left as they are); otherwise a zero-filled one is returned."""
+    ctx, dev = saved.ctx, saved.splats.device
+    w, h = saved.img_size
+    if out is None:
+        out = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+    if not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (h, w, 3)
+            and out.device == torch.device(dev)):
+        raise BrushHipError("render_normal: `out` must be a contiguous float32 [%d, %d, 3] tensor on %s" % (h, w, dev))
+    ctx.check(ctx.lib.bh_render_normal(ctx._h, C.byref(saved.out), _ptr(saved._folded[0]), _normal_mode(mode), _ptr(out)))
+    return out
+
+
+def depth_to_normal(depth, camera, ctx: Optional[Context] = None):
+    """Camera-space normals [H,W,3] f32 of a z-depth map [H,W] (bh_depth_to_normal): central differences of the back-projected
+    points, 0 on the border and wherever the pixel or one of its four neighbours holds no finite depth > 0.  Pinhole cameras only."""
+    dev = depth.device
+    ctx = ctx or get_context(dev)
+    depth = _f32c(depth, dev)
+    if depth.dim() != 2:
+        raise ValueError("depth_to_normal: the depth map must be [H, W]")
+    h, w = depth.shape
+    cam = _camera_of(camera, (h, w))
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_depth_to_normal(ctx._h, C.byref(cam), _ptr(depth), h, w, _ptr(out)))
+    return out
+
+
+def depth_to_normal_backward(depth, v_normal, camera, ctx: Optional[Context] = None):
+    """v_depth [H,W] f32 = the gradient of <v_normal, depth_to_normal(depth)> (bh_depth_to_normal_backward): a gather without
+    atomics, the same bits on every call."""
+    dev = depth.device
+    ctx = ctx or get_context(dev)
+    depth = _f32c(depth, dev)
+    if depth.dim() != 2:
+        raise ValueError("depth_to_normal_backward: the depth map must be [H, W]")
+    h, w = depth.shape
+    v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
+    cam = _camera_of(camera, (h, w))
+    out = torch.empty((h, w), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_depth_to_normal_backward(ctx._h, C.byref(cam), _ptr(depth), _ptr(v_normal), h, w, _ptr(out)))
     return out
 
 

@@ -59,6 +59,7 @@
 #include "brush_hip_pose.h"
 #include "brush_hip_exposure.h"
 #include "brush_hip_depth_loss.h"
+#include "brush_hip_normal.h"
 
 namespace brush_hip {
 
@@ -446,6 +447,39 @@ class RenderNode {
                                                   g.v_transforms.data(), g.v_raw_opacities.data()));
         ctx_.sync();
         return g;
+    }
+    // The node's normal map [H,W,3] f32 in camera space (brush_hip_normal.h): BH_NORMAL_ACCUMULATED or BH_NORMAL_UNIT.  Rows outside a
+    // tile-row window stay 0.
+    DeviceBuffer<float> normal(uint32_t mode = BH_NORMAL_ACCUMULATED) const {
+        DeviceBuffer<float> d;
+        d.resize((size_t)aux.img_w * aux.img_h * 3);
+        d.zero();
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the fill is ordered before the ctx stream's kernel
+        ctx_.check(bh_render_normal(ctx_.get(), &aux.raw, folded_.t, mode, d.data()));
+        ctx_.sync();
+        return d;
+    }
+    // gradients of <v_output, image> + <v_depth, depth(depth_mode)> + <v_normal, normal(normal_mode)> in one backward; v_output and
+    // v_depth may be nullptr
+    SplatGrads backward_normal(const float* v_output, const float* v_depth, uint32_t depth_mode, const float* v_normal,
+                               uint32_t normal_mode = BH_NORMAL_ACCUMULATED) const {
+        const uint32_t n = splats_.num_splats();
+        SplatGrads g;
+        g.v_transforms.resize((size_t)n * 10);
+        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
+        g.v_raw_opacities.resize(n);
+        g.v_refine_weight.resize(n);
+        ctx_.check(bh_render_backward_normal_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, folded_.t,
+                                                   splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(), g.v_sh_coeffs.data(),
+                                                   g.v_raw_opacities.data(), g.v_refine_weight.data()));
+        if (splats_.min_scale)
+            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
+                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
+        ctx_.sync();
+        return g;
+    }
+    SplatGrads backward_normal(const float* v_normal, uint32_t normal_mode = BH_NORMAL_ACCUMULATED) const {
+        return backward_normal(nullptr, nullptr, BH_DEPTH_EXPECTED, v_normal, normal_mode);
     }
     // gradients of <v_output, image> and, into v_viewmat (device, 12 floats in the layout of BhCamera.vm), its gradient with respect
     // to the camera's view matrix (brush_hip_pose.h); the four splat outputs are backward(v_output)'s
@@ -1213,6 +1247,37 @@ inline void eval_depth_metrics(const Context& ctx, const float* depth, const BhD
 }
 // bh_train_step on this ctx adds the depth term of `target` (copied; its gt must outlive the steps); nullptr detaches
 inline void train_set_depth(const Context& ctx, const BhDepthTarget* target) { ctx.check(bh_train_set_depth(ctx.get(), target)); }
+
+// ---- normal maps (brush_hip_normal.h; not in the reference) ---------------------------------------------------------------------------
+// the camera-space normal [N,3] of every splat: the axis of the smallest scale of the rendered (folded) transforms, facing the camera
+inline DeviceBuffer<float> splat_normals(const Context& ctx, const Splats& splats, const Camera& camera) {
+    static_assert(BH_NORMAL_ACCUMULATED == 0u && BH_NORMAL_UNIT == 1u, "normal modes");
+    const BhCamera cam = camera.uniforms(16, 16);   // (the normals read the view matrix only)
+    const detail::Folded f = detail::fold(ctx, splats);
+    DeviceBuffer<float> out;
+    out.resize((size_t)splats.num_splats() * 3);
+    ctx.check(bh_splat_normals(ctx.get(), &cam, f.t, splats.num_splats(), out.data()));
+    ctx.sync();   // the folded temporaries die with this scope
+    return out;
+}
+// camera-space normals [H,W,3] of a z-depth map [H,W] on the device (pinhole cameras only), and the gradient of <v_normal, normals>
+inline DeviceBuffer<float> depth_to_normal(const Context& ctx, const Camera& camera, const float* depth, uint32_t h, uint32_t w) {
+    const BhCamera cam = camera.uniforms(w, h);
+    DeviceBuffer<float> out;
+    out.resize((size_t)h * w * 3);
+    ctx.check(bh_depth_to_normal(ctx.get(), &cam, depth, h, w, out.data()));
+    ctx.sync();
+    return out;
+}
+inline DeviceBuffer<float> depth_to_normal_backward(const Context& ctx, const Camera& camera, const float* depth, const float* v_normal, uint32_t h,
+                                                    uint32_t w) {
+    const BhCamera cam = camera.uniforms(w, h);
+    DeviceBuffer<float> out;
+    out.resize((size_t)h * w);
+    ctx.check(bh_depth_to_normal_backward(ctx.get(), &cam, depth, v_normal, h, w, out.data()));
+    ctx.sync();
+    return out;
+}
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
 // compute_knn_scales in place: columns 7..9 of splats.transforms = ln(clamp((d1 + d2) / 4, 1e-3, 0.1 median_size)) (bh_knn_log_scales).
