@@ -1189,7 +1189,9 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
     return 0;
 }
 
-int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, const ForwardState** fs) {
+int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_code, const char* who, const ForwardState** fs) {
+    if (!(saved->flags & BH_FLAG_BWD_INFO)) return set_error(ctx, not_bwd_code, std::string(who) + ": the saved forward was not a BH_FLAG_BWD_INFO forward");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
     for (const Retained& rt : ctx->retained)
         if (rt.fs.out.generation == saved->generation && rt.fs.out.out_img == saved->out_img) { *fs = &rt.fs; return 0; }
@@ -1230,10 +1232,8 @@ int bh_render_backward_saved(bh_ctx* ctx, const BhRenderOut* saved, const float*
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!saved || !v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
         return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_saved: null argument");
-    if (!(saved->flags & BH_FLAG_BWD_INFO)) return set_error(ctx, BH_ERR_STATE, "render_backward_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
     const ForwardState* fs = nullptr;
-    BH_TRY(find_saved_forward(ctx, saved, "render_backward_saved", &fs));
+    BH_TRY(find_saved_bwd_forward(ctx, saved, BH_ERR_STATE, "render_backward_saved", &fs));
     return backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
                          /*span_floats=*/0, /*want_refine=*/true);
 }

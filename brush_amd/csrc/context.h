@@ -195,6 +195,12 @@ inline __host__ __device__ uint32_t band_slots(uint32_t num_tiles) {
 inline __host__ __device__ uint32_t band_tile(uint32_t band, uint32_t i, uint32_t per, uint32_t mode) {
     return mode ? ((i / BAND_CHUNK) * 8u + band) * BAND_CHUNK + (i % BAND_CHUNK) : band * per + i;
 }
+// block -> tile of the window, for every blend launch of band_slots() * 8 blocks (>= num_tiles: the slot names no tile)
+BH_DEV uint32_t tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode) {
+    const uint32_t per = band_slots(num_tiles);
+    const uint32_t i = b >> 3;
+    return i < per ? band_tile(b & 7u, i, per, band_mode) : 0xFFFFFFFFu;
+}
 // SPLIT TILES (round 6, rasterize.hip): the forward blend cannot be cut along a tile's list (a pixel's stop rule needs everything in
 // front of it), so a launch lasts as long as its heaviest tile — one wave working through its list at a lone wave's pace.  The few
 // tiles whose forecast work (the view's last frame) is several times their band's mean are blended by FOUR waves, one per 8 x 8 pixel
@@ -490,10 +496,12 @@ int set_error(bh_ctx* ctx, int code, const std::string& msg);
 // api.hip: the forward pipeline of one request (arguments already checked), and the host's wait for a tag word a kernel stores
 int forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
 int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, const char* what);
-// api.hip: *fs = the saved state of the forward `saved` names — a retained one or the ctx's most recent forward (the ctx's own
-// record either way, no copy); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished first).
-// Valid until the next call that retains, releases or renders on the ctx.
-int find_saved_forward(bh_ctx* ctx, const BhRenderOut* saved, const char* who, const ForwardState** fs);
+// api.hip: look up the saved BH_FLAG_BWD_INFO forward or refuse.  `saved` without the flag is refused with `not_bwd_code` (the
+// entry points differ: BH_ERR_STATE in api.hip and pose.hip, BH_ERR_INVALID_ARG for the maps) under `who`'s name; then the ctx's
+// device is made current and *fs = the saved state of the forward `saved` names — a retained one or the ctx's most recent forward
+// (the ctx's own record either way, no copy); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished
+// first).  Valid until the next call that retains, releases or renders on the ctx.
+int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_code, const char* who, const ForwardState** fs);
 // api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth or a normal term (then K17
 // does not run)
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,

@@ -1,6 +1,6 @@
-// device_blend.h — the arithmetic every blend kernel shares (K16 / K17 in rasterize.hip, the depth kernels in depth.hip):
-// one copy of exp_blend and of a pixel's alpha / transmittance step, so that what one kernel blends another one replays
-// decision for decision.
+// device_blend.h — the arithmetic every blend kernel shares (K16 / K17 in rasterize.hip, the depth and normal maps' one blend
+// skeleton in device_map_blend.h): one copy of exp_blend and of a pixel's alpha / transmittance step, so that what one kernel
+// blends another one replays decision for decision.
 #pragma once
 #include "device_math.h"
 

@@ -7,38 +7,22 @@
 //
 //   * splat normals: one thread per splat, dense [N,3] (bh_splat_normals) or compact [Nv,3] over global_from_compact_gid (what
 //     the two blends stage);
-//   * forward: the shape of depth_forward_kernel.  A staged splat is 12 floats (x y c00/2 c01 | c11/2 alpha0 sigma_cut nx | ny nz - -),
-//     three uniform ds_read_b128 per splat, three fmas per contributing pair;
-//   * backward: one wave per tile, forward-order replay as depth_backward_kernel with a 3-vector cotangent g per pixel: the "colour"
-//     of splat i is g . n_i, the remaining sum S starts at g . N (an accumulated-normal forward into scratch precedes the replay).
-//     UNIT mode turns v into g = (v - (v . u) u) / |N| in the prologue, so both modes are one replay.  P Q R2 R3 R4 Vs join the
-//     [Nv,10] accumulator between K17 and K18 in the columns depth uses; Vn = sum of vis * g goes to a compact [Nv,3] vector that a
-//     small kernel behind K18 carries to the quaternions;
+//   * forward and backward: device_map_blend.h's map_forward_kernel / map_backward_kernel, shared with depth.hip; NormalMap below is
+//     what a normal map adds to them.  A staged splat is 12 floats (x y c00/2 c01 | c11/2 alpha0 sigma_cut nx | ny nz - -), three
+//     uniform ds_read_b128 per splat, three fmas per contributing pair.  The backward replays with a 3-vector cotangent g per
+//     pixel: the "colour" of splat i is g . n_i, the remaining sum S starts at g . N (an accumulated-normal forward into scratch
+//     precedes the replay).  UNIT mode turns v into g = (v - (v . u) u) / |N| in the prologue, so both modes are one replay.
+//     P Q R2 R3 R4 Vs join the [Nv,10] accumulator between K17 and K18 in the columns depth uses; Vn = sum of vis * g goes to a
+//     compact [Nv,3] vector that a small kernel behind K18 carries to the quaternions;
 //   * depth -> normal and its backward: streaming kernels, one thread per pixel; the backward is a gather without atomics.
-#include <algorithm>
-
 #include "context.h"
-#include "device_blend.h"
+#include "device_map_blend.h"
 #include "../../include/brush_hip_depth.h"
 #include "../../include/brush_hip_normal.h"
 
 namespace bh {
 
 namespace {
-
-constexpr int NORMAL_STRIDE = 12;   // floats per staged splat
-constexpr int NORMAL_BATCH = 64;
-
-struct NormalUniforms {
-    uint32_t tile_bw, num_tiles, tile_begin, img_w, img_h, band_mode;
-};
-
-// block -> tile of the window (depth.hip depth_tile_of_block's band map)
-BH_DEV uint32_t normal_tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode) {
-    const uint32_t per = band_slots(num_tiles);
-    const uint32_t i = b >> 3;
-    return i < per ? band_tile(b & 7u, i, per, band_mode) : 0xFFFFFFFFu;
-}
 
 // the view a splat normal needs: rotation (column-major) and translation of the view matrix
 struct NormalView {
@@ -90,265 +74,68 @@ __global__ __launch_bounds__(256) void splat_normals_kernel(uint64_t n, NormalVi
     o[2] = f.n.z;
 }
 
-// lane i stages splat i of the batch; the diagonal of the conic halved as in K16 (bit-identical sigma, rasterize.hip stage_batch)
-template <bool SMOOTH>
-BH_DEV uint32_t stage_normal_batch(const uint32_t* __restrict__ isect_gids, const float* __restrict__ projected, const float* __restrict__ normals,
-                                   uint32_t batch_start, uint32_t cnt, int lane, float* s_splat) {
-    uint32_t cg = 0;
-    if ((uint32_t)lane < cnt) {
-        cg = isect_gids[batch_start + lane];
-        const float* p = projected + (size_t)cg * 9;
-        float v[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) v[k] = p[k];
+// What a normal map adds to the map skeleton.  MODE: BH_NORMAL_ACCUMULATED / UNIT (the backward does not read it).
+//
+// Backward.  Unit normals U = N / |N|: dU = (dN - (dN . u) u) / |N|, so both modes are ONE replay with a per-pixel cotangent g
+// (accumulated: g = v; unit: g = (v - (v . u) u) / |N|, 0 where |N| == 0).  The "colour" of splat i at the pixel is cv = g . n_i and
+// S = the remaining sum of w_j (g . n_j): it starts at g . N.
+template <uint32_t MODE>
+struct NormalMap {
+    static constexpr int STRIDE = 12, NACC = 3, NV = 3;
+    struct Rec { float4 s0, s1, s2; };   // x y c00/2 c01 | c11/2 a sigma_cut nx | ny nz - -
+    static BH_DEV Rec load(const float* p) {
+        return Rec{*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), *reinterpret_cast<const float4*>(p + 8)};
+    }
+    static BH_DEV float cut(const Rec& r) { return r.s1.z; }
+    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, const float* __restrict__ normals, uint32_t cg) {
         const float* nn = normals + (size_t)cg * 3;
         const float nx = nn[0], ny = nn[1], nz = nn[2];
-        float4* d = reinterpret_cast<float4*>(s_splat + lane * NORMAL_STRIDE);
         d[0] = make_float4(v[0], v[1], 0.5f * v[2], v[3]);
-        d[1] = make_float4(0.5f * v[4], v[5], blend_sigma_cut<SMOOTH>(v[5]), nx);
+        d[1] = make_float4(0.5f * v[4], v[5], sigma_cut, nx);
         d[2] = make_float4(ny, nz, 0.0f, 0.0f);
     }
-    return cg;
-}
-
-// ---------------------------------------------------------------------------
-// forward
-// ---------------------------------------------------------------------------
-// MODE: BH_NORMAL_ACCUMULATED / UNIT.  A finished pixel keeps a negative T (K16's convention).
-template <bool SMOOTH, uint32_t MODE>
-__global__ __launch_bounds__(64, 8) void normal_forward_kernel(NormalUniforms u, const uint32_t* __restrict__ isect_gids,
-                                                               const uint32_t* __restrict__ tile_offsets, const uint32_t* __restrict__ tile_offsets_far,
-                                                               const float* __restrict__ projected, const float* __restrict__ normals,
-                                                               float* __restrict__ out_normal) {
-    __shared__ __attribute__((aligned(16))) float s_splat[NORMAL_BATCH * NORMAL_STRIDE];
-    const uint32_t local_tile = normal_tile_of_block(blockIdx.x, u.num_tiles, u.band_mode);
-    if (local_tile >= u.num_tiles) return;
-    const uint32_t tile = u.tile_begin + local_tile;
-    const int lane = threadIdx.x;
-    const uint32_t px0 = (tile % u.tile_bw) * TILE_WIDTH + (lane & 7), py0 = (tile / u.tile_bw) * TILE_WIDTH + (lane >> 3);
-    const float pcx[2] = {(float)px0 + 0.5f, (float)(px0 + 8) + 0.5f};
-    const float pcy[2] = {(float)py0 + 0.5f, (float)(py0 + 8) + 0.5f};
-    float tr[4], ax[4], ay[4], az[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
-        tr[q] = (px < u.img_w && py < u.img_h) ? 1.0f : -1.0f;
-        ax[q] = ay[q] = az[q] = 0.0f;
+    static BH_DEV void fold(const Rec& r, bool ok, bool sat, float alpha_eff, float next_t, float& T, float* acc) {
+        const float vis = (ok && !sat) ? alpha_eff * T : 0.0f;
+        acc[0] = __builtin_fmaf(r.s1.w, vis, acc[0]);   // (one explicit fma per channel and term, as the colour channels)
+        acc[1] = __builtin_fmaf(r.s2.x, vis, acc[1]);
+        acc[2] = __builtin_fmaf(r.s2.y, vis, acc[2]);
+        T = ok ? (sat ? -T : next_t) : T;
     }
-    auto any_live = [&]() {
-        bool l = false;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) l = l || tr[q] > 0.0f;
-        return l;
+    static BH_DEV void store(float* __restrict__ out, size_t pix, const float* acc, float T) {
+        float x = acc[0], y = acc[1], z = acc[2];
+        if (MODE == BH_NORMAL_UNIT) {
+            const float len = __builtin_sqrtf(__builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
+            const float inv = len == 0.0f ? 0.0f : 1.0f / len;
+            x *= inv; y *= inv; z *= inv;
+        }
+        float* o = out + pix * 3;
+        o[0] = x; o[1] = y; o[2] = z;
+    }
+
+    struct BwdMaps {
+        const float* __restrict__ normal_acc;   // [H,W,3] the frame's accumulated normals
+        const float* __restrict__ v_normal;     // [H,W,3]
+        uint32_t unit;
     };
-    uint32_t sign_mask = 0x80000000u;   // kept in a VGPR: an SGPR operand halves a VALU op's issue rate
-    asm volatile("" : "+v"(sign_mask));
-    // the tile's blended splats, front to back: the near list, then the far slice's (all zero for a tile the near slice finished)
-    const uint32_t lo0 = tile_offsets[tile * 2], hi0 = tile_offsets[tile * 2 + 1];
-    uint32_t lo1 = 0u, hi1 = 0u;
-    if (tile_offsets_far) { lo1 = tile_offsets_far[tile * 2]; hi1 = tile_offsets_far[tile * 2 + 1]; }
-    bool done = false;
-#pragma nounroll
-    for (int part = 0; part < 2 && !done; ++part) {
-        const uint32_t range_lo = part ? lo1 : lo0, range_hi = part ? hi1 : hi0;
-        for (uint32_t batch_start = range_lo; batch_start < range_hi && !done; batch_start += NORMAL_BATCH) {
-            if (__ballot(any_live()) == 0ull) { done = true; break; }
-            const uint32_t cnt = min((uint32_t)NORMAL_BATCH, range_hi - batch_start);
-            __syncthreads();  // previous batch fully consumed (single wave: cheap)
-            stage_normal_batch<SMOOTH>(isect_gids, projected, normals, batch_start, cnt, lane, s_splat);
-            __syncthreads();
-            for (uint32_t t = 0; t < cnt; ++t) {
-                const float4 s0 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE]);      // x y c00/2 c01
-                const float4 s1 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 4]);  // c11/2 a sigma_cut nx
-                const float4 s2 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 8]);  // ny nz - -
-                const uint32_t cut_bits = f2u(s1.z);
-                float a_xx[2], b_x[2], c_y[2], dy[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const float dx = pcx[k] - s0.x;
-                    a_xx[k] = (s0.z * dx) * dx;
-                    b_x[k] = s0.w * dx;
-                    dy[k] = pcy[k] - s0.y;
-                    c_y[k] = s1.x * dy[k];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int k = q & 1, m = q >> 1;
-                    const float half_qv = __builtin_fmaf(c_y[m], dy[m], a_xx[k]);
-                    const float sigma = __builtin_fmaf(b_x[k], dy[m], half_qv);
-                    const bool pre = ((f2u(tr[q]) & sign_mask) | f2u(sigma)) <= cut_bits;
-                    if (__ballot(pre) != 0ull) {
-                        const float alpha = blend_alpha(s1.y, sigma);
-                        float alpha_eff, next_t;
-                        bool sat;
-                        const bool ok = blend_step<SMOOTH>(alpha, pre, tr[q], alpha_eff, next_t, sat);
-                        const bool contrib = ok && !sat;
-                        const float vis = contrib ? alpha_eff * tr[q] : 0.0f;
-                        ax[q] = __builtin_fmaf(s1.w, vis, ax[q]);   // (one explicit fma per channel and term, as the colour channels)
-                        ay[q] = __builtin_fmaf(s2.x, vis, ay[q]);
-                        az[q] = __builtin_fmaf(s2.y, vis, az[q]);
-                        tr[q] = ok ? (sat ? -tr[q] : next_t) : tr[q];
-                    }
-                }
-                // every pixel of the tile is done: the rest of the batch cannot contribute (checked every 8th splat, as K16 does)
-                if ((t & 7u) == 7u && __ballot(any_live()) == 0ull) { done = true; break; }
-            }
+    struct Pix { float g[3] = {0.0f, 0.0f, 0.0f}; };
+    static BH_DEV float prologue(const BwdMaps& m, size_t pixel, Pix& px) {
+        const size_t pix = pixel * 3;
+        const float nx = m.normal_acc[pix], ny = m.normal_acc[pix + 1], nz = m.normal_acc[pix + 2];
+        float vx = m.v_normal[pix], vy = m.v_normal[pix + 1], vz = m.v_normal[pix + 2];
+        if (m.unit) {
+            const float len = __builtin_sqrtf(__builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx)));
+            const float inv = len == 0.0f ? 0.0f : 1.0f / len;
+            const float ux = nx * inv, uy = ny * inv, uz = nz * inv;
+            const float vu = __builtin_fmaf(vz, uz, __builtin_fmaf(vy, uy, vx * ux));
+            vx = __builtin_fmaf(-vu, ux, vx) * inv;
+            vy = __builtin_fmaf(-vu, uy, vy) * inv;
+            vz = __builtin_fmaf(-vu, uz, vz) * inv;
         }
+        px.g[0] = vx; px.g[1] = vy; px.g[2] = vz;
+        return __builtin_fmaf(vz, nz, __builtin_fmaf(vy, ny, vx * nx));
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
-        if (px < u.img_w && py < u.img_h) {
-            float x = ax[q], y = ay[q], z = az[q];
-            if (MODE == BH_NORMAL_UNIT) {
-                const float len = __builtin_sqrtf(__builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
-                const float inv = len == 0.0f ? 0.0f : 1.0f / len;
-                x *= inv; y *= inv; z *= inv;
-            }
-            float* o = out_normal + ((size_t)px + (size_t)py * u.img_w) * 3;
-            o[0] = x; o[1] = y; o[2] = z;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// backward
-// ---------------------------------------------------------------------------
-// Unit normals U = N / |N|: dU = (dN - (dN . u) u) / |N|, so both modes are ONE replay with a per-pixel cotangent g (accumulated:
-// g = v; unit: g = (v - (v . u) u) / |N|, 0 where |N| == 0).  The "colour" of splat i at the pixel is cv = g . n_i and
-// S = the remaining sum of w_j (g . n_j), including the splat in flight, as in K17: it starts at g . N.
-template <bool SMOOTH>
-__global__ __launch_bounds__(64, 6) void normal_backward_kernel(NormalUniforms u, const uint32_t unit, const uint32_t* __restrict__ isect_gids,
-                                                                const uint32_t* __restrict__ tile_offsets, const uint32_t* __restrict__ tile_offsets_far,
-                                                                const float* __restrict__ projected, const float* __restrict__ normals,
-                                                                const float* __restrict__ normal_acc, const float* __restrict__ v_normal,
-                                                                float* __restrict__ v_combined, float* __restrict__ v_n) {
-    __shared__ __attribute__((aligned(16))) float s_splat[NORMAL_BATCH * NORMAL_STRIDE];
-    __shared__ uint32_t s_cg[NORMAL_BATCH];
-    const uint32_t local_tile = normal_tile_of_block(blockIdx.x, u.num_tiles, u.band_mode);
-    if (local_tile >= u.num_tiles) return;
-    const uint32_t tile = u.tile_begin + local_tile;
-    const uint32_t lo0 = tile_offsets[tile * 2], hi0 = tile_offsets[tile * 2 + 1];
-    uint32_t lo1 = 0u, hi1 = 0u;
-    if (tile_offsets_far) { lo1 = tile_offsets_far[tile * 2]; hi1 = tile_offsets_far[tile * 2 + 1]; }
-    if (hi0 <= lo0 && hi1 <= lo1) return;
-    const int lane = threadIdx.x;
-    const uint32_t px0 = (tile % u.tile_bw) * TILE_WIDTH + (lane & 7), py0 = (tile / u.tile_bw) * TILE_WIDTH + (lane >> 3);
-    const float pcx[2] = {(float)px0 + 0.5f, (float)(px0 + 8) + 0.5f};
-    const float pcy[2] = {(float)py0 + 0.5f, (float)(py0 + 8) + 0.5f};
-    float sS[4], sw[4], gx[4], gy[4], gz[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t px = px0 + 8 * (q & 1), py = py0 + 8 * (q >> 1);
-        sS[q] = sw[q] = gx[q] = gy[q] = gz[q] = 0.0f;
-        if (px < u.img_w && py < u.img_h) {
-            const size_t pix = ((size_t)px + (size_t)py * u.img_w) * 3;
-            const float nx = normal_acc[pix], ny = normal_acc[pix + 1], nz = normal_acc[pix + 2];
-            float vx = v_normal[pix], vy = v_normal[pix + 1], vz = v_normal[pix + 2];
-            if (unit) {
-                const float len = __builtin_sqrtf(__builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx)));
-                const float inv = len == 0.0f ? 0.0f : 1.0f / len;
-                const float ux = nx * inv, uy = ny * inv, uz = nz * inv;
-                const float vu = __builtin_fmaf(vz, uz, __builtin_fmaf(vy, uy, vx * ux));
-                vx = __builtin_fmaf(-vu, ux, vx) * inv;
-                vy = __builtin_fmaf(-vu, uy, vy) * inv;
-                vz = __builtin_fmaf(-vu, uz, vz) * inv;
-            }
-            gx[q] = vx; gy[q] = vy; gz[q] = vz;
-            sS[q] = __builtin_fmaf(vz, nz, __builtin_fmaf(vy, ny, vx * nx));
-            sw[q] = 1.0f;
-        }
-    }
-    float aP = 0.f, aQ = 0.f, aR2 = 0.f, aR3 = 0.f, aR4 = 0.f, aVs = 0.f, aNx = 0.f, aNy = 0.f, aNz = 0.f;
-#pragma nounroll
-    for (int part = 0; part < 2; ++part) {
-        const uint32_t range_lo = part ? lo1 : lo0, range_hi = part ? hi1 : hi0;
-        for (uint32_t batch_start = range_lo; batch_start < range_hi; batch_start += NORMAL_BATCH) {
-            const uint32_t cnt = min((uint32_t)NORMAL_BATCH, range_hi - batch_start);
-            __syncthreads();
-            const uint32_t my_cg = stage_normal_batch<SMOOTH>(isect_gids, projected, normals, batch_start, cnt, lane, s_splat);
-            s_cg[lane] = my_cg;
-            __syncthreads();
-            for (uint32_t t = 0; t < cnt; ++t) {
-                const float4 s0 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE]);      // x y c00/2 c01
-                const float4 s1 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 4]);  // c11/2 a sigma_cut nx
-                const float4 s2 = *reinterpret_cast<const float4*>(&s_splat[t * NORMAL_STRIDE + 8]);  // ny nz - -
-                const uint32_t cut_bits = f2u(s1.z);
-                float dxp[2], dyp[2], a_xx[2], b_x[2], c_y[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    dxp[k] = pcx[k] - s0.x;
-                    a_xx[k] = (s0.z * dxp[k]) * dxp[k];
-                    b_x[k] = s0.w * dxp[k];
-                    dyp[k] = pcy[k] - s0.y;
-                    c_y[k] = s1.x * dyp[k];
-                }
-                bool any = false;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int k = q & 1, m = q >> 1;
-                    // --- replay: the forward's arithmetic, instruction for instruction ---
-                    const float half_qv = __builtin_fmaf(c_y[m], dyp[m], a_xx[k]);
-                    const float sigma = __builtin_fmaf(b_x[k], dyp[m], half_qv);
-                    const bool pre = sw[q] > 0.0f && f2u(sigma) <= cut_bits;
-                    if (__ballot(pre) != 0ull) {
-                        const float alpha_raw = s1.y * exp_blend(-sigma);
-                        const float alpha = __builtin_fminf(0.999f, alpha_raw);
-                        const float T = sw[q];
-                        float alpha_eff, next_t;
-                        bool sat;
-                        const bool ok = blend_step<SMOOTH>(alpha, pre, T, alpha_eff, next_t, sat);
-                        sw[q] = (ok && sat) ? 0.0f : T;   // the pixel is done WITHOUT this splat
-                        if (ok && !sat) {
-                            // --- gradients (tolerance-checked) ---
-                            const float vis = alpha_eff * T;
-                            aNx = __builtin_fmaf(vis, gx[q], aNx);
-                            aNy = __builtin_fmaf(vis, gy[q], aNy);
-                            aNz = __builtin_fmaf(vis, gz[q], aNz);
-                            const float cv = __builtin_fmaf(gz[q], s2.y, __builtin_fmaf(gy[q], s2.x, gx[q] * s1.w));
-                            const float v_alpha_eff = __builtin_fmaf(T, cv, -sS[q]) * __builtin_amdgcn_rcpf(1.0f - alpha_eff);
-                            const float v_alpha = SMOOTH ? v_alpha_eff * (alpha_cutoff_weight(alpha) + alpha * alpha_cutoff_weight_deriv(alpha)) : v_alpha_eff;
-                            // geometry / opacity gradients only below the alpha clamp
-                            const float v_sigma = alpha_raw <= 0.999f ? -alpha * v_alpha : 0.0f;
-                            const float ux = v_sigma * dxp[k], uy = v_sigma * dyp[m];
-                            aP += ux;
-                            aQ += uy;
-                            aR2 = __builtin_fmaf(ux, dxp[k], aR2);
-                            aR3 = __builtin_fmaf(ux, dyp[m], aR3);
-                            aR4 = __builtin_fmaf(uy, dyp[m], aR4);
-                            aVs += v_sigma;
-                            sS[q] = __builtin_fmaf(-vis, cv, sS[q]);
-                            sw[q] = next_t;
-                            any = true;
-                        }
-                    }
-                }
-                if (__ballot(any) != 0ull) {
-                    // the nine RAW sums leave through K17's register butterfly, three registers where depth needs two:
-                    // k0 holds P R2 Q R3 in rows 0..3, k1 R4 Nx Vs Ny, k2 Nz - - -
-                    const float h0 = swap32_add(aP, aQ), h1 = swap32_add(aR2, aR3), h2 = swap32_add(aR4, aVs), h3 = swap32_add(aNx, aNy);
-                    const float h4 = swap32_add(aNz, 0.0f);
-                    const float k0 = row_allreduce(swap16_add(h0, h1));
-                    const float k1 = row_allreduce(swap16_add(h2, h3));
-                    const float k2 = row_allreduce(swap16_add(h4, 0.0f));
-                    const int ri = lane & 15, rrow = lane >> 4;
-                    const int c = ((rrow & 1) << 1) | (rrow >> 1);   // which of the register's four components this row holds
-                    const uint32_t cg = s_cg[t];
-                    if (ri == 0) {
-                        unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + c], k0);               // P Q R2 R3: columns 0..3
-                    } else if (ri == 1) {
-                        if (c == 0) unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + 4], k1);   // R4
-                        else if (c == 1) unsafeAtomicAdd(&v_combined[(size_t)cg * 10 + 8], k1);   // Vs
-                        else unsafeAtomicAdd(&v_n[(size_t)cg * 3 + (c - 2)], k1);            // Vn x, y
-                    } else if (ri == 2) {
-                        if (c == 0) unsafeAtomicAdd(&v_n[(size_t)cg * 3 + 2], k2);           // Vn z
-                    }
-                    aP = aQ = aR2 = aR3 = aR4 = aVs = aNx = aNy = aNz = 0.0f;
-                }
-            }
-        }
-    }
-}
+    static BH_DEV float cv(const Rec& r, const Pix& px) { return __builtin_fmaf(px.g[2], r.s2.y, __builtin_fmaf(px.g[1], r.s2.x, px.g[0] * r.s1.w)); }
+};
 
 // v_quat += the chain of Vn through the sign, R_view^T, column k of the rotation matrix and the quaternion's normalisation, behind
 // K18 in its dense mode: a row K18 skipped (its ten sums are zero) is zero in the zero-filled dense output, so a splat that
@@ -478,17 +265,6 @@ __global__ __launch_bounds__(256) void depth_to_normal_backward_kernel(PinholeK 
     v_depth[p] = g;
 }
 
-NormalUniforms normal_uniforms(const bh_ctx* ctx, const ViewUniforms& vu) {
-    NormalUniforms u;
-    u.tile_bw = vu.tile_bw;
-    u.num_tiles = vu.tile_bw * (vu.tile_y1 - vu.tile_y0);
-    u.tile_begin = vu.tile_bw * vu.tile_y0;
-    u.img_w = vu.img_w;
-    u.img_h = vu.img_h;
-    u.band_mode = ctx->knob_band_mode;
-    return u;
-}
-
 NormalView normal_view(const float* vm) {
     NormalView v;
     for (int i = 0; i < 12; ++i) v.vm[i] = vm[i];
@@ -526,17 +302,14 @@ int launch_compact_normals(bh_ctx* ctx, const ForwardState& fs, const float* tra
 // the blend over the saved lists (num_intersections > 0, num_listed_splats > 0, compact normals already queued)
 int launch_normal_forward(bh_ctx* ctx, const ForwardState& fs, const float* normals, uint32_t mode, float* out_normal) {
     const BhRenderOut& r = fs.out;
-    const NormalUniforms u = normal_uniforms(ctx, fs.uniforms);
+    const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     if (u.num_tiles == 0) return 0;
-    const dim3 grid(band_slots(u.num_tiles) * 8u), block(64);
     const bool smooth = fs.flags & BH_FLAG_SMOOTH_CUTOFF;
-#define BH_NORMAL_FWD(S, M) hipLaunchKernelGGL((normal_forward_kernel<S, M>), grid, block, 0, ctx->stream, u, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far, r.projected, normals, out_normal)
     switch (mode) {
-        case BH_NORMAL_ACCUMULATED: if (smooth) BH_NORMAL_FWD(true, BH_NORMAL_ACCUMULATED); else BH_NORMAL_FWD(false, BH_NORMAL_ACCUMULATED); break;
-        case BH_NORMAL_UNIT: if (smooth) BH_NORMAL_FWD(true, BH_NORMAL_UNIT); else BH_NORMAL_FWD(false, BH_NORMAL_UNIT); break;
+        case BH_NORMAL_ACCUMULATED: launch_map_forward<NormalMap<BH_NORMAL_ACCUMULATED>>(ctx, u, smooth, r, normals, out_normal); break;
+        case BH_NORMAL_UNIT: launch_map_forward<NormalMap<BH_NORMAL_UNIT>>(ctx, u, smooth, r, normals, out_normal); break;
         default: return set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: unknown normal mode");
     }
-#undef BH_NORMAL_FWD
     BH_LAUNCH_CHECK(ctx, "normal_forward_kernel");
     return 0;
 }
@@ -554,21 +327,16 @@ PinholeK pinhole_of(const BhCamera* cam, uint32_t h, uint32_t w) {
 int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
-    const NormalUniforms u = normal_uniforms(ctx, fs.uniforms);
+    const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     NormalScratch s;
     BH_TRY(normal_scratch(ctx, nv, (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
     BH_HIP(ctx, hipMemsetAsync(s.v_n, 0, s.vec_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
     BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
     BH_TRY(launch_normal_forward(ctx, fs, s.normals, BH_NORMAL_ACCUMULATED, s.acc));
-    const dim3 grid(band_slots(u.num_tiles) * 8u), block(64);
-    const uint32_t unit = term.mode == BH_NORMAL_UNIT ? 1u : 0u;
-    if (fs.flags & BH_FLAG_SMOOTH_CUTOFF)
-        hipLaunchKernelGGL((normal_backward_kernel<true>), grid, block, 0, ctx->stream, u, unit, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far,
-                           r.projected, s.normals, s.acc, term.v_normal, v_combined, s.v_n);
-    else
-        hipLaunchKernelGGL((normal_backward_kernel<false>), grid, block, 0, ctx->stream, u, unit, r.compact_gid_from_isect, r.tile_offsets, r.tile_offsets_far,
-                           r.projected, s.normals, s.acc, term.v_normal, v_combined, s.v_n);
+    using P = NormalMap<BH_NORMAL_ACCUMULATED>;
+    const P::BwdMaps maps{s.acc, term.v_normal, term.mode == BH_NORMAL_UNIT ? 1u : 0u};
+    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, s.normals, maps, v_combined, s.v_n);
     BH_LAUNCH_CHECK(ctx, "normal_backward_kernel");
     return 0;
 }
@@ -607,17 +375,11 @@ int bh_render_normal(bh_ctx* ctx, const BhRenderOut* saved, const float* transfo
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!saved || !out) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: null argument");
     if (mode > BH_NORMAL_UNIT) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: unknown normal mode");
-    if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: the saved forward was not a BH_FLAG_BWD_INFO forward");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
     const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_forward(ctx, saved, "render_normal", &found));
+    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_INVALID_ARG, "render_normal", &found));
     const bh::ForwardState& fs = *found;
-    if (fs.out.num_intersections == 0 || fs.out.num_listed_splats == 0) {   // nothing listed: both modes are 0 over the rendered window
-        const bh::ViewUniforms& vu = fs.uniforms;
-        const size_t row0 = (size_t)vu.tile_y0 * bh::TILE_WIDTH, row1 = std::min<size_t>((size_t)vu.tile_y1 * bh::TILE_WIDTH, vu.img_h);
-        if (row1 > row0) BH_HIP(ctx, hipMemsetAsync(out + row0 * vu.img_w * 3, 0, (row1 - row0) * vu.img_w * 3 * 4, ctx->stream));
-        return 0;
-    }
+    // nothing listed: both modes are 0
+    if (fs.out.num_intersections == 0 || fs.out.num_listed_splats == 0) return bh::clear_map_window(ctx, fs.uniforms, out, 3);
     if (!transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: null transforms");
     bh::ProfScope ps(ctx, "RenderNormal");
     bh::NormalScratch s;
@@ -636,10 +398,8 @@ int bh_render_backward_normal_saved(bh_ctx* ctx, const BhRenderOut* saved, const
     if (normal_mode > BH_NORMAL_UNIT) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown normal mode");
     if (v_depth && depth_mode == BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: median depth has no gradient");
     if (v_depth && depth_mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown depth mode");
-    if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
     const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_forward(ctx, saved, "render_backward_normal_saved", &found));
+    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_INVALID_ARG, "render_backward_normal_saved", &found));
     const bh::ForwardState& fs = *found;
     if (fs.n > 0 && !transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: null transforms");
     bh::DepthTerm depth;

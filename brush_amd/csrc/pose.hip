@@ -32,10 +32,8 @@ int bh_render_backward_pose_saved(bh_ctx* ctx, const BhRenderOut* saved, const f
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!saved || !v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight || !v_viewmat)
         return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_pose_saved: null argument");
-    if (!(saved->flags & BH_FLAG_BWD_INFO)) return bh::set_error(ctx, BH_ERR_STATE, "render_backward_pose_saved: the saved forward was not a BH_FLAG_BWD_INFO forward");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
     const bh::ForwardState* fs = nullptr;
-    BH_TRY(bh::find_saved_forward(ctx, saved, "render_backward_pose_saved", &fs));
+    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_STATE, "render_backward_pose_saved", &fs));
     return bh::backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
                              /*span_floats=*/0, /*want_refine=*/true, /*depth=*/nullptr, v_viewmat);
 }

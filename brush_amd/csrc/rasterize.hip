@@ -140,14 +140,9 @@ constexpr int SPLAT_STRIDE = 12;
 constexpr int BATCH = 64;
 constexpr uint32_t SPLIT_GROUP = 4;   // splats a quadrant wave of a split tile takes at a time (rasterize_kernel, NQ == 1)
 
-// exp() in the blend loops, and a pixel's alpha / transmittance step: device_blend.h (shared with depth.hip)
+// exp() in the blend loops, and a pixel's alpha / transmittance step: device_blend.h (shared with the map kernels, device_map_blend.h)
 
-// 8 XCDs take workgroups round-robin; each XCD owns a band of tiles (context.h XCD BANDS).  (>= num_tiles: the slot names no tile)
-BH_DEV uint32_t tile_of_block(uint32_t b, uint32_t num_tiles, uint32_t band_mode) {
-    const uint32_t per = band_slots(num_tiles);
-    const uint32_t i = b >> 3;
-    return i < per ? band_tile(b & 7u, i, per, band_mode) : 0xFFFFFFFFu;
-}
+// 8 XCDs take workgroups round-robin; each XCD owns a band of tiles (context.h XCD BANDS, tile_of_block)
 
 // Stage one batch of up to 64 splats of this tile into LDS (lane i stages splat i).
 // Everything that is per-splat rather than per-pixel is done here once by the
