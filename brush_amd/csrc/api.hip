@@ -430,6 +430,8 @@ const Option kOptions[] = {
      [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 16, &u) || !(u == 0 || u == 4 || u == 8 || u == 16)) return false; c->knob_sort_kpt = u; return true; }},
     {"grad_allreduce", "ring|direct: the dense gradient block's collective — ncclAllReduce, or reduce-scatter + all-gather over grouped send/recv",
      [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "ring") { c->knob_direct_allreduce = false; return true; } if (w == "direct") { c->knob_direct_allreduce = true; return true; } return false; }},
+    {"update_sparse", "0..256: an update block with at most this many non-dormant rows fetches them in one round trip (0: never; 256: every block that may skip dormant rows; default 64 at SH degree 0, else 0)",
+     [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 256, &u)) return false; c->knob_update_sparse = (int)u; return true; }},
 };
 constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
 }  // namespace

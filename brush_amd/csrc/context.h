@@ -482,6 +482,7 @@ struct bh_ctx {
     bool knob_direct_allreduce = false;   // option grad_allreduce=direct: reduce-scatter + all-gather over grouped send / recv (comm.hip)
     uint32_t knob_k5_exact_spw = 32;  // BH_K5_EXACT_SPW = 16 | 32 | 64 (A/B): splats per wave of K5 for complete lists
     bool knob_no_dormant = false;     // BH_UPDATE_NO_DORMANT (A/B, tests): the update kernel fetches and updates dormant splats like everyone else
+    int knob_update_sparse = -1;      // option update_sparse: non-dormant rows up to which an update block takes its one-round-trip path (-1: the default of launch_train_update)
     bool knob_update_early = false;   // BH_UPDATE_EARLY (A/B): the update kernel's blocks of SH degree >= 1 issue all their loads up front
     uint32_t knob_update_rows = 0;    // BH_UPDATE_ROWS: 64 | 128 | 256 splats per block of the update kernel
     uint32_t knob_sort_kpt = 0;       // BH_SORT_KPT: 4 | 8 | 16 keys per thread of the radix sort

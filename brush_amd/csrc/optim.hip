@@ -160,6 +160,7 @@ struct UpdateArgs {
     uint32_t vis_clamp;    // tile-partitioned frame: visible arrives summed over strips -> min(v, 1)
     uint32_t dormant_skip; // 0 = BH_UPDATE_NO_DORMANT (A/B, tests): dormant splats are fetched and updated like everyone else
     uint32_t masked;       // the gradient tensors were not zero-filled: row i holds a gradient iff the sign bit of refine_weight[i] is set (K18's mark), else it is 0
+    uint32_t sparse_max;   // option update_sparse: a block with at most this many non-dormant rows takes the one-round-trip path (0 = no block does)
     float tab_t[10];       // lr_mean x3, lr_rotation x4, lr_scale x3
     float tab_sh[75];      // 1 for the DC coefficient, 1/lr_coeffs_sh_scale for the rest
     // visibility-gated noise on the means (train.rs:389-416) drawn on the device and added right behind the Adam update
@@ -173,7 +174,10 @@ struct UpdateArgs {
 // component).  The element arithmetic is identical either way.
 // ROWS: splats per block (multiple of 4, <= OPT_WG) — fewer for long SH rows keeps more blocks resident per CU.
 // S_IT: float4s of the block's SH rows per thread when the loads are issued up front (0: every section fetches its own inputs).
-template <bool VEC, int ROWS, int S_IT_>
+// SPARSE: the kernel has the second path for blocks with few non-dormant rows (launched when option update_sparse is not 0).
+constexpr uint32_t UPDATE_SPARSE_DEFAULT = 64;   // non-dormant rows of a 256-row block at SH degree 0 up to which the sparse path runs
+
+template <bool VEC, int ROWS, int S_IT_, bool SPARSE>
 __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     float* __restrict__ transforms, float* __restrict__ m1_t, float* __restrict__ m2_t, const float* __restrict__ g_t,
     float* __restrict__ sh, float* __restrict__ m1_sh, float* __restrict__ m2_sh, const float* __restrict__ g_sh,
@@ -190,7 +194,9 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     float* s_v = s_dyn + (uint32_t)ROWS * pitch;      // [rows]
     float* s_mask = s_v + (uint32_t)ROWS;             // [rows] 1 = the row's gradient was written, 2 = the splat is dormant (only with u.masked)
     float* s_nz = s_mask + (uint32_t)ROWS;            // [rows] != 0: some moment of the splat is non-zero after this step (only with u.masked)
-    float* s_noise = s_nz + (uint32_t)ROWS;           // [rows][3], only with noise_on
+    uint32_t* s_list = reinterpret_cast<uint32_t*>(s_nz + (uint32_t)ROWS);   // [rows] the block's non-dormant rows, ascending (sparse path)
+    uint32_t* s_cnt = s_list + (uint32_t)ROWS;        // [4] non-dormant rows of each wave
+    float* s_noise = reinterpret_cast<float*>(s_cnt + 4);   // [rows][3], only with noise_on
     // masked (block-uniform): the gradient tensors were not zero-filled — row r of them counts iff K18 marked the splat: the sign
     // bit of its (non-negative) refine weight, a vector that WAS cleared.
     // No barrier stands in front of what the block fetches: the SH staging below reads the marks it needs straight from global
@@ -211,6 +217,16 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     // carries no marks (every splat is processed until it is found dormant again).  A dormant splat costs its eleven per-splat
     // words (44 B: statistics, marks, opacity moments) and nothing else.  Not on the first step (the moment tensors may hold anything).
     const bool dorm_ok = masked && !a.first && u.dormant_skip != 0u;
+    // SPARSE blocks (option update_sparse, kernel-uniform switch `sparse_on`).  With the skip, what a block still fetches behind its
+    // per-splat section depends only on WHICH rows are not dormant, yet the sections below fetch it in three further dependent
+    // round trips (SH gradients behind their marks, transforms, SH rows), and at SH degree 0 a block of the bench scene keeps a
+    // few dozen rows.  A block with at most u.sparse_max such rows compacts them into an LDS list and issues every remaining load
+    // — gradients, both moments and the parameters of the transforms, gradients, first moment and parameters of the SH rows — in ONE
+    // round trip, element-wise over the listed rows (see `sparse` below).  While the switch is on nobody stages SH gradients up
+    // front (a sparse block never wants the dormant rows'): a block over the threshold stages them behind the per-splat section's
+    // barrier, marks from LDS — the same number of dependent trips as up-front staging behind global marks.  With the option at 0
+    // the launcher picks the instantiations without the path (SPARSE = false): the one-path kernel, statement for statement.
+    const bool sparse_on = SPARSE && dorm_ok && u.sparse_max != 0u;
     const uint32_t* mark_rows = reinterpret_cast<const uint32_t*>(refine_weight) + row0;
     const float rcp_len = 1.0f / (float)row_len;
     const uint32_t sh_count = nrows * row_len;
@@ -253,12 +269,12 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     float in_m2sh = m2_sh[si];
     if (EARLY) asm volatile("" ::: "memory");   // (compiler-only: the loads above are issued HERE, not sunk to their uses behind the staging loop)
     // ---- SH gradients -> LDS (coalesced), its loads queue behind the ones above
-    {
+    auto stage_sh = [&](auto row_marked) {
         const uint32_t vec_end = VEC ? (sh_count & ~3u) : 0u;
         for (uint32_t e = threadIdx.x * 4u; e < vec_end; e += OPT_WG * 4u) {
             // (a float4 spans at most two rows: the first and the last component's)
             const uint32_t ra = (uint32_t)(((float)e + 0.5f) * rcp_len), rb = (uint32_t)(((float)(e + 3u) + 0.5f) * rcp_len);
-            const bool wa = !masked || (mark_rows[ra] >> 31) != 0u, wb = !masked || (mark_rows[rb] >> 31) != 0u;
+            const bool wa = !masked || row_marked(ra), wb = !masked || row_marked(rb);
             float4 g4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (wa || wb) g4 = *reinterpret_cast<const float4*>(&g_sh[sh_base + e]);
             const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
@@ -271,9 +287,10 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
         }
         for (uint32_t e = vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
             const uint32_t r = (uint32_t)(((float)e + 0.5f) * rcp_len);
-            s_g[r * pitch + (e - r * row_len)] = (!masked || (mark_rows[r] >> 31) != 0u) ? g_sh[sh_base + e] * u.gscale : 0.0f;
+            s_g[r * pitch + (e - r * row_len)] = (!masked || row_marked(r)) ? g_sh[sh_base + e] * u.gscale : 0.0f;
         }
-    }
+    };
+    if (!sparse_on) stage_sh([&](uint32_t r) { return (mark_rows[r] >> 31) != 0u; });
     // (one wait for all of it)
     if (EARLY && VEC) {
 #pragma unroll
@@ -286,6 +303,7 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     }
     if (EARLY) asm volatile("" : "+v"(in_rw), "+v"(in_rn), "+v"(in_vis), "+v"(in_vw), "+v"(in_ms), "+v"(in_sr), "+v"(in_go), "+v"(in_m1o), "+v"(in_m2o), "+v"(in_op), "+v"(in_m2sh));
     // ---- statistics + opacity: one splat per thread
+    bool live = false;   // this thread's row exists and is not dormant
     if (threadIdx.x < nrows) {
         const uint64_t i = row0 + threadIdx.x;
         const float rw_raw = in_rw;
@@ -294,6 +312,7 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
         //  moments without rewriting m2_sh cannot make the step skip a splat whose moments are not zero)
         const bool dormant = dorm_ok && !written && f2u(in_m2sh) == 0x80000000u && in_vis == 0.0f && in_m1o == 0.0f && in_m2o == 0.0f;
         if (masked) s_mask[threadIdx.x] = written ? 1.0f : (dormant ? 2.0f : 0.0f);
+        live = !dormant;
         // (masked: K18 stored the weight with the sign bit as the mark; an unmarked entry is the zero the forward left)
         {
             const float rn_old = in_rn, vw_old = in_vw, ms_old = in_ms;
@@ -332,138 +351,259 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
             s_noise[threadIdx.x * 3u + 2u] = nz[2];
         }
     }
+    // (sparse_on) this row's place among the block's non-dormant rows: within its wave here, the waves' counts through LDS
+    uint32_t my_pos = 0;
+    if (sparse_on) {
+        const uint64_t bal = __ballot(live);
+        my_pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if ((threadIdx.x & 63u) == 0u) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
+    }
     if (u.noise_on || masked) __syncthreads();   // block-uniform
-    // ---- transforms: full second moment, per-column lr
-    {
-        const uint32_t count = nrows * 10u;
-        const uint64_t base = row0 * 10u;
-        auto one = [&](float g_raw, bool written, float m1v, float m2v, float pv, uint32_t e, float& o_m1, float& o_m2, float& o_p) {
-            const uint32_t r = (e * 52429u) >> 19;  // e / 10 (e < 2560)
-            const uint32_t c = e - r * 10u;
-            const float g = written ? g_raw * u.gscale : 0.0f;
-            const float mm1 = a.first ? g * a.f1 : m1v * a.beta1 + g * a.f1;
-            const float gsq = g * g;
-            const float mm2 = a.first ? gsq * a.f2 : m2v * a.beta2 + gsq * a.f2;
-            o_m1 = mm1;
-            o_m2 = mm2;
-            float p = pv;
-            float m1c = mm1;
-            adam_elem(p, g, m1c, mm2, a, u.tab_t[c] * 1.0f);
-            if (u.noise_on && c < 3u) p = p + s_noise[r * 3u + c];
-            o_p = p;
-        };
-        const uint32_t vec_end = t_vec_end;
+    // ---- one element of the transforms (full second moment, per-column lr) / of the SH rows (gradient and the row's second
+    // moment from LDS: s_g / s_v, e = row * row_len + column in THEIR indexing) — shared by both paths below
+    auto one_t = [&](float g_raw, bool written, float m1v, float m2v, float pv, uint32_t e, float& o_m1, float& o_m2, float& o_p) {
+        const uint32_t r = (e * 52429u) >> 19;  // e / 10 (e < 2560)
+        const uint32_t c = e - r * 10u;
+        const float g = written ? g_raw * u.gscale : 0.0f;
+        const float mm1 = a.first ? g * a.f1 : m1v * a.beta1 + g * a.f1;
+        const float gsq = g * g;
+        const float mm2 = a.first ? gsq * a.f2 : m2v * a.beta2 + gsq * a.f2;
+        o_m1 = mm1;
+        o_m2 = mm2;
+        float p = pv;
+        float m1c = mm1;
+        adam_elem(p, g, m1c, mm2, a, u.tab_t[c] * 1.0f);
+        if (u.noise_on && c < 3u) p = p + s_noise[r * 3u + c];
+        o_p = p;
+    };
+    auto one_sh = [&](float m1v, float pv, uint32_t e, float& o_m1, float& o_p) {
+        const uint32_t r = (uint32_t)(((float)e + 0.5f) * rcp_len);
+        const uint32_t c = e - r * row_len;
+        const float gi = s_g[r * pitch + c];
+        float mm1 = a.first ? gi * a.f1 : m1v * a.beta1 + gi * a.f1;
+        o_m1 = mm1;
+        float p = pv;
+        adam_elem(p, gi, mm1, s_v[r], a, u.tab_sh[c] * u.lr_sh);
+        o_p = p;
+    };
+    auto row_of = [&](uint32_t e) { return (uint32_t)(((float)e + 0.5f) * rcp_len); };
+    uint32_t n_live = 0;
+    bool sparse = false;   // block-uniform
+    if (sparse_on) {
+        uint32_t before = 0;
 #pragma unroll
-        for (int k = 0; k < T_IT; ++k) {
-            const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
-            if (e >= vec_end) break;
-            const uint64_t i = base + e;
-            const uint32_t ra = (e * 52429u) >> 19, rb = ((e + 3u) * 52429u) >> 19;   // the float4's first and last row
-            const float ka = masked ? s_mask[ra] : 1.0f, kb = masked ? s_mask[rb] : 1.0f;
-            if (ka == 2.0f && kb == 2.0f) continue;   // both rows dormant: nothing to fetch, nothing moves
-            const float4 g4 = EARLY ? tg[k] : *reinterpret_cast<const float4*>(&g_t[i]);
-            float4 m14 = EARLY ? tm1[k] : *reinterpret_cast<const float4*>(&m1_t[i]);
-            float4 m24 = EARLY ? tm2[k] : *reinterpret_cast<const float4*>(&m2_t[i]);
-            float4 p4 = EARLY ? tp[k] : *reinterpret_cast<const float4*>(&transforms[i]);
-            const bool wa = ka == 1.0f, wb = kb == 1.0f;
-            const float4 m1_old = m14, m2_old = m24, p_old = p4;
-            one(g4.x, wa, m14.x, m24.x, p4.x, e, m14.x, m24.x, p4.x);
-            one(g4.y, (((e + 1u) * 52429u) >> 19) == ra ? wa : wb, m14.y, m24.y, p4.y, e + 1, m14.y, m24.y, p4.y);
-            one(g4.z, (((e + 2u) * 52429u) >> 19) == ra ? wa : wb, m14.z, m24.z, p4.z, e + 2, m14.z, m24.z, p4.z);
-            one(g4.w, wb, m14.w, m24.w, p4.w, e + 3, m14.w, m24.w, p4.w);
-            if (masked) {   // which rows still carry a non-zero moment (the dormant mark is set from this at the end)
-                const uint32_t r1 = ((e + 1u) * 52429u) >> 19, r2 = ((e + 2u) * 52429u) >> 19;
-                if (m14.x != 0.0f || m24.x != 0.0f) s_nz[ra] = 1.0f;
-                if (m14.y != 0.0f || m24.y != 0.0f) s_nz[r1] = 1.0f;
-                if (m14.z != 0.0f || m24.z != 0.0f) s_nz[r2] = 1.0f;
-                if (m14.w != 0.0f || m24.w != 0.0f) s_nz[rb] = 1.0f;
-            }
-            // A store whose four values are bit for bit what was loaded is left out.  That is the case for every splat that has
-            // never received a gradient (moments 0, gradient 0: the moments stay 0 and the parameter does not move) — nine tenths
-            // of the bench scene, where most splats lie behind saturated tiles in every view; a scene whose splats all reach a
-            // pixel now and then writes everything, as before.  The update is HBM-bound and 3 of its 7 streams are stores.
-            if (a.first || !same_bits4(m14, m1_old)) *reinterpret_cast<float4*>(&m1_t[i]) = m14;
-            if (a.first || !same_bits4(m24, m2_old)) *reinterpret_cast<float4*>(&m2_t[i]) = m24;
-            if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&transforms[i]) = p4;
+        for (uint32_t wv = 0; wv < (uint32_t)OPT_WG / 64u; ++wv) {
+            const uint32_t cw = s_cnt[wv];
+            n_live += cw;
+            before += wv < (threadIdx.x >> 6) ? cw : 0u;
         }
-        for (uint32_t e = vec_end + threadIdx.x; e < count; e += OPT_WG) {
-            const uint64_t i = base + e;
-            float o1, o2, op;
-            const uint32_t r = (e * 52429u) >> 19;
-            one(g_t[i], !masked || s_mask[r] == 1.0f, m1_t[i], m2_t[i], transforms[i], e, o1, o2, op);
-            m1_t[i] = o1;
-            m2_t[i] = o2;
-            transforms[i] = op;
-            if (masked && (o1 != 0.0f || o2 != 0.0f)) s_nz[r] = 1.0f;
-        }
+        n_live = __builtin_amdgcn_readfirstlane(n_live);
+        my_pos += before;
+        sparse = n_live <= u.sparse_max;
     }
-    // ---- SH: per-row second moment (adam_scaled.rs:99-104,152-165), row sums in index order
-    __syncthreads();
-    if (threadIdx.x < nrows) {
-        const float* g = s_g + threadIdx.x * pitch;
-        float acc = 0.0f;
-        for (uint32_t c = 0; c < row_len; ++c) acc += g[c] * g[c];
-        const float row_gsq = acc / (float)row_len;
-        const uint64_t r = row0 + threadIdx.x;
-        const float v_old = in_m2sh;
-        const float v = a.first ? row_gsq * a.f2 : v_old * a.beta2 + row_gsq * a.f2;
-        const bool is_dormant = masked && s_mask[threadIdx.x] == 2.0f;
-        // (a dormant row keeps its -0.0: the recurrence would turn it into +0.0 and un-mark it every step)
-        if (!is_dormant && (a.first || !same_bits(v, v_old))) m2_sh[r] = v;
-        s_v[threadIdx.x] = v;
-        if (masked && v != 0.0f) s_nz[threadIdx.x] = 1.0f;
-    }
-    __syncthreads();
-    {
-        auto one = [&](float m1v, float pv, uint32_t e, float& o_m1, float& o_p) {
-            const uint32_t r = (uint32_t)(((float)e + 0.5f) * rcp_len);
-            const uint32_t c = e - r * row_len;
-            const float gi = s_g[r * pitch + c];
-            float mm1 = a.first ? gi * a.f1 : m1v * a.beta1 + gi * a.f1;
-            o_m1 = mm1;
-            float p = pv;
-            adam_elem(p, gi, mm1, s_v[r], a, u.tab_sh[c] * u.lr_sh);
-            o_p = p;
-        };
-        const uint32_t vec_end = s_vec_end;
-        auto row_of = [&](uint32_t e) { return (uint32_t)(((float)e + 0.5f) * rcp_len); };
-        auto four = [&](float4 m14, float4 p4, uint32_t e) {
-            const uint64_t i = sh_base + e;
-            const float4 m1_old = m14, p_old = p4;
-            one(m14.x, p4.x, e, m14.x, p4.x);
-            one(m14.y, p4.y, e + 1, m14.y, p4.y);
-            one(m14.z, p4.z, e + 2, m14.z, p4.z);
-            one(m14.w, p4.w, e + 3, m14.w, p4.w);
-            if (masked) {
-                if (m14.x != 0.0f) s_nz[row_of(e)] = 1.0f;
-                if (m14.y != 0.0f) s_nz[row_of(e + 1u)] = 1.0f;
-                if (m14.z != 0.0f) s_nz[row_of(e + 2u)] = 1.0f;
-                if (m14.w != 0.0f) s_nz[row_of(e + 3u)] = 1.0f;
-            }
-            if (a.first || !same_bits4(m14, m1_old)) *reinterpret_cast<float4*>(&m1_sh[i]) = m14;
-            if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&sh[i]) = p4;
-        };
-        if (sh_early) {
+    if (sparse) {
+        // ---- SPARSE: the listed rows in chunks of at most ch_rows (one chunk for nearly every block the threshold lets in).  Per
+        // chunk: every load in one round trip, element-wise — lane x of trip k holds column x % 10 (x % row_len) of listed row
+        // x / 10 (x / row_len), so a row's words stay on neighbouring lanes; a lane past the chunk's end loads its block's element 0
+        // and drops it.  Gradients follow the mark: an unmarked row's lanes read the first-moment word they load anyway, not the
+        // gradient tensor, and take 0.  The arithmetic is one_t / one_sh, the stores are left out per element where the dense path
+        // decides per float4 (a store it adds there rewrites the bits that are in memory), so both paths leave the same tensors —
+        // short of one corner: a dormant row's moment that holds -0.0 stays -0.0 here, where the dense path rewrites it as +0.0 if
+        // the row shares a float4 with a non-dormant one (as it stays in the dense path when both of the float4's rows are dormant).
+        constexpr uint32_t SP_T = 2, SP_S = 2;   // trips per chunk over the transforms / the SH rows
+        const uint32_t ch_s = (SP_S * (uint32_t)OPT_WG) / row_len, ch_rows = ch_s < (SP_T * (uint32_t)OPT_WG) / 10u ? ch_s : (SP_T * (uint32_t)OPT_WG) / 10u;
+        if (live) s_list[my_pos] = threadIdx.x;
+        __syncthreads();
+        for (uint32_t j0 = 0; j0 < n_live; j0 += ch_rows) {   // (block-uniform bounds)
+            const uint32_t cn = n_live - j0 < ch_rows ? n_live - j0 : ch_rows;
+            float tg[SP_T], tm1[SP_T], tm2[SP_T], tp[SP_T], sg[SP_S], sm1[SP_S], sp[SP_S];
+            uint32_t te[SP_T], sr[SP_S];       // the element's index in the block's transforms / the SH element's row; ~0u: a lane past the end
+            bool tw[SP_T], sw[SP_S];           // its row's gradient was written
 #pragma unroll
-            for (int k = 0; k < S_IT; ++k) {
+            for (uint32_t k = 0; k < SP_T; ++k) {
+                const uint32_t x = threadIdx.x + k * (uint32_t)OPT_WG;
+                const uint32_t j = (x * 52429u) >> 19;   // x / 10
+                const bool ok = x < cn * 10u;
+                uint32_t r = 0u;
+                if (ok) r = s_list[j0 + j];
+                const uint32_t e = ok ? r * 10u + (x - j * 10u) : 0u;
+                tw[k] = ok && s_mask[r] == 1.0f;
+                te[k] = ok ? e : ~0u;
+                const uint64_t i = t_base + e;
+                tg[k] = *(tw[k] ? &g_t[i] : &m1_t[i]);
+                tm1[k] = m1_t[i];
+                tm2[k] = m2_t[i];
+                tp[k] = transforms[i];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < SP_S; ++k) {
+                const uint32_t x = threadIdx.x + k * (uint32_t)OPT_WG;
+                const uint32_t j = row_of(x);            // x / row_len, exact for x < 2^16
+                const bool ok = x < cn * row_len;
+                uint32_t r = 0u;
+                if (ok) r = s_list[j0 + j];
+                const uint32_t e = ok ? r * row_len + (x - j * row_len) : 0u;
+                sw[k] = ok && s_mask[r] == 1.0f;
+                sr[k] = ok ? r : ~0u;
+                const uint64_t i = sh_base + e;
+                sg[k] = *(sw[k] ? &g_sh[i] : &m1_sh[i]);
+                sm1[k] = m1_sh[i];
+                sp[k] = sh[i];
+            }
+            asm volatile("" ::: "memory");   // (compiler-only: every load above is issued in front of the first use below)
+            // SH gradients, scaled, into s_g rows by position in the chunk: s_g[x / row_len][x % row_len] is element x of one_sh
+#pragma unroll
+            for (uint32_t k = 0; k < SP_S; ++k) {
+                const uint32_t x = threadIdx.x + k * (uint32_t)OPT_WG;
+                const uint32_t j = row_of(x);
+                if (sr[k] != ~0u) s_g[j * pitch + (x - j * row_len)] = sw[k] ? sg[k] * u.gscale : 0.0f;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < SP_T; ++k) {
+                if (te[k] == ~0u) continue;
+                const uint64_t i = t_base + te[k];
+                float o1, o2, op;
+                one_t(tg[k], tw[k], tm1[k], tm2[k], tp[k], te[k], o1, o2, op);
+                if (o1 != 0.0f || o2 != 0.0f) s_nz[(te[k] * 52429u) >> 19] = 1.0f;
+                if (!same_bits(o1, tm1[k])) m1_t[i] = o1;
+                if (!same_bits(o2, tm2[k])) m2_t[i] = o2;
+                if (!same_bits(op, tp[k])) transforms[i] = op;
+            }
+            __syncthreads();
+            // the rows' second moment: the row's own thread (it holds the old value), sums in index order
+            if (live && my_pos >= j0 && my_pos - j0 < cn) {
+                const float* g = s_g + (my_pos - j0) * pitch;
+                float acc = 0.0f;
+                for (uint32_t c = 0; c < row_len; ++c) acc += g[c] * g[c];
+                const float row_gsq = acc / (float)row_len;
+                const float v_old = in_m2sh;
+                const float v = a.first ? row_gsq * a.f2 : v_old * a.beta2 + row_gsq * a.f2;
+                if (!same_bits(v, v_old)) m2_sh[row0 + threadIdx.x] = v;
+                s_v[my_pos - j0] = v;
+                if (v != 0.0f) s_nz[threadIdx.x] = 1.0f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t k = 0; k < SP_S; ++k) {
+                if (sr[k] == ~0u) continue;
+                const uint32_t x = threadIdx.x + k * (uint32_t)OPT_WG;
+                const uint64_t i = sh_base + sr[k] * row_len + (x - row_of(x) * row_len);
+                float o1, op;
+                one_sh(sm1[k], sp[k], x, o1, op);
+                if (o1 != 0.0f) s_nz[sr[k]] = 1.0f;
+                if (!same_bits(o1, sm1[k])) m1_sh[i] = o1;
+                if (!same_bits(op, sp[k])) sh[i] = op;
+            }
+            if (j0 + ch_rows < n_live) __syncthreads();   // the next chunk overwrites s_g / s_v
+        }
+    } else {
+        if (sparse_on) stage_sh([&](uint32_t r) { return s_mask[r] == 1.0f; });
+        // ---- transforms: full second moment, per-column lr
+        {
+            const uint32_t count = nrows * 10u;
+            const uint64_t base = row0 * 10u;
+            const uint32_t vec_end = t_vec_end;
+#pragma unroll
+            for (int k = 0; k < T_IT; ++k) {
                 const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
                 if (e >= vec_end) break;
-                four(sm1[k], sp[k], e);
+                const uint64_t i = base + e;
+                const uint32_t ra = (e * 52429u) >> 19, rb = ((e + 3u) * 52429u) >> 19;   // the float4's first and last row
+                const float ka = masked ? s_mask[ra] : 1.0f, kb = masked ? s_mask[rb] : 1.0f;
+                if (ka == 2.0f && kb == 2.0f) continue;   // both rows dormant: nothing to fetch, nothing moves
+                const float4 g4 = EARLY ? tg[k] : *reinterpret_cast<const float4*>(&g_t[i]);
+                float4 m14 = EARLY ? tm1[k] : *reinterpret_cast<const float4*>(&m1_t[i]);
+                float4 m24 = EARLY ? tm2[k] : *reinterpret_cast<const float4*>(&m2_t[i]);
+                float4 p4 = EARLY ? tp[k] : *reinterpret_cast<const float4*>(&transforms[i]);
+                const bool wa = ka == 1.0f, wb = kb == 1.0f;
+                const float4 m1_old = m14, m2_old = m24, p_old = p4;
+                one_t(g4.x, wa, m14.x, m24.x, p4.x, e, m14.x, m24.x, p4.x);
+                one_t(g4.y, (((e + 1u) * 52429u) >> 19) == ra ? wa : wb, m14.y, m24.y, p4.y, e + 1, m14.y, m24.y, p4.y);
+                one_t(g4.z, (((e + 2u) * 52429u) >> 19) == ra ? wa : wb, m14.z, m24.z, p4.z, e + 2, m14.z, m24.z, p4.z);
+                one_t(g4.w, wb, m14.w, m24.w, p4.w, e + 3, m14.w, m24.w, p4.w);
+                if (masked) {   // which rows still carry a non-zero moment (the dormant mark is set from this at the end)
+                    const uint32_t r1 = ((e + 1u) * 52429u) >> 19, r2 = ((e + 2u) * 52429u) >> 19;
+                    if (m14.x != 0.0f || m24.x != 0.0f) s_nz[ra] = 1.0f;
+                    if (m14.y != 0.0f || m24.y != 0.0f) s_nz[r1] = 1.0f;
+                    if (m14.z != 0.0f || m24.z != 0.0f) s_nz[r2] = 1.0f;
+                    if (m14.w != 0.0f || m24.w != 0.0f) s_nz[rb] = 1.0f;
+                }
+                // A store whose four values are bit for bit what was loaded is left out.  That is the case for every splat that has
+                // never received a gradient (moments 0, gradient 0: the moments stay 0 and the parameter does not move) — nine tenths
+                // of the bench scene, where most splats lie behind saturated tiles in every view; a scene whose splats all reach a
+                // pixel now and then writes everything, as before.  The update is HBM-bound and 3 of its 7 streams are stores.
+                if (a.first || !same_bits4(m14, m1_old)) *reinterpret_cast<float4*>(&m1_t[i]) = m14;
+                if (a.first || !same_bits4(m24, m2_old)) *reinterpret_cast<float4*>(&m2_t[i]) = m24;
+                if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&transforms[i]) = p4;
             }
-        } else {
-            for (uint32_t e = threadIdx.x * 4u; e < vec_end; e += OPT_WG * 4u) {
-                // (a float4 spans at most two rows for row_len >= 3: the first and the last component's)
-                if (masked && s_mask[row_of(e)] == 2.0f && s_mask[row_of(e + 3u)] == 2.0f) continue;   // dormant rows: nothing to fetch
-                four(*reinterpret_cast<const float4*>(&m1_sh[sh_base + e]), *reinterpret_cast<const float4*>(&sh[sh_base + e]), e);
+            for (uint32_t e = vec_end + threadIdx.x; e < count; e += OPT_WG) {
+                const uint64_t i = base + e;
+                float o1, o2, op;
+                const uint32_t r = (e * 52429u) >> 19;
+                one_t(g_t[i], !masked || s_mask[r] == 1.0f, m1_t[i], m2_t[i], transforms[i], e, o1, o2, op);
+                m1_t[i] = o1;
+                m2_t[i] = o2;
+                transforms[i] = op;
+                if (masked && (o1 != 0.0f || o2 != 0.0f)) s_nz[r] = 1.0f;
             }
         }
-        for (uint32_t e = vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
-            const uint64_t i = sh_base + e;
-            float o1, op;
-            one(m1_sh[i], sh[i], e, o1, op);
-            m1_sh[i] = o1;
-            sh[i] = op;
-            if (masked && o1 != 0.0f) s_nz[row_of(e)] = 1.0f;
+        // ---- SH: per-row second moment (adam_scaled.rs:99-104,152-165), row sums in index order
+        __syncthreads();
+        if (threadIdx.x < nrows) {
+            const float* g = s_g + threadIdx.x * pitch;
+            float acc = 0.0f;
+            for (uint32_t c = 0; c < row_len; ++c) acc += g[c] * g[c];
+            const float row_gsq = acc / (float)row_len;
+            const uint64_t r = row0 + threadIdx.x;
+            const float v_old = in_m2sh;
+            const float v = a.first ? row_gsq * a.f2 : v_old * a.beta2 + row_gsq * a.f2;
+            const bool is_dormant = masked && s_mask[threadIdx.x] == 2.0f;
+            // (a dormant row keeps its -0.0: the recurrence would turn it into +0.0 and un-mark it every step)
+            if (!is_dormant && (a.first || !same_bits(v, v_old))) m2_sh[r] = v;
+            s_v[threadIdx.x] = v;
+            if (masked && v != 0.0f) s_nz[threadIdx.x] = 1.0f;
+        }
+        __syncthreads();
+        {
+            const uint32_t vec_end = s_vec_end;
+            auto four = [&](float4 m14, float4 p4, uint32_t e) {
+                const uint64_t i = sh_base + e;
+                const float4 m1_old = m14, p_old = p4;
+                one_sh(m14.x, p4.x, e, m14.x, p4.x);
+                one_sh(m14.y, p4.y, e + 1, m14.y, p4.y);
+                one_sh(m14.z, p4.z, e + 2, m14.z, p4.z);
+                one_sh(m14.w, p4.w, e + 3, m14.w, p4.w);
+                if (masked) {
+                    if (m14.x != 0.0f) s_nz[row_of(e)] = 1.0f;
+                    if (m14.y != 0.0f) s_nz[row_of(e + 1u)] = 1.0f;
+                    if (m14.z != 0.0f) s_nz[row_of(e + 2u)] = 1.0f;
+                    if (m14.w != 0.0f) s_nz[row_of(e + 3u)] = 1.0f;
+                }
+                if (a.first || !same_bits4(m14, m1_old)) *reinterpret_cast<float4*>(&m1_sh[i]) = m14;
+                if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&sh[i]) = p4;
+            };
+            if (sh_early) {
+#pragma unroll
+                for (int k = 0; k < S_IT; ++k) {
+                    const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
+                    if (e >= vec_end) break;
+                    four(sm1[k], sp[k], e);
+                }
+            } else {
+                for (uint32_t e = threadIdx.x * 4u; e < vec_end; e += OPT_WG * 4u) {
+                    // (a float4 spans at most two rows for row_len >= 3: the first and the last component's)
+                    if (masked && s_mask[row_of(e)] == 2.0f && s_mask[row_of(e + 3u)] == 2.0f) continue;   // dormant rows: nothing to fetch
+                    four(*reinterpret_cast<const float4*>(&m1_sh[sh_base + e]), *reinterpret_cast<const float4*>(&sh[sh_base + e]), e);
+                }
+            }
+            for (uint32_t e = vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
+                const uint64_t i = sh_base + e;
+                float o1, op;
+                one_sh(m1_sh[i], sh[i], e, o1, op);
+                m1_sh[i] = o1;
+                sh[i] = op;
+                if (masked && o1 != 0.0f) s_nz[row_of(e)] = 1.0f;
+            }
         }
     }
     // ---- a splat whose moments are ALL zero after this step is dormant from now on: the mark is the sign of its m2_sh (== -0.0f)
@@ -496,6 +636,9 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, c
     const bool same_state = ctx->marks_m2_sh == st->m2_sh && ctx->marks_m1_t == st->m1_transforms && ctx->marks_n == n && ctx->marks_step + 1u == t;
     ctx->marks_m2_sh = st->m2_sh; ctx->marks_m1_t = st->m1_transforms; ctx->marks_n = n; ctx->marks_step = t;
     u.dormant_skip = (ctx->knob_no_dormant || !same_state) ? 0u : 1u;
+    // option update_sparse (read here, at every launch).  Its default is measured at SH degree 0 only — 256-row blocks of three SH
+    // words a row; longer rows keep the one-path kernel unless the option asks for the sparse path
+    u.sparse_max = ctx->knob_update_sparse >= 0 ? (uint32_t)ctx->knob_update_sparse : (u.sh_len == 3u ? UPDATE_SPARSE_DEFAULT : 0u);
     u.noise_on = noise ? 1u : 0u;
     u.noise_step = noise ? noise->step : 0u;
     u.noise_scale = noise ? noise->scale : 0.0f;
@@ -507,15 +650,18 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, c
     // SH degree 3: 0.368 ms @256, 0.300 @128, 0.290 @64, 0.327 @32; degree 0 is best at 256)
     uint32_t rows = u.sh_len <= 12 ? 256u : (u.sh_len <= 27 ? 128u : 64u);
     if (ctx->knob_update_rows) rows = ctx->knob_update_rows;  // developer knob BH_UPDATE_ROWS (read once at bh_create)
-    const size_t lds = ((size_t)rows * (u.sh_len + 1) + 3 * rows + (noise ? 3 * rows : 0)) * sizeof(float);
+    const size_t lds = ((size_t)rows * (u.sh_len + 1) + 4 * rows + 4 + (noise ? 3 * rows : 0)) * sizeof(float);   // s_g, s_v, s_mask, s_nz, s_list, s_cnt, s_noise
     const unsigned nb = (unsigned)(((uint64_t)n + rows - 1) / rows);
     const void* vec_ptrs[] = {st->transforms, st->m1_transforms, st->m2_transforms, g_t, st->sh_coeffs, st->m1_sh, g_sh};
     bool vec = true;
     for (const void* q : vec_ptrs) vec = vec && ((uintptr_t)q & 15u) == 0;
-#define BH_LAUNCH_UPDATE(V, R, S)                                                                                                       \
-    hipLaunchKernelGGL((train_update_kernel<V, R, S>), dim3(nb), dim3(OPT_WG), lds, ctx->stream, st->transforms, st->m1_transforms,      \
+#define BH_LAUNCH_UPDATE_(V, R, S, P)                                                                                                   \
+    hipLaunchKernelGGL((train_update_kernel<V, R, S, P>), dim3(nb), dim3(OPT_WG), lds, ctx->stream, st->transforms, st->m1_transforms,   \
                        st->m2_transforms, g_t, st->sh_coeffs, st->m1_sh, st->m2_sh, g_sh, st->raw_opacities, st->m1_opac, st->m2_opac, \
                        g_o, st->refine_weight_norm, st->vis_weight, st->max_screen_size, refine_weight, visible, screen_radius, u)
+    // (the up-front loads, S > 0, have fetched every row before anything is known about them: no sparse path there)
+#define BH_LAUNCH_UPDATE(V, R, S)                                                                                                       \
+    do { if (S == 0 && u.sparse_max != 0u) BH_LAUNCH_UPDATE_(V, R, 0, true); else BH_LAUNCH_UPDATE_(V, R, S, false); } while (0)
     // float4s of a block's SH rows per thread: 1 (<= 1024 floats), 4 (128 x 27), 5 (64 x 75); 0 = no up-front loads
     const uint32_t sh_f4 = (rows * u.sh_len / 4u + OPT_WG - 1) / OPT_WG;
     // (off by default: measured again with the store skipping and the fixed-trip loops in place, the sections' own loads win at
@@ -535,6 +681,7 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, c
         else BH_LAUNCH_UPDATE(true, 64, 5);
     }
 #undef BH_LAUNCH_UPDATE
+#undef BH_LAUNCH_UPDATE_
     BH_LAUNCH_CHECK(ctx, "train_update_kernel");
     return 0;
 }
