@@ -422,8 +422,6 @@ const Option kOptions[] = {
      [](bh_ctx* c, const char* v) { return parse_u32(v, 0, 1, &c->knob_loss_bands); }},
     {"update_rows", "0|64|128|256: splats per block of the update kernel (0 = default)",
      [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 256, &u) || !(u == 0 || u == 64 || u == 128 || u == 256)) return false; c->knob_update_rows = u; return true; }},
-    {"update_early", "0|1: the update kernel's blocks issue all their loads up front",
-     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_update_early); }},
     {"no_dormant", "0|1: the update kernel fetches and updates dormant splats like everyone else",
      [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_no_dormant); }},
     {"sort_kpt", "0|4|8|16: keys per thread of the generic radix sort (0 = default)",
@@ -1781,15 +1779,19 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     const bool noise_fused = noise_on && !batch->noise_samples && !st->min_scale;
     {
         ProfScope ps(ctx, "OptimizerStep");
-        float tab[10];
-        for (int i = 0; i < 3; ++i) tab[i] = (float)lr_mean;
-        for (int i = 3; i < 7; ++i) tab[i] = (float)cfg->lr_rotation;
-        for (int i = 7; i < 10; ++i) tab[i] = (float)cfg->lr_scale;
         const NoiseArgs na{batch->noise_seed, step, noise_scale, cfg->median_scene_scale};
+        UpdateCall uc;
+        uc.g_transforms = g_tr; uc.g_sh = g_sh; uc.g_opac = g_op;
+        uc.refine_weight = s_refine; uc.visible = s_visible; uc.screen_radius = s_radius;
+        uc.gscale = grad_scale; uc.vis_clamp = tile_mode;
+        for (int i = 0; i < 3; ++i) uc.tab_t[i] = (float)lr_mean;
+        for (int i = 3; i < 7; ++i) uc.tab_t[i] = (float)cfg->lr_rotation;
+        for (int i = 7; i < 10; ++i) uc.tab_t[i] = (float)cfg->lr_scale;
         // sh: DC at full lr, bands >= 1 scaled by 1/lr_coeffs_sh_scale
-        BH_TRY(launch_train_update(ctx, st, g_tr, g_sh, g_op, s_refine, s_visible, s_radius, grad_scale, tile_mode, tab,
-                                   (float)cfg->lr_coeffs_dc, 1.0f / cfg->lr_coeffs_sh_scale, (float)cfg->lr_opac, step, 0.9f, 0.999f, 1e-15f,
-                                   noise_fused ? &na : nullptr, masked_grads));
+        uc.lr_sh = (float)cfg->lr_coeffs_dc; uc.sh_rest_scale = 1.0f / cfg->lr_coeffs_sh_scale; uc.lr_opac = (float)cfg->lr_opac;
+        uc.t = step; uc.beta1 = 0.9f; uc.beta2 = 0.999f; uc.eps = 1e-15f;
+        uc.noise = noise_fused ? &na : nullptr; uc.masked_rows = masked_grads;
+        BH_TRY(launch_train_update(ctx, st, uc));
     }
     st->step_count = step;   // the update is queued: the step counts
     if (noise_on && !noise_fused) {

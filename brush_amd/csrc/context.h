@@ -483,7 +483,6 @@ struct bh_ctx {
     uint32_t knob_k5_exact_spw = 32;  // BH_K5_EXACT_SPW = 16 | 32 | 64 (A/B): splats per wave of K5 for complete lists
     bool knob_no_dormant = false;     // BH_UPDATE_NO_DORMANT (A/B, tests): the update kernel fetches and updates dormant splats like everyone else
     int knob_update_sparse = -1;      // option update_sparse: non-dormant rows up to which an update block takes its one-round-trip path (-1: the default of launch_train_update)
-    bool knob_update_early = false;   // BH_UPDATE_EARLY (A/B): the update kernel's blocks of SH degree >= 1 issue all their loads up front
     uint32_t knob_update_rows = 0;    // BH_UPDATE_ROWS: 64 | 128 | 256 splats per block of the update kernel
     uint32_t knob_sort_kpt = 0;       // BH_SORT_KPT: 4 | 8 | 16 keys per thread of the radix sort
     // the update kernel's dormant marks (sign of m2_sh, optim.hip) are trusted only on the state this ctx updated last step
@@ -730,10 +729,19 @@ int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* 
 // statistics + the three Adam updates of a train step in one launch (tab_t: per-column lr of `transforms`)
 // noise != NULL: the visibility-gated mean noise of train.rs:389-416, drawn on the device (device_rng.h), rides on the same launch
 struct NoiseArgs { uint64_t seed; uint32_t step; float scale, clamp_abs; };
-int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, const float* g_sh, const float* g_o,
-                        const float* refine_weight, const float* visible, const float* screen_radius, float gscale,
-                        bool vis_clamp, const float* tab_t, float lr_sh, float sh_rest_scale, float lr_opac, uint32_t t,
-                        float beta1, float beta2, float eps, const NoiseArgs* noise = nullptr, bool masked_rows = false);
+struct UpdateCall {
+    const float *g_transforms, *g_sh, *g_opac;               // gradients [n,10], [n,3C], [n]
+    const float *refine_weight, *visible, *screen_radius;   // the frame's per-splat outputs the statistics gather
+    float gscale;            // factor on every gradient (1/world for data parallel over cameras, else 1)
+    bool vis_clamp;          // `visible` arrives summed over strips: min(v, 1)
+    float tab_t[10];         // lr_mean x3, lr_rotation x4, lr_scale x3
+    float lr_sh, sh_rest_scale, lr_opac;   // SH: DC at lr_sh, bands >= 1 at lr_sh * sh_rest_scale
+    uint32_t t;              // 1-based step
+    float beta1, beta2, eps;
+    const NoiseArgs* noise;  // NULL: no noise on this launch
+    bool masked_rows;        // the gradient tensors were not zero-filled: row i counts iff the sign bit of refine_weight[i] is set
+};
+int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const UpdateCall& c);
 int launch_gather_stats(bh_ctx* ctx, float* refine_weight_norm, float* vis_weight, float* max_screen_size,
                         const float* refine_weight, const float* visible, const float* screen_radius, uint64_t n);
 // samples == NULL: drawn on the device from (seed, step, splat)

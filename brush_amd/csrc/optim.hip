@@ -23,12 +23,28 @@ BH_DEV bool same_bits4(const float4& a, const float4& b) {
     return ((f2u(a.x) ^ f2u(b.x)) | (f2u(a.y) ^ f2u(b.y)) | (f2u(a.z) ^ f2u(b.z)) | (f2u(a.w) ^ f2u(b.w))) == 0u;
 }
 
-BH_DEV void adam_elem(float& p, float g, float& m1, float v, const AdamArgs& a, float step) {
+// ---- The element arithmetic of AdamScaled (adam_scaled.rs:75-147), written once: the fused update kernel must leave the bits
+// the stand-alone kernels leave, and both the oracle's.
+// One step of the first moment (g: the gradient) / of the second (gsq: its square, or a row's mean of squares).  `old` comes by
+// address because the first step must not read it: it may be the tensor's element, which may hold anything then.  The betas
+// are read inside the arm that uses them (as every call site did when it spelled this out): the compiler keeps the branch.
+BH_DEV float moment1_step(const AdamArgs& a, const float* old, float g) { return a.first ? g * a.f1 : *old * a.beta1 + g * a.f1; }
+BH_DEV float moment2_step(const AdamArgs& a, const float* old, float gsq) { return a.first ? gsq * a.f2 : *old * a.beta2 + gsq * a.f2; }
+// the parameter after the step: m1 / v are the moments of THIS step, `step` the element's learning rate
+BH_DEV float adam_elem(float p, float m1, float v, const AdamArgs& a, float step) {
     const float m1c = m1 / a.bc1;
     const float m2c = v / a.bc2;
     const float upd = m1c / (__builtin_sqrtf(m2c) + a.eps);
-    p = p - upd * step;
+    return p - upd * step;
 }
+// a row's second moment (adam_scaled.rs:99-104,152-165) from its gradients g[0..row_len): the mean of their squares, summed
+// sequentially in index order (the oracle's order, so the result is bit-identical), then the recurrence
+BH_DEV float row_moment2(const float* g, uint32_t row_len, const float* v_old, const AdamArgs& a) {
+    float s = 0.0f;
+    for (uint32_t c = 0; c < row_len; ++c) s += g[c] * g[c];
+    return moment2_step(a, v_old, s / (float)row_len);
+}
+BH_DEV uint32_t row10(uint32_t e) { return (e * 52429u) >> 19; }   // e / 10, exact for e < 2560 (a block's transforms)
 
 // full second moment: one thread per element
 __global__ __launch_bounds__(OPT_WG) void adam_full_kernel(float* __restrict__ param, const float* __restrict__ grad,
@@ -37,24 +53,21 @@ __global__ __launch_bounds__(OPT_WG) void adam_full_kernel(float* __restrict__ p
     const uint64_t i = (uint64_t)blockIdx.x * OPT_WG + threadIdx.x;
     if (i >= count) return;
     const float g = grad[i];
-    float mm1 = a.first ? g * a.f1 : m1[i] * a.beta1 + g * a.f1;
-    const float gsq = g * g;
-    const float mm2 = a.first ? gsq * a.f2 : m2[i] * a.beta2 + gsq * a.f2;
+    const float mm1 = moment1_step(a, &m1[i], g);
+    const float mm2 = moment2_step(a, &m2[i], g * g);
     m1[i] = mm1;
     m2[i] = mm2;
     const float step = col_scale ? col_scale[i % row_len] * a.lr : a.lr;
-    float p = param[i];
-    adam_elem(p, g, mm1, mm2, a, step);
-    param[i] = p;
+    param[i] = adam_elem(param[i], mm1, mm2, a, step);
 }
 
 // second moment reduced to one scalar per row (adam_scaled.rs:99-104,152-165).
 // A block owns 256 consecutive rows: the gradient tile is staged through LDS with
 // coalesced loads (row pitch row_len+1: conflict-free for the per-row pass), thread r
-// forms row r's sum of squares sequentially in index order (the oracle's order, so the
-// result is bit-identical), and the update pass runs element-wise, coalesced, reading
-// the row's v back from LDS.  (One thread per row made every access a 4*row_len-byte
-// stride: 4.3 ms at 1 M splats / SH degree 3; this layout moves the same bytes at HBM speed.)
+// forms row r's second moment (row_moment2), and the update pass runs element-wise,
+// coalesced, reading the row's v back from LDS.  (One thread per row made every access a
+// 4*row_len-byte stride: 4.3 ms at 1 M splats / SH degree 3; this layout moves the same
+// bytes at HBM speed.)
 constexpr int ADAM_ROWS = 256;
 
 __global__ __launch_bounds__(OPT_WG) void adam_rowreduced_kernel(float* __restrict__ param, const float* __restrict__ grad,
@@ -76,12 +89,8 @@ __global__ __launch_bounds__(OPT_WG) void adam_rowreduced_kernel(float* __restri
     }
     __syncthreads();
     if (threadIdx.x < nrows) {
-        const float* g = s_g + threadIdx.x * pitch;
-        float s = 0.0f;
-        for (uint32_t c = 0; c < row_len; ++c) s += g[c] * g[c];
-        const float row_gsq = s / (float)row_len;
         const uint64_t r = row0 + threadIdx.x;
-        const float v = a.first ? row_gsq * a.f2 : m2[r] * a.beta2 + row_gsq * a.f2;
+        const float v = row_moment2(s_g + threadIdx.x * pitch, row_len, &m2[r], a);
         m2[r] = v;
         s_v[threadIdx.x] = v;
     }
@@ -91,12 +100,10 @@ __global__ __launch_bounds__(OPT_WG) void adam_rowreduced_kernel(float* __restri
         const uint32_t c = e - r * row_len;
         const uint64_t i = base + e;
         const float gi = s_g[r * pitch + c];
-        float mm1 = a.first ? gi * a.f1 : m1[i] * a.beta1 + gi * a.f1;
+        const float mm1 = moment1_step(a, &m1[i], gi);
         m1[i] = mm1;
         const float step = col_scale ? col_scale[c] * a.lr : a.lr;
-        float p = param[i];
-        adam_elem(p, gi, mm1, s_v[r], a, step);
-        param[i] = p;
+        param[i] = adam_elem(param[i], mm1, s_v[r], a, step);
     }
 }
 
@@ -113,10 +120,8 @@ static float powi_f32(float a, int b) {
     return recip ? 1.0f / r : r;
 }
 
-int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
-                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps) {
-    if (rows == 0 || row_len == 0) return 0;
-    if (t == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "adam: t is 1-based");
+// the constants of step t (1-based)
+static AdamArgs make_adam_args(float beta1, float beta2, float eps, float lr, uint32_t t) {
     AdamArgs a;
     a.beta1 = beta1; a.beta2 = beta2;
     a.f1 = 1.0f - beta1; a.f2 = 1.0f - beta2;
@@ -124,6 +129,14 @@ int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* 
     a.bc2 = 1.0f - powi_f32(beta2, (int)t);
     a.eps = eps; a.lr = lr;
     a.first = t == 1 ? 1u : 0u;
+    return a;
+}
+
+int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
+                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps) {
+    if (rows == 0 || row_len == 0) return 0;
+    if (t == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "adam: t is 1-based");
+    const AdamArgs a = make_adam_args(beta1, beta2, eps, lr, t);
     if (reduce_m2) {
         if (row_len > 255) return set_error(ctx, BH_ERR_UNSUPPORTED, "adam (reduced second moment): row_len must be <= 255");
         const uint64_t nb = (rows + ADAM_ROWS - 1) / ADAM_ROWS;
@@ -146,15 +159,15 @@ int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* 
 // ---------------------------------------------------------------------------
 // The train step's whole "after the backward" tail in ONE launch: RefineRecord::gather_stats
 // (stats.rs:40-50) + the three AdamScaled updates (train.rs:300-381) with the data-parallel
-// 1/K gradient scale folded in.  A block owns 256 consecutive splats, so every tensor it touches
-// is one contiguous run: transforms 2560 floats, SH 256*3C floats (staged through LDS for the
-// per-row second moment, as adam_rowreduced_kernel), opacity / statistics 256 floats.  The
+// 1/K gradient scale folded in.  A block owns ROWS (64, 128 or 256) consecutive splats, so every
+// tensor it touches is one contiguous run: transforms 10*ROWS floats, SH ROWS*3C floats (staged through
+// LDS for the per-row second moment, as adam_rowreduced_kernel), opacity / statistics ROWS floats.  The
 // element arithmetic is that of the stand-alone kernels above (bit-identical results); what
 // goes away is five launches, the lr-table upload and the separate gradient-scale pass.
 // ---------------------------------------------------------------------------
 struct UpdateArgs {
-    AdamArgs a;            // betas / bias corrections of step t (shared: the three params step together)
-    float lr_sh, lr_opac;  // transforms use lr 1.0 with the per-column table (train.rs:328-350)
+    AdamArgs a;            // betas / bias corrections of step t (shared: the three params step together; a.lr is not read)
+    float lr_sh, lr_opac;  // the transforms' rates are the per-column table tab_t (train.rs:328-350)
     float gscale;          // 1/world for data parallel over cameras, else 1
     uint32_t n, sh_len;    // splats, 3*C
     uint32_t vis_clamp;    // tile-partitioned frame: visible arrives summed over strips -> min(v, 1)
@@ -173,11 +186,12 @@ struct UpdateArgs {
 // 256 rows, so it is aligned whenever the tensor is; a float4 may straddle two rows, rows/columns are resolved per
 // component).  The element arithmetic is identical either way.
 // ROWS: splats per block (multiple of 4, <= OPT_WG) — fewer for long SH rows keeps more blocks resident per CU.
-// S_IT: float4s of the block's SH rows per thread when the loads are issued up front (0: every section fetches its own inputs).
 // SPARSE: the kernel has the second path for blocks with few non-dormant rows (launched when option update_sparse is not 0).
 constexpr uint32_t UPDATE_SPARSE_DEFAULT = 64;   // non-dormant rows of a 256-row block at SH degree 0 up to which the sparse path runs
+// s_mask[row] (only with u.masked): nobody wrote the row's gradient (it counts as 0) / K18 wrote it / the splat is dormant
+constexpr float ROW_UNWRITTEN = 0.0f, ROW_WRITTEN = 1.0f, ROW_DORMANT = 2.0f;
 
-template <bool VEC, int ROWS, int S_IT_, bool SPARSE>
+template <bool VEC, int ROWS, bool SPARSE>
 __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     float* __restrict__ transforms, float* __restrict__ m1_t, float* __restrict__ m2_t, const float* __restrict__ g_t,
     float* __restrict__ sh, float* __restrict__ m1_sh, float* __restrict__ m2_sh, const float* __restrict__ g_sh,
@@ -192,7 +206,7 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     const uint32_t row_len = u.sh_len, pitch = row_len + 1;
     float* s_g = s_dyn;                       // [rows][row_len + 1]
     float* s_v = s_dyn + (uint32_t)ROWS * pitch;      // [rows]
-    float* s_mask = s_v + (uint32_t)ROWS;             // [rows] 1 = the row's gradient was written, 2 = the splat is dormant (only with u.masked)
+    float* s_mask = s_v + (uint32_t)ROWS;             // [rows] ROW_* (only with u.masked)
     float* s_nz = s_mask + (uint32_t)ROWS;            // [rows] != 0: some moment of the splat is non-zero after this step (only with u.masked)
     uint32_t* s_list = reinterpret_cast<uint32_t*>(s_nz + (uint32_t)ROWS);   // [rows] the block's non-dormant rows, ascending (sparse path)
     uint32_t* s_cnt = s_list + (uint32_t)ROWS;        // [4] non-dormant rows of each wave
@@ -232,48 +246,24 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     const uint32_t sh_count = nrows * row_len;
     const uint64_t sh_base = row0 * row_len;
     // ---- the sections below are separated by barriers (marks and noise travel through LDS, the SH rows need their second moment
-    // first) and each fetches its own inputs: a block is a chain of dependent global round trips.  What shortened it (round 4):
-    // the per-splat section's eleven loads are unconditional and issued together, the transforms loop has a fixed trip count
-    // (unrolled: its loads leave together).  EARLY (S_IT_ > 0, BH_UPDATE_EARLY=1) goes further — every load of the block in front
-    // of the first barrier — and loses: see launch_train_update.
-    constexpr bool EARLY = S_IT_ > 0;
+    // first) and each fetches its own inputs: a block is a chain of dependent global round trips.  To keep it short the
+    // per-splat section's eleven loads are unconditional and issued together, and the transforms loop has a fixed trip count
+    // (unrolled: its loads leave together).
     constexpr int T_IT = (ROWS * 10 / 4 + OPT_WG - 1) / OPT_WG;          // float4s of the block's transforms per thread
-    constexpr int S_IT = S_IT_ > 0 ? S_IT_ : 1;                          // ... of its SH rows (launch_train_update's choice)
     const uint32_t t_count = nrows * 10u, t_vec_end = VEC ? (t_count & ~3u) : 0u;
     const uint64_t t_base = row0 * 10u;
     const uint32_t s_vec_end = VEC ? (sh_count & ~3u) : 0u;
-    const bool sh_early = EARLY && VEC && s_vec_end <= (uint32_t)S_IT * OPT_WG * 4u;   // block-uniform (false only under BH_UPDATE_ROWS)
-    float4 tg[T_IT], tm1[T_IT], tm2[T_IT], tp[T_IT], sm1[S_IT], sp[S_IT];
-    if (EARLY && VEC) {
-#pragma unroll
-        for (int k = 0; k < T_IT; ++k) {
-            const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
-            const uint64_t i = t_base + (e < t_vec_end ? e : 0u);   // (clamped: unconditional loads, masked at the use)
-            tg[k] = *reinterpret_cast<const float4*>(&g_t[i]);
-            tm1[k] = *reinterpret_cast<const float4*>(&m1_t[i]);
-            tm2[k] = *reinterpret_cast<const float4*>(&m2_t[i]);
-            tp[k] = *reinterpret_cast<const float4*>(&transforms[i]);
-        }
-#pragma unroll
-        for (int k = 0; k < S_IT; ++k) {
-            const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
-            const uint64_t i = sh_base + ((sh_early && e < s_vec_end) ? e : 0u);
-            sm1[k] = *reinterpret_cast<const float4*>(&m1_sh[i]);
-            sp[k] = *reinterpret_cast<const float4*>(&sh[i]);
-        }
-    }
     // this thread's splat (clamped for the threads behind the block's last row)
     const uint64_t si = row0 + (threadIdx.x < nrows ? threadIdx.x : 0u);
     float in_rw = refine_weight[si], in_rn = refine_weight_norm[si], in_vis = visible[si], in_vw = vis_weight[si];
     float in_ms = max_screen_size[si], in_sr = screen_radius[si], in_go = g_o[si], in_m1o = m1_o[si], in_m2o = m2_o[si], in_op = opac[si];
     float in_m2sh = m2_sh[si];
-    if (EARLY) asm volatile("" ::: "memory");   // (compiler-only: the loads above are issued HERE, not sunk to their uses behind the staging loop)
+    auto row_of = [&](uint32_t e) { return (uint32_t)(((float)e + 0.5f) * rcp_len); };   // e / row_len, exact for e < 2^16
     // ---- SH gradients -> LDS (coalesced), its loads queue behind the ones above
     auto stage_sh = [&](auto row_marked) {
-        const uint32_t vec_end = VEC ? (sh_count & ~3u) : 0u;
-        for (uint32_t e = threadIdx.x * 4u; e < vec_end; e += OPT_WG * 4u) {
+        for (uint32_t e = threadIdx.x * 4u; e < s_vec_end; e += OPT_WG * 4u) {
             // (a float4 spans at most two rows: the first and the last component's)
-            const uint32_t ra = (uint32_t)(((float)e + 0.5f) * rcp_len), rb = (uint32_t)(((float)(e + 3u) + 0.5f) * rcp_len);
+            const uint32_t ra = row_of(e), rb = row_of(e + 3u);
             const bool wa = !masked || row_marked(ra), wb = !masked || row_marked(rb);
             float4 g4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (wa || wb) g4 = *reinterpret_cast<const float4*>(&g_sh[sh_base + e]);
@@ -281,27 +271,16 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t ee = e + k;
-                const uint32_t r = (uint32_t)(((float)ee + 0.5f) * rcp_len);  // ee / row_len, exact for ee < 2^16
+                const uint32_t r = row_of(ee);
                 s_g[r * pitch + (ee - r * row_len)] = (r == ra ? wa : wb) ? gv[k] * u.gscale : 0.0f;
             }
         }
-        for (uint32_t e = vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
-            const uint32_t r = (uint32_t)(((float)e + 0.5f) * rcp_len);
+        for (uint32_t e = s_vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
+            const uint32_t r = row_of(e);
             s_g[r * pitch + (e - r * row_len)] = (!masked || row_marked(r)) ? g_sh[sh_base + e] * u.gscale : 0.0f;
         }
     };
     if (!sparse_on) stage_sh([&](uint32_t r) { return (mark_rows[r] >> 31) != 0u; });
-    // (one wait for all of it)
-    if (EARLY && VEC) {
-#pragma unroll
-        for (int k = 0; k < T_IT; ++k)
-            asm volatile("" : "+v"(tg[k].x), "+v"(tg[k].y), "+v"(tg[k].z), "+v"(tg[k].w), "+v"(tm1[k].x), "+v"(tm1[k].y), "+v"(tm1[k].z), "+v"(tm1[k].w),
-                              "+v"(tm2[k].x), "+v"(tm2[k].y), "+v"(tm2[k].z), "+v"(tm2[k].w), "+v"(tp[k].x), "+v"(tp[k].y), "+v"(tp[k].z), "+v"(tp[k].w));
-#pragma unroll
-        for (int k = 0; k < S_IT; ++k)
-            asm volatile("" : "+v"(sm1[k].x), "+v"(sm1[k].y), "+v"(sm1[k].z), "+v"(sm1[k].w), "+v"(sp[k].x), "+v"(sp[k].y), "+v"(sp[k].z), "+v"(sp[k].w));
-    }
-    if (EARLY) asm volatile("" : "+v"(in_rw), "+v"(in_rn), "+v"(in_vis), "+v"(in_vw), "+v"(in_ms), "+v"(in_sr), "+v"(in_go), "+v"(in_m1o), "+v"(in_m2o), "+v"(in_op), "+v"(in_m2sh));
     // ---- statistics + opacity: one splat per thread
     bool live = false;   // this thread's row exists and is not dormant
     if (threadIdx.x < nrows) {
@@ -311,7 +290,7 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
         // (the mark is checked against the two moments this thread has loaded anyway: a caller that restored or edited the opacity
         //  moments without rewriting m2_sh cannot make the step skip a splat whose moments are not zero)
         const bool dormant = dorm_ok && !written && f2u(in_m2sh) == 0x80000000u && in_vis == 0.0f && in_m1o == 0.0f && in_m2o == 0.0f;
-        if (masked) s_mask[threadIdx.x] = written ? 1.0f : (dormant ? 2.0f : 0.0f);
+        if (masked) s_mask[threadIdx.x] = written ? ROW_WRITTEN : (dormant ? ROW_DORMANT : ROW_UNWRITTEN);
         live = !dormant;
         // (masked: K18 stored the weight with the sign bit as the mark; an unmarked entry is the zero the forward left)
         {
@@ -326,12 +305,10 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
         }
         const float g = written ? in_go * u.gscale : 0.0f;
         const float m1_old = in_m1o, m2_old = in_m2o;
-        float mm1 = a.first ? g * a.f1 : m1_old * a.beta1 + g * a.f1;
-        const float gsq = g * g;
-        const float mm2 = a.first ? gsq * a.f2 : m2_old * a.beta2 + gsq * a.f2;
+        const float mm1 = moment1_step(a, &m1_old, g);
+        const float mm2 = moment2_step(a, &m2_old, g * g);
         const float p_old = in_op;
-        float p = p_old;
-        adam_elem(p, g, mm1, mm2, a, u.lr_opac);
+        const float p = adam_elem(p_old, mm1, mm2, a, u.lr_opac);
         // (stores of values that did not change are left out, here and below: see the note at the transforms)
         if (a.first || !same_bits(mm1, m1_old)) m1_o[i] = mm1;
         if (a.first || !same_bits(mm2, m2_old)) m2_o[i] = mm2;
@@ -362,31 +339,24 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     // ---- one element of the transforms (full second moment, per-column lr) / of the SH rows (gradient and the row's second
     // moment from LDS: s_g / s_v, e = row * row_len + column in THEIR indexing) — shared by both paths below
     auto one_t = [&](float g_raw, bool written, float m1v, float m2v, float pv, uint32_t e, float& o_m1, float& o_m2, float& o_p) {
-        const uint32_t r = (e * 52429u) >> 19;  // e / 10 (e < 2560)
+        const uint32_t r = row10(e);
         const uint32_t c = e - r * 10u;
         const float g = written ? g_raw * u.gscale : 0.0f;
-        const float mm1 = a.first ? g * a.f1 : m1v * a.beta1 + g * a.f1;
-        const float gsq = g * g;
-        const float mm2 = a.first ? gsq * a.f2 : m2v * a.beta2 + gsq * a.f2;
+        const float mm1 = moment1_step(a, &m1v, g);
+        const float mm2 = moment2_step(a, &m2v, g * g);
         o_m1 = mm1;
         o_m2 = mm2;
-        float p = pv;
-        float m1c = mm1;
-        adam_elem(p, g, m1c, mm2, a, u.tab_t[c] * 1.0f);
+        float p = adam_elem(pv, mm1, mm2, a, u.tab_t[c]);
         if (u.noise_on && c < 3u) p = p + s_noise[r * 3u + c];
         o_p = p;
     };
     auto one_sh = [&](float m1v, float pv, uint32_t e, float& o_m1, float& o_p) {
-        const uint32_t r = (uint32_t)(((float)e + 0.5f) * rcp_len);
+        const uint32_t r = row_of(e);
         const uint32_t c = e - r * row_len;
-        const float gi = s_g[r * pitch + c];
-        float mm1 = a.first ? gi * a.f1 : m1v * a.beta1 + gi * a.f1;
+        const float mm1 = moment1_step(a, &m1v, s_g[r * pitch + c]);
         o_m1 = mm1;
-        float p = pv;
-        adam_elem(p, gi, mm1, s_v[r], a, u.tab_sh[c] * u.lr_sh);
-        o_p = p;
+        o_p = adam_elem(pv, mm1, s_v[r], a, u.tab_sh[c] * u.lr_sh);
     };
-    auto row_of = [&](uint32_t e) { return (uint32_t)(((float)e + 0.5f) * rcp_len); };
     uint32_t n_live = 0;
     bool sparse = false;   // block-uniform
     if (sparse_on) {
@@ -422,12 +392,12 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
 #pragma unroll
             for (uint32_t k = 0; k < SP_T; ++k) {
                 const uint32_t x = threadIdx.x + k * (uint32_t)OPT_WG;
-                const uint32_t j = (x * 52429u) >> 19;   // x / 10
+                const uint32_t j = row10(x);
                 const bool ok = x < cn * 10u;
                 uint32_t r = 0u;
                 if (ok) r = s_list[j0 + j];
                 const uint32_t e = ok ? r * 10u + (x - j * 10u) : 0u;
-                tw[k] = ok && s_mask[r] == 1.0f;
+                tw[k] = ok && s_mask[r] == ROW_WRITTEN;
                 te[k] = ok ? e : ~0u;
                 const uint64_t i = t_base + e;
                 tg[k] = *(tw[k] ? &g_t[i] : &m1_t[i]);
@@ -443,7 +413,7 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
                 uint32_t r = 0u;
                 if (ok) r = s_list[j0 + j];
                 const uint32_t e = ok ? r * row_len + (x - j * row_len) : 0u;
-                sw[k] = ok && s_mask[r] == 1.0f;
+                sw[k] = ok && s_mask[r] == ROW_WRITTEN;
                 sr[k] = ok ? r : ~0u;
                 const uint64_t i = sh_base + e;
                 sg[k] = *(sw[k] ? &g_sh[i] : &m1_sh[i]);
@@ -464,21 +434,16 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
                 const uint64_t i = t_base + te[k];
                 float o1, o2, op;
                 one_t(tg[k], tw[k], tm1[k], tm2[k], tp[k], te[k], o1, o2, op);
-                if (o1 != 0.0f || o2 != 0.0f) s_nz[(te[k] * 52429u) >> 19] = 1.0f;
+                if (o1 != 0.0f || o2 != 0.0f) s_nz[row10(te[k])] = 1.0f;
                 if (!same_bits(o1, tm1[k])) m1_t[i] = o1;
                 if (!same_bits(o2, tm2[k])) m2_t[i] = o2;
                 if (!same_bits(op, tp[k])) transforms[i] = op;
             }
             __syncthreads();
-            // the rows' second moment: the row's own thread (it holds the old value), sums in index order
+            // the rows' second moment: the row's own thread (it holds the old value)
             if (live && my_pos >= j0 && my_pos - j0 < cn) {
-                const float* g = s_g + (my_pos - j0) * pitch;
-                float acc = 0.0f;
-                for (uint32_t c = 0; c < row_len; ++c) acc += g[c] * g[c];
-                const float row_gsq = acc / (float)row_len;
-                const float v_old = in_m2sh;
-                const float v = a.first ? row_gsq * a.f2 : v_old * a.beta2 + row_gsq * a.f2;
-                if (!same_bits(v, v_old)) m2_sh[row0 + threadIdx.x] = v;
+                const float v = row_moment2(s_g + (my_pos - j0) * pitch, row_len, &in_m2sh, a);
+                if (!same_bits(v, in_m2sh)) m2_sh[row0 + threadIdx.x] = v;
                 s_v[my_pos - j0] = v;
                 if (v != 0.0f) s_nz[threadIdx.x] = 1.0f;
             }
@@ -497,32 +462,29 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
             if (j0 + ch_rows < n_live) __syncthreads();   // the next chunk overwrites s_g / s_v
         }
     } else {
-        if (sparse_on) stage_sh([&](uint32_t r) { return s_mask[r] == 1.0f; });
+        if (sparse_on) stage_sh([&](uint32_t r) { return s_mask[r] == ROW_WRITTEN; });
         // ---- transforms: full second moment, per-column lr
         {
-            const uint32_t count = nrows * 10u;
-            const uint64_t base = row0 * 10u;
-            const uint32_t vec_end = t_vec_end;
 #pragma unroll
             for (int k = 0; k < T_IT; ++k) {
                 const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
-                if (e >= vec_end) break;
-                const uint64_t i = base + e;
-                const uint32_t ra = (e * 52429u) >> 19, rb = ((e + 3u) * 52429u) >> 19;   // the float4's first and last row
-                const float ka = masked ? s_mask[ra] : 1.0f, kb = masked ? s_mask[rb] : 1.0f;
-                if (ka == 2.0f && kb == 2.0f) continue;   // both rows dormant: nothing to fetch, nothing moves
-                const float4 g4 = EARLY ? tg[k] : *reinterpret_cast<const float4*>(&g_t[i]);
-                float4 m14 = EARLY ? tm1[k] : *reinterpret_cast<const float4*>(&m1_t[i]);
-                float4 m24 = EARLY ? tm2[k] : *reinterpret_cast<const float4*>(&m2_t[i]);
-                float4 p4 = EARLY ? tp[k] : *reinterpret_cast<const float4*>(&transforms[i]);
-                const bool wa = ka == 1.0f, wb = kb == 1.0f;
+                if (e >= t_vec_end) break;
+                const uint64_t i = t_base + e;
+                const uint32_t ra = row10(e), rb = row10(e + 3u);   // the float4's first and last row
+                const float ka = masked ? s_mask[ra] : ROW_WRITTEN, kb = masked ? s_mask[rb] : ROW_WRITTEN;
+                if (ka == ROW_DORMANT && kb == ROW_DORMANT) continue;   // both rows dormant: nothing to fetch, nothing moves
+                const float4 g4 = *reinterpret_cast<const float4*>(&g_t[i]);
+                float4 m14 = *reinterpret_cast<const float4*>(&m1_t[i]);
+                float4 m24 = *reinterpret_cast<const float4*>(&m2_t[i]);
+                float4 p4 = *reinterpret_cast<const float4*>(&transforms[i]);
+                const bool wa = ka == ROW_WRITTEN, wb = kb == ROW_WRITTEN;
                 const float4 m1_old = m14, m2_old = m24, p_old = p4;
                 one_t(g4.x, wa, m14.x, m24.x, p4.x, e, m14.x, m24.x, p4.x);
-                one_t(g4.y, (((e + 1u) * 52429u) >> 19) == ra ? wa : wb, m14.y, m24.y, p4.y, e + 1, m14.y, m24.y, p4.y);
-                one_t(g4.z, (((e + 2u) * 52429u) >> 19) == ra ? wa : wb, m14.z, m24.z, p4.z, e + 2, m14.z, m24.z, p4.z);
+                one_t(g4.y, row10(e + 1u) == ra ? wa : wb, m14.y, m24.y, p4.y, e + 1, m14.y, m24.y, p4.y);
+                one_t(g4.z, row10(e + 2u) == ra ? wa : wb, m14.z, m24.z, p4.z, e + 2, m14.z, m24.z, p4.z);
                 one_t(g4.w, wb, m14.w, m24.w, p4.w, e + 3, m14.w, m24.w, p4.w);
                 if (masked) {   // which rows still carry a non-zero moment (the dormant mark is set from this at the end)
-                    const uint32_t r1 = ((e + 1u) * 52429u) >> 19, r2 = ((e + 2u) * 52429u) >> 19;
+                    const uint32_t r1 = row10(e + 1u), r2 = row10(e + 2u);
                     if (m14.x != 0.0f || m24.x != 0.0f) s_nz[ra] = 1.0f;
                     if (m14.y != 0.0f || m24.y != 0.0f) s_nz[r1] = 1.0f;
                     if (m14.z != 0.0f || m24.z != 0.0f) s_nz[r2] = 1.0f;
@@ -536,36 +498,29 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
                 if (a.first || !same_bits4(m24, m2_old)) *reinterpret_cast<float4*>(&m2_t[i]) = m24;
                 if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&transforms[i]) = p4;
             }
-            for (uint32_t e = vec_end + threadIdx.x; e < count; e += OPT_WG) {
-                const uint64_t i = base + e;
+            for (uint32_t e = t_vec_end + threadIdx.x; e < t_count; e += OPT_WG) {
+                const uint64_t i = t_base + e;
                 float o1, o2, op;
-                const uint32_t r = (e * 52429u) >> 19;
-                one_t(g_t[i], !masked || s_mask[r] == 1.0f, m1_t[i], m2_t[i], transforms[i], e, o1, o2, op);
+                const uint32_t r = row10(e);
+                one_t(g_t[i], !masked || s_mask[r] == ROW_WRITTEN, m1_t[i], m2_t[i], transforms[i], e, o1, o2, op);
                 m1_t[i] = o1;
                 m2_t[i] = o2;
                 transforms[i] = op;
                 if (masked && (o1 != 0.0f || o2 != 0.0f)) s_nz[r] = 1.0f;
             }
         }
-        // ---- SH: per-row second moment (adam_scaled.rs:99-104,152-165), row sums in index order
+        // ---- SH: per-row second moment
         __syncthreads();
         if (threadIdx.x < nrows) {
-            const float* g = s_g + threadIdx.x * pitch;
-            float acc = 0.0f;
-            for (uint32_t c = 0; c < row_len; ++c) acc += g[c] * g[c];
-            const float row_gsq = acc / (float)row_len;
-            const uint64_t r = row0 + threadIdx.x;
-            const float v_old = in_m2sh;
-            const float v = a.first ? row_gsq * a.f2 : v_old * a.beta2 + row_gsq * a.f2;
-            const bool is_dormant = masked && s_mask[threadIdx.x] == 2.0f;
+            const float v = row_moment2(s_g + threadIdx.x * pitch, row_len, &in_m2sh, a);
+            const bool is_dormant = masked && s_mask[threadIdx.x] == ROW_DORMANT;
             // (a dormant row keeps its -0.0: the recurrence would turn it into +0.0 and un-mark it every step)
-            if (!is_dormant && (a.first || !same_bits(v, v_old))) m2_sh[r] = v;
+            if (!is_dormant && (a.first || !same_bits(v, in_m2sh))) m2_sh[row0 + threadIdx.x] = v;
             s_v[threadIdx.x] = v;
             if (masked && v != 0.0f) s_nz[threadIdx.x] = 1.0f;
         }
         __syncthreads();
         {
-            const uint32_t vec_end = s_vec_end;
             auto four = [&](float4 m14, float4 p4, uint32_t e) {
                 const uint64_t i = sh_base + e;
                 const float4 m1_old = m14, p_old = p4;
@@ -582,21 +537,12 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
                 if (a.first || !same_bits4(m14, m1_old)) *reinterpret_cast<float4*>(&m1_sh[i]) = m14;
                 if (!same_bits4(p4, p_old)) *reinterpret_cast<float4*>(&sh[i]) = p4;
             };
-            if (sh_early) {
-#pragma unroll
-                for (int k = 0; k < S_IT; ++k) {
-                    const uint32_t e = (threadIdx.x + (uint32_t)k * OPT_WG) * 4u;
-                    if (e >= vec_end) break;
-                    four(sm1[k], sp[k], e);
-                }
-            } else {
-                for (uint32_t e = threadIdx.x * 4u; e < vec_end; e += OPT_WG * 4u) {
-                    // (a float4 spans at most two rows for row_len >= 3: the first and the last component's)
-                    if (masked && s_mask[row_of(e)] == 2.0f && s_mask[row_of(e + 3u)] == 2.0f) continue;   // dormant rows: nothing to fetch
-                    four(*reinterpret_cast<const float4*>(&m1_sh[sh_base + e]), *reinterpret_cast<const float4*>(&sh[sh_base + e]), e);
-                }
+            for (uint32_t e = threadIdx.x * 4u; e < s_vec_end; e += OPT_WG * 4u) {
+                // (a float4 spans at most two rows for row_len >= 3: the first and the last component's)
+                if (masked && s_mask[row_of(e)] == ROW_DORMANT && s_mask[row_of(e + 3u)] == ROW_DORMANT) continue;   // dormant rows: nothing to fetch
+                four(*reinterpret_cast<const float4*>(&m1_sh[sh_base + e]), *reinterpret_cast<const float4*>(&sh[sh_base + e]), e);
             }
-            for (uint32_t e = vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
+            for (uint32_t e = s_vec_end + threadIdx.x; e < sh_count; e += OPT_WG) {
                 const uint64_t i = sh_base + e;
                 float o1, op;
                 one_sh(m1_sh[i], sh[i], e, o1, op);
@@ -609,27 +555,21 @@ __global__ __launch_bounds__(OPT_WG) void train_update_kernel(
     // ---- a splat whose moments are ALL zero after this step is dormant from now on: the mark is the sign of its m2_sh (== -0.0f)
     if (masked) {   // block-uniform
         __syncthreads();
-        if (threadIdx.x < nrows && s_mask[threadIdx.x] != 2.0f && s_nz[threadIdx.x] == 0.0f) m2_sh[row0 + threadIdx.x] = -0.0f;
+        if (threadIdx.x < nrows && s_mask[threadIdx.x] != ROW_DORMANT && s_nz[threadIdx.x] == 0.0f) m2_sh[row0 + threadIdx.x] = -0.0f;
     }
 }
 
-int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, const float* g_sh, const float* g_o,
-                        const float* refine_weight, const float* visible, const float* screen_radius, float gscale,
-                        bool vis_clamp, const float* tab_t, float lr_sh, float sh_rest_scale, float lr_opac, uint32_t t,
-                        float beta1, float beta2, float eps, const NoiseArgs* noise, bool masked_rows) {
-    const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
+int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const UpdateCall& c) {
+    const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1), t = c.t;
     if (n == 0) return 0;
     if (t == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "adam: t is 1-based");
+    const float *g_t = c.g_transforms, *g_sh = c.g_sh, *g_o = c.g_opac;
+    const NoiseArgs* noise = c.noise;
     UpdateArgs u;
-    u.a.beta1 = beta1; u.a.beta2 = beta2;
-    u.a.f1 = 1.0f - beta1; u.a.f2 = 1.0f - beta2;
-    u.a.bc1 = 1.0f - powi_f32(beta1, (int)t);
-    u.a.bc2 = 1.0f - powi_f32(beta2, (int)t);
-    u.a.eps = eps; u.a.lr = 1.0f;
-    u.a.first = t == 1 ? 1u : 0u;
-    u.lr_sh = lr_sh; u.lr_opac = lr_opac; u.gscale = gscale;
-    u.n = n; u.sh_len = 3 * C; u.vis_clamp = vis_clamp ? 1u : 0u;
-    u.masked = masked_rows ? 1u : 0u;
+    u.a = make_adam_args(c.beta1, c.beta2, c.eps, 1.0f, t);   // (the kernel reads no a.lr)
+    u.lr_sh = c.lr_sh; u.lr_opac = c.lr_opac; u.gscale = c.gscale;
+    u.n = n; u.sh_len = 3 * C; u.vis_clamp = c.vis_clamp ? 1u : 0u;
+    u.masked = c.masked_rows ? 1u : 0u;
     // Marks are trusted only on a state this context updated at the previous step (same tensors, consecutive step count): a state
     // seen for the first time, re-bound to other tensors (refine, a checkpoint restore) or with a step counter that jumped is
     // processed in full once — that step re-derives every mark from the moments it finds.
@@ -644,8 +584,8 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, c
     u.noise_scale = noise ? noise->scale : 0.0f;
     u.noise_clamp = noise ? noise->clamp_abs : 0.0f;
     u.noise_seed = noise ? noise->seed : 0ull;
-    for (int i = 0; i < 10; ++i) u.tab_t[i] = tab_t[i];
-    for (uint32_t k = 0; k < 75; ++k) u.tab_sh[k] = (k / 3 == 0) ? 1.0f : sh_rest_scale;
+    for (int i = 0; i < 10; ++i) u.tab_t[i] = c.tab_t[i];
+    for (uint32_t k = 0; k < 75; ++k) u.tab_sh[k] = (k / 3 == 0) ? 1.0f : c.sh_rest_scale;
     // splats per block: ~13 KB of LDS-staged SH gradients keeps >= 8 blocks resident per CU (measured at 1 M splats:
     // SH degree 3: 0.368 ms @256, 0.300 @128, 0.290 @64, 0.327 @32; degree 0 is best at 256)
     uint32_t rows = u.sh_len <= 12 ? 256u : (u.sh_len <= 27 ? 128u : 64u);
@@ -655,33 +595,24 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const float* g_t, c
     const void* vec_ptrs[] = {st->transforms, st->m1_transforms, st->m2_transforms, g_t, st->sh_coeffs, st->m1_sh, g_sh};
     bool vec = true;
     for (const void* q : vec_ptrs) vec = vec && ((uintptr_t)q & 15u) == 0;
-#define BH_LAUNCH_UPDATE_(V, R, S, P)                                                                                                   \
-    hipLaunchKernelGGL((train_update_kernel<V, R, S, P>), dim3(nb), dim3(OPT_WG), lds, ctx->stream, st->transforms, st->m1_transforms,   \
+#define BH_LAUNCH_UPDATE(V, R, P)                                                                                                       \
+    hipLaunchKernelGGL((train_update_kernel<V, R, P>), dim3(nb), dim3(OPT_WG), lds, ctx->stream, st->transforms, st->m1_transforms,    \
                        st->m2_transforms, g_t, st->sh_coeffs, st->m1_sh, st->m2_sh, g_sh, st->raw_opacities, st->m1_opac, st->m2_opac, \
-                       g_o, st->refine_weight_norm, st->vis_weight, st->max_screen_size, refine_weight, visible, screen_radius, u)
-    // (the up-front loads, S > 0, have fetched every row before anything is known about them: no sparse path there)
-#define BH_LAUNCH_UPDATE(V, R, S)                                                                                                       \
-    do { if (S == 0 && u.sparse_max != 0u) BH_LAUNCH_UPDATE_(V, R, 0, true); else BH_LAUNCH_UPDATE_(V, R, S, false); } while (0)
-    // float4s of a block's SH rows per thread: 1 (<= 1024 floats), 4 (128 x 27), 5 (64 x 75); 0 = no up-front loads
-    const uint32_t sh_f4 = (rows * u.sh_len / 4u + OPT_WG - 1) / OPT_WG;
-    // (off by default: measured again with the store skipping and the fixed-trip loops in place, the sections' own loads win at
-    //  every degree — degree 3: 158 vs 209 us on the bench scene, 194 vs 233 us with every store forced — the 57 instead of 99
-    //  VGPRs are worth more than the shorter chain; BH_UPDATE_EARLY=1 selects the up-front loads)
-    const bool early = vec && rows != 256u && ctx->knob_update_early;
-    if (rows == 256u) { if (vec) BH_LAUNCH_UPDATE(true, 256, 0); else BH_LAUNCH_UPDATE(false, 256, 0); }
-    else if (rows == 128u) {
-        if (!vec) BH_LAUNCH_UPDATE(false, 128, 0);
-        else if (!early) BH_LAUNCH_UPDATE(true, 128, 0);
-        else if (sh_f4 <= 1u) BH_LAUNCH_UPDATE(true, 128, 1);
-        else BH_LAUNCH_UPDATE(true, 128, 4);
-    } else {
-        if (!vec) BH_LAUNCH_UPDATE(false, 64, 0);
-        else if (!early) BH_LAUNCH_UPDATE(true, 64, 0);
-        else if (sh_f4 <= 1u) BH_LAUNCH_UPDATE(true, 64, 1);
-        else BH_LAUNCH_UPDATE(true, 64, 5);
+                       g_o, st->refine_weight_norm, st->vis_weight, st->max_screen_size, c.refine_weight, c.visible, c.screen_radius, u)
+#define BH_LAUNCH_UPDATE_ROWS(R)                                                                        \
+    case R:                                                                                             \
+        if (vec) { if (sparse) BH_LAUNCH_UPDATE(true, R, true); else BH_LAUNCH_UPDATE(true, R, false); }    \
+        else { if (sparse) BH_LAUNCH_UPDATE(false, R, true); else BH_LAUNCH_UPDATE(false, R, false); }      \
+        break
+    const bool sparse = u.sparse_max != 0u;   // 0: the instantiations without the second path
+    switch (rows) {
+        BH_LAUNCH_UPDATE_ROWS(64);
+        BH_LAUNCH_UPDATE_ROWS(128);
+        BH_LAUNCH_UPDATE_ROWS(256);
+        default: return set_error(ctx, BH_ERR_INVALID_ARG, "update_rows must be 64, 128 or 256");
     }
+#undef BH_LAUNCH_UPDATE_ROWS
 #undef BH_LAUNCH_UPDATE
-#undef BH_LAUNCH_UPDATE_
     BH_LAUNCH_CHECK(ctx, "train_update_kernel");
     return 0;
 }

@@ -30,7 +30,7 @@ _LEGACY_ENV_OPTIONS = (   # (environment variable, option key, value or None = t
     ("BH_TRAIN_ZERO_GRADS", "zero_grads", "1"), ("BH_CUT_MIN_PAIRS", "cut_min_pairs", None), ("BH_CUT_SORT_ALL", "cut_sort_all", "1"),
     ("BH_NO_VIEW_HASH", "no_view_hash", "1"), ("BH_CUT_MARGIN_FIXED", "cut_margin_fixed", "1"), ("BH_CUT_CTRL", "cut_ctrl", None),
     ("BH_READBACK_COPY", "readback_copy", "1"), ("BH_EVENT_WAITS", "event_waits", "1"), ("BH_K16_ORDER", "k16_order", None),
-    ("BH_CUT_MARGIN_PCT", "cut_margin_pct", None), ("BH_UPDATE_EARLY", "update_early", "1"), ("BH_UPDATE_NO_DORMANT", "no_dormant", "1"),
+    ("BH_CUT_MARGIN_PCT", "cut_margin_pct", None), ("BH_UPDATE_NO_DORMANT", "no_dormant", "1"),
     ("BH_K5_EXACT_SPW", "k5_exact_spw", None), ("BH_TILE_SORT_LSD", "tile_sort", "lsd"), ("BH_LOSS_BANDS", "loss_bands", None),
     ("BH_UPDATE_ROWS", "update_rows", None), ("BH_SORT_KPT", "sort_kpt", None),
 )

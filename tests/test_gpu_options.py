@@ -28,7 +28,7 @@ def test_set_option_validates_keys_and_values(dev):
     ctx.set_option("cut_min_pairs", 0)
     ctx.set_option("tile_sort", "lsd")
     ctx.set_option("cut_ctrl", "1.5:0.998:0.5:0.3333")
-    for k, v in (("no_such_key", "1"), ("k16_order", "3"), ("tile_sort", "fast"), ("update_rows", "100"), ("event_waits", "yes"),
+    for k, v in (("no_such_key", "1"), ("update_early", "1"), ("k16_order", "3"), ("tile_sort", "fast"), ("update_rows", "100"), ("event_waits", "yes"),
                  ("cut_ctrl", "0.5:2:0:9"), ("auto_exact_share", "1.5"), ("cut_min_pairs", "")):
         with pytest.raises(ba.BrushHipError):
             ctx.set_option(k, v)

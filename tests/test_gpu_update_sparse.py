@@ -34,10 +34,13 @@ def _scene(n, sh_degree):
                             tan_half_fov=(math.tan(math.radians(50)), math.tan(math.radians(50))))
 
 
-def _train(ba, dev, sc, cams, option, steps=9, after_first=None):
-    """`steps` default stochastic steps over `cams`; option: None (default), a value of update_sparse, or a function step -> value."""
+def _train(ba, dev, sc, cams, option, steps=9, after_first=None, options=None):
+    """`steps` default stochastic steps over `cams`; option: None (default), a value of update_sparse, or a function step -> value;
+    options: further option keys, set once."""
     ctx = ba.Context(dev)
     try:
+        for k, v in (options or {}).items():
+            ctx.set_option(k, v)
         gt = torch.from_numpy(synth.synthetic_gt_packed(W, H).view(np.int32)).to(dev)
         spl = ba.Splats(sc["transforms"].copy(), sc["sh"].copy(), sc["raw_opac"].copy(), device=dev)
         tr = ba.SplatTrainer(ba.TrainConfig(), median_scene_scale=3.0, ctx=ctx, seed=77)
@@ -120,6 +123,70 @@ def test_paths_alternate(dev, n, sh_degree):
     _assert_same_bits(a, _dense(ba, dev, n, sh_degree), "alternating")
     b = _train(ba, dev, _scene(n, sh_degree), _views(W, H, 3), lambda s: 0 if s % 2 else 256)
     _assert_same_bits(b, _dense(ba, dev, n, sh_degree), "alternating, sparse first")
+
+
+@pytest.mark.parametrize("n", [65, 129, 300])   # one full block of 64 / of 128 rows plus one row; a ragged tail behind several blocks
+@pytest.mark.parametrize("sh_degree", [0, 1])
+@pytest.mark.parametrize("rows", [64, 128])
+def test_block_sizes_off_their_default(dev, rows, sh_degree, n):
+    """Option update_rows: the 64- and 128-row instantiations, which by default run only at SH degree >= 2, on short SH rows.  Under
+    the same block size the sparse path, forced and at its default, leaves the bits of the dense path."""
+    import brush_amd as ba
+    sc, cams = _scene(n, sh_degree), _views(W, H, 3)
+    ref = _train(ba, dev, sc, cams, 0, options={"update_rows": rows})
+    _assert_same_bits(_train(ba, dev, sc, cams, 256, options={"update_rows": rows}), ref, "update_sparse=256")
+    _assert_same_bits(_train(ba, dev, sc, cams, None, options={"update_rows": rows}), ref, "default")
+    if n == 300:   # some splats were found dormant (the runs skipped them: all three carry the same marks), others trained
+        marks = ref["m2_sh"].view(torch.int32) == MARK
+        assert 0 < int(marks.sum()) < n, int(marks.sum())
+        assert bool((ref["m2_t"].abs().sum(1) > 0).any())
+
+
+def _misalign_m1_t(state):
+    """Rebinds the transforms' first moment to a copy whose data pointer is 4 mod 16: the launcher then takes the scalar
+    (VEC = false) instantiations for every tensor.  (The step after this one finds a state it has not seen and processes every
+    splat; the marks count again from the step behind it.)"""
+    old = state["m1_t"]
+    buf = torch.empty(old.numel() + 1, dtype=old.dtype, device=old.device)
+    new = buf[1:].view(old.shape)
+    new.copy_(old)
+    assert new.data_ptr() % 16 == 4
+    state["m1_t"] = new
+
+
+_SCALAR_CASES = (("update_sparse=256", 256, None), ("update_sparse=0", 0, None), ("no_dormant=1", None, {"no_dormant": 1}))
+_LAYOUTS = {}
+
+
+def _layout_runs(ba, dev, sh_degree, misaligned):
+    """The three runs of _SCALAR_CASES on one layout of the state, computed once."""
+    key = (sh_degree, misaligned)
+    if key not in _LAYOUTS:
+        sc, cams = _scene(300, sh_degree), _views(W, H, 3)
+        _LAYOUTS[key] = {what: _train(ba, dev, sc, cams, sparse, after_first=_misalign_m1_t if misaligned else None, options=opts)
+                         for what, sparse, opts in _SCALAR_CASES}
+    return _LAYOUTS[key]
+
+
+@pytest.mark.parametrize("sh_degree", [0, 2])
+@pytest.mark.parametrize("misaligned", [True, False])
+def test_scalar_instantiations(dev, misaligned, sh_degree):
+    """A state tensor off a 16-byte boundary selects the kernel's scalar instantiations (no other test reaches them): there, as on
+    the aligned layout, the sparse path, the dense path and the run that skips no dormant splat leave the same bits."""
+    import brush_amd as ba
+    runs = _layout_runs(ba, dev, sh_degree, misaligned)
+    for what, _, _ in _SCALAR_CASES[1:]:
+        _assert_same_bits(runs[what], runs[_SCALAR_CASES[0][0]], what + " against " + _SCALAR_CASES[0][0])
+
+
+@pytest.mark.parametrize("sh_degree", [0, 2])
+def test_scalar_layout_leaves_the_aligned_layouts_bits(dev, sh_degree):
+    """The scalar instantiations against the vector ones, run for run (the element arithmetic is the same; what differs is which
+    stores are left out)."""
+    import brush_amd as ba
+    a, b = _layout_runs(ba, dev, sh_degree, True), _layout_runs(ba, dev, sh_degree, False)
+    for what, _, _ in _SCALAR_CASES:
+        _assert_same_bits(a[what], b[what], what + ": misaligned against aligned")
 
 
 def _run_masked(ba, dev, zero_fill, sc, cams, gt, steps, poison, sparse):
