@@ -38,6 +38,9 @@ Names and argument meaning follow the reference (paths under
     splat_normals / render_normal / RenderNode.normal / RenderNode.backward(v_normal=) / depth_to_normal / depth_to_normal_backward
                                          rendered and depth-derived normal maps with their gradients (not in the reference; the maps
                                          2DGS / gsplat compare for normal consistency; include/brush_hip_normal.h)
+    normal_consistency_value_and_grad / TrainConfig.normal_loss_weight   the normal-consistency regulariser those maps exist for: a
+                                         fused loss with both gradients and a term in the step (not in the reference; 2DGS's
+                                         normal loss; include/brush_hip_normal_loss.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -51,6 +54,6 @@ from .host import (  # noqa: F401
     knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
     Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
     PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
-    splat_normals, render_normal, depth_to_normal, depth_to_normal_backward,
+    splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -294,6 +294,17 @@ NORMAL_SYMBOLS = {
     "bh_depth_to_normal_backward": (C.c_int, [C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
 }
 
+# every symbol include/brush_hip_normal_loss.h declares (normal consistency: the fused operator and the step's normal term)
+class BhNormalTermConfig(C.Structure):
+    _fields_ = [("weight", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+NORMAL_LOSS_SYMBOLS = {
+    "bh_normal_consistency_value_and_grad": (C.c_int, [C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bh_train_set_normal": (C.c_int, [C.c_void_p, C.POINTER(BhNormalTermConfig)]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -333,7 +344,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS))
     return _lib
 
 
@@ -342,6 +353,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

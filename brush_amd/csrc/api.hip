@@ -1117,7 +1117,7 @@ namespace bh {
 // floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
 // depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
 // v_viewmat (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined.
-// normal (normal.hip): a normal term's raw sums join the accumulator like depth's; only with dense, zero-filled outputs.
+// normal (normal.hip): a normal term's raw sums join the accumulator like depth's; its Vn lands behind depth's v_z, on row marks too.
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
                   size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat, const NormalTerm* normal) {
@@ -1138,7 +1138,6 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         row_marks = span == GradClears::ROW_MARKS;
         // (ROW_MARKS: the single-GPU train step reads only the rows K18 writes and marks — its forward cleared the marks)
         if (row_marks && !one_span) return set_error(ctx, BH_ERR_STATE, "internal: row-marked gradients without the train step's gradient span");
-        if (row_marks && normal) return set_error(ctx, BH_ERR_STATE, "internal: a normal term with row-marked gradients");
         const bool span_done = one_span && span != GradClears::NONE;
         if (one_span && (span_floats & 3u) == 0 && (reinterpret_cast<uintptr_t>(v_transforms) & 15u) == 0) {
             // v_combined and the exchange buffer's gradient span cleared by ONE launch (hipMemsetAsync spends two or
@@ -1179,7 +1178,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
         if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
-        if (normal) BH_TRY(launch_normal_vn_scatter(ctx, fs, transforms, v_transforms));
+        if (normal) BH_TRY(launch_normal_vn_scatter(ctx, fs, transforms, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
     }
     if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
         ProfScope ps(ctx, "PoseGrad");
@@ -1504,6 +1503,17 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (ctx->pose_grad)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a depth target and a pose-gradient buffer cannot be attached together (the pose pass does not carry the depth term's gradient)");
     }
+    // a normal-consistency term (brush_hip_normal_loss.h): refused before anything is queued; weight <= 0 is no term at all
+    const bool normal_wanted = ctx->normal_attached && ctx->normal_term.weight > 0.0f;
+    if (normal_wanted) {
+        if (batch->camera.model != BH_CAMERA_PINHOLE)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs a pinhole camera (the normals of a depth map are defined for it alone)");
+        const ViewUniforms nu = make_uniforms(batch->camera);
+        if (batch->image_hook || nu.tile_y0 != 0u || nu.tile_y1 != nu.tile_bh)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs the whole frame on this rank (no tile-row partition)");
+        if (ctx->pose_grad)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a normal term and a pose-gradient buffer cannot be attached together (the pose pass does not carry the normal term's gradient)");
+    }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
     const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
@@ -1666,17 +1676,34 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // ---- depth term (brush_hip_depth_loss.h): the frame is final here — a second attempt with complete lists has replaced it, if
     // there was one — so the expected depth is that of the state the backward replays.  E and v_depth live in a slot of their own
     // until the backward (SLOT_DEPTH is the depth backward's scratch and may move).  loss += the term's, in f32, behind LPIPS.
+    // ---- normal term (brush_hip_normal_loss.h): on the same final frame, with the same expected-depth map (rendered once).  N and
+    // v_normal live in a slot of their own too (SLOT_NORMAL is the normal backward's scratch).  The fused operator adds its v_depth to
+    // the depth loss's, or writes it where there is none; loss += the term's, in f32, behind the depth term's.
     DepthTerm depth_term;
-    const bool depth_on = depth_target != nullptr && ctx->latest.out.num_intersections > 0 && n > 0;   // (an empty frame has no valid pixel)
-    if (depth_on) {
+    NormalTerm normal_term;
+    const bool frame_listed = ctx->latest.out.num_intersections > 0 && n > 0;   // (an empty frame has no valid pixel)
+    const bool depth_on = depth_target != nullptr && frame_listed;
+    const bool normal_on = normal_wanted && frame_listed;
+    if (depth_on || normal_on) {
         ProfScope ps(ctx, "DepthTerm");
         auto* e_map = (float*)ensure(ctx, SLOT_DEPTH_TERM, (hw * 2 + 4) * 4);
         if (!e_map) return BH_ERR_OOM;
         float* v_depth = e_map + hw;
         BH_TRY(launch_depth_forward(ctx, ctx->latest, BH_DEPTH_EXPECTED, e_map));
-        BH_TRY(launch_depth_loss(ctx, e_map, *depth_target, v_depth + hw, v_depth, loss_dev, loss_host));
+        if (depth_on) BH_TRY(launch_depth_loss(ctx, e_map, *depth_target, v_depth + hw, v_depth, loss_dev, loss_host));
         depth_term.v_depth = v_depth;
         depth_term.mode = BH_DEPTH_EXPECTED;
+        if (normal_on) {
+            ProfScope pn(ctx, "NormalTerm");
+            auto* n_map = (float*)ensure(ctx, SLOT_NORMAL_TERM, (hw * 6 + 4) * 4);
+            if (!n_map) return BH_ERR_OOM;
+            float* v_normal = n_map + hw * 3;
+            BH_TRY(launch_normal_map(ctx, ctx->latest, r_transforms, BH_NORMAL_ACCUMULATED, n_map));
+            BH_TRY(launch_normal_loss(ctx, batch->camera, n_map, e_map, ctx->latest.out.out_img, H, W, ctx->normal_term.weight, /*accumulate_v_depth=*/depth_on,
+                                      v_normal + hw * 3, v_normal, v_depth, loss_dev, loss_host));
+            normal_term.v_normal = v_normal;
+            normal_term.mode = BH_NORMAL_ACCUMULATED;
+        }
     }
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
@@ -1733,7 +1760,8 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // (padding included): one zero-fill, if the forward's K1 did not clear it.
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
     BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
-                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, depth_on ? &depth_term : nullptr, ctx->pose_grad));
+                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, (depth_on || normal_on) ? &depth_term : nullptr, ctx->pose_grad,
+                         normal_on ? &normal_term : nullptr));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

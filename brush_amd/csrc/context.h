@@ -14,6 +14,7 @@
 #include "../../include/brush_hip_image.h"
 #include "../../include/brush_hip_exposure.h"
 #include "../../include/brush_hip_depth_loss.h"
+#include "../../include/brush_hip_normal_loss.h"
 #include "device_math.h"
 
 namespace bh {
@@ -83,8 +84,10 @@ enum Slot : int {
     SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
     SLOT_EXPOSED,            // bh_train_step with an exposure table: [H,W,4] the exposed frame the loss reads (out_img stays as rendered)
     SLOT_DEPTH_LOSS,         // bh_depth_loss_value_and_grad / bh_eval_depth_metrics: one f64 row of 4 per block (depth_loss.hip)
-    SLOT_DEPTH_TERM,         // bh_train_step with a depth target: expected depth [H,W] | v_depth [H,W] | the term's loss pair (4 floats)
+    SLOT_DEPTH_TERM,         // bh_train_step with a depth target or a normal term: expected depth [H,W] | v_depth [H,W] | the depth term's loss pair (4 floats)
     SLOT_NORMAL,             // bh_render_normal / bh_render_backward_normal_saved: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip)
+    SLOT_NORMAL_LOSS,        // bh_normal_consistency_value_and_grad: one f64 row of 4 per block, 2 used (normal_loss.hip)
+    SLOT_NORMAL_TERM,        // bh_train_step with a normal term: accumulated normals [H,W,3] | v_normal [H,W,3] | the term's loss pair (4 floats)
     SLOT_COUNT
 };
 
@@ -401,6 +404,8 @@ struct bh_ctx {
     float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
     bool depth_attached = false;      // bh_train_set_depth: the step adds the depth term of depth_target (brush_hip_depth_loss.h); weight <= 0 = off
     BhDepthTarget depth_target{};
+    bool normal_attached = false;     // bh_train_set_normal: the step adds the normal-consistency term (brush_hip_normal_loss.h); weight <= 0 = off
+    BhNormalTermConfig normal_term{};
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
@@ -514,13 +519,22 @@ int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& 
 int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows = false, float* v_sh_coeffs = nullptr,
                             float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
 int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, float* out_depth);
-// normal.hip: the normal term between K17 and K18 (raw sums into v_combined, Vn into SLOT_NORMAL), and Vn -> v_quat behind a K18
-// that wrote dense, zero-filled outputs (never the row-marked train-step path)
+// normal.hip: the normal term between K17 and K18 (raw sums into v_combined, Vn into SLOT_NORMAL), and Vn -> v_quat behind K18 and
+// depth's scatter; mark_rows as launch_depth_vz_scatter's
 int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined);
-int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms);
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms, bool mark_rows = false,
+                             float* v_sh_coeffs = nullptr, float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
+// ... and the normal map `mode` of a saved forward with something listed (bh_render_normal, the train step's normal term)
+int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transforms, uint32_t mode, float* out);
+// normal_loss.hip: the fused normal-consistency operator on the ctx stream (arguments already checked; weight > 0).  accum != NULL (train
+// step): loss[0] is added to accum[0] in f32 and the total copied to accum_host
+int launch_normal_loss(bh_ctx* ctx, const BhCamera& cam, const float* normal, const float* depth, const float* image, uint32_t h, uint32_t w, float weight,
+                       bool accumulate_v_depth, float* loss, float* v_normal, float* v_depth, float* accum, float* accum_host);
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);
+// ... and its final block alone, for normal_loss.hip: loss = { f32(c * column 0 of the f64 rows), column 1 }, accum as above
+int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, float c, float* loss, float* accum, float* accum_host);
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
                      const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);

@@ -6,16 +6,12 @@
 #include <cmath>
 
 #include "context.h"
+#include "device_f64_sum.h"
 
 namespace bh {
 
 namespace {
 
-constexpr int DL_WG = 256;
-constexpr int DL_WAVES = DL_WG / 64;
-// the grid depends on H W alone and is capped at 4 blocks per CU: a 1080p frame is two passes of the capped grid
-constexpr uint32_t DL_MAX_BLOCKS = 1024;
-constexpr int DL_ROW = 4;            // f64 words per block row (the loss uses 2, the metrics 4)
 constexpr int DL_FINAL_WG = 256;     // the final block: lane i adds rows i, i + 256, ... in index order, then the lanes in lane order
 
 struct DepthLossArgs {
@@ -24,30 +20,6 @@ struct DepthLossArgs {
     float scale, offset;
     float c;   // weight / (H W), rounded once on the host
 };
-
-BH_DEV double dl_wave_sum(double x) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);   // every lane adds the same pairs in the same order
-    return x;
-}
-
-// the block's K sums -> row blockIdx.x of partials (the columns behind K stay unwritten and unread)
-template <int K>
-BH_DEV void dl_block_store(const double (&s)[K], double (*wave_rows)[DL_ROW], double* __restrict__ partials) {
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double r = dl_wave_sum(s[k]);
-        if (lane == 0) wave_rows[wave][k] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)K) {
-        double r = wave_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < DL_WAVES; ++w) r += wave_rows[w][threadIdx.x];
-        partials[(size_t)blockIdx.x * DL_ROW + threadIdx.x] = r;
-    }
-}
 
 // t = fmaf(scale, gt, offset); valid: gt finite, t > 0, E > 0
 BH_DEV bool dl_target(const DepthLossArgs& a, float e, float g, float& t) {
@@ -174,6 +146,12 @@ int check_target(bh_ctx* ctx, const BhDepthTarget* t, const char* who) {
 
 }  // namespace
 
+int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, float c, float* loss, float* accum, float* accum_host) {
+    hipLaunchKernelGGL(depth_loss_final_kernel, dim3(1), dim3(DL_FINAL_WG), 0, ctx->stream, rows, partials, c, loss, accum, accum_host);
+    BH_LAUNCH_CHECK(ctx, "depth_loss_final_kernel");
+    return 0;
+}
+
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host) {
     const DepthLossArgs a = dl_args(t);
     auto* partials = (double*)ensure(ctx, SLOT_DEPTH_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
@@ -184,9 +162,7 @@ int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, f
     else { if (v_depth) BH_DL(BH_DEPTH_LOSS_DISPARITY, true); else BH_DL(BH_DEPTH_LOSS_DISPARITY, false); }
 #undef BH_DL
     BH_LAUNCH_CHECK(ctx, "depth_loss_kernel");
-    hipLaunchKernelGGL(depth_loss_final_kernel, dim3(1), dim3(DL_FINAL_WG), 0, ctx->stream, grid.x, partials, a.c, loss, accum, accum_host);
-    BH_LAUNCH_CHECK(ctx, "depth_loss_final_kernel");
-    return 0;
+    return launch_loss_pair_final(ctx, grid.x, partials, a.c, loss, accum, accum_host);
 }
 
 }  // namespace bh

@@ -17,6 +17,7 @@
 //   * depth -> normal and its backward: streaming kernels, one thread per pixel; the backward is a gather without atomics.
 #include "context.h"
 #include "device_map_blend.h"
+#include "device_depth_normal.h"
 #include "../../include/brush_hip_depth.h"
 #include "../../include/brush_hip_normal.h"
 
@@ -140,9 +141,14 @@ struct NormalMap {
 // v_quat += the chain of Vn through the sign, R_view^T, column k of the rotation matrix and the quaternion's normalisation, behind
 // K18 in its dense mode: a row K18 skipped (its ten sums are zero) is zero in the zero-filled dense output, so a splat that
 // received only Vn is still written
-__global__ __launch_bounds__(256) void normal_vn_scatter_kernel(uint32_t nv, NormalView v, const uint32_t* __restrict__ global_from_compact,
-                                                                const float* __restrict__ transforms, const float* __restrict__ v_n,
-                                                                float* __restrict__ v_transforms) {
+// MARK (behind a K18 in marking mode: the single-GPU train step; depth.hip's depth_vz_scatter_marking_kernel has the contract): a splat
+// with a non-zero Vn may sit in a row K18 skipped, which holds last step's bytes and carries no mark.  Such a row is first cleared
+// whole and marked in the sign bit of its refine weight, so that the accumulate below leaves what a zero-filled row would hold, bit
+// for bit; a marked row (K18's, or depth's scatter, which runs in front of this one) is accumulated into as it is.
+template <bool MARK>
+BH_DEV void vn_scatter_row(uint32_t nv, const NormalView& v, uint32_t sh_floats, const uint32_t* __restrict__ global_from_compact,
+                           const float* __restrict__ transforms, const float* __restrict__ v_n, float* __restrict__ v_transforms,
+                           float* __restrict__ v_sh, float* __restrict__ v_raw_opac, float* __restrict__ v_refine) {
     const uint32_t cg = blockIdx.x * 256u + threadIdx.x;
     if (cg >= nv) return;
     const float vx = v_n[(size_t)cg * 3], vy = v_n[(size_t)cg * 3 + 1], vz = v_n[(size_t)cg * 3 + 2];
@@ -172,47 +178,40 @@ __global__ __launch_bounds__(256) void normal_vn_scatter_kernel(uint32_t nv, Nor
     // qn = q / |q|: v_q = (d - qn (qn . d)) / |q|
     const float along = qdot(f.qn, d);
     float* vt = v_transforms + (size_t)gid * 10;
+    if (MARK) {
+        const uint32_t mark = f2u(v_refine[gid]);
+        if (!(mark >> 31)) {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) vt[k] = 0.0f;
+            float* sh = v_sh + (size_t)gid * sh_floats;
+            for (uint32_t k = 0; k < sh_floats; ++k) sh[k] = 0.0f;
+            v_raw_opac[gid] = 0.0f;
+            v_refine[gid] = u2f(mark | 0x80000000u);
+        }
+    }
     vt[3] += (d.w - w * along) * f.inv_len;
     vt[4] += (d.x - x * along) * f.inv_len;
     vt[5] += (d.y - y * along) * f.inv_len;
     vt[6] += (d.z - z * along) * f.inv_len;
 }
 
+__global__ __launch_bounds__(256) void normal_vn_scatter_kernel(uint32_t nv, NormalView v, const uint32_t* __restrict__ global_from_compact,
+                                                                const float* __restrict__ transforms, const float* __restrict__ v_n,
+                                                                float* __restrict__ v_transforms) {
+    vn_scatter_row<false>(nv, v, 0u, global_from_compact, transforms, v_n, v_transforms, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void normal_vn_scatter_marking_kernel(uint32_t nv, NormalView v, uint32_t sh_floats,
+                                                                        const uint32_t* __restrict__ global_from_compact,
+                                                                        const float* __restrict__ transforms, const float* __restrict__ v_n,
+                                                                        float* __restrict__ v_transforms, float* __restrict__ v_sh,
+                                                                        float* __restrict__ v_raw_opac, float* __restrict__ v_refine) {
+    vn_scatter_row<true>(nv, v, sh_floats, global_from_compact, transforms, v_n, v_transforms, v_sh, v_raw_opac, v_refine);
+}
+
 // ---------------------------------------------------------------------------
 // depth -> normal
 // ---------------------------------------------------------------------------
-struct PinholeK {
-    float fx, fy, cx, cy;
-    uint32_t w, h;
-};
-
-BH_DEV bool depth_ok(float d) { return is_finite_f32(d) && d > 0.0f; }
-
-// The stencil centred at (x, y): valid, the cross product c = gy x gx and the pieces its backward needs.
-struct Stencil {
-    bool valid;
-    float kxl, kxr, kx, kyu, kyd, ky;
-    Vec3A gx, gy, c;
-};
-
-BH_DEV Stencil depth_stencil(const PinholeK& k, const float* __restrict__ depth, uint32_t x, uint32_t y) {
-    Stencil s;
-    s.valid = false;
-    if (x < 1u || y < 1u || x + 2u > k.w || y + 2u > k.h) return s;   // 1 <= x <= W-2, 1 <= y <= H-2
-    const size_t p = (size_t)x + (size_t)y * k.w;
-    const float dc = depth[p], dl = depth[p - 1], dr = depth[p + 1], du = depth[p - k.w], dd = depth[p + k.w];
-    if (!(depth_ok(dc) && depth_ok(dl) && depth_ok(dr) && depth_ok(du) && depth_ok(dd))) return s;
-    s.valid = true;
-    const float fxc = ((float)x + 0.5f) - k.cx, fyc = ((float)y + 0.5f) - k.cy;
-    s.kx = fxc / k.fx; s.kxl = (fxc - 1.0f) / k.fx; s.kxr = (fxc + 1.0f) / k.fx;
-    s.ky = fyc / k.fy; s.kyu = (fyc - 1.0f) / k.fy; s.kyd = (fyc + 1.0f) / k.fy;
-    s.gx = v3(s.kxr * dr - s.kxl * dl, s.ky * dr - s.ky * dl, dr - dl);
-    s.gy = v3(s.kx * dd - s.kx * du, s.kyd * dd - s.kyu * du, dd - du);
-    // c = gy x gx
-    s.c = v3(s.gy.y * s.gx.z - s.gy.z * s.gx.y, s.gy.z * s.gx.x - s.gy.x * s.gx.z, s.gy.x * s.gx.y - s.gy.y * s.gx.x);
-    return s;
-}
-
 __global__ __launch_bounds__(256) void depth_to_normal_kernel(PinholeK k, const float* __restrict__ depth, float* __restrict__ out) {
     const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (p >= (size_t)k.w * k.h) return;
@@ -227,27 +226,6 @@ __global__ __launch_bounds__(256) void depth_to_normal_kernel(PinholeK k, const 
     out[p * 3] = ox;
     out[p * 3 + 1] = oy;
     out[p * 3 + 2] = oz;
-}
-
-// d <v, c / |c|> / d (the depth of neighbour `which` of the stencil at (x, y)): 0 left, 1 right, 2 up, 3 down; 0 for an invalid stencil
-BH_DEV float stencil_grad(const PinholeK& k, const float* __restrict__ depth, const float* __restrict__ v_normal, uint32_t x, uint32_t y, int which) {
-    const Stencil s = depth_stencil(k, depth, x, y);
-    if (!s.valid) return 0.0f;
-    const float len = length(s.c);
-    if (len == 0.0f) return 0.0f;
-    const float inv = 1.0f / len;
-    const Vec3A u = scale(s.c, inv);
-    const size_t p = ((size_t)x + (size_t)y * k.w) * 3;
-    const Vec3A v = v3(v_normal[p], v_normal[p + 1], v_normal[p + 2]);
-    const Vec3A vc = scale(sub(v, scale(u, dot(v, u))), inv);
-    if (which < 2) {
-        // c = gy x gx: v_gx = vc x gy
-        const Vec3A vg = v3(vc.y * s.gy.z - vc.z * s.gy.y, vc.z * s.gy.x - vc.x * s.gy.z, vc.x * s.gy.y - vc.y * s.gy.x);
-        return which == 0 ? -dot(vg, v3(s.kxl, s.ky, 1.0f)) : dot(vg, v3(s.kxr, s.ky, 1.0f));
-    }
-    // v_gy = gx x vc
-    const Vec3A vg = v3(s.gx.y * vc.z - s.gx.z * vc.y, s.gx.z * vc.x - s.gx.x * vc.z, s.gx.x * vc.y - s.gx.y * vc.x);
-    return which == 2 ? -dot(vg, v3(s.kx, s.kyu, 1.0f)) : dot(vg, v3(s.kx, s.kyd, 1.0f));
 }
 
 // a gather in a fixed order (no atomics): pixel (x, y) is the right neighbour of the stencil at x-1, the left one of x+1, the lower
@@ -323,6 +301,14 @@ PinholeK pinhole_of(const BhCamera* cam, uint32_t h, uint32_t w) {
 
 }  // namespace
 
+// The normal map `mode` of the saved forward `fs` (something is listed); the compact splat normals go through SLOT_NORMAL.
+int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transforms, uint32_t mode, float* out) {
+    NormalScratch s;
+    BH_TRY(normal_scratch(ctx, fs.out.num_listed_splats, 0, /*backward=*/false, &s));
+    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
+    return launch_normal_forward(ctx, fs, s.normals, mode, out);
+}
+
 // The normal term of a backward, between K17 and K18: v_combined += its raw sums, Vn (SLOT_NORMAL) = sum of vis * g.
 int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined) {
     const BhRenderOut& r = fs.out;
@@ -341,13 +327,22 @@ int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm
     return 0;
 }
 
-// Vn -> the quaternion columns of the dense, zero-filled v_transforms, behind K18 (never the row-marked train-step path)
-int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms) {
+// Vn -> the quaternion columns of v_transforms, behind K18 (and behind depth's scatter): dense and zero-filled, or (mark_rows, the
+// single-GPU train step) row-marked
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms, bool mark_rows, float* v_sh_coeffs,
+                             float* v_raw_opacities, float* v_refine_weight) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     if (nv == 0 || r.num_intersections == 0) return 0;
     const size_t vec_floats = ((size_t)nv * 3u + 63u) & ~(size_t)63u;
     const float* v_n = (const float*)ctx->slots[SLOT_NORMAL].ptr + vec_floats;
+    if (mark_rows) {
+        const uint32_t sh_floats = (fs.sh_degree + 1) * (fs.sh_degree + 1) * 3;
+        hipLaunchKernelGGL(normal_vn_scatter_marking_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, normal_view(fs.uniforms.vm), sh_floats,
+                           r.global_from_compact_gid, transforms, v_n, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight);
+        BH_LAUNCH_CHECK(ctx, "normal_vn_scatter_marking_kernel");
+        return 0;
+    }
     hipLaunchKernelGGL(normal_vn_scatter_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, normal_view(fs.uniforms.vm),
                        r.global_from_compact_gid, transforms, v_n, v_transforms);
     BH_LAUNCH_CHECK(ctx, "normal_vn_scatter_kernel");
@@ -382,10 +377,7 @@ int bh_render_normal(bh_ctx* ctx, const BhRenderOut* saved, const float* transfo
     if (fs.out.num_intersections == 0 || fs.out.num_listed_splats == 0) return bh::clear_map_window(ctx, fs.uniforms, out, 3);
     if (!transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_normal: null transforms");
     bh::ProfScope ps(ctx, "RenderNormal");
-    bh::NormalScratch s;
-    BH_TRY(bh::normal_scratch(ctx, fs.out.num_listed_splats, 0, /*backward=*/false, &s));
-    BH_TRY(bh::launch_compact_normals(ctx, fs, transforms, s.normals));
-    return bh::launch_normal_forward(ctx, fs, s.normals, mode, out);
+    return bh::launch_normal_map(ctx, fs, transforms, mode, out);
 }
 
 int bh_render_backward_normal_saved(bh_ctx* ctx, const BhRenderOut* saved, const float* v_output, const float* v_depth, uint32_t depth_mode,

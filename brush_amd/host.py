@@ -752,6 +752,33 @@ def depth_loss_value_and_grad(depth, gt, kind="l1", weight=1.0, scale=1.0, offse
     return loss, v_depth
 
 
+def normal_consistency_value_and_grad(normal, depth, image, camera, weight=1.0, v_depth=None, ctx: Optional[Context] = None):
+    """The fused normal-consistency operator (bh_normal_consistency_value_and_grad; include/brush_hip_normal_loss.h) between an
+    accumulated normal map [H,W,3] and the normals of the expected-depth map [H,W] of the same frame, weighted by the alpha of `image`
+    [H,W,4] (a constant): -> (loss [2] device f32 = (weight * sum A (1 - N . u) / (H W), valid pixels), v_normal [H,W,3], v_depth
+    [H,W]).  `v_depth`: a contiguous f32 [H,W] tensor the depth gradient is ADDED to in place (and returned); None: a fresh one.
+    Pinhole cameras only.  Queued on the ctx stream: nothing is read back."""
+    dev = depth.device
+    ctx = ctx or get_context(dev)
+    depth = _f32c(depth, dev)
+    if depth.dim() != 2:
+        raise ValueError("normal_consistency_value_and_grad: the depth map must be [H, W]")
+    h, w = depth.shape
+    normal = _f32c(normal, dev).reshape(h, w, 3)
+    image = _f32c(image, dev).reshape(h, w, 4)
+    accumulate = v_depth is not None
+    if accumulate and (v_depth.dtype != torch.float32 or tuple(v_depth.shape) != (h, w) or not v_depth.is_contiguous() or v_depth.device != dev):
+        raise BrushHipError("normal_consistency_value_and_grad: `v_depth` must be a contiguous float32 [%d, %d] tensor on %s" % (h, w, dev))
+    cam = camera.uniforms((w, h))
+    loss = torch.empty((2,), dtype=torch.float32, device=dev)
+    v_normal = torch.empty_like(normal)
+    if not accumulate:
+        v_depth = torch.empty_like(depth)
+    ctx.check(ctx.lib.bh_normal_consistency_value_and_grad(ctx._h, C.byref(cam), _ptr(normal), _ptr(depth), _ptr(image), h, w, float(weight),
+                                                           1 if accumulate else 0, _ptr(loss), _ptr(v_normal), _ptr(v_depth)))
+    return loss, v_normal, v_depth
+
+
 def eval_depth_metrics(depth, gt, kind="l1", scale=1.0, offset=0.0, ctx: Optional[Context] = None, out=None):
     """Held-out depth metrics (bh_eval_depth_metrics) of an expected-depth map against a target: -> device f32 [4] = (abs-rel, RMSE,
     share of pixels with max(E / z, z / E) < 1.25, valid pixels); validity as in depth_loss_value_and_grad.  Nothing is read back."""
@@ -1223,6 +1250,10 @@ class TrainConfig:
     depth_loss_weight: float = 0.0
     depth_loss_weight_end: Optional[float] = None
     depth_loss_kind: str = "l1"   # "l1": SceneBatch.depth holds depth; "disparity": it holds inverse depth
+    # not in the reference: > 0 adds the normal-consistency term (brush_hip_normal_loss.h; 2DGS's regulariser) from step
+    # normal_loss_from_iter on (2DGS starts it at 7000); pinhole cameras, whole frames
+    normal_loss_weight: float = 0.0
+    normal_loss_from_iter: int = 0
 
     def depth_weight_at(self, step: int) -> float:
         """The depth term's weight at step `step` (from 1): w0 * (w1 / w0) ** ((step - 1) / total_train_iters)."""
@@ -1815,6 +1846,12 @@ class SplatTrainer:
             ctx.check(ctx.lib.bh_train_set_depth(ctx._h, C.byref(dt)))
         else:
             ctx.check(ctx.lib.bh_train_set_depth(ctx._h, None))
+        # the normal term is ctx state too (bh_train_set_normal): attached from normal_loss_from_iter on, detached otherwise and behind the step
+        nw = float(getattr(c, "normal_loss_weight", 0.0))
+        if nw > 0.0 and self.step_count + 1 >= int(getattr(c, "normal_loss_from_iter", 0)):
+            ctx.check(ctx.lib.bh_train_set_normal(ctx._h, C.byref(_ffi.BhNormalTermConfig(weight=nw))))
+        else:
+            ctx.check(ctx.lib.bh_train_set_normal(ctx._h, None))
         if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
             self.batch_patch(b)
         lw = float(getattr(c, "lpips_loss_weight", 0.0))
@@ -1834,6 +1871,7 @@ class SplatTrainer:
                                             float(scale), C.byref(stats)))
         finally:
             ctx.lib.bh_train_set_depth(ctx._h, None)
+            ctx.lib.bh_train_set_normal(ctx._h, None)
             if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
             if ex is not None:

@@ -30,6 +30,8 @@
 //                                                   transform per training view, Adam on the device; brush_hip_exposure.h)
 //   brush_hip::depth_loss_value_and_grad / eval_depth_metrics / train_set_depth   not in the reference: depth supervision (a fused
 //                                                   depth loss, the step's depth term, held-out depth metrics; brush_hip_depth_loss.h)
+//   brush_hip::normal_consistency_value_and_grad / train_set_normal   not in the reference: the normal-consistency regulariser (a fused
+//                                                   loss with both gradients, the step's normal term; brush_hip_normal_loss.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -60,6 +62,7 @@
 #include "brush_hip_exposure.h"
 #include "brush_hip_depth_loss.h"
 #include "brush_hip_normal.h"
+#include "brush_hip_normal_loss.h"
 
 namespace brush_hip {
 
@@ -1277,6 +1280,23 @@ inline DeviceBuffer<float> depth_to_normal_backward(const Context& ctx, const Ca
     ctx.check(bh_depth_to_normal_backward(ctx.get(), &cam, depth, v_normal, h, w, out.data()));
     ctx.sync();
     return out;
+}
+
+// ---- normal consistency (brush_hip_normal_loss.h; not in the reference) ---------------------------------------------------------------
+// loss [2] (device) = (weight * sum A (1 - N . u) / (H W), valid pixels), v_normal [H,W,3], v_depth [H,W] (accumulate_v_depth: added
+// to); normal = an accumulated normal map, depth = the expected depth, image = the frame [H,W,4] (its alpha, a constant); nothing is read back
+inline void normal_consistency_value_and_grad(const Context& ctx, const Camera& camera, const float* normal, const float* depth, const float* image,
+                                              uint32_t h, uint32_t w, float weight, bool accumulate_v_depth, float* loss, float* v_normal, float* v_depth) {
+    static_assert(sizeof(BhNormalTermConfig) == 16, "BhNormalTermConfig layout");
+    const BhCamera cam = camera.uniforms(w, h);
+    ctx.check(bh_normal_consistency_value_and_grad(ctx.get(), &cam, normal, depth, image, h, w, weight, accumulate_v_depth ? 1u : 0u, loss, v_normal, v_depth));
+}
+// bh_train_step on this ctx adds the normal-consistency term at `weight` (<= 0: no term); nullptr detaches
+inline void train_set_normal(const Context& ctx, const BhNormalTermConfig* cfg) { ctx.check(bh_train_set_normal(ctx.get(), cfg)); }
+inline void train_set_normal(const Context& ctx, float weight) {
+    BhNormalTermConfig cfg{};
+    cfg.weight = weight;
+    train_set_normal(ctx, &cfg);
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
