@@ -470,6 +470,8 @@ struct bh_ctx {
     bool dsort_spl_written = false;   // a frame has written it (until then a frame sorts a sample first)
     bool knob_dsort_splitters = true; // option dsort_splitters: the split digit from the previous frame's quantiles (0: always the linear split)
     bool adam_lds_raised = false;     // adam_rowreduced_kernel's > 64 KB dynamic-LDS opt-in was made on this ctx's device
+    uint32_t update_lds_raised = 0;   // likewise train_update_kernel: one bit per instantiation (optim.hip launch_train_update)
+    size_t lds_optin_max = 0;         // the device's opt-in limit of dynamic LDS per block, 0: not asked yet (optim.hip max_dynamic_lds)
     // developer knobs (A/B measurements): bh_set_option
     bool knob_no_lpt = false;         // option no_lpt: backward tiles in index order
     bool knob_bwd_wide_rows = false;  // option bwd_wide_rows: the blend backward forms the accumulator's addresses in 64 bits whatever its size (rasterize.hip)

@@ -132,17 +132,36 @@ static AdamArgs make_adam_args(float beta1, float beta2, float eps, float lr, ui
     return a;
 }
 
+// the most dynamic LDS a block may ask for on the ctx's device once the kernel has opted in (hipFuncAttributeMaxDynamicSharedMemorySize):
+// the device attribute, read once per ctx; a runtime that does not report the opt-in limit leaves the plain per-block limit
+static size_t max_dynamic_lds(bh_ctx* ctx) {
+    if (ctx->lds_optin_max == 0) {
+        int optin = 0, plain = 0;
+        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, ctx->device) != hipSuccess) { (void)hipGetLastError(); optin = 0; }
+        if (hipDeviceGetAttribute(&plain, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) { (void)hipGetLastError(); plain = 0; }
+        const int best = optin > plain ? optin : plain;
+        ctx->lds_optin_max = best > 0 ? (size_t)best : (size_t)64 * 1024;
+    }
+    return ctx->lds_optin_max;
+}
+
 int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
                 const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps) {
     if (rows == 0 || row_len == 0) return 0;
     if (t == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "adam: t is 1-based");
     const AdamArgs a = make_adam_args(beta1, beta2, eps, lr, t);
     if (reduce_m2) {
+        // 256 rows of row_len + 1 floats and the rows' second moments in LDS: what fits is the device's word (the opt-in limit of
+        // dynamic LDS per block, 160 KB on gfx950: row_len <= 158), refused here, in front of any launch
         if (row_len > 255) return set_error(ctx, BH_ERR_UNSUPPORTED, "adam (reduced second moment): row_len must be <= 255");
         const uint64_t nb = (rows + ADAM_ROWS - 1) / ADAM_ROWS;
         const size_t lds = ((size_t)ADAM_ROWS * (row_len + 1) + ADAM_ROWS) * sizeof(float);
+        const size_t lds_max = max_dynamic_lds(ctx);
+        if (lds > lds_max)
+            return set_error(ctx, BH_ERR_UNSUPPORTED, "adam (reduced second moment): row_len " + std::to_string(row_len) + " needs " + std::to_string(lds) +
+                                                          " bytes of LDS per block, the device allows " + std::to_string(lds_max));
         if (lds > 64 * 1024 && !ctx->adam_lds_raised) {  // above the default dynamic-LDS limit (row_len > 62): opt in once per ctx (the attribute is per device)
-            BH_HIP(ctx, hipFuncSetAttribute((const void*)adam_rowreduced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            BH_HIP(ctx, hipFuncSetAttribute((const void*)adam_rowreduced_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
             ctx->adam_lds_raised = true;
         }
         hipLaunchKernelGGL(adam_rowreduced_kernel, dim3((unsigned)nb), dim3(OPT_WG), lds, ctx->stream, param, grad, m1, m2, rows, row_len, col_scale, a);
@@ -605,6 +624,30 @@ int launch_train_update(bh_ctx* ctx, const BhTrainState* st, const UpdateCall& c
         else { if (sparse) BH_LAUNCH_UPDATE(false, R, true); else BH_LAUNCH_UPDATE(false, R, false); }      \
         break
     const bool sparse = u.sparse_max != 0u;   // 0: the instantiations without the second path
+    if (rows != 64u && rows != 128u && rows != 256u) return set_error(ctx, BH_ERR_INVALID_ARG, "update_rows must be 64, 128 or 256");
+    // 256-row blocks of SH degree 4 stage 85 KB: above the default dynamic-LDS limit, the instantiation opts in once per ctx
+    // (the attribute is per device), and what the device cannot give is refused in front of the launch
+    if (lds > 64 * 1024) {
+        const size_t lds_max = max_dynamic_lds(ctx);
+        if (lds > lds_max) return set_error(ctx, BH_ERR_INVALID_ARG, "update_rows " + std::to_string(rows) + " at this SH degree needs more LDS per block than the device allows");
+        const uint32_t bit = 1u << ((vec ? 1u : 0u) | (sparse ? 2u : 0u) | (rows == 64u ? 0u : rows == 128u ? 4u : 8u));
+        if (!(ctx->update_lds_raised & bit)) {
+#define BH_RAISE_UPDATE(V, R, P) BH_HIP(ctx, hipFuncSetAttribute((const void*)train_update_kernel<V, R, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max))
+#define BH_RAISE_UPDATE_ROWS(R)                                                                     \
+    case R:                                                                                         \
+        if (vec) { if (sparse) BH_RAISE_UPDATE(true, R, true); else BH_RAISE_UPDATE(true, R, false); }  \
+        else { if (sparse) BH_RAISE_UPDATE(false, R, true); else BH_RAISE_UPDATE(false, R, false); }    \
+        break
+            switch (rows) {
+                BH_RAISE_UPDATE_ROWS(64);
+                BH_RAISE_UPDATE_ROWS(128);
+                BH_RAISE_UPDATE_ROWS(256);
+            }
+#undef BH_RAISE_UPDATE_ROWS
+#undef BH_RAISE_UPDATE
+            ctx->update_lds_raised |= bit;
+        }
+    }
     switch (rows) {
         BH_LAUNCH_UPDATE_ROWS(64);
         BH_LAUNCH_UPDATE_ROWS(128);

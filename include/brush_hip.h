@@ -334,7 +334,10 @@ int bh_image_loss_value_and_grad(bh_ctx* ctx, const float* img_hwc4, const uint3
 /* One AdamScaled step on a [rows,row_len] parameter.  t = state.time after this
  * step (1 on the first call: moments are initialised, not decayed).  col_scale
  * [row_len] device or NULL.  reduce_m2 != 0: second moment is one scalar per row
- * (m2 has `rows` entries).  beta1=.9 beta2=.999 eps=1e-15 in the reference. */
+ * (m2 has `rows` entries).  beta1=.9 beta2=.999 eps=1e-15 in the reference.
+ * reduce_m2 stages 256 rows in LDS, (256 * (row_len + 1) + 256) * 4 bytes per block: a row_len over 255, or one whose block
+ * exceeds the device's opt-in limit of dynamic LDS per block (160 KB on gfx950: row_len <= 158), returns BH_ERR_UNSUPPORTED
+ * before anything is launched; the tensors are untouched. */
 int bh_adam_step(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows,
                  uint32_t row_len, const float* col_scale, float lr, uint32_t t, int reduce_m2, float beta1,
                  float beta2, float eps);

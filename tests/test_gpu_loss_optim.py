@@ -73,22 +73,67 @@ def test_ssim_of_identical_images_is_one(dev):
     assert float((lm - 1.0).abs().max()) < 1e-5
 
 
-@pytest.mark.parametrize("rows,row_len,reduce_m2", [(1000, 10, False), (777, 48, True), (5000, 3, True), (4097, 1, False)])
-def test_adam_step_bit_exact_vs_oracle(dev, oracle_lib, rows, row_len, reduce_m2):
-    """adam_scaled.rs:75-147: identical operation sequence -> bit-exact over 4 steps."""
+# adam_rowreduced_kernel stages 256 rows of row_len + 1 floats and their 256 second moments in LDS; a gfx950 block may opt in to
+# 160 KB (the CU's whole LDS): (256 * (row_len + 1) + 256) * 4 <= 160 * 1024 holds up to row_len 158
+ADAM_LONGEST_ROW = 158
+
+
+@pytest.mark.parametrize("rows,row_len,reduce_m2,classes", [
+    pytest.param(1000, 10, False, False, id="1000-10-False"), pytest.param(777, 48, True, False, id="777-48-True"),
+    pytest.param(5000, 3, True, False, id="5000-3-True"), pytest.param(4097, 1, False, False, id="4097-1-False"),
+    pytest.param(257, 63, True, True, id="257-63-True-classes"),   # the first row length over the 64 KB a kernel gets without opting in
+    pytest.param(300, ADAM_LONGEST_ROW, True, True, id="300-longest-True-classes"),   # the longest that fits
+    pytest.param(1000, 10, False, True, id="1000-10-False-classes"), pytest.param(777, 48, True, True, id="777-48-True-classes"),
+])
+def test_adam_step_bit_exact_vs_oracle(dev, oracle_lib, rows, row_len, reduce_m2, classes):
+    """adam_scaled.rs:75-147: identical operation sequence -> bit-exact over 4 steps.  classes: the gradients are
+    update_ref.elements' (per row a mix of normal * 10^[-6..0], tiny values whose square is subnormal or zero, values up to 1e18,
+    +0.0 and -0.0) instead of one scale per step."""
     import brush_amd as ba
+    import update_ref as ur
     rng = np.random.default_rng(rows)
     p = rng.normal(size=(rows, row_len)).astype(np.float32)
     m1 = np.zeros_like(p)
     m2 = np.zeros(rows if reduce_m2 else (rows, row_len), np.float32)
     scale = rng.uniform(0.1, 1.0, row_len).astype(np.float32)
+    mix = rng.integers(0, len(ur.MIXES), rows) if classes else None
     tp, tm1, tm2, ts = (torch.from_numpy(a.copy()).to(dev) for a in (p, m1, m2, scale))
     for t in range(1, 5):
-        g = (rng.normal(size=(rows, row_len)) * 10.0 ** rng.integers(-6, 1)).astype(np.float32)
+        if classes:
+            g = ur.elements(rng, mix, row_len)
+        else:
+            g = (rng.normal(size=(rows, row_len)) * 10.0 ** rng.integers(-6, 1)).astype(np.float32)
         oracle_lib.adam_step(p, g, m1, m2, 0.01, t, col_scale=scale, reduce_m2=reduce_m2)
         ba.adam_step(tp, torch.from_numpy(g).to(dev), tm1, tm2, 0.01, t, col_scale=ts, reduce_m2=reduce_m2)
+        if classes:   # bit for bit, the sign of a zero included
+            for got, want, what in ((tp, p, "param"), (tm1, m1, "m1"), (tm2, m2, "m2")):
+                assert ur.first_difference(got.cpu().numpy(), want) is None, ("step %d" % t, what, ur.first_difference(got.cpu().numpy(), want))
         assert np.array_equal(tp.cpu().numpy(), p), "step %d" % t
         assert np.array_equal(tm1.cpu().numpy(), m1) and np.array_equal(tm2.cpu().numpy(), m2)
+    assert np.isfinite(p).all() and np.isfinite(m2).all()
+
+
+def test_adam_step_refuses_a_row_that_does_not_fit_in_lds(dev):
+    """One word over the longest row: BH_ERR_UNSUPPORTED (-5) from the host-side check — nothing is launched, the tensors keep
+    their bits, and the context goes on working (a launch that fails leaves an error code of the runtime, -2)."""
+    import brush_amd as ba
+    rows, row_len = 300, ADAM_LONGEST_ROW + 1
+    rng = np.random.default_rng(5)
+    host = [rng.normal(size=(rows, row_len)).astype(np.float32) for _ in range(3)] + [rng.random(rows, dtype=np.float32)]
+    p, g, m1, m2 = (torch.from_numpy(a.copy()).to(dev) for a in host)
+    ctx = ba.Context(dev)
+    try:
+        with pytest.raises(ba.BrushHipError, match=r"brush_hip error -5: .*row_len 159") as e:
+            ba.adam_step(p, g, m1, m2, 0.01, 2, reduce_m2=True, ctx=ctx)
+        assert "LDS" in str(e.value)
+        ctx.sync()
+        for t, a in zip((p, g, m1, m2), host):
+            assert np.array_equal(t.cpu().numpy().view(np.int32), a.view(np.int32))
+        ba.adam_step(p[:, :ADAM_LONGEST_ROW].contiguous(), g[:, :ADAM_LONGEST_ROW].contiguous(), m1[:, :ADAM_LONGEST_ROW].contiguous(), m2, 0.01, 2,
+                     reduce_m2=True, ctx=ctx)
+        ctx.sync()
+    finally:
+        ctx.close()
 
 
 def test_gather_stats(dev, oracle_lib):
