@@ -41,6 +41,9 @@ Names and argument meaning follow the reference (paths under
     normal_consistency_value_and_grad / TrainConfig.normal_loss_weight   the normal-consistency regulariser those maps exist for: a
                                          fused loss with both gradients and a term in the step (not in the reference; 2DGS's
                                          normal loss; include/brush_hip_normal_loss.h)
+    render_distortion / RenderNode.distortion / RenderNode.backward(v_distortion=) / distortion_loss / TrainConfig.distortion_loss_weight
+                                         distortion maps with their gradient, the loss and a term in the step (not in the reference;
+                                         2DGS's depth distortion; include/brush_hip_distortion.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -55,5 +58,6 @@ from .host import (  # noqa: F401
     Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
     PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
+    render_distortion, distortion_loss,
 )
 from ._ffi import BrushHipError  # noqa: F401

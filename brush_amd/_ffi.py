@@ -305,6 +305,27 @@ NORMAL_LOSS_SYMBOLS = {
     "bh_train_set_normal": (C.c_int, [C.c_void_p, C.POINTER(BhNormalTermConfig)]),
 }
 
+# every symbol include/brush_hip_distortion.h declares (distortion maps, their backward, the loss and the step's distortion term)
+DISTORTION_Z, DISTORTION_NDC = 0, 1
+
+
+class BhDistortionConfig(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("near_z", C.c_float), ("far_z", C.c_float), ("reserved", C.c_uint32)]
+
+
+class BhDistortionTermConfig(C.Structure):
+    _fields_ = [("weight", C.c_float), ("kind", C.c_uint32), ("near_z", C.c_float), ("far_z", C.c_float)]
+
+
+DISTORTION_SYMBOLS = {
+    "bh_render_distortion": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.POINTER(BhDistortionConfig), C.c_void_p]),
+    "bh_render_distortion_moments": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.POINTER(BhDistortionConfig), C.c_void_p]),
+    "bh_render_backward_distortion_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                      C.c_void_p, C.POINTER(BhDistortionConfig)] + [C.c_void_p] * 7),
+    "bh_distortion_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
+    "bh_train_set_distortion": (C.c_int, [C.c_void_p, C.POINTER(BhDistortionTermConfig)]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -344,7 +365,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS))
     return _lib
 
 
@@ -353,6 +374,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

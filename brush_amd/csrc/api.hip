@@ -1118,15 +1118,19 @@ namespace bh {
 // depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
 // v_viewmat (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined.
 // normal (normal.hip): a normal term's raw sums join the accumulator like depth's; its Vn lands behind depth's v_z, on row marks too.
+// distortion (distortion.hip): its raw sums join the accumulator behind depth's and normal's; its v_z joins the depth term's vector (one
+// scatter serves both) or, without a depth term, goes through the same scatter from a vector of its own, on row marks too.
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat, const NormalTerm* normal) {
+                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat, const NormalTerm* normal,
+                  const DistortionTerm* distortion) {
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
     auto* v_combined = (float*)ensure(ctx, SLOT_V_COMBINED, nvpad * 10 * 4 + 16);   // + room to clear whole float4s
     if (!v_combined) return BH_ERR_OOM;
     bool row_marks = false;
+    const float* scatter_v_z = nullptr;   // the v_z vector behind K18: NULL = the depth term's
     {
         ProfScope ps(ctx, "ZeroGradBuffers");
         // what the forward's kernels cleared on their way (K5: v_combined; K1: the train step's gradient span) is done
@@ -1171,13 +1175,15 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                              r.tile_offsets_far, want_refine, &fs.jobs, nv));
         if (depth) BH_TRY(launch_depth_backward(ctx, fs, *depth, v_combined));
         if (normal) BH_TRY(launch_normal_backward(ctx, fs, *normal, transforms, v_combined));
+        // (behind launch_depth_backward: SLOT_DEPTH has its final size and v_z is filled)
+        if (distortion) BH_TRY(launch_distortion_backward(ctx, fs, *distortion, v_combined, depth ? (float*)ctx->slots[SLOT_DEPTH].ptr : nullptr, &scatter_v_z));
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
         BH_TRY(launch_project_backward(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs,
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
-        if (depth) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
+        if (depth || distortion) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight, scatter_v_z));
         if (normal) BH_TRY(launch_normal_vn_scatter(ctx, fs, transforms, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
     }
     if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
@@ -1514,6 +1520,15 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (ctx->pose_grad)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a normal term and a pose-gradient buffer cannot be attached together (the pose pass does not carry the normal term's gradient)");
     }
+    // a distortion term (brush_hip_distortion.h): refused before anything is queued; attached only with a weight > 0 and a checked kind
+    const bool distortion_wanted = ctx->distortion_attached;
+    if (distortion_wanted) {
+        const ViewUniforms xu = make_uniforms(batch->camera);
+        if (batch->image_hook || xu.tile_y0 != 0u || xu.tile_y1 != xu.tile_bh)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the distortion term needs the whole frame on this rank (no tile-row partition)");
+        if (ctx->pose_grad)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a distortion term and a pose-gradient buffer cannot be attached together (the pose pass does not carry the distortion term's gradient)");
+    }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
     const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
@@ -1705,6 +1720,24 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
             normal_term.mode = BH_NORMAL_ACCUMULATED;
         }
     }
+    // ---- distortion term (brush_hip_distortion.h): on the same final frame, behind the normal term.  The moment map lives in a slot of
+    // its own until the backward, which reads it instead of rendering it again; the cotangent is the constant weight / (H W), so no
+    // [H,W] map of it exists.  loss += the term's, in f32, behind the normal term's.
+    DistortionTerm distortion_term;
+    const bool distortion_on = distortion_wanted && frame_listed && ctx->latest.out.num_listed_splats > 0;
+    if (distortion_on) {
+        ProfScope pd(ctx, "DistortionTerm");
+        auto* moments = (float*)ensure(ctx, SLOT_DISTORTION_TERM, (hw * 4 + 4) * 4);
+        if (!moments) return BH_ERR_OOM;
+        const BhDistortionTermConfig& dc = ctx->distortion_term;
+        distortion_term.kind = dc.kind;
+        distortion_term.near_z = dc.near_z;
+        distortion_term.far_z = dc.far_z;
+        distortion_term.gain = (float)((double)dc.weight / (double)hw);
+        BH_TRY(launch_distortion_map(ctx, ctx->latest, distortion_term, /*moments=*/true, moments));
+        BH_TRY(launch_distortion_loss(ctx, moments, H, W, 4u, dc.weight, moments + hw * 4, loss_dev, loss_host));
+        distortion_term.moments = moments;
+    }
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
     // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling
@@ -1761,7 +1794,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
     BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
                          /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, (depth_on || normal_on) ? &depth_term : nullptr, ctx->pose_grad,
-                         normal_on ? &normal_term : nullptr));
+                         normal_on ? &normal_term : nullptr, distortion_on ? &distortion_term : nullptr));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

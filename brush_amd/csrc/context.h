@@ -15,6 +15,7 @@
 #include "../../include/brush_hip_exposure.h"
 #include "../../include/brush_hip_depth_loss.h"
 #include "../../include/brush_hip_normal_loss.h"
+#include "../../include/brush_hip_distortion.h"
 #include "device_math.h"
 
 namespace bh {
@@ -88,6 +89,9 @@ enum Slot : int {
     SLOT_NORMAL,             // bh_render_normal / bh_render_backward_normal_saved: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip)
     SLOT_NORMAL_LOSS,        // bh_normal_consistency_value_and_grad: one f64 row of 4 per block, 2 used (normal_loss.hip)
     SLOT_NORMAL_TERM,        // bh_train_step with a normal term: accumulated normals [H,W,3] | v_normal [H,W,3] | the term's loss pair (4 floats)
+    SLOT_DISTORTION,         // bh_render_distortion / bh_render_backward_distortion_saved: NDC depths m [Nv] | v_m (the term's own v_z) [Nv] | the frame's moment map [H,W,4] (distortion.hip)
+    SLOT_DISTORTION_LOSS,    // bh_distortion_loss: one f64 row of 4 per block, 2 used (distortion.hip)
+    SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
     SLOT_COUNT
 };
 
@@ -369,6 +373,15 @@ struct NormalTerm {
     uint32_t mode = 0;                 // BH_NORMAL_ACCUMULATED or BH_NORMAL_UNIT
 };
 
+// The distortion term of a backward (distortion.hip, brush_hip_distortion.h): <v_distortion, dist of the forward>
+struct DistortionTerm {
+    const float* v_distortion = nullptr;   // [H,W], or NULL: the uniform cotangent `gain` at every pixel
+    float gain = 0.0f;
+    uint32_t kind = 0;                     // BH_DISTORTION_Z or BH_DISTORTION_NDC
+    float near_z = 0.0f, far_z = 0.0f;     // NDC only
+    const float* moments = nullptr;        // [H,W,4] the frame's moment map if the caller has rendered it (the train step), or NULL
+};
+
 }  // namespace bh
 
 // The blend backward accumulates RAW per-splat sums into v_combined and the projection backward maps them to the reference's
@@ -406,6 +419,8 @@ struct bh_ctx {
     BhDepthTarget depth_target{};
     bool normal_attached = false;     // bh_train_set_normal: the step adds the normal-consistency term (brush_hip_normal_loss.h); weight <= 0 = off
     BhNormalTermConfig normal_term{};
+    bool distortion_attached = false; // bh_train_set_distortion: the step adds the distortion term (brush_hip_distortion.h); only ever true with a weight > 0
+    BhDistortionTermConfig distortion_term{};
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
@@ -514,12 +529,12 @@ int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_co
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
                   const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
                   size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr,
-                  const NormalTerm* normal = nullptr);
+                  const NormalTerm* normal = nullptr, const DistortionTerm* distortion = nullptr);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
 int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
 // mark_rows (the single-GPU train step's ROW_MARKS span): a row K18 did not write is stored whole (zeros but the mean) and marked
 int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows = false, float* v_sh_coeffs = nullptr,
-                            float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
+                            float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr, const float* v_z = nullptr);
 int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, float* out_depth);
 // normal.hip: the normal term between K17 and K18 (raw sums into v_combined, Vn into SLOT_NORMAL), and Vn -> v_quat behind K18 and
 // depth's scatter; mark_rows as launch_depth_vz_scatter's
@@ -532,6 +547,15 @@ int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transfor
 // step): loss[0] is added to accum[0] in f32 and the total copied to accum_host
 int launch_normal_loss(bh_ctx* ctx, const BhCamera& cam, const float* normal, const float* depth, const float* image, uint32_t h, uint32_t w, float weight,
                        bool accumulate_v_depth, float* loss, float* v_normal, float* v_depth, float* accum, float* accum_host);
+// distortion.hip: the distortion term between K17 and K18, behind the depth term's replay (raw sums into v_combined; its v_z added into
+// depth_v_z, the depth term's filled vector, or stored in a vector of its own in SLOT_DISTORTION: *v_z_out is the one the scatter reads)
+int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& term, float* v_combined, float* depth_v_z, const float** v_z_out);
+// ... the distortion map (moments: the moment map [H,W,4]) of a saved forward with something listed, the kind's check and the loss
+// (accum as launch_depth_loss's)
+int launch_distortion_map(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& term, bool moments, float* out);
+int check_distortion_kind(bh_ctx* ctx, uint32_t kind, float near_z, float far_z, const char* who);
+int launch_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w, uint32_t channels, float weight, float* loss, float* accum,
+                           float* accum_host);
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);

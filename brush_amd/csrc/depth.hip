@@ -80,6 +80,7 @@ struct DepthMap {
         return px.g[0] * __builtin_fmaf(-px.e, a, d);
     }
     static BH_DEV float cv(const Rec& r, const Pix& px) { return px.g[0] * (r.s1.z - px.e); }
+    static BH_DEV float vg(const Rec&, const Pix& px, int i) { return px.g[i]; }
 };
 
 // v_mean += (row 2 of the view matrix) * v_z, behind K18: a row K18 skipped (its ten sums are zero) is zero in the dense output
@@ -166,12 +167,13 @@ int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& 
     return 0;
 }
 
+// v_z: the vector to scatter (the distortion term's own, where no depth term runs); NULL: the depth term's (SLOT_DEPTH)
 int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows, float* v_sh_coeffs, float* v_raw_opacities,
-                            float* v_refine_weight) {
+                            float* v_refine_weight, const float* v_z) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     if (nv == 0 || r.num_intersections == 0) return 0;
-    const float* v_z = (const float*)ctx->slots[SLOT_DEPTH].ptr;
+    if (!v_z) v_z = (const float*)ctx->slots[SLOT_DEPTH].ptr;
     const float* vm = fs.uniforms.vm;   // column-major rotation: row 2 = (vm[2], vm[5], vm[8])
     if (mark_rows) {
         const uint32_t sh_floats = (fs.sh_degree + 1) * (fs.sh_degree + 1) * 3;

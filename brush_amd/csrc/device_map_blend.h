@@ -1,4 +1,5 @@
-// device_map_blend.h — the one blend skeleton of the attribute maps (depth.hip: depth maps, normal.hip: normal maps).
+// device_map_blend.h — the one blend skeleton of the attribute maps (depth.hip: depth maps, normal.hip: normal maps,
+// distortion.hip: distortion maps).
 //
 // A map is one more blend over the lists a BH_FLAG_BWD_INFO forward saved: K16's splats in K16's order with K16's alpha, cut-off,
 // clamp and saturation rule (device_blend.h), folding a per-splat attribute where K16 folds its colour.  Everything the maps share
@@ -16,6 +17,7 @@
 //   BwdMaps, Pix, prologue(m, pix, px)   the map pointers the backward reads (passed by value), a pixel's cotangent (g[NV] and
 //                                whatever else cv needs) and its start: fills px, returns S = the pixel's remaining sum
 //   cv(r, px)                    the "colour" of the splat at the pixel
+//   vg(r, px, i)                 the factor of V sum i for this splat at this pixel (depth and normal: the pixel's cotangent g[i] alone)
 #pragma once
 #include <algorithm>
 
@@ -168,7 +170,7 @@ void launch_map_forward(bh_ctx* ctx, const MapUniforms& u, bool smooth, const Bh
 // ---------------------------------------------------------------------------
 // One wave per tile, forward-order replay with the pixel state in registers like K17.  Per pixel a cotangent px (P::prologue) and
 // S = the remaining sum of w_j cv_j, including the splat in flight, as in K17 (it needs the pixel's total: an accumulated-map
-// forward into scratch precedes this kernel).  P Q R2 R3 R4 Vs join v_combined in K17's columns; V_i = sum of vis * g_i goes to
+// forward into scratch precedes this kernel).  P Q R2 R3 R4 Vs join v_combined in K17's columns; V_i = sum of vis * vg_i goes to
 // v_attr[cg * NV + i], which a small kernel of the map's own carries on behind K18.
 template <bool SMOOTH, class P>
 __global__ __launch_bounds__(64, 6) void map_backward_kernel(MapUniforms u, const uint32_t* __restrict__ isect_gids,
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(64, 6) void map_backward_kernel(MapUniforms u, cons
                             // --- gradients (tolerance-checked) ---
                             const float vis = alpha_eff * T;
 #pragma unroll
-                            for (int i = 0; i < NV; ++i) aV[i] = __builtin_fmaf(vis, pix[q].g[i], aV[i]);
+                            for (int i = 0; i < NV; ++i) aV[i] = __builtin_fmaf(vis, P::vg(r, pix[q], i), aV[i]);
                             const float cv = P::cv(r, pix[q]);
                             const float v_alpha_eff = __builtin_fmaf(T, cv, -sS[q]) * __builtin_amdgcn_rcpf(1.0f - alpha_eff);
                             const float v_alpha = SMOOTH ? v_alpha_eff * (alpha_cutoff_weight(alpha) + alpha * alpha_cutoff_weight_deriv(alpha)) : v_alpha_eff;

@@ -136,6 +136,7 @@ struct NormalMap {
         return __builtin_fmaf(vz, nz, __builtin_fmaf(vy, ny, vx * nx));
     }
     static BH_DEV float cv(const Rec& r, const Pix& px) { return __builtin_fmaf(px.g[2], r.s2.y, __builtin_fmaf(px.g[1], r.s2.x, px.g[0] * r.s1.w)); }
+    static BH_DEV float vg(const Rec&, const Pix& px, int i) { return px.g[i]; }
 };
 
 // v_quat += the chain of Vn through the sign, R_view^T, column k of the rotation matrix and the quaternion's normalisation, behind

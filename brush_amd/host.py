@@ -573,15 +573,21 @@ class RenderNode:
         its length (0 where that is 0); a forward of a tile-row window writes its rows, the rest is 0."""
         return render_normal(self, mode)
 
-    def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False, v_normal=None, normal_mode="accumulated"):
-        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>] [+ <v_normal, normal(normal_mode)>]; v_output may be None
-        when v_depth or v_normal is given.
+    def distortion(self, kind="z", near=0.2, far=1000.0):
+        """The node's distortion map [H,W] f32 (bh_render_distortion): sum over pairs of w_i w_j (m_i - m_j)^2 with m = z ("z") or
+        2DGS's far (z - near) / ((far - near) z) ("ndc"); a forward of a tile-row window writes its rows, the rest is 0."""
+        return render_distortion(self, kind, near, far)
+
+    def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False, v_normal=None, normal_mode="accumulated", v_distortion=None,
+                 distortion="z", distortion_near=0.2, distortion_far=1000.0):
+        """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>] [+ <v_normal, normal(normal_mode)>] [+ <v_distortion,
+        distortion(kind `distortion`, distortion_near, distortion_far)>]; v_output may be None when another cotangent is given.
         pose=True (bh_render_backward_pose_saved): also "v_viewmat", the twelve f32 of the gradient with respect to the camera's
         view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
-        if v_output is None and v_depth is None and v_normal is None:
+        if v_output is None and v_depth is None and v_normal is None and v_distortion is None:
             raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
         if v_output is not None:
             v_output = _f32c(v_output, dev).reshape(h, w, 4)
@@ -591,7 +597,21 @@ class RenderNode:
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
         v_vm = None
-        if v_normal is not None:
+        if v_distortion is not None:
+            if pose:
+                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_distortion)")
+            v_distortion = _f32c(v_distortion, dev).reshape(h, w)
+            if v_depth is not None:
+                v_depth = _f32c(v_depth, dev).reshape(h, w)
+            if v_normal is not None:
+                v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
+            cfg = _distortion_config(distortion, distortion_near, distortion_far)
+            ctx.check(ctx.lib.bh_render_backward_distortion_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
+                                                                  _ptr(v_depth) if v_depth is not None else None, _depth_mode(depth_mode),
+                                                                  _ptr(v_normal) if v_normal is not None else None, _normal_mode(normal_mode),
+                                                                  _ptr(v_distortion), C.byref(cfg), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
+                                                                  _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+        elif v_normal is not None:
             if pose:
                 raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_normal)")
             v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
@@ -690,6 +710,55 @@ def render_normal(saved: "RenderNode", mode="accumulated", out=None):
         raise BrushHipError("render_normal: `out` must be a contiguous float32 [%d, %d, 3] tensor on %s" % (h, w, dev))
     ctx.check(ctx.lib.bh_render_normal(ctx._h, C.byref(saved.out), _ptr(saved._folded[0]), _normal_mode(mode), _ptr(out)))
     return out
+
+
+DISTORTION_KINDS = {"z": _ffi.DISTORTION_Z, "ndc": _ffi.DISTORTION_NDC}
+
+
+def _distortion_kind(kind):
+    return int(DISTORTION_KINDS[kind]) if isinstance(kind, str) else int(kind)
+
+
+def _distortion_config(kind, near, far):
+    return _ffi.BhDistortionConfig(kind=_distortion_kind(kind), near_z=float(near), far_z=float(far))
+
+
+def render_distortion(saved: "RenderNode", kind="z", near=0.2, far=1000.0, out=None, moments=False):
+    """Distortion map [H,W] f32 of a differentiable render's saved state (bh_render_distortion; include/brush_hip_distortion.h), or —
+    moments=True — its moment map [H,W,4] = (A, M1', M2', r) (bh_render_distortion_moments; what distortion_loss and the backward
+    read).  The node must be the ctx's most recent forward or a retained one.  `out`: a contiguous f32 tensor of that shape to write
+    into (rows outside a tile-row window are left as they are); otherwise a zero-filled one is returned."""
+    ctx, dev = saved.ctx, saved.splats.device
+    w, h = saved.img_size
+    shape = (h, w, 4) if moments else (h, w)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=dev)
+    if not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape
+            and out.device == torch.device(dev)):
+        raise BrushHipError("render_distortion: `out` must be a contiguous float32 %s tensor on %s" % (list(shape), dev))
+    cfg = _distortion_config(kind, near, far)
+    fn = ctx.lib.bh_render_distortion_moments if moments else ctx.lib.bh_render_distortion
+    ctx.check(fn(ctx._h, C.byref(saved.out), C.byref(cfg), _ptr(out)))
+    return out
+
+
+def distortion_loss(dist_or_moments, weight=1.0, ctx: Optional[Context] = None):
+    """weight * sum(dist) / (H W) of a distortion map [H,W] or a moment map [H,W,4] (bh_distortion_loss): -> loss [2] device f32 =
+    (the loss, the number of pixels).  f64 sums in a fixed order: two calls give the same bits.  The gradient with respect to the
+    distortion map is the constant weight / (H W).  Queued on the ctx stream: nothing is read back."""
+    dev = dist_or_moments.device
+    ctx = ctx or get_context(dev)
+    m = _f32c(dist_or_moments, dev)
+    if m.dim() == 2:
+        channels = 1
+    elif m.dim() == 3 and m.shape[2] == 4:
+        channels = 4
+    else:
+        raise ValueError("distortion_loss: a distortion map [H, W] or a moment map [H, W, 4]")
+    h, w = m.shape[0], m.shape[1]
+    loss = torch.empty((2,), dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.bh_distortion_loss(ctx._h, _ptr(m), h, w, channels, float(weight), _ptr(loss)))
+    return loss
 
 
 def depth_to_normal(depth, camera, ctx: Optional[Context] = None):
@@ -1254,6 +1323,13 @@ class TrainConfig:
     # normal_loss_from_iter on (2DGS starts it at 7000); pinhole cameras, whole frames
     normal_loss_weight: float = 0.0
     normal_loss_from_iter: int = 0
+    # not in the reference: > 0 adds the distortion term (brush_hip_distortion.h; 2DGS's depth distortion, its companion regulariser)
+    # from step distortion_loss_from_iter on (2DGS starts it at 3000); kind "z", or "ndc" with distortion_near / distortion_far
+    distortion_loss_weight: float = 0.0
+    distortion_loss_from_iter: int = 0
+    distortion_kind: str = "z"
+    distortion_near: float = 0.2
+    distortion_far: float = 1000.0
 
     def depth_weight_at(self, step: int) -> float:
         """The depth term's weight at step `step` (from 1): w0 * (w1 / w0) ** ((step - 1) / total_train_iters)."""
@@ -1852,6 +1928,14 @@ class SplatTrainer:
             ctx.check(ctx.lib.bh_train_set_normal(ctx._h, C.byref(_ffi.BhNormalTermConfig(weight=nw))))
         else:
             ctx.check(ctx.lib.bh_train_set_normal(ctx._h, None))
+        # ... and so is the distortion term (bh_train_set_distortion), from distortion_loss_from_iter on
+        xw = float(getattr(c, "distortion_loss_weight", 0.0))
+        if xw > 0.0 and self.step_count + 1 >= int(getattr(c, "distortion_loss_from_iter", 0)):
+            xt = _ffi.BhDistortionTermConfig(weight=xw, kind=_distortion_kind(getattr(c, "distortion_kind", "z")),
+                                             near_z=float(getattr(c, "distortion_near", 0.2)), far_z=float(getattr(c, "distortion_far", 1000.0)))
+            ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, C.byref(xt)))
+        else:
+            ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, None))
         if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
             self.batch_patch(b)
         lw = float(getattr(c, "lpips_loss_weight", 0.0))
@@ -1872,6 +1956,7 @@ class SplatTrainer:
         finally:
             ctx.lib.bh_train_set_depth(ctx._h, None)
             ctx.lib.bh_train_set_normal(ctx._h, None)
+            ctx.lib.bh_train_set_distortion(ctx._h, None)
             if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
             if ex is not None:

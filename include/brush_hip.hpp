@@ -32,6 +32,9 @@
 //                                                   depth loss, the step's depth term, held-out depth metrics; brush_hip_depth_loss.h)
 //   brush_hip::normal_consistency_value_and_grad / train_set_normal   not in the reference: the normal-consistency regulariser (a fused
 //                                                   loss with both gradients, the step's normal term; brush_hip_normal_loss.h)
+//   RenderNode::distortion / backward_distortion, brush_hip::distortion_loss / train_set_distortion   not in the reference: distortion
+//                                                   maps (2DGS's depth distortion), their gradient, the loss and the step's term
+//                                                   (brush_hip_distortion.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -63,6 +66,7 @@
 #include "brush_hip_depth_loss.h"
 #include "brush_hip_normal.h"
 #include "brush_hip_normal_loss.h"
+#include "brush_hip_distortion.h"
 
 namespace brush_hip {
 
@@ -483,6 +487,41 @@ class RenderNode {
     }
     SplatGrads backward_normal(const float* v_normal, uint32_t normal_mode = BH_NORMAL_ACCUMULATED) const {
         return backward_normal(nullptr, nullptr, BH_DEPTH_EXPECTED, v_normal, normal_mode);
+    }
+    // The node's distortion map [H,W] f32 (brush_hip_distortion.h): sum over pairs of w_i w_j (m_i - m_j)^2, m = z (BH_DISTORTION_Z) or
+    // 2DGS's far (z - near) / ((far - near) z) (BH_DISTORTION_NDC).  moments: the moment map [H,W,4] = (A, M1', M2', r) instead.  Rows
+    // outside a tile-row window stay 0.
+    DeviceBuffer<float> distortion(const BhDistortionConfig& cfg = BhDistortionConfig{}, bool moments = false) const {
+        static_assert(sizeof(BhDistortionConfig) == 16, "BhDistortionConfig layout");
+        DeviceBuffer<float> d;
+        d.resize((size_t)aux.img_w * aux.img_h * (moments ? 4 : 1));
+        d.zero();
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the fill is ordered before the ctx stream's kernel
+        ctx_.check(moments ? bh_render_distortion_moments(ctx_.get(), &aux.raw, &cfg, d.data()) : bh_render_distortion(ctx_.get(), &aux.raw, &cfg, d.data()));
+        ctx_.sync();
+        return d;
+    }
+    // gradients of <v_output, image> + <v_depth, depth(depth_mode)> + <v_normal, normal(normal_mode)> + <v_distortion, distortion(cfg)>
+    // in one backward; every cotangent but v_distortion may be nullptr
+    SplatGrads backward_distortion(const float* v_output, const float* v_depth, uint32_t depth_mode, const float* v_normal, uint32_t normal_mode,
+                                   const float* v_distortion, const BhDistortionConfig& cfg = BhDistortionConfig{}) const {
+        const uint32_t n = splats_.num_splats();
+        SplatGrads g;
+        g.v_transforms.resize((size_t)n * 10);
+        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
+        g.v_raw_opacities.resize(n);
+        g.v_refine_weight.resize(n);
+        ctx_.check(bh_render_backward_distortion_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, v_distortion, &cfg,
+                                                       folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(), g.v_sh_coeffs.data(),
+                                                       g.v_raw_opacities.data(), g.v_refine_weight.data()));
+        if (splats_.min_scale)
+            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
+                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
+        ctx_.sync();
+        return g;
+    }
+    SplatGrads backward_distortion(const float* v_distortion, const BhDistortionConfig& cfg = BhDistortionConfig{}) const {
+        return backward_distortion(nullptr, nullptr, BH_DEPTH_EXPECTED, nullptr, BH_NORMAL_ACCUMULATED, v_distortion, cfg);
     }
     // gradients of <v_output, image> and, into v_viewmat (device, 12 floats in the layout of BhCamera.vm), its gradient with respect
     // to the camera's view matrix (brush_hip_pose.h); the four splat outputs are backward(v_output)'s
@@ -1297,6 +1336,25 @@ inline void train_set_normal(const Context& ctx, float weight) {
     BhNormalTermConfig cfg{};
     cfg.weight = weight;
     train_set_normal(ctx, &cfg);
+}
+
+// ---- distortion (brush_hip_distortion.h; not in the reference) -------------------------------------------------------------------------
+// loss [2] (device) = (weight * sum(dist) / (H W), pixels) of a distortion map (channels 1) or a moment map (channels 4); nothing is read back
+inline void distortion_loss(const Context& ctx, const float* map, uint32_t h, uint32_t w, uint32_t channels, float weight, float* loss) {
+    ctx.check(bh_distortion_loss(ctx.get(), map, h, w, channels, weight, loss));
+}
+// bh_train_step on this ctx adds the distortion term (weight <= 0: no term); nullptr detaches
+inline void train_set_distortion(const Context& ctx, const BhDistortionTermConfig* cfg) {
+    static_assert(sizeof(BhDistortionTermConfig) == 16, "BhDistortionTermConfig layout");
+    ctx.check(bh_train_set_distortion(ctx.get(), cfg));
+}
+inline void train_set_distortion(const Context& ctx, float weight, uint32_t kind = BH_DISTORTION_Z, float near_z = 0.2f, float far_z = 1000.0f) {
+    BhDistortionTermConfig cfg{};
+    cfg.weight = weight;
+    cfg.kind = kind;
+    cfg.near_z = near_z;
+    cfg.far_z = far_z;
+    train_set_distortion(ctx, &cfg);
 }
 
 // ---- point-cloud initialisation (brush-train/src/splat_init.rs:179-242; train_stream.rs:100-123) ---------------------------------
