@@ -44,6 +44,9 @@ Names and argument meaning follow the reference (paths under
     render_distortion / RenderNode.distortion / RenderNode.backward(v_distortion=) / distortion_loss / TrainConfig.distortion_loss_weight
                                          distortion maps with their gradient, the loss and a term in the step (not in the reference;
                                          2DGS's depth distortion; include/brush_hip_distortion.h)
+    BilateralGridTable / SplatTrainer(bilagrid=)   per-view bilateral grids: a grid of affine colour transforms per training view, sliced
+                                         at (x, y, luminance) before the loss, with a total-variation term and Adam on the device (not in
+                                         the reference; gsplat's lib_bilagrid; include/brush_hip_bilagrid.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -58,6 +61,6 @@ from .host import (  # noqa: F401
     Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
     PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
-    render_distortion, distortion_loss,
+    render_distortion, distortion_loss, BilateralGridTable,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -268,6 +268,23 @@ EXPOSURE_SYMBOLS = {
     "bh_train_set_exposure": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/brush_hip_bilagrid.h declares (per-view bilateral grids: a device table of grids of affine colour transforms)
+BILAGRID_SYMBOLS = {
+    "bh_bilagrid_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_bilagrid_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bh_bilagrid_dims": (C.c_int, [C.c_void_p, C.c_void_p, u32p, u32p, u32p, u32p]),
+    "bh_bilagrid_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_bilagrid_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_bilagrid_get_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, fp]),
+    "bh_bilagrid_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, fp, fp, u32p]),
+    "bh_bilagrid_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, fp, fp, C.c_uint32]),
+    "bh_bilagrid_set_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bh_bilagrid_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_bilagrid_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_int]),
+    "bh_bilagrid_tv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bh_train_set_bilagrid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float]),
+}
+
 # every symbol include/brush_hip_depth_loss.h declares (depth supervision: the fused depth loss, the step's depth term, depth metrics)
 DEPTH_LOSS_L1, DEPTH_LOSS_DISPARITY = 0, 1   # BH_DEPTH_LOSS_*
 
@@ -365,7 +382,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS))
     return _lib
 
 
@@ -374,6 +391,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

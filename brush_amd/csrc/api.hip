@@ -296,6 +296,7 @@ void bh_destroy(bh_ctx* ctx) {
     if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);
     if (ctx->image_tab_ev) (void)hipEventDestroy(ctx->image_tab_ev);
     bh::exposure_free_all(ctx);
+    bh::bilagrid_free_all(ctx);
     if (ctx->comm) (void)bh_comm_destroy(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1496,6 +1497,19 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (batch->image_hook || eu.tile_y0 != 0u || eu.tile_y1 != eu.tile_bh)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the exposure term needs the whole frame on this rank (no tile-row partition)");
     }
+    // a bilateral-grid table (brush_hip_bilagrid.h): the exposure table's rules, and the two are alternatives
+    bh_bilagrid* const bilagrid = ctx->bilagrid;
+    if (bilagrid) {
+        if (exposure)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: an exposure table and a bilateral-grid table cannot be attached together (they are alternatives: detach one)");
+        if (batch->view_id == 0u || batch->view_id > bilagrid_views(bilagrid))
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table the batch's view_id must be 1 .. n_views");
+        const ViewUniforms gu = make_uniforms(batch->camera);
+        if (batch->image_hook || gu.tile_y0 != 0u || gu.tile_y1 != gu.tile_bh)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the bilateral-grid term needs the whole frame on this rank (no tile-row partition)");
+        if ((uint64_t)batch->camera.img_w * batch->camera.img_h > 0x7FFFFFFFull)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table h * w must stay below 2^31");
+    }
     // a depth target (brush_hip_depth_loss.h): refused before anything is queued; weight <= 0 is no term at all
     const BhDepthTarget* const depth_target = (ctx->depth_attached && ctx->depth_target.weight > 0.0f) ? &ctx->depth_target : nullptr;
     if (depth_target) {
@@ -1631,6 +1645,8 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // with an exposure table the loss reads the exposed frame from a slot of its own: out_img is what K17 replays from
     float* exposed = nullptr;
     if (exposure && !(exposed = (float*)ensure(ctx, SLOT_EXPOSED, hw * 16))) return BH_ERR_OOM;
+    // ... and with a bilateral-grid table the sliced frame, likewise (from here on `exposed` is either one's corrected frame)
+    if (bilagrid && !(exposed = (float*)ensure(ctx, SLOT_BILAGRID_SLICED, hw * 16))) return BH_ERR_OOM;
     // the loss scalar goes straight into pinned host memory (bh_sync hands it to stats->loss): no copy launch
     float* loss_host = reinterpret_cast<float*>(ctx->host_counters) + HOST_LOSS_WORD;
     const float dl_rgb = 1.0f / (float)(hw * 3);
@@ -1652,9 +1668,13 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
             return launch_image_loss_fused_window(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, wu.tile_y0, wu.tile_y1,
                                                   loss_dev, v_output, loss_host, started_host, started_tag);
         }
-        if (exposed) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
+        if (exposure) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
             ProfScope ps(ctx, "Exposure");
             BH_TRY(launch_exposure_apply(ctx, exposure, batch->view_id, ro.out_img, H, W, exposed));
+        }
+        if (bilagrid) {   // (likewise)
+            ProfScope ps(ctx, "Bilagrid");
+            BH_TRY(launch_bilagrid_slice(ctx, bilagrid, batch->view_id, ro.out_img, H, W, exposed));
         }
         return launch_image_loss_fused(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
                                        started_tag);
@@ -1683,9 +1703,21 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // in place on the device (no host wait)
     if (lpips_on) BH_TRY(lpips_train_term(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
     // ---- exposure backward: v_output becomes A^T v' in place (x = the frame as rendered), the view's row takes its Adam step
-    if (exposed) {
+    if (exposure) {
         ProfScope ps(ctx, "Exposure");
         BH_TRY(launch_exposure_backward(ctx, exposure, batch->view_id, ro.out_img, v_output, H, W, v_output, /*update=*/true));
+    }
+    // ---- bilateral grid: loss += tv_weight TV(grid) in f32 (no launch at weight 0), then v_output becomes v_img in place and the
+    // view's grid takes its Adam step on v_g + tv_weight dTV
+    if (bilagrid) {
+        ProfScope ps(ctx, "Bilagrid");
+        const float tvw = ctx->bilagrid_tv_weight;
+        if (tvw != 0.0f) {
+            float* tv_value = bilagrid_tv_scratch(ctx);
+            if (!tv_value) return BH_ERR_OOM;
+            BH_TRY(launch_bilagrid_tv(ctx, bilagrid, batch->view_id, tv_value, tvw, loss_dev, loss_host));
+        }
+        BH_TRY(launch_bilagrid_backward(ctx, bilagrid, batch->view_id, ro.out_img, v_output, H, W, v_output, tvw, /*update=*/true));
     }
 
     // ---- depth term (brush_hip_depth_loss.h): the frame is final here — a second attempt with complete lists has replaced it, if

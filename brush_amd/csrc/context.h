@@ -13,6 +13,7 @@
 #include "../../include/brush_hip_lpips.h"
 #include "../../include/brush_hip_image.h"
 #include "../../include/brush_hip_exposure.h"
+#include "../../include/brush_hip_bilagrid.h"
 #include "../../include/brush_hip_depth_loss.h"
 #include "../../include/brush_hip_normal_loss.h"
 #include "../../include/brush_hip_distortion.h"
@@ -92,6 +93,8 @@ enum Slot : int {
     SLOT_DISTORTION,         // bh_render_distortion / bh_render_backward_distortion_saved: NDC depths m [Nv] | v_m (the term's own v_z) [Nv] | the frame's moment map [H,W,4] (distortion.hip)
     SLOT_DISTORTION_LOSS,    // bh_distortion_loss: one f64 row of 4 per block, 2 used (distortion.hip)
     SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
+    SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
+    SLOT_BILAGRID_SLICED,    // bh_train_step with a bilateral-grid table: [H,W,4] the sliced frame the loss reads (out_img stays as rendered)
     SLOT_COUNT
 };
 
@@ -423,6 +426,9 @@ struct bh_ctx {
     BhDistortionTermConfig distortion_term{};
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
+    bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
+    float bilagrid_tv_weight = 0.0f;  // ... and adds this much of the grid's total variation to the loss
+    std::vector<bh_bilagrid*> bilagrids;   // every table of this ctx (brush_hip_bilagrid.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
@@ -571,6 +577,16 @@ int launch_exposure_apply(bh_ctx* ctx, const bh_exposure* tab, uint32_t view, co
 int launch_exposure_backward(bh_ctx* ctx, bh_exposure* tab, uint32_t view, const float* img, const float* v_exposed, uint32_t h, uint32_t w,
                              float* v_img, bool update);
 void exposure_free_all(bh_ctx* ctx);   // bh_destroy
+// bilagrid.hip: the slice of `img` with the grid of `view` (1 .. bilagrid_views), its backward: v_img (in place allowed), grad[view] =
+// v_g + tv_weight dTV and one Adam step of the row when `update`, and TV of the row into value[0]; accum as launch_depth_loss's, with
+// weight * TV added (brush_hip_bilagrid.h).  The view and the image size are already checked.
+uint32_t bilagrid_views(const bh_bilagrid* tab);
+int launch_bilagrid_slice(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out);
+int launch_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* tab, uint32_t view, const float* img, const float* v_sliced, uint32_t h, uint32_t w, float* v_img,
+                             float tv_weight, bool update);
+int launch_bilagrid_tv(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, float* value, float weight, float* accum, float* accum_host);
+float* bilagrid_tv_scratch(bh_ctx* ctx);   // four floats of SLOT_BILAGRID for the train step's TV value
+void bilagrid_free_all(bh_ctx* ctx);   // bh_destroy
 
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view

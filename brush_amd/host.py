@@ -1069,6 +1069,142 @@ class ExposureTable:
 
 
 # ---------------------------------------------------------------------------
+# Per-view bilateral grids (include/brush_hip_bilagrid.h)
+# ---------------------------------------------------------------------------
+class BilateralGridTable:
+    """A device table of one bilateral grid per training view: g[Hg,Wg,L,12] f32, a grid of row-major 3x4 colour matrices looked up
+    by trilinear interpolation at (x, y, luminance) and applied to the rasterizer's image before the loss, with its Adam moments
+    and update on the device (bh_bilagrid_*; gsplat's lib_bilagrid).  `grid` is (Wg, Hg, L), gsplat's (grid_X, grid_Y, grid_W).
+    Views are numbered from 1.  Nothing here reads back except the getters (`params`, `grads`, `state`, and `tv` on request).
+    SplatTrainer(bilagrid=table) attaches it to the train step.  Data parallel over cameras: the table is per process, nothing is
+    all-reduced, a view must stay with one rank."""
+
+    def __init__(self, n_views, grid=(16, 16, 8), lr=2e-3, beta1=0.9, beta2=0.999, eps=1e-15, ctx: Optional[Context] = None):
+        ctx = ctx or get_context()
+        self.ctx, self.lib, self.n_views = ctx, ctx.lib, int(n_views)
+        self.grid_w, self.grid_h, self.grid_l = (int(v) for v in grid)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.bh_bilagrid_create(ctx._h, self.n_views, self.grid_w, self.grid_h, self.grid_l, C.byref(h)))
+        self._h = h
+        self.shape = (self.grid_h, self.grid_w, self.grid_l, 12)   # one view's row
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
+        self.set_lr(lr)
+
+    def set_lr(self, lr):
+        """The learning rate of every following update (bh_bilagrid_set_adam); 0 freezes the grids while their moments still move."""
+        self.ctx.check(self.lib.bh_bilagrid_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
+        self.lr = float(lr)
+
+    def _get(self, fn):
+        import numpy as np
+        out = np.empty((self.n_views,) + self.shape, np.float32)
+        self.ctx.check(fn(self.ctx._h, self._h, 1, self.n_views, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    @property
+    def params(self):
+        """[V,Hg,Wg,L,12] f32 numpy copy of every grid (one synchronisation); assign an array of the same shape to set them."""
+        return self._get(self.lib.bh_bilagrid_get_params)
+
+    @params.setter
+    def params(self, value):
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(value, np.float32))
+        if a.shape != (self.n_views,) + self.shape:
+            raise ValueError("params must be %r" % ((self.n_views,) + self.shape,))
+        self.ctx.check(self.lib.bh_bilagrid_set_params(self.ctx._h, self._h, 1, self.n_views, a.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_view(self, view, g):
+        """The grid of `view` (from 1) = g [Hg,Wg,L,12]."""
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(g, np.float32))
+        if a.shape != self.shape:
+            raise ValueError("a view's grid must be %r" % (self.shape,))
+        self.ctx.check(self.lib.bh_bilagrid_set_params(self.ctx._h, self._h, int(view), 1, a.ctypes.data_as(C.POINTER(C.c_float))))
+
+    @property
+    def grads(self):
+        """[V,Hg,Wg,L,12] f32: the last gradient written for each grid, the TV term's included (zeros for an untouched row)."""
+        return self._get(self.lib.bh_bilagrid_get_grad)
+
+    def state(self, view):
+        """(m1, m2 [Hg,Wg,L,12] f32, t) of row `view`: its Adam moments and step count."""
+        import numpy as np
+        m1, m2, t = np.empty(self.shape, np.float32), np.empty(self.shape, np.float32), C.c_uint32()
+        p = C.POINTER(C.c_float)
+        self.ctx.check(self.lib.bh_bilagrid_get_state(self.ctx._h, self._h, int(view), m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
+        return m1, m2, int(t.value)
+
+    def set_state(self, view, m1, m2, t):
+        """Puts a row's Adam state back (resuming from a checkpoint)."""
+        import numpy as np
+        a, b = np.ascontiguousarray(m1, np.float32), np.ascontiguousarray(m2, np.float32)
+        if a.shape != self.shape or b.shape != self.shape:
+            raise ValueError("moments must be %r" % (self.shape,))
+        p = C.POINTER(C.c_float)
+        self.ctx.check(self.lib.bh_bilagrid_set_state(self.ctx._h, self._h, int(view), a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+
+    def slice(self, view, img, out=None):
+        """y = A(x, y, luminance) x of `img` [H,W,4] f32 with the grid of `view`; `out` may be `img` (in place)."""
+        img = _aligned_hwc4(img, img.device)
+        if out is None:
+            out = torch.empty_like(img)
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        self.ctx.check(self.lib.bh_bilagrid_slice(self.ctx._h, self._h, int(view), _ptr(img), h, w, _ptr(out)))
+        return out
+
+    def backward(self, view, img, v_sliced, tv_weight=0.0, update=False, out=None):
+        """v_img of the cotangent `v_sliced` (`out` may be `v_sliced`), grads[view] = v_g of (img, v_sliced) + tv_weight dTV/dg, and
+        with `update` one Adam step of the grid of `view` on it."""
+        img = _aligned_hwc4(img, img.device)
+        v = _aligned_hwc4(v_sliced, img.device)
+        if v.shape != img.shape:
+            raise ValueError("v_sliced must have the shape of img")
+        if out is None:
+            out = torch.empty_like(v)
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        self.ctx.check(self.lib.bh_bilagrid_backward(self.ctx._h, self._h, int(view), _ptr(img), _ptr(v), h, w, _ptr(out), float(tv_weight),
+                                                     1 if update else 0))
+        return out
+
+    def tv(self, view, out=None):
+        """The total variation of the grid of `view` as a device tensor of one f32 (`out`, or a new one on the ctx's device)."""
+        if out is None:
+            out = torch.empty(1, dtype=torch.float32, device=self.ctx.device)
+        self.ctx.check(self.lib.bh_bilagrid_tv(self.ctx._h, self._h, int(view), _ptr(out)))
+        return out
+
+    def to_gsplat(self):
+        """Every grid in gsplat's layout: grids[v, k, l, j, i] = g[v][j][i][l][k], a [V,12,L,Hg,Wg] f32 numpy array."""
+        import numpy as np
+        return np.ascontiguousarray(self.params.transpose(0, 4, 3, 1, 2))
+
+    def from_gsplat(self, grids):
+        """Sets every grid from gsplat's BilateralGrid.grids [V,12,L,Hg,Wg] (a numpy array or a tensor)."""
+        import numpy as np
+        a = np.asarray(grids.detach().cpu().numpy() if hasattr(grids, "detach") else grids, np.float32)
+        if a.shape != (self.n_views, 12, self.grid_l, self.grid_h, self.grid_w):
+            raise ValueError("grids must be [%d, 12, %d, %d, %d]" % (self.n_views, self.grid_l, self.grid_h, self.grid_w))
+        self.params = a.transpose(0, 3, 4, 2, 1)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):   # (a closed context has freed its tables)
+                self.lib.bh_bilagrid_destroy(self.ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------
 # PLY at the edges (brush-serde)
 # ---------------------------------------------------------------------------
 def splat_to_ply(splats: Splats, up_axis=None, ctx: Optional[Context] = None) -> bytes:
@@ -1666,7 +1802,8 @@ class SplatTrainer:
     def __init__(self, config: TrainConfig, median_scene_scale: float = 1.0, process_group=None, ctx: Optional[Context] = None,
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
                  allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None,
-                 exposure: Optional["ExposureTable"] = None, exposure_lr=None):
+                 exposure: Optional["ExposureTable"] = None, exposure_lr=None, bilagrid: Optional["BilateralGridTable"] = None, bilagrid_lr=None,
+                 bilagrid_tv_weight: float = 10.0):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -1688,7 +1825,13 @@ class SplatTrainer:
         exposure: an ExposureTable (bh_train_set_exposure): every step exposes its frame with the row of the batch's view_id
         (1 .. n_views) before the loss and updates that row on the device: no readback, no synchronisation.  exposure_lr: an
         optional callable of the step number (from 1) giving the table's learning rate for that step.  Not with partition
-        "tiles"."""
+        "tiles".
+
+        bilagrid: a BilateralGridTable (bh_train_set_bilagrid), the alternative to `exposure` for photometric effects that vary over
+        the frame or with brightness: every step slices its frame with the grid of the batch's view_id before the loss, adds
+        bilagrid_tv_weight times the grid's total variation to the loss (10 is gsplat's weight) and updates that grid on the
+        device.  bilagrid_lr: an optional callable of the step number (from 1), as exposure_lr.  Not with partition "tiles" and
+        not together with `exposure`."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if pose_optimizer is not None and partition == "tiles":
@@ -1698,6 +1841,11 @@ class SplatTrainer:
         self.pose_optimizer = pose_optimizer
         self._pose_buf = None
         self.exposure, self.exposure_lr = exposure, exposure_lr
+        if bilagrid is not None and partition == "tiles":
+            raise ValueError("bilagrid is not available with partition 'tiles'")
+        if bilagrid is not None and exposure is not None:
+            raise ValueError("bilagrid and exposure are alternatives: pass one of them")
+        self.bilagrid, self.bilagrid_lr, self.bilagrid_tv_weight = bilagrid, bilagrid_lr, float(bilagrid_tv_weight)
         if allreduce not in ("ring", "direct"):
             raise ValueError("allreduce must be 'ring' (all_reduce / ncclAllReduce) or 'direct' (reduce-scatter + all-gather over point-to-point messages)")
         # how long messages of the gradient exchange are summed: the collective library's all-reduce, or the direct algorithm for a
@@ -1950,6 +2098,11 @@ class SplatTrainer:
             if self.exposure_lr is not None:
                 ex.set_lr(self.exposure_lr(self.step_count + 1))
             ctx.check(ctx.lib.bh_train_set_exposure(ctx._h, ex._h))
+        bg = self.bilagrid
+        if bg is not None:
+            if self.bilagrid_lr is not None:
+                bg.set_lr(self.bilagrid_lr(self.step_count + 1))
+            ctx.check(ctx.lib.bh_train_set_bilagrid(ctx._h, bg._h, self.bilagrid_tv_weight))
         try:
             ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                             float(scale), C.byref(stats)))
@@ -1961,6 +2114,8 @@ class SplatTrainer:
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
             if ex is not None:
                 ctx.lib.bh_train_set_exposure(ctx._h, None)
+            if bg is not None:
+                ctx.lib.bh_train_set_bilagrid(ctx._h, None, 0.0)
         if po is not None:
             po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
         self.step_count = st.step_count

@@ -35,6 +35,9 @@
 //   RenderNode::distortion / backward_distortion, brush_hip::distortion_loss / train_set_distortion   not in the reference: distortion
 //                                                   maps (2DGS's depth distortion), their gradient, the loss and the step's term
 //                                                   (brush_hip_distortion.h)
+//   brush_hip::BilateralGridTable / train_set_bilagrid   not in the reference: per-view bilateral grids (a grid of affine colour
+//                                                   transforms per training view, sliced at (x, y, luminance), TV term, Adam on the
+//                                                   device; gsplat's lib_bilagrid; brush_hip_bilagrid.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -67,6 +70,7 @@
 #include "brush_hip_normal.h"
 #include "brush_hip_normal_loss.h"
 #include "brush_hip_distortion.h"
+#include "brush_hip_bilagrid.h"
 
 namespace brush_hip {
 
@@ -1268,6 +1272,82 @@ private:
 // bh_train_step on this ctx exposes its frame with the row of the batch's view_id and updates that row; nullptr detaches
 inline void train_set_exposure(const Context& ctx, const ExposureTable* table) {
     ctx.check(bh_train_set_exposure(ctx.get(), table ? table->get() : nullptr));
+}
+
+// ---- per-view bilateral grids (brush_hip_bilagrid.h; not in the reference) ----------------------------------------------------------
+// A device table of one grid g[Hg][Wg][L][12] of row-major 3x4 colour matrices per training view, sliced by trilinear interpolation at
+// (x, y, luminance), with Adam on the device (bh_bilagrid_*).  Views are numbered from 1.  Move-only; destroy it before its Context (a
+// Context that dies first frees the table itself, and this handle must then not be used).  Only the getters read back.
+class BilateralGridTable {
+public:
+    BilateralGridTable(const Context& ctx, uint32_t n_views, uint32_t grid_w = 16, uint32_t grid_h = 16, uint32_t grid_l = 8, double lr = 2e-3,
+                       double beta1 = 0.9, double beta2 = 0.999, double eps = 1e-15)
+        : ctx_(&ctx), n_(n_views), row_((size_t)grid_w * grid_h * grid_l * 12), beta1_(beta1), beta2_(beta2), eps_(eps) {
+        ctx.check(bh_bilagrid_create(ctx.get(), n_views, grid_w, grid_h, grid_l, &h_));
+        set_lr(lr);
+    }
+    BilateralGridTable(const BilateralGridTable&) = delete;
+    BilateralGridTable& operator=(const BilateralGridTable&) = delete;
+    BilateralGridTable(BilateralGridTable&& o) noexcept : ctx_(o.ctx_), h_(o.h_), n_(o.n_), row_(o.row_), beta1_(o.beta1_), beta2_(o.beta2_), eps_(o.eps_) {
+        o.h_ = nullptr;
+    }
+    ~BilateralGridTable() { if (h_) (void)bh_bilagrid_destroy(ctx_->get(), h_); }
+    bh_bilagrid* get() const { return h_; }
+    uint32_t n_views() const { return n_; }
+    size_t row_floats() const { return row_; }   // Hg Wg L 12
+    std::array<uint32_t, 3> grid() const {        // (Wg, Hg, L)
+        std::array<uint32_t, 3> g{};
+        ctx_->check(bh_bilagrid_dims(ctx_->get(), h_, nullptr, &g[0], &g[1], &g[2]));
+        return g;
+    }
+    void set_lr(double lr) { ctx_->check(bh_bilagrid_set_adam(ctx_->get(), h_, lr, beta1_, beta2_, eps_)); }
+    // every grid, [V,Hg,Wg,L,12] on the host (one synchronisation each)
+    std::vector<float> params() const {
+        std::vector<float> out((size_t)n_ * row_);
+        ctx_->check(bh_bilagrid_get_params(ctx_->get(), h_, 1, n_, out.data()));
+        return out;
+    }
+    std::vector<float> grads() const {
+        std::vector<float> out((size_t)n_ * row_);
+        ctx_->check(bh_bilagrid_get_grad(ctx_->get(), h_, 1, n_, out.data()));
+        return out;
+    }
+    void set_params(const std::vector<float>& rows, uint32_t first_view = 1) {
+        ctx_->check(bh_bilagrid_set_params(ctx_->get(), h_, first_view, (uint32_t)(rows.size() / row_), rows.data()));
+    }
+    struct State { std::vector<float> m1, m2; uint32_t t; };
+    State state(uint32_t view) const {
+        State s{std::vector<float>(row_), std::vector<float>(row_), 0u};
+        ctx_->check(bh_bilagrid_get_state(ctx_->get(), h_, view, s.m1.data(), s.m2.data(), &s.t));
+        return s;
+    }
+    void set_state(uint32_t view, const State& s) {
+        if (s.m1.size() != row_ || s.m2.size() != row_) throw Error(BH_ERR_INVALID_ARG, "BilateralGridTable::set_state: moments of another grid size");
+        ctx_->check(bh_bilagrid_set_state(ctx_->get(), h_, view, s.m1.data(), s.m2.data(), s.t));
+    }
+    // out = the slice of img [h,w,4] (device) with the grid of `view`; out may be img
+    void slice(uint32_t view, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) const {
+        ctx_->check(bh_bilagrid_slice(ctx_->get(), h_, view, img_hwc4, h, w, out_hwc4));
+    }
+    // v_img of v_sliced (may be in place), grads[view] = v_g + tv_weight dTV, and with `update` one Adam step of the grid
+    void backward(uint32_t view, const float* img_hwc4, const float* v_sliced, uint32_t h, uint32_t w, float* v_img, float tv_weight = 0.0f,
+                  bool update = false) {
+        ctx_->check(bh_bilagrid_backward(ctx_->get(), h_, view, img_hwc4, v_sliced, h, w, v_img, tv_weight, update ? 1 : 0));
+    }
+    // value_dev[0] = the total variation of the grid of `view`; nothing is read back
+    void tv(uint32_t view, float* value_dev) const { ctx_->check(bh_bilagrid_tv(ctx_->get(), h_, view, value_dev)); }
+
+private:
+    const Context* ctx_;
+    bh_bilagrid* h_ = nullptr;
+    uint32_t n_;
+    size_t row_;
+    double beta1_, beta2_, eps_;
+};
+// bh_train_step on this ctx slices its frame with the grid of the batch's view_id, adds tv_weight TV to the loss and updates that grid;
+// nullptr detaches.  Not together with an exposure table.
+inline void train_set_bilagrid(const Context& ctx, const BilateralGridTable* table, float tv_weight = 10.0f) {
+    ctx.check(bh_train_set_bilagrid(ctx.get(), table ? table->get() : nullptr, tv_weight));
 }
 
 // ---- depth supervision (brush_hip_depth_loss.h; not in the reference) --------------------------------------------------------------
