@@ -11,6 +11,7 @@
 
 #include "context.h"
 #include "device_rng.h"
+#include "view_table.h"
 
 namespace bh {
 
@@ -295,8 +296,7 @@ void bh_destroy(bh_ctx* ctx) {
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
     if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);
     if (ctx->image_tab_ev) (void)hipEventDestroy(ctx->image_tab_ev);
-    bh::exposure_free_all(ctx);
-    bh::bilagrid_free_all(ctx);
+    bh::view_tables_free_all(ctx);
     if (ctx->comm) (void)bh_comm_destroy(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1481,6 +1481,15 @@ extern "C" int bh_train_step(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState
     return rc;
 }
 
+// the two families of refusals a term of the step can meet, by the term's noun
+static int refuse_partial_frame(bh_ctx* ctx, const char* term) {
+    return set_error(ctx, BH_ERR_INVALID_ARG, std::string("train_step: the ") + term + " needs the whole frame on this rank (no tile-row partition)");
+}
+static int refuse_with_pose_grad(bh_ctx* ctx, const char* a_term, const char* the_term) {
+    return set_error(ctx, BH_ERR_INVALID_ARG, std::string("train_step: ") + a_term + " and a pose-gradient buffer cannot be attached together (the pose pass does not carry the " +
+                                                  the_term + "'s gradient)");
+}
+
 static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* st, const BhTrainBatch* batch,
                            bh_grad_hook hook, void* hook_user, float grad_scale, BhTrainStats* stats) {
     if (!cfg || !st || !batch || !stats) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null argument");
@@ -1488,25 +1497,24 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         !st->m2_sh || !st->m1_opac || !st->m2_opac || !st->refine_weight_norm || !st->vis_weight || !st->max_screen_size ||
         !batch->gt_packed)
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null state tensor");
-    // an exposure table (brush_hip_exposure.h): the batch's view names the row, and the term needs the whole frame on this rank
+    // the camera's tile-row window, and whether this rank has the whole frame to itself: every term below but the image loss needs that
+    const ViewUniforms win_u = make_uniforms(batch->camera);
+    const bool whole_frame = !batch->image_hook && win_u.tile_y0 == 0u && win_u.tile_y1 == win_u.tile_bh;
+    // an exposure table (brush_hip_exposure.h): the batch's view names the row
     bh_exposure* const exposure = ctx->exposure;
     if (exposure) {
-        if (batch->view_id == 0u || batch->view_id > exposure_views(exposure))
+        if (batch->view_id == 0u || batch->view_id > exposure->n_views)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with an exposure table the batch's view_id must be 1 .. n_views");
-        const ViewUniforms eu = make_uniforms(batch->camera);
-        if (batch->image_hook || eu.tile_y0 != 0u || eu.tile_y1 != eu.tile_bh)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the exposure term needs the whole frame on this rank (no tile-row partition)");
+        if (!whole_frame) return refuse_partial_frame(ctx, "exposure term");
     }
     // a bilateral-grid table (brush_hip_bilagrid.h): the exposure table's rules, and the two are alternatives
     bh_bilagrid* const bilagrid = ctx->bilagrid;
     if (bilagrid) {
         if (exposure)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: an exposure table and a bilateral-grid table cannot be attached together (they are alternatives: detach one)");
-        if (batch->view_id == 0u || batch->view_id > bilagrid_views(bilagrid))
+        if (batch->view_id == 0u || batch->view_id > bilagrid->n_views)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table the batch's view_id must be 1 .. n_views");
-        const ViewUniforms gu = make_uniforms(batch->camera);
-        if (batch->image_hook || gu.tile_y0 != 0u || gu.tile_y1 != gu.tile_bh)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the bilateral-grid term needs the whole frame on this rank (no tile-row partition)");
+        if (!whole_frame) return refuse_partial_frame(ctx, "bilateral-grid term");
         if ((uint64_t)batch->camera.img_w * batch->camera.img_h > 0x7FFFFFFFull)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table h * w must stay below 2^31");
     }
@@ -1517,31 +1525,22 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (depth_target->h != batch->camera.img_h || depth_target->w != batch->camera.img_w)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth target's size differs from the camera's");
         if (depth_target->kind > BH_DEPTH_LOSS_DISPARITY) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: unknown depth loss kind");
-        const ViewUniforms du = make_uniforms(batch->camera);
-        if (batch->image_hook || du.tile_y0 != 0u || du.tile_y1 != du.tile_bh)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth term needs the whole frame on this rank (no tile-row partition)");
-        if (ctx->pose_grad)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a depth target and a pose-gradient buffer cannot be attached together (the pose pass does not carry the depth term's gradient)");
+        if (!whole_frame) return refuse_partial_frame(ctx, "depth term");
+        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a depth target", "depth term");
     }
     // a normal-consistency term (brush_hip_normal_loss.h): refused before anything is queued; weight <= 0 is no term at all
     const bool normal_wanted = ctx->normal_attached && ctx->normal_term.weight > 0.0f;
     if (normal_wanted) {
         if (batch->camera.model != BH_CAMERA_PINHOLE)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs a pinhole camera (the normals of a depth map are defined for it alone)");
-        const ViewUniforms nu = make_uniforms(batch->camera);
-        if (batch->image_hook || nu.tile_y0 != 0u || nu.tile_y1 != nu.tile_bh)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs the whole frame on this rank (no tile-row partition)");
-        if (ctx->pose_grad)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a normal term and a pose-gradient buffer cannot be attached together (the pose pass does not carry the normal term's gradient)");
+        if (!whole_frame) return refuse_partial_frame(ctx, "normal term");
+        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a normal term", "normal term");
     }
     // a distortion term (brush_hip_distortion.h): refused before anything is queued; attached only with a weight > 0 and a checked kind
     const bool distortion_wanted = ctx->distortion_attached;
     if (distortion_wanted) {
-        const ViewUniforms xu = make_uniforms(batch->camera);
-        if (batch->image_hook || xu.tile_y0 != 0u || xu.tile_y1 != xu.tile_bh)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the distortion term needs the whole frame on this rank (no tile-row partition)");
-        if (ctx->pose_grad)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a distortion term and a pose-gradient buffer cannot be attached together (the pose pass does not carry the distortion term's gradient)");
+        if (!whole_frame) return refuse_partial_frame(ctx, "distortion term");
+        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a distortion term", "distortion term");
     }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
@@ -1598,7 +1597,6 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     const bool exchanging = hook || (ctx->comm && (ctx->comm_world > 1 || ctx->knob_force_exchange));
     // one frame split over the ranks by strips of tile rows: the caller's image hook moves the strips / halos, or — no hook, a
     // communicator on the ctx, a proper tile-row window in the camera — the library exchanges the halos itself (comm.hip)
-    const ViewUniforms win_u = make_uniforms(batch->camera);
     const bool window_partial = win_u.tile_y0 != 0u || win_u.tile_y1 != win_u.tile_bh;
     // (a one-rank communicator has no neighbours: a window without strip_loss then runs as it does without a communicator)
     const bool native_tiles = !batch->image_hook && window_partial && ctx->comm != nullptr && !hook && (batch->strip_loss || ctx->comm_world > 1);
@@ -1606,8 +1604,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a tile-row window without an image hook needs strip_loss = 1 (the library exchanges the strips' halos, not whole frames)");
     const bool tile_mode = batch->image_hook != nullptr || native_tiles;
     const bool lpips_on = ctx->lpips != nullptr && ctx->lpips_weight > 0.0f;
-    if (lpips_on && (tile_mode || window_partial))
-        return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the LPIPS term needs the whole frame on this rank (no tile-row partition)");
+    if (lpips_on && !whole_frame) return refuse_partial_frame(ctx, "LPIPS term");
     const bool masked_grads = !exchanging && !tile_mode && !ctx->knob_zero_grads && n > 0;
     if (masked_grads) {
         fwd.grad_begin = exch + o_ref;
@@ -1622,8 +1619,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // ---- tile-partitioned frame: fetch the other ranks' strips (not in the reference: SURVEY.md §8e)
     if (tile_mode) {
         ProfScope ps(ctx, "ImageExchange");
-        const ViewUniforms& wu = win_u;
-        const uint32_t r0 = wu.tile_y0 * TILE_WIDTH, r1 = wu.tile_y1 * TILE_WIDTH < H ? wu.tile_y1 * TILE_WIDTH : H;
+        const uint32_t r0 = win_u.tile_y0 * TILE_WIDTH, r1 = win_u.tile_y1 * TILE_WIDTH < H ? win_u.tile_y1 * TILE_WIDTH : H;
         if (native_tiles) BH_TRY(comm_exchange_strip_halos(ctx, ro.out_img, H, W, r0, r1));
         else if (batch->image_hook(batch->image_hook_user, ro.out_img, H, W, r0, r1) != 0) return set_error(ctx, BH_ERR_STATE, "image hook failed");
     }
@@ -1642,11 +1638,10 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     auto* v_output = (float*)ensure(ctx, SLOT_V_OUTPUT, hw * 16);
     auto* loss_dev = (float*)ensure(ctx, SLOT_LOSS_SCALAR, 16);
     if (!v_output || !loss_dev) return BH_ERR_OOM;
-    // with an exposure table the loss reads the exposed frame from a slot of its own: out_img is what K17 replays from
-    float* exposed = nullptr;
-    if (exposure && !(exposed = (float*)ensure(ctx, SLOT_EXPOSED, hw * 16))) return BH_ERR_OOM;
-    // ... and with a bilateral-grid table the sliced frame, likewise (from here on `exposed` is either one's corrected frame)
-    if (bilagrid && !(exposed = (float*)ensure(ctx, SLOT_BILAGRID_SLICED, hw * 16))) return BH_ERR_OOM;
+    // with an exposure or a bilateral-grid table the loss reads the exposed / sliced frame from a slot of its own: out_img is what
+    // K17 replays from
+    float* corrected = nullptr;
+    if ((exposure || bilagrid) && !(corrected = (float*)ensure(ctx, SLOT_CORRECTED, hw * 16))) return BH_ERR_OOM;
     // the loss scalar goes straight into pinned host memory (bh_sync hands it to stats->loss): no copy launch
     float* loss_host = reinterpret_cast<float*>(ctx->host_counters) + HOST_LOSS_WORD;
     const float dl_rgb = 1.0f / (float)(hw * 3);
@@ -1664,19 +1659,18 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (tile_mode && batch->strip_loss) {
             // one frame over several ranks: the hook delivered only the 21-px halos; loss and dL/dimg for this rank's strip
             // (stats->loss is the strip's share of the mean: the ranks' shares add up to the frame's loss)
-            const ViewUniforms wu = make_uniforms(batch->camera);
-            return launch_image_loss_fused_window(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, wu.tile_y0, wu.tile_y1,
+            return launch_image_loss_fused_window(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, win_u.tile_y0, win_u.tile_y1,
                                                   loss_dev, v_output, loss_host, started_host, started_tag);
         }
         if (exposure) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
             ProfScope ps(ctx, "Exposure");
-            BH_TRY(launch_exposure_apply(ctx, exposure, batch->view_id, ro.out_img, H, W, exposed));
+            BH_TRY(launch_exposure_apply(ctx, exposure, batch->view_id, ro.out_img, H, W, corrected));
         }
         if (bilagrid) {   // (likewise)
             ProfScope ps(ctx, "Bilagrid");
-            BH_TRY(launch_bilagrid_slice(ctx, bilagrid, batch->view_id, ro.out_img, H, W, exposed));
+            BH_TRY(launch_bilagrid_slice(ctx, bilagrid, batch->view_id, ro.out_img, H, W, corrected));
         }
-        return launch_image_loss_fused(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
+        return launch_image_loss_fused(ctx, corrected ? corrected : ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
                                        started_tag);
     };
 #ifdef BH_TEST_HOOKS
@@ -1701,7 +1695,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     }
     // ---- LPIPS (train.rs:265-273): on the frame's final image, GT composited as the loss above does it; loss and dL/dimg grow
     // in place on the device (no host wait)
-    if (lpips_on) BH_TRY(lpips_train_term(ctx, exposed ? exposed : ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
+    if (lpips_on) BH_TRY(lpips_train_term(ctx, corrected ? corrected : ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
     // ---- exposure backward: v_output becomes A^T v' in place (x = the frame as rendered), the view's row takes its Adam step
     if (exposure) {
         ProfScope ps(ctx, "Exposure");

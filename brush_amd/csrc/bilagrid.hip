@@ -8,24 +8,11 @@
 //   bilagrid_final_kernel     per grid element: the units' partial rows in index order + the TV gradient -> grad and the f64 sum
 //   bilagrid_step_kernel      Adam on the f64 sum (a launch of its own: the TV gradient above reads neighbouring parameters)
 //   bilagrid_tv_kernel        TV of a row, one block, f64
-#include <algorithm>
-#include <cmath>
-#include <vector>
-
+// The table itself — a bh_bilagrid is a ViewTable of rows of gh gw gl 12 with f32 moments, plus the grid's sides — and every entry
+// point that only manages it are view_table.h's; the wave butterfly and the Adam step are device_f64_sum.h's.
 #include "../../include/brush_hip_bilagrid.h"
-#include "context.h"
-
-struct bh_bilagrid {
-    uint32_t n_views = 0, gw = 0, gh = 0, gl = 0;
-    size_t row = 0;               // floats per view: gh gw gl 12
-    void* mem = nullptr;          // one allocation: param | grad | m1 | m2 | t
-    float* param = nullptr;       // [V,row]
-    float* grad = nullptr;        // [V,row]
-    float* m1 = nullptr;          // [V,row]
-    float* m2 = nullptr;          // [V,row]
-    uint32_t* t = nullptr;        // [V]
-    double lr = 2e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-15;   // passed to the update by value
-};
+#include "device_f64_sum.h"
+#include "view_table.h"
 
 namespace bh {
 
@@ -194,12 +181,6 @@ __global__ __launch_bounds__(BG_WG) void bilagrid_pixel_kernel(const float4* __r
     }
 }
 
-BH_DEV double bg_wave_sum(double x) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);   // every lane adds the same pairs in the same order
-    return x;
-}
-
 // One halving step of the row butterfly: partners `mask` lanes apart split their N entries between them — the lane with the bit clear
 // keeps the lower half, the other the upper half — and each adds the partner's copy of the half it keeps: N / 2 exchanges, not N.
 template <int N>
@@ -329,13 +310,8 @@ __global__ __launch_bounds__(BG_WG) void bilagrid_step_kernel(const double* __re
                                                               double beta2, double eps) {
     const uint32_t e = blockIdx.x * BG_WG + threadIdx.x;
     if (e >= row) return;
-    const double tn = (double)*t;
-    const double gq = gsum[e];
-    const double a = beta1 * (double)m1[e] + (1.0 - beta1) * gq;
-    const double b = beta2 * (double)m2[e] + (1.0 - beta2) * gq * gq;
-    const double ah = a / (1.0 - pow(beta1, tn));
-    const double bh = b / (1.0 - pow(beta2, tn));
-    param[e] = (float)((double)param[e] - lr * ah / (sqrt(bh) + eps));
+    double a, b;
+    param[e] = adam_step_f64(gsum[e], param[e], (double)m1[e], (double)m2[e], (double)*t, lr, beta1, beta2, eps, a, b);
     m1[e] = (float)a;
     m2[e] = (float)b;
 }
@@ -354,7 +330,7 @@ __global__ __launch_bounds__(BG_WG) void bilagrid_tv_kernel(const float* __restr
         if (j + 1u < g.gh) { const double d = (double)param[e + sy] - v; s = fma(d * d, 0.5 * tv.cy, s); }
         if (i + 1u < g.gw) { const double d = (double)param[e + sx] - v; s = fma(d * d, 0.5 * tv.cx, s); }
     }
-    s = bg_wave_sum(s);
+    s = dl_wave_sum(s);
     if ((threadIdx.x & 63u) == 0u) wave_sums[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -404,8 +380,6 @@ static uint32_t bilagrid_bands(uint32_t h, uint32_t w, uint32_t gh, uint32_t gw,
     return (uint32_t)std::max<uint64_t>(bands, 1u);
 }
 
-uint32_t bilagrid_views(const bh_bilagrid* tab) { return tab->n_views; }
-
 int launch_bilagrid_slice(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out) {
     const uint32_t pixels = h * w;
     hipLaunchKernelGGL(bilagrid_slice_kernel, dim3(pixel_grid(pixels)), dim3(BG_WG), 0, ctx->stream,
@@ -448,43 +422,16 @@ int launch_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* tab, uint32_t view, const
                        tab->t + (view - 1), g, ncx, ncy, bands, row, (double)tv_weight, tv_of(tab), update ? 1 : 0);
     BH_LAUNCH_CHECK(ctx, "bilagrid_final_kernel");
     if (update) {
-        hipLaunchKernelGGL(bilagrid_step_kernel, dim3(blocks), dim3(BG_WG), 0, ctx->stream, gsum, tab->param + off, tab->m1 + off, tab->m2 + off,
-                           tab->t + (view - 1), row, tab->lr, tab->beta1, tab->beta2, tab->eps);
+        hipLaunchKernelGGL(bilagrid_step_kernel, dim3(blocks), dim3(BG_WG), 0, ctx->stream, gsum, tab->param + off, static_cast<float*>(tab->m1) + off,
+                           static_cast<float*>(tab->m2) + off, tab->t + (view - 1), row, tab->lr, tab->beta1, tab->beta2, tab->eps);
         BH_LAUNCH_CHECK(ctx, "bilagrid_step_kernel");
     }
-    return 0;
-}
-
-static void bilagrid_free(bh_bilagrid* tab) {
-    if (tab->mem) (void)hipFree(tab->mem);
-    delete tab;
-}
-
-void bilagrid_free_all(bh_ctx* ctx) {
-    for (bh_bilagrid* tab : ctx->bilagrids) bilagrid_free(tab);
-    ctx->bilagrids.clear();
-    ctx->bilagrid = nullptr;
-}
-
-// the table is one of this ctx's and the views first .. first + count - 1 are rows of it
-static int check_rows(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t first, uint32_t count, const char* who) {
-    if (!tab || std::find(ctx->bilagrids.begin(), ctx->bilagrids.end(), tab) == ctx->bilagrids.end())
-        return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": not a bilateral-grid table of this context");
-    if (first == 0 || count == 0 || first > tab->n_views || count > tab->n_views - first + 1)
-        return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": view out of range (views are numbered 1 .. n_views)");
     return 0;
 }
 
 static int check_image(bh_ctx* ctx, uint32_t h, uint32_t w, const char* who) {
     if (h == 0 || w == 0) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": an image of zero size");
     if ((uint64_t)h * w > 0x7FFFFFFFull) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": h * w must stay below 2^31");
-    return 0;
-}
-
-static int read_back(bh_ctx* ctx, void* host, const void* dev, size_t bytes) {
-    BH_HIP(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    deliver_pending_loss(ctx);
     return 0;
 }
 
@@ -495,59 +442,22 @@ using namespace bh;
 extern "C" {
 
 int bh_bilagrid_create(bh_ctx* ctx, uint32_t n_views, uint32_t grid_w, uint32_t grid_h, uint32_t grid_l, bh_bilagrid** table) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!table) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_create: null argument");
-    *table = nullptr;
-    if (n_views == 0 || n_views > (1u << 24)) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_create: n_views must be 1 .. 2^24");
+    BH_TRY(view_table_create_args(ctx, table, n_views, "bilagrid_create"));
     if (grid_w == 0 || grid_h == 0 || grid_l == 0 || grid_w > 1024u || grid_h > 1024u || grid_l > 1024u ||
         (uint64_t)grid_w * grid_h * grid_l * 12u > (1ull << 22))
         return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_create: grid sides must be 1 .. 1024 and a view at most 2^22 floats");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t v = n_views, row = (size_t)grid_w * grid_h * grid_l * 12, bytes = v * row * 4 * 4 + v * 4;
-    void* mem = nullptr;
-    BH_HIP(ctx, hipMalloc(&mem, bytes));
-    auto* tab = new bh_bilagrid;
-    tab->n_views = n_views;
-    tab->gw = grid_w; tab->gh = grid_h; tab->gl = grid_l;
-    tab->row = row;
-    tab->mem = mem;
-    tab->param = static_cast<float*>(mem);
-    tab->grad = tab->param + v * row;
-    tab->m1 = tab->grad + v * row;
-    tab->m2 = tab->m1 + v * row;
-    tab->t = reinterpret_cast<uint32_t*>(tab->m2 + v * row);
-    static const float ident12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    std::vector<float> ident(row);
-    for (size_t i = 0; i < row; ++i) ident[i] = ident12[i % 12];
-    hipError_t e = hipMemsetAsync(mem, 0, bytes, ctx->stream);
-    for (size_t i = 0; i < v && e == hipSuccess; ++i) e = hipMemcpyAsync(tab->param + i * row, ident.data(), row * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (the staging vector dies here)
-    if (e != hipSuccess) {
-        bilagrid_free(tab);
-        return check_hip(ctx, e, "bilagrid_create");
-    }
-    deliver_pending_loss(ctx);
-    ctx->bilagrids.push_back(tab);
-    *table = tab;
+    ViewTable* tab = nullptr;
+    BH_TRY(view_table_create(ctx, VT_BILAGRID, n_views, (size_t)grid_w * grid_h * grid_l * 12, "bilagrid_create", &tab));
+    *table = static_cast<bh_bilagrid*>(tab);
+    (*table)->gw = grid_w; (*table)->gh = grid_h; (*table)->gl = grid_l;
     return 0;
 }
 
-int bh_bilagrid_destroy(bh_ctx* ctx, bh_bilagrid* table) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    auto it = std::find(ctx->bilagrids.begin(), ctx->bilagrids.end(), table);
-    if (!table || it == ctx->bilagrids.end()) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_destroy: not a bilateral-grid table of this context");
-    if (ctx->bilagrid == table) ctx->bilagrid = nullptr;   // an attached table is detached first
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);   // kernels queued on the table have run
-    deliver_pending_loss(ctx);
-    ctx->bilagrids.erase(it);
-    bilagrid_free(table);
-    return 0;
-}
+int bh_bilagrid_destroy(bh_ctx* ctx, bh_bilagrid* table) { return view_table_destroy(ctx, VT_BILAGRID, table, "bilagrid_destroy"); }
 
 int bh_bilagrid_dims(bh_ctx* ctx, bh_bilagrid* table, uint32_t* n_views, uint32_t* grid_w, uint32_t* grid_h, uint32_t* grid_l) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(check_rows(ctx, table, 1, 1, "bilagrid_dims"));
+    BH_TRY(check_rows(ctx, VT_BILAGRID, table, 1, 1, "bilagrid_dims"));
     if (n_views) *n_views = table->n_views;
     if (grid_w) *grid_w = table->gw;
     if (grid_h) *grid_h = table->gh;
@@ -556,74 +466,34 @@ int bh_bilagrid_dims(bh_ctx* ctx, bh_bilagrid* table, uint32_t* n_views, uint32_
 }
 
 int bh_bilagrid_set_params(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, const float* host) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!host) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_set_params: null argument");
-    BH_TRY(check_rows(ctx, table, first_view, count, "bilagrid_set_params"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemcpyAsync(table->param + (size_t)(first_view - 1) * table->row, host, (size_t)count * table->row * 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (pageable host memory of this size is staged: the caller's array may die on return)
-    deliver_pending_loss(ctx);
-    return 0;
+    return view_table_set_params(ctx, VT_BILAGRID, table, first_view, count, host, "bilagrid_set_params");
 }
 
 int bh_bilagrid_get_params(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, float* host) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!host) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_get_params: null argument");
-    BH_TRY(check_rows(ctx, table, first_view, count, "bilagrid_get_params"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    return read_back(ctx, host, table->param + (size_t)(first_view - 1) * table->row, (size_t)count * table->row * 4);
+    return view_table_get_rows(ctx, VT_BILAGRID, table, &ViewTable::param, first_view, count, host, "bilagrid_get_params");
 }
 
 int bh_bilagrid_get_grad(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, float* host) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!host) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_get_grad: null argument");
-    BH_TRY(check_rows(ctx, table, first_view, count, "bilagrid_get_grad"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    return read_back(ctx, host, table->grad + (size_t)(first_view - 1) * table->row, (size_t)count * table->row * 4);
+    return view_table_get_rows(ctx, VT_BILAGRID, table, &ViewTable::grad, first_view, count, host, "bilagrid_get_grad");
 }
 
 int bh_bilagrid_get_state(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, float* m1, float* m2, uint32_t* t) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!m1 || !m2 || !t) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_get_state: null argument");
-    BH_TRY(check_rows(ctx, table, view, 1, "bilagrid_get_state"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t off = (size_t)(view - 1) * table->row;
-    BH_HIP(ctx, hipMemcpyAsync(m1, table->m1 + off, table->row * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(m2, table->m2 + off, table->row * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return read_back(ctx, t, table->t + (view - 1), 4);
+    return view_table_get_state(ctx, VT_BILAGRID, table, view, m1, m2, t, "bilagrid_get_state");
 }
 
 int bh_bilagrid_set_state(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const float* m1, const float* m2, uint32_t t) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!m1 || !m2) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_set_state: null argument");
-    BH_TRY(check_rows(ctx, table, view, 1, "bilagrid_set_state"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t off = (size_t)(view - 1) * table->row;
-    BH_HIP(ctx, hipMemcpyAsync(table->m1 + off, m1, table->row * 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(table->m2 + off, m2, table->row * 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(table->t + (view - 1), &t, 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (as set_params)
-    deliver_pending_loss(ctx);
-    return 0;
+    return view_table_set_state(ctx, VT_BILAGRID, table, view, m1, m2, t, "bilagrid_set_state");
 }
 
 int bh_bilagrid_set_adam(bh_ctx* ctx, bh_bilagrid* table, double lr, double beta1, double beta2, double eps) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(check_rows(ctx, table, 1, 1, "bilagrid_set_adam"));
-    if (!(lr >= 0.0) || !std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0) || !std::isfinite(eps))
-        return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_set_adam: needs lr >= 0, 0 <= beta < 1 and eps > 0, all finite");
-    table->lr = lr;
-    table->beta1 = beta1;
-    table->beta2 = beta2;
-    table->eps = eps;
-    return 0;
+    return view_table_set_adam(ctx, VT_BILAGRID, table, lr, beta1, beta2, eps, "bilagrid_set_adam");
 }
 
 int bh_bilagrid_slice(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !out_hwc4) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_slice: null argument");
     BH_TRY(check_image(ctx, h, w, "bilagrid_slice"));
-    BH_TRY(check_rows(ctx, table, view, 1, "bilagrid_slice"));
+    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_slice"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_slice(ctx, table, view, img_hwc4, h, w, out_hwc4);
 }
@@ -634,7 +504,7 @@ int bh_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const f
     if (!img_hwc4 || !v_sliced || !v_img) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_backward: null argument");
     BH_TRY(check_image(ctx, h, w, "bilagrid_backward"));
     if (!(tv_weight >= 0.0f) || !std::isfinite(tv_weight)) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_backward: tv_weight must be finite and >= 0");
-    BH_TRY(check_rows(ctx, table, view, 1, "bilagrid_backward"));
+    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_backward"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_backward(ctx, table, view, img_hwc4, v_sliced, h, w, v_img, tv_weight, update != 0);
 }
@@ -642,15 +512,14 @@ int bh_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const f
 int bh_bilagrid_tv(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, float* value_dev) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!value_dev) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_tv: null argument");
-    BH_TRY(check_rows(ctx, table, view, 1, "bilagrid_tv"));
+    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_tv"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_tv(ctx, table, view, value_dev, 0.0f, nullptr, nullptr);
 }
 
 int bh_train_set_bilagrid(bh_ctx* ctx, bh_bilagrid* table, float tv_weight) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    if (table && std::find(ctx->bilagrids.begin(), ctx->bilagrids.end(), table) == ctx->bilagrids.end())
-        return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_bilagrid: not a bilateral-grid table of this context");
+    BH_TRY(view_table_attachable(ctx, VT_BILAGRID, table, "train_set_bilagrid"));
     if (table && (!(tv_weight >= 0.0f) || !std::isfinite(tv_weight)))
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_bilagrid: tv_weight must be finite and >= 0");
     ctx->bilagrid = table;

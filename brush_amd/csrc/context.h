@@ -84,7 +84,7 @@ enum Slot : int {
     SLOT_DEPTH,              // bh_render_backward_depth_saved: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip)
     SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
     SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
-    SLOT_EXPOSED,            // bh_train_step with an exposure table: [H,W,4] the exposed frame the loss reads (out_img stays as rendered)
+    SLOT_CORRECTED,          // bh_train_step with an exposure or a bilateral-grid table (never both): [H,W,4] the exposed / sliced frame the loss reads (out_img stays as rendered)
     SLOT_DEPTH_LOSS,         // bh_depth_loss_value_and_grad / bh_eval_depth_metrics: one f64 row of 4 per block (depth_loss.hip)
     SLOT_DEPTH_TERM,         // bh_train_step with a depth target or a normal term: expected depth [H,W] | v_depth [H,W] | the depth term's loss pair (4 floats)
     SLOT_NORMAL,             // bh_render_normal / bh_render_backward_normal_saved: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip)
@@ -94,7 +94,6 @@ enum Slot : int {
     SLOT_DISTORTION_LOSS,    // bh_distortion_loss: one f64 row of 4 per block, 2 used (distortion.hip)
     SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
     SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
-    SLOT_BILAGRID_SLICED,    // bh_train_step with a bilateral-grid table: [H,W,4] the sliced frame the loss reads (out_img stays as rendered)
     SLOT_COUNT
 };
 
@@ -377,6 +376,8 @@ struct NormalTerm {
 };
 
 // The distortion term of a backward (distortion.hip, brush_hip_distortion.h): <v_distortion, dist of the forward>
+struct ViewTable;   // view_table.h: the host core of bh_exposure and bh_bilagrid
+
 struct DistortionTerm {
     const float* v_distortion = nullptr;   // [H,W], or NULL: the uniform cotangent `gain` at every pixel
     float gain = 0.0f;
@@ -424,11 +425,10 @@ struct bh_ctx {
     BhNormalTermConfig normal_term{};
     bool distortion_attached = false; // bh_train_set_distortion: the step adds the distortion term (brush_hip_distortion.h); only ever true with a weight > 0
     BhDistortionTermConfig distortion_term{};
+    std::vector<bh::ViewTable*> view_tables;   // every per-view table of this ctx, of either kind (view_table.h): bh_destroy frees what is left
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
-    std::vector<bh_exposure*> exposures;   // every table of this ctx (brush_hip_exposure.h): bh_destroy frees what is left
     bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
     float bilagrid_tv_weight = 0.0f;  // ... and adds this much of the grid's total variation to the loss
-    std::vector<bh_bilagrid*> bilagrids;   // every table of this ctx (brush_hip_bilagrid.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
@@ -570,24 +570,19 @@ int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, f
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
                      const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);
-// exposure.hip: y = A x + b with the row of `view` (1 .. exposure_views), and its backward: v_img = A^T v_exposed (in place
+// exposure.hip: y = A x + b with the row of `view` (1 .. n_views), and its backward: v_img = A^T v_exposed (in place
 // allowed), grad[view] = v_m, and one Adam step of the row when `update` (brush_hip_exposure.h).  The view is already checked.
-uint32_t exposure_views(const bh_exposure* tab);
 int launch_exposure_apply(bh_ctx* ctx, const bh_exposure* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out);
 int launch_exposure_backward(bh_ctx* ctx, bh_exposure* tab, uint32_t view, const float* img, const float* v_exposed, uint32_t h, uint32_t w,
                              float* v_img, bool update);
-void exposure_free_all(bh_ctx* ctx);   // bh_destroy
-// bilagrid.hip: the slice of `img` with the grid of `view` (1 .. bilagrid_views), its backward: v_img (in place allowed), grad[view] =
+// bilagrid.hip: the slice of `img` with the grid of `view` (1 .. n_views), its backward: v_img (in place allowed), grad[view] =
 // v_g + tv_weight dTV and one Adam step of the row when `update`, and TV of the row into value[0]; accum as launch_depth_loss's, with
 // weight * TV added (brush_hip_bilagrid.h).  The view and the image size are already checked.
-uint32_t bilagrid_views(const bh_bilagrid* tab);
 int launch_bilagrid_slice(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out);
 int launch_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* tab, uint32_t view, const float* img, const float* v_sliced, uint32_t h, uint32_t w, float* v_img,
                              float tv_weight, bool update);
 int launch_bilagrid_tv(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, float* value, float weight, float* accum, float* accum_host);
 float* bilagrid_tv_scratch(bh_ctx* ctx);   // four floats of SLOT_BILAGRID for the train step's TV value
-void bilagrid_free_all(bh_ctx* ctx);   // bh_destroy
-
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view
 // id whose camera is new, or a failed allocation.  A second attempt (!req.allow_cut) leaves the view's gap and LRU stamp alone.

@@ -13,6 +13,7 @@
 // sort do the compaction: no per-splat atomics, deterministic tie order (by id).
 #include "context.h"
 #include "device_camera.h"
+#include "device_f64_sum.h"
 #include "device_sh.h"
 
 namespace bh {
@@ -1067,18 +1068,9 @@ int launch_project_backward(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, boo
 //   to v_t:  v_mean_c + W v_mean_from_sh          to v_W:  v_mean_c (x) mean + 2 vcc W Sigma + t (x) v_mean_from_sh
 // (the last terms are -W v_p and -t (x) v_p with v_p = -v_mean_from_sh, folded per splat: both are linear in the sum).
 // The rows of v_combined are RasterizeGrads here (K18 has run); a row whose geometry and colour entries are all zero gives zero.
-// The twelve f32 contributions are widened to f64 and summed in a fixed order: a lane-exchange butterfly inside the wave, the
-// block's waves in wave order through LDS, one f64 row per block; pose_grad_final_kernel adds the rows in index order.
+// The twelve f32 contributions are widened to f64 and summed in a fixed order (device_f64_sum.h): a lane-exchange butterfly inside the
+// wave, the block's waves in wave order through LDS, one f64 row per block; pose_grad_final_kernel adds the rows in index order.
 constexpr int POSE_WAVES = PROJ_WG / 64;
-// pose_grad_final_kernel: 85 runs of consecutive rows x 12 entries = 1020 lanes.  The pass waits on memory, one dependent f64
-// add per row: at 1 M splats / 1080p (3400 rows) 16 runs took 64 us, five times K18
-constexpr int POSE_FINAL_CHUNKS = 85;
-
-BH_DEV double wave_sum_f64(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);   // every lane adds the same pairs in the same order
-    return x;
-}
 
 template <int DEG, bool PINHOLE>
 __global__ __launch_bounds__(PROJ_WG) void pose_grad_kernel(
@@ -1145,45 +1137,18 @@ __global__ __launch_bounds__(PROJ_WG) void pose_grad_kernel(
         c[6] = w2.x; c[7] = w2.y; c[8] = w2.z;
         c[9] = vt.x; c[10] = vt.y; c[11] = vt.z;
     }
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    double s[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        const double s = wave_sum_f64((double)c[k]);
-        if (lane == 0) wave_rows[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double s = wave_rows[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < POSE_WAVES; ++w) s += wave_rows[w][threadIdx.x];
-        partials[(size_t)blockIdx.x * 12 + threadIdx.x] = s;
-    }
+    for (int k = 0; k < 12; ++k) s[k] = (double)c[k];
+    dl_block_store<12, 12, POSE_WAVES>(s, wave_rows, partials);
 }
 
-// one block: lane (chunk, k) adds entry k of its run of consecutive rows in index order, lane k then adds the runs in order
-__global__ __launch_bounds__(POSE_FINAL_CHUNKS * 12) void pose_grad_final_kernel(uint32_t rows, const double* __restrict__ partials,
-                                                                                 float* __restrict__ v_viewmat) {
-    __shared__ double runs[POSE_FINAL_CHUNKS][12];
-    const uint32_t chunk = threadIdx.x / 12u, k = threadIdx.x % 12u;
-    const uint32_t per = (rows + POSE_FINAL_CHUNKS - 1) / POSE_FINAL_CHUNKS;
-    const uint32_t r0 = chunk * per < rows ? chunk * per : rows;
-    const uint32_t r1 = r0 + per < rows ? r0 + per : rows;
-    double s = 0.0;
-    uint32_t r = r0;
-    for (; r + 4 <= r1; r += 4) {   // four loads in flight, the adds in index order
-        const double a0 = partials[(size_t)r * 12 + k], a1 = partials[(size_t)(r + 1) * 12 + k];
-        const double a2 = partials[(size_t)(r + 2) * 12 + k], a3 = partials[(size_t)(r + 3) * 12 + k];
-        s += a0; s += a1; s += a2; s += a3;
-    }
-    for (; r < r1; ++r) s += partials[(size_t)r * 12 + k];
-    runs[chunk][k] = s;
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double total = runs[0][threadIdx.x];
-#pragma unroll
-        for (int i = 1; i < POSE_FINAL_CHUNKS; ++i) total += runs[i][threadIdx.x];
-        v_viewmat[threadIdx.x] = (float)total;
-    }
+// one block: the rows' twelve totals (dl_final_rows12), the loop over the runs unrolled whole
+__global__ __launch_bounds__(DL_FINAL_CHUNKS * 12) void pose_grad_final_kernel(uint32_t rows, const double* __restrict__ partials,
+                                                                               float* __restrict__ v_viewmat) {
+    __shared__ double runs[DL_FINAL_CHUNKS][12];
+    const double total = dl_final_rows12<DL_FINAL_CHUNKS - 1>(rows, partials, runs);
+    if (threadIdx.x < 12) v_viewmat[threadIdx.x] = (float)total;
 }
 
 template <bool PINHOLE>
@@ -1213,7 +1178,7 @@ int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, 
     if (!partials) return BH_ERR_OOM;
     if (u.model == CAM_PINHOLE) BH_TRY(launch_pose_deg<true>(ctx, u, nv, mip, sh_degree, transforms, sh, gid, v_combined, partials));
     else BH_TRY(launch_pose_deg<false>(ctx, u, nv, mip, sh_degree, transforms, sh, gid, v_combined, partials));
-    hipLaunchKernelGGL(pose_grad_final_kernel, dim3(1), dim3(POSE_FINAL_CHUNKS * 12), 0, ctx->stream, rows, partials, v_viewmat);
+    hipLaunchKernelGGL(pose_grad_final_kernel, dim3(1), dim3(DL_FINAL_CHUNKS * 12), 0, ctx->stream, rows, partials, v_viewmat);
     BH_LAUNCH_CHECK(ctx, "pose_grad_final_kernel");
     return 0;
 }

@@ -962,80 +962,123 @@ class PoseOptimizer:
 
 
 # ---------------------------------------------------------------------------
-# Per-view exposure compensation (include/brush_hip_exposure.h)
+# Per-view colour tables: exposure compensation (include/brush_hip_exposure.h) and bilateral grids
+# (include/brush_hip_bilagrid.h)
 # ---------------------------------------------------------------------------
-class ExposureTable:
-    """A device table of one affine colour transform m[12] (row-major 3x4, column 3 the offset) per training view, with its Adam
-    moments and update on the device (bh_exposure_*): y = A x + b on the rasterizer's image before the loss.  Views are numbered
-    from 1 (row i is view id i + 1, as SceneLoader numbers them).  Nothing here reads back except the getters (`params`, `grads`,
-    `state`).  SplatTrainer(exposure=table) attaches it to the train step.  Data parallel over cameras: the table is per process,
-    nothing is all-reduced, a view must stay with one rank."""
+def _hwc4_out(img, out):
+    """The result tensor of an [H,W,4] operator on `img`: a new one, or the caller's `out` once it fits."""
+    if out is None:
+        return torch.empty_like(img)
+    if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+    return out
 
-    def __init__(self, n_views, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, ctx: Optional[Context] = None):
+
+class _ViewTable:
+    """What the per-view device tables share (csrc/view_table.h): V rows of `shape` f32 parameters, numbered from 1, each with its
+    gradient, its Adam moments (of the kind's dtype) and its step count.  A subclass names the C symbols' prefix and the moment type,
+    opens the table with `_open` and checks the moments it is handed in `_moment`."""
+    _prefix = None                      # "bh_exposure" | "bh_bilagrid"
+    _moment_np, _moment_c = None, None  # the moments' numpy dtype and ctypes type
+
+    def _fn(self, name):
+        return getattr(self.lib, "%s_%s" % (self._prefix, name))
+
+    def _open(self, ctx, n_views, shape, create_args, lr, beta1, beta2, eps):
         ctx = ctx or get_context()
-        self.ctx, self.lib, self.n_views = ctx, ctx.lib, int(n_views)
+        self.ctx, self.lib, self.n_views, self.shape = ctx, ctx.lib, int(n_views), tuple(shape)   # shape: one view's row
         h = C.c_void_p()
-        ctx.check(ctx.lib.bh_exposure_create(ctx._h, self.n_views, C.byref(h)))
+        ctx.check(self._fn("create")(ctx._h, self.n_views, *create_args, C.byref(h)))
         self._h = h
         self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
         self.set_lr(lr)
 
     def set_lr(self, lr):
-        """The learning rate of every following update (bh_exposure_set_adam); 0 freezes the rows while their moments still move."""
-        self.ctx.check(self.lib.bh_exposure_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
+        """The learning rate of every following update (bh_*_set_adam); 0 freezes the rows while their moments still move."""
+        self.ctx.check(self._fn("set_adam")(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
         self.lr = float(lr)
 
     def _get(self, fn):
         import numpy as np
-        out = np.empty((self.n_views, 12), np.float32)
+        out = np.empty((self.n_views,) + self.shape, np.float32)
         self.ctx.check(fn(self.ctx._h, self._h, 1, self.n_views, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def _set_rows(self, first, count, a):
+        self.ctx.check(self._fn("set_params")(self.ctx._h, self._h, int(first), int(count), a.ctypes.data_as(C.POINTER(C.c_float))))
+
     @property
     def params(self):
-        """[V,12] f32 numpy copy of every row (one synchronisation); assign an array of the same shape to set them."""
-        return self._get(self.lib.bh_exposure_get_params)
+        """[V, *shape] f32 numpy copy of every row (one synchronisation); assign an array of the same shape to set them."""
+        return self._get(self._fn("get_params"))
 
     @params.setter
     def params(self, value):
         import numpy as np
         a = np.ascontiguousarray(np.asarray(value, np.float32))
-        if a.shape != (self.n_views, 12):
-            raise ValueError("params must be [%d, 12]" % self.n_views)
-        self.ctx.check(self.lib.bh_exposure_set_params(self.ctx._h, self._h, 1, self.n_views, a.ctypes.data_as(C.POINTER(C.c_float))))
+        if a.shape != (self.n_views,) + self.shape:
+            raise ValueError("params must be " + self._params_shape_text())
+        self._set_rows(1, self.n_views, a)
+
+    @property
+    def grads(self):
+        """[V, *shape] f32: the last gradient written for each row, a TV term's included (zeros for a row no backward has touched)."""
+        return self._get(self._fn("get_grad"))
+
+    def state(self, view):
+        """(m1, m2 [*shape] of the moments' dtype, t) of row `view`: its Adam moments and step count."""
+        import numpy as np
+        m1, m2, t = np.empty(self.shape, self._moment_np), np.empty(self.shape, self._moment_np), C.c_uint32()
+        p = C.POINTER(self._moment_c)
+        self.ctx.check(self._fn("get_state")(self.ctx._h, self._h, int(view), m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
+        return m1, m2, int(t.value)
+
+    def set_state(self, view, m1, m2, t):
+        """Puts a row's Adam state back (resuming from a checkpoint)."""
+        a, b = self._moment(m1), self._moment(m2)
+        p = C.POINTER(self._moment_c)
+        self.ctx.check(self._fn("set_state")(self.ctx._h, self._h, int(view), a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):   # (a closed context has freed its tables)
+                self._fn("destroy")(self.ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ExposureTable(_ViewTable):
+    """A device table of one affine colour transform m[12] (row-major 3x4, column 3 the offset) per training view, with its Adam
+    moments (f64) and update on the device (bh_exposure_*): y = A x + b on the rasterizer's image before the loss.  Views are numbered
+    from 1 (row i is view id i + 1, as SceneLoader numbers them).  Nothing here reads back except the getters (`params`, `grads`
+    [V,12] f32, `state` (m1 [12] f64, m2 [12] f64, t)).  SplatTrainer(exposure=table) attaches it to the train step.  Data parallel
+    over cameras: the table is per process, nothing is all-reduced, a view must stay with one rank."""
+    _prefix, _moment_np, _moment_c = "bh_exposure", "float64", C.c_double
+
+    def __init__(self, n_views, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, ctx: Optional[Context] = None):
+        self._open(ctx, n_views, (12,), (), lr, beta1, beta2, eps)
+
+    def _params_shape_text(self):
+        return "[%d, 12]" % self.n_views
+
+    def _moment(self, m):
+        import numpy as np
+        return np.ascontiguousarray(m, np.float64).reshape(12)
 
     def set_view(self, view, m):
         """Row `view` (from 1) = the twelve floats m."""
         a = (C.c_float * 12)(*[float(v) for v in m])
         self.ctx.check(self.lib.bh_exposure_set_params(self.ctx._h, self._h, int(view), 1, a))
 
-    @property
-    def grads(self):
-        """[V,12] f32: the last v_m written for each row (zeros for a row no backward has touched)."""
-        return self._get(self.lib.bh_exposure_get_grad)
-
-    def state(self, view):
-        """(m1 [12] f64, m2 [12] f64, t) of row `view`: its Adam moments and step count."""
-        import numpy as np
-        m1, m2, t = np.empty(12, np.float64), np.empty(12, np.float64), C.c_uint32()
-        dp = C.POINTER(C.c_double)
-        self.ctx.check(self.lib.bh_exposure_get_state(self.ctx._h, self._h, int(view), m1.ctypes.data_as(dp), m2.ctypes.data_as(dp), C.byref(t)))
-        return m1, m2, int(t.value)
-
-    def set_state(self, view, m1, m2, t):
-        """Puts a row's Adam state back (resuming from a checkpoint)."""
-        import numpy as np
-        a, b = np.ascontiguousarray(m1, np.float64).reshape(12), np.ascontiguousarray(m2, np.float64).reshape(12)
-        dp = C.POINTER(C.c_double)
-        self.ctx.check(self.lib.bh_exposure_set_state(self.ctx._h, self._h, int(view), a.ctypes.data_as(dp), b.ctypes.data_as(dp), int(t)))
-
     def apply(self, view, img, out=None):
         """y = A x + b of `img` [H,W,4] f32 with row `view`; `out` may be `img` (in place)."""
         img = _aligned_hwc4(img, img.device)
-        if out is None:
-            out = torch.empty_like(img)
-        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
-            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        out = _hwc4_out(img, out)
         h, w = int(img.shape[0]), int(img.shape[1])
         self.ctx.check(self.lib.bh_exposure_apply(self.ctx._h, self._h, int(view), _ptr(img), h, w, _ptr(out)))
         return out
@@ -1047,72 +1090,34 @@ class ExposureTable:
         v = _aligned_hwc4(v_exposed, img.device)
         if v.shape != img.shape:
             raise ValueError("v_exposed must have the shape of img")
-        if out is None:
-            out = torch.empty_like(v)
-        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
-            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        out = _hwc4_out(img, out)
         h, w = int(img.shape[0]), int(img.shape[1])
         self.ctx.check(self.lib.bh_exposure_backward(self.ctx._h, self._h, int(view), _ptr(img), _ptr(v), h, w, _ptr(out), 1 if update else 0))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self.ctx, "_h", None):   # (a closed context has freed its tables)
-                self.lib.bh_exposure_destroy(self.ctx._h, self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-# ---------------------------------------------------------------------------
-# Per-view bilateral grids (include/brush_hip_bilagrid.h)
-# ---------------------------------------------------------------------------
-class BilateralGridTable:
+class BilateralGridTable(_ViewTable):
     """A device table of one bilateral grid per training view: g[Hg,Wg,L,12] f32, a grid of row-major 3x4 colour matrices looked up
     by trilinear interpolation at (x, y, luminance) and applied to the rasterizer's image before the loss, with its Adam moments
-    and update on the device (bh_bilagrid_*; gsplat's lib_bilagrid).  `grid` is (Wg, Hg, L), gsplat's (grid_X, grid_Y, grid_W).
-    Views are numbered from 1.  Nothing here reads back except the getters (`params`, `grads`, `state`, and `tv` on request).
-    SplatTrainer(bilagrid=table) attaches it to the train step.  Data parallel over cameras: the table is per process, nothing is
-    all-reduced, a view must stay with one rank."""
+    (f32) and update on the device (bh_bilagrid_*; gsplat's lib_bilagrid).  `grid` is (Wg, Hg, L), gsplat's (grid_X, grid_Y, grid_W).
+    Views are numbered from 1.  Nothing here reads back except the getters (`params`, `grads` [V,Hg,Wg,L,12] f32, `state` (m1, m2
+    [Hg,Wg,L,12] f32, t), and `tv` on request).  SplatTrainer(bilagrid=table) attaches it to the train step.  Data parallel over
+    cameras: the table is per process, nothing is all-reduced, a view must stay with one rank."""
+    _prefix, _moment_np, _moment_c = "bh_bilagrid", "float32", C.c_float
 
     def __init__(self, n_views, grid=(16, 16, 8), lr=2e-3, beta1=0.9, beta2=0.999, eps=1e-15, ctx: Optional[Context] = None):
-        ctx = ctx or get_context()
-        self.ctx, self.lib, self.n_views = ctx, ctx.lib, int(n_views)
         self.grid_w, self.grid_h, self.grid_l = (int(v) for v in grid)
-        h = C.c_void_p()
-        ctx.check(ctx.lib.bh_bilagrid_create(ctx._h, self.n_views, self.grid_w, self.grid_h, self.grid_l, C.byref(h)))
-        self._h = h
-        self.shape = (self.grid_h, self.grid_w, self.grid_l, 12)   # one view's row
-        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
-        self.set_lr(lr)
+        self._open(ctx, n_views, (self.grid_h, self.grid_w, self.grid_l, 12), (self.grid_w, self.grid_h, self.grid_l), lr, beta1, beta2, eps)
 
-    def set_lr(self, lr):
-        """The learning rate of every following update (bh_bilagrid_set_adam); 0 freezes the grids while their moments still move."""
-        self.ctx.check(self.lib.bh_bilagrid_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
-        self.lr = float(lr)
+    def _params_shape_text(self):
+        return "%r" % ((self.n_views,) + self.shape,)
 
-    def _get(self, fn):
+    def _moment(self, m):
         import numpy as np
-        out = np.empty((self.n_views,) + self.shape, np.float32)
-        self.ctx.check(fn(self.ctx._h, self._h, 1, self.n_views, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
-
-    @property
-    def params(self):
-        """[V,Hg,Wg,L,12] f32 numpy copy of every grid (one synchronisation); assign an array of the same shape to set them."""
-        return self._get(self.lib.bh_bilagrid_get_params)
-
-    @params.setter
-    def params(self, value):
-        import numpy as np
-        a = np.ascontiguousarray(np.asarray(value, np.float32))
-        if a.shape != (self.n_views,) + self.shape:
-            raise ValueError("params must be %r" % ((self.n_views,) + self.shape,))
-        self.ctx.check(self.lib.bh_bilagrid_set_params(self.ctx._h, self._h, 1, self.n_views, a.ctypes.data_as(C.POINTER(C.c_float))))
+        a = np.ascontiguousarray(m, np.float32)
+        if a.shape != self.shape:
+            raise ValueError("moments must be %r" % (self.shape,))
+        return a
 
     def set_view(self, view, g):
         """The grid of `view` (from 1) = g [Hg,Wg,L,12]."""
@@ -1120,37 +1125,12 @@ class BilateralGridTable:
         a = np.ascontiguousarray(np.asarray(g, np.float32))
         if a.shape != self.shape:
             raise ValueError("a view's grid must be %r" % (self.shape,))
-        self.ctx.check(self.lib.bh_bilagrid_set_params(self.ctx._h, self._h, int(view), 1, a.ctypes.data_as(C.POINTER(C.c_float))))
-
-    @property
-    def grads(self):
-        """[V,Hg,Wg,L,12] f32: the last gradient written for each grid, the TV term's included (zeros for an untouched row)."""
-        return self._get(self.lib.bh_bilagrid_get_grad)
-
-    def state(self, view):
-        """(m1, m2 [Hg,Wg,L,12] f32, t) of row `view`: its Adam moments and step count."""
-        import numpy as np
-        m1, m2, t = np.empty(self.shape, np.float32), np.empty(self.shape, np.float32), C.c_uint32()
-        p = C.POINTER(C.c_float)
-        self.ctx.check(self.lib.bh_bilagrid_get_state(self.ctx._h, self._h, int(view), m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
-        return m1, m2, int(t.value)
-
-    def set_state(self, view, m1, m2, t):
-        """Puts a row's Adam state back (resuming from a checkpoint)."""
-        import numpy as np
-        a, b = np.ascontiguousarray(m1, np.float32), np.ascontiguousarray(m2, np.float32)
-        if a.shape != self.shape or b.shape != self.shape:
-            raise ValueError("moments must be %r" % (self.shape,))
-        p = C.POINTER(C.c_float)
-        self.ctx.check(self.lib.bh_bilagrid_set_state(self.ctx._h, self._h, int(view), a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+        self._set_rows(view, 1, a)
 
     def slice(self, view, img, out=None):
         """y = A(x, y, luminance) x of `img` [H,W,4] f32 with the grid of `view`; `out` may be `img` (in place)."""
         img = _aligned_hwc4(img, img.device)
-        if out is None:
-            out = torch.empty_like(img)
-        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
-            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        out = _hwc4_out(img, out)
         h, w = int(img.shape[0]), int(img.shape[1])
         self.ctx.check(self.lib.bh_bilagrid_slice(self.ctx._h, self._h, int(view), _ptr(img), h, w, _ptr(out)))
         return out
@@ -1162,10 +1142,7 @@ class BilateralGridTable:
         v = _aligned_hwc4(v_sliced, img.device)
         if v.shape != img.shape:
             raise ValueError("v_sliced must have the shape of img")
-        if out is None:
-            out = torch.empty_like(v)
-        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.data_ptr() % 16:
-            raise ValueError("out must be a contiguous, 16-byte aligned f32 [H,W,4]")
+        out = _hwc4_out(img, out)
         h, w = int(img.shape[0]), int(img.shape[1])
         self.ctx.check(self.lib.bh_bilagrid_backward(self.ctx._h, self._h, int(view), _ptr(img), _ptr(v), h, w, _ptr(out), float(tv_weight),
                                                      1 if update else 0))
@@ -1190,18 +1167,6 @@ class BilateralGridTable:
         if a.shape != (self.n_views, 12, self.grid_l, self.grid_h, self.grid_w):
             raise ValueError("grids must be [%d, 12, %d, %d, %d]" % (self.n_views, self.grid_l, self.grid_h, self.grid_w))
         self.params = a.transpose(0, 3, 4, 2, 1)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self.ctx, "_h", None):   # (a closed context has freed its tables)
-                self.lib.bh_bilagrid_destroy(self.ctx._h, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------

@@ -250,6 +250,10 @@ def test_errors(ctx, dev):
             other.check(other.lib.bh_train_set_bilagrid(other._h, tab._h, 1.0))
     finally:
         other.close()
+    # ... and so is a handle of the other kind of per-view table on the same context
+    import util
+    util.assert_wrong_kind_handles_refused(ba, ctx)
+    assert np.array_equal(tab.params, before) and tab.state(1)[2] == 0 and not tab.grads.any()
     tab.close()
     tab.close()
 

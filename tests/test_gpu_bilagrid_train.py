@@ -217,6 +217,62 @@ def test_checkpoint_round_trip_resumes_to_the_same_bits(dev):
         ctx.close()
 
 
+def _corrected_step(ba, ctx, sc, dev, w, h, kind):
+    """One train step of the untouched scene `sc` with a colour table of `kind` on `ctx`: the loss, the splats and the table afterwards."""
+    spl = _splats(ba, sc, dev)
+    if kind == "exposure":
+        tab = ba.ExposureTable(2, lr=0.01, ctx=ctx)
+        tab.set_view(2, (np.eye(3, 4).reshape(12) + np.random.default_rng(5).uniform(-0.2, 0.2, 12)).astype(np.float32))
+        tr = ba.SplatTrainer(ba.TrainConfig(background_color=BG), median_scene_scale=3.0, ctx=ctx, exposure=tab)
+    else:
+        tab = ba.BilateralGridTable(2, grid=GRID, lr=0.01, ctx=ctx)
+        tab.set_view(2, _g())
+        tr = ba.SplatTrainer(ba.TrainConfig(background_color=BG), median_scene_scale=3.0, ctx=ctx, bilagrid=tab, bilagrid_tv_weight=10.0)
+    _, st = tr.step(ba.SceneBatch(_gt(dev, w, h), util.hip_camera(ba, synth.default_camera_params(w, h)), view_id=2), spl)
+    ctx.sync()
+    out = dict(loss=np.float32(st.loss), params=tab.params, grads=tab.grads, transforms=spl.transforms.cpu().numpy(),
+               sh=spl.sh_coeffs.cpu().numpy(), opac=spl.raw_opacities.cpu().numpy())
+    assert tab.state(2)[2] == 1 and out["grads"][1].any()
+    tab.close()
+    return out
+
+
+@pytest.mark.parametrize("w,h", [(W, H), (16, 16)])
+def test_both_colour_tables_take_turns_on_one_context(dev, w, h):
+    """The exposed frame and the sliced frame share one scratch slot of the context: a step with an exposure table, then a step with a
+    bilateral-grid table on the SAME context (the trainer detaches its table after every step) give what each gives on a context of its
+    own — the loss, the table's gradient and its updated parameters bit for bit.  Both steps start from the untouched scene, so that
+    the second does not inherit the first one's splats: at 64x48 (twelve tiles) an updated splat is reproducible only up to the order of
+    the blend backward's float atomics (tests/test_gpu_options.py), so there the splats are held to util.assert_adam_close, and to the
+    bit on the one-tile frame, where whole steps repeat (tests/test_gpu_pose_train.py)."""
+    import brush_amd as ba
+    one_tile = (w, h) == (16, 16)
+    sc = synth.make_scene(6000, 0xD0A, sh_degree=1, log_scale_range=(math.log(0.05), math.log(0.4)),
+                          tan_half_fov=(math.tan(math.radians(50)), math.tan(math.radians(50)))) if one_tile else _scene()
+    shared = ba.Context(dev)
+    try:
+        got = [_corrected_step(ba, shared, sc, dev, w, h, kind) for kind in ("exposure", "bilagrid")]
+    finally:
+        shared.close()
+    cfg = ba.TrainConfig()
+    for kind, a in zip(("exposure", "bilagrid"), got):
+        fresh = ba.Context(dev)
+        try:
+            b = _corrected_step(ba, fresh, sc, dev, w, h, kind)
+        finally:
+            fresh.close()
+        assert math.isfinite(a["loss"]) and a["loss"].tobytes() == b["loss"].tobytes(), (kind, a["loss"], b["loss"])
+        assert np.array_equal(a["params"].view(np.int32), b["params"].view(np.int32)), kind
+        assert np.array_equal(a["grads"].view(np.int32), b["grads"].view(np.int32)), kind
+        if one_tile:
+            for k in ("transforms", "sh", "opac"):
+                assert np.array_equal(a[k].view(np.int32), b[k].view(np.int32)), (kind, k)
+        else:
+            util.assert_adam_close(a["transforms"][:, 3:7], b["transforms"][:, 3:7], cfg.lr_rotation, 1, kind + " rotation")
+            util.assert_adam_close(a["transforms"][:, 7:10], b["transforms"][:, 7:10], cfg.lr_scale, 1, kind + " scale")
+            util.assert_adam_close(a["opac"], b["opac"], cfg.lr_opac, 1, kind + " opacity")
+
+
 def test_step_refuses_a_second_colour_table_and_an_unknown_view(dev):
     import brush_amd as ba
     sc = _scene()

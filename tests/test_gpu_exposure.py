@@ -212,6 +212,25 @@ def test_errors_change_nothing(ctx, dev):
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
     for s0, s1 in zip(before[2], after[2]):
         assert np.array_equal(s0[0], s1[0]) and np.array_equal(s0[1], s1[1]) and s0[2] == s1[2]
+    # a handle of the other kind of per-view table is a stranger to either kind's entry points
+    import util
+    util.assert_wrong_kind_handles_refused(ba, ctx)
+    # the setters have taken their values when they return: the caller's arrays may change or die at once
+    two = _table(ctx, views=2)
+    want = [0.5 + k for k in range(12)]
+    src = list(want)
+    two.set_view(2, src)
+    src[:] = [-1.0] * 12
+    del src
+    assert np.array_equal(two.params[1], np.asarray(want, np.float32)) and np.array_equal(two.params[0], er.IDENTITY.astype(np.float32))
+    m1, m2 = np.arange(12, dtype=np.float64) + 0.125, np.arange(12, dtype=np.float64) + 100.0
+    a, b = m1.copy(), m2.copy()
+    two.set_state(2, a, b, 7)
+    a[:] = -1.0
+    b[:] = -2.0
+    del a, b
+    s = two.state(2)
+    assert np.array_equal(s[0], m1) and np.array_equal(s[1], m2) and s[2] == 7 and two.state(1)[2] == 0
 
 
 def test_step_errors_and_destroying_an_attached_table(ctx, dev):

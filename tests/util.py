@@ -166,6 +166,41 @@ def assert_adam_close(a, b, lr, steps=1, what="", extra_abs=0.0):
     assert float(d.max()) <= 2.1 * lr * steps + extra_abs, (what, float(d.max()))
 
 
+def assert_wrong_kind_handles_refused(ba, ctx):
+    """An exposure table and a bilateral-grid table on one context: each handle given to the other kind's get_params, set_adam and
+    bh_train_set_* is refused with -1 and an error that names the kind the entry point expects, and neither table's parameters,
+    gradients or Adam state move.  No image is involved."""
+    import ctypes as C
+    lib, h = ctx.lib, ctx._h
+    exp, grid = ba.ExposureTable(1, ctx=ctx), ba.BilateralGridTable(1, grid=(1, 1, 1), ctx=ctx)
+    exp.set_view(1, np.arange(12) * 0.25)
+    exp.set_state(1, np.arange(12) + 1.0, np.arange(12) + 2.0, 3)
+    grid.set_view(1, (np.arange(12, dtype=np.float32) * 0.5).reshape(1, 1, 1, 12))
+    grid.set_state(1, np.full((1, 1, 1, 12), 4.0, np.float32), np.full((1, 1, 1, 12), 5.0, np.float32), 6)
+
+    def snap(t):
+        return (t.params, t.grads) + t.state(1)
+
+    before = snap(exp) + snap(grid)
+    buf = (C.c_float * 12)()
+    calls = (
+        ("not an exposure table of this context", lambda: lib.bh_exposure_get_params(h, grid._h, 1, 1, buf)),
+        ("not an exposure table of this context", lambda: lib.bh_exposure_set_adam(h, grid._h, 0.5, 0.9, 0.999, 1e-8)),
+        ("not an exposure table of this context", lambda: lib.bh_train_set_exposure(h, grid._h)),
+        ("not a bilateral-grid table of this context", lambda: lib.bh_bilagrid_get_params(h, exp._h, 1, 1, buf)),
+        ("not a bilateral-grid table of this context", lambda: lib.bh_bilagrid_set_adam(h, exp._h, 0.5, 0.9, 0.999, 1e-15)),
+        ("not a bilateral-grid table of this context", lambda: lib.bh_train_set_bilagrid(h, exp._h, 1.0)),
+    )
+    for text, call in calls:
+        assert call() == -1
+        assert text in lib.bh_last_error(h).decode()
+    assert not any(buf)
+    for a, b in zip(before, snap(exp) + snap(grid)):
+        assert np.array_equal(a, b)
+    exp.close()
+    grid.close()
+
+
 def random_camera(seed):
     """crates/brush-bench-test/tests/finite_diff.rs:592-606 (pinhole, identity rotation, same SplitMix64 stream)."""
     rng = Sm64(((seed * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF) ^ 0xCAFE)
