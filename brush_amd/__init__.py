@@ -47,6 +47,9 @@ Names and argument meaning follow the reference (paths under
     BilateralGridTable / SplatTrainer(bilagrid=)   per-view bilateral grids: a grid of affine colour transforms per training view, sliced
                                          at (x, y, luminance) before the loss, with a total-variation term and Adam on the device (not in
                                          the reference; gsplat's lib_bilagrid; include/brush_hip_bilagrid.h)
+    TsdfVolume / fuse_views / mesh_to_ply    mesh extraction: rendered depth maps fused into a TSDF volume (8 views per pass over the
+                                         volume), its zero level set by marching tetrahedra, a triangle-mesh PLY (not in the
+                                         reference; include/brush_hip_mesh.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -62,5 +65,6 @@ from .host import (  # noqa: F401
     PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
     render_distortion, distortion_loss, BilateralGridTable,
+    TsdfVolume, mesh_to_ply, fuse_views,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -343,6 +343,28 @@ DISTORTION_SYMBOLS = {
     "bh_train_set_distortion": (C.c_int, [C.c_void_p, C.POINTER(BhDistortionTermConfig)]),
 }
 
+# every symbol include/brush_hip_mesh.h declares (mesh extraction: TSDF fusion of depth maps, marching tetrahedra, the mesh PLY)
+TSDF_MAX_BATCH = 8   # BH_TSDF_MAX_BATCH
+
+
+class BhTsdfGrid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+                ("trunc", C.c_float), ("max_weight", C.c_float), ("reserved", C.c_uint32), ("tw", C.c_void_p), ("rgb", C.c_void_p)]
+
+
+class BhTsdfIntegrateConfig(C.Structure):
+    _fields_ = [("depth_min", C.c_float), ("depth_max", C.c_float), ("alpha_min", C.c_float), ("reserved", C.c_uint32)]
+
+
+MESH_SYMBOLS = {
+    "bh_tsdf_clear": (C.c_int, [C.c_void_p, C.POINTER(BhTsdfGrid)]),
+    "bh_tsdf_integrate": (C.c_int, [C.c_void_p, C.POINTER(BhTsdfGrid), C.c_uint32, C.POINTER(BhCamera), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(BhTsdfIntegrateConfig)]),
+    "bh_tsdf_extract_count": (C.c_int, [C.c_void_p, C.POINTER(BhTsdfGrid), u32p, u32p]),
+    "bh_tsdf_extract": (C.c_int, [C.c_void_p, C.POINTER(BhTsdfGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p]),
+    "bh_mesh_to_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -382,7 +404,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS))
     return _lib
 
 
@@ -391,6 +413,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -17,6 +17,7 @@
 #include "../../include/brush_hip_depth_loss.h"
 #include "../../include/brush_hip_normal_loss.h"
 #include "../../include/brush_hip_distortion.h"
+#include "../../include/brush_hip_mesh.h"
 #include "device_math.h"
 
 namespace bh {
@@ -94,6 +95,7 @@ enum Slot : int {
     SLOT_DISTORTION_LOSS,    // bh_distortion_loss: one f64 row of 4 per block, 2 used (distortion.hip)
     SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
     SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
+    SLOT_TSDF,               // bh_tsdf_extract[_count]: per sample the edge mask / triangle count / corner bits [n] | the vertex scan [n] | the triangle scan [n] (tsdf.hip)
     SLOT_COUNT
 };
 

@@ -1470,6 +1470,176 @@ def bounds_median_size(extent):
     return sorted(float(x) for x in extent)[1] * 2.0
 
 
+# ---------------------------------------------------------------------------
+# Mesh extraction: TSDF fusion of depth maps, marching tetrahedra, mesh PLY (include/brush_hip_mesh.h)
+# ---------------------------------------------------------------------------
+def mesh_to_ply(vertices, triangles, colours=None, ctx: Optional[Context] = None) -> bytes:
+    """A triangle mesh (vertices [V,3] f32, triangles [M,3] indices, colours [V,3] f32 in [0,1] or None) as a binary little-endian
+    PLY (bh_mesh_to_ply): rows packed on the device, one device-to-host copy."""
+    dev = vertices.device
+    ctx = ctx or get_context(dev)
+    vertices = _f32c(vertices, dev).reshape(-1, 3)
+    n_v = vertices.shape[0]
+    if colours is not None:
+        colours = _f32c(colours, dev).reshape(-1, 3)
+        if colours.shape[0] != n_v:
+            raise ValueError("mesh_to_ply: %d colours for %d vertices" % (colours.shape[0], n_v))
+    triangles = torch.as_tensor(triangles, device=dev)
+    if triangles.dtype != torch.int32:
+        triangles = triangles.to(torch.int32)
+    triangles = triangles.contiguous().reshape(-1, 3)
+    args = (_ptr(vertices), _ptr(colours) if colours is not None else None, n_v, _ptr(triangles), triangles.shape[0])
+    need = C.c_uint64(0)
+    ctx.check(ctx.lib.bh_mesh_to_ply(ctx._h, *args, None, 0, C.byref(need)))
+    buf = (C.c_char * need.value)()
+    ctx.check(ctx.lib.bh_mesh_to_ply(ctx._h, *args, buf, need.value, C.byref(need)))
+    return bytes(buf)
+
+
+class TsdfVolume:
+    """A dense truncated signed distance volume on the device (include/brush_hip_mesh.h): `dims` = (nx, ny, nz) samples at
+    origin + voxel_size * (i, j, k), x fastest.  `tw` [nz,ny,nx,2] f32 holds {tsdf in units of trunc, weight}, `rgb` [nz,ny,nx,3] the
+    mean colour (None with colour=False).  integrate() fuses depth maps (KinectFusion's running mean, up to 8 views per launch),
+    extract_mesh() is marching tetrahedra at the zero level, to_ply() the mesh as a PLY file."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, max_weight=64.0, colour=True, device=None, ctx: Optional[Context] = None):
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(v) for v in dims)
+        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
+        self.max_weight = float(max_weight)
+        # refused here, before the device is touched (the library refuses the same)
+        if len(self.origin) != 3 or len(self.dims) != 3:
+            raise ValueError("TsdfVolume: origin and dims have three entries")
+        if min(self.dims) < 2:
+            raise ValueError("TsdfVolume: every dimension must be at least 2")
+        if self.dims[0] * self.dims[1] * self.dims[2] > 2 ** 31 - 1:
+            raise ValueError("TsdfVolume: more than 2^31 - 1 samples")
+        if not (math.isfinite(self.voxel_size) and self.voxel_size > 0.0):
+            raise ValueError("TsdfVolume: voxel_size must be a finite number > 0")
+        if not (math.isfinite(self.trunc) and self.trunc > 0.0):
+            raise ValueError("TsdfVolume: trunc must be a finite number > 0")
+        if not self.max_weight >= 1.0:
+            raise ValueError("TsdfVolume: max_weight must be at least 1")
+        self.ctx = ctx or get_context(device)
+        self.device = self.ctx.device
+        nx, ny, nz = self.dims
+        self.tw = torch.empty((nz, ny, nx, 2), dtype=torch.float32, device=self.device)
+        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if colour else None
+        self.clear()
+
+    @classmethod
+    def from_bounds(cls, bounds, resolution, **kw):
+        """A volume over the box bounds = (center[3], extent[3]) (half sizes, as splat_bounds returns them) with `resolution`
+        samples along its longest side and cubic voxels."""
+        center, extent = bounds
+        resolution = int(resolution)
+        if resolution < 2:
+            raise ValueError("TsdfVolume.from_bounds: resolution must be at least 2")
+        voxel = 2.0 * max(float(e) for e in extent) / (resolution - 1)
+        if not voxel > 0.0:
+            raise ValueError("TsdfVolume.from_bounds: an empty box")
+        dims = tuple(max(2, int(math.ceil(2.0 * float(e) / voxel)) + 1) for e in extent)
+        origin = tuple(float(c) - 0.5 * voxel * (d - 1) for c, d in zip(center, dims))
+        return cls(origin, voxel, dims, **kw)
+
+    def grid(self) -> "_ffi.BhTsdfGrid":
+        g = _ffi.BhTsdfGrid()
+        g.origin = (C.c_float * 3)(*self.origin)
+        g.voxel_size = self.voxel_size
+        g.nx, g.ny, g.nz = self.dims
+        g.trunc, g.max_weight, g.reserved = self.trunc, self.max_weight, 0
+        g.tw = self.tw.data_ptr()
+        g.rgb = self.rgb.data_ptr() if self.rgb is not None else None
+        return g
+
+    @staticmethod
+    def check_views(cameras, shapes):
+        """The BhCamera array of `cameras` for depth maps of `shapes` [(H, W), ...]; ValueError for what bh_tsdf_integrate refuses
+        (a lens model other than the pinhole, a tile-row window, a camera of another size), before the device is touched."""
+        cams = (_ffi.BhCamera * len(cameras))()
+        for v, (cam, shape) in enumerate(zip(cameras, shapes)):
+            if len(shape) != 2:
+                raise ValueError("TsdfVolume.integrate: a depth map must be [H, W]")
+            cams[v] = _camera_of(cam, shape)
+            if cams[v].model != _ffi.CAMERA_PINHOLE:
+                raise ValueError("TsdfVolume.integrate: pinhole cameras only")
+            if cams[v].tile_row_begin != 0 or cams[v].tile_row_end != 0:
+                raise ValueError("TsdfVolume.integrate: a camera with a tile-row window")
+            if (cams[v].img_h, cams[v].img_w) != tuple(shape):
+                raise ValueError("TsdfVolume.integrate: camera %d is %dx%d, its depth map %dx%d" % (v, cams[v].img_w, cams[v].img_h, shape[1], shape[0]))
+        return cams
+
+    def clear(self):
+        g = self.grid()
+        self.ctx.check(self.ctx.lib.bh_tsdf_clear(self.ctx._h, C.byref(g)))
+
+    def integrate(self, depths, cameras, images=None, depth_min=0.0, depth_max=math.inf, alpha_min=0.5):
+        """Fuses depths[v] [H,W] f32 (z-depth, 0 = none) seen by cameras[v] (Camera or BhCamera, pinhole) into the volume, in order;
+        images[v] [H,W,4] f32 gives the alpha test and, with colour, the colour.  Queued: nothing is read back."""
+        depths, cameras = list(depths), list(cameras)
+        if len(depths) != len(cameras) or (images is not None and len(images) != len(depths)):
+            raise ValueError("TsdfVolume.integrate: as many cameras (and images) as depth maps")
+        n = len(depths)
+        if n == 0:
+            return
+        cams = self.check_views(cameras, [tuple(d.shape) for d in depths])
+        dev = self.device
+        depths = [_f32c(d, dev) for d in depths]
+        dptr = (C.c_void_p * n)(*[d.data_ptr() for d in depths])
+        iptr = None
+        if images is not None:
+            images = [_f32c(im, dev).reshape(d.shape[0], d.shape[1], 4) for im, d in zip(images, depths)]
+            iptr = (C.c_void_p * n)(*[im.data_ptr() for im in images])
+        cfg = _ffi.BhTsdfIntegrateConfig(float(depth_min), float(depth_max), float(alpha_min), 0)
+        g = self.grid()
+        self.ctx.check(self.ctx.lib.bh_tsdf_integrate(self.ctx._h, C.byref(g), n, cams, dptr, iptr, C.byref(cfg)))
+
+    def count(self):
+        """(n_vertices, n_triangles) of the zero level set (bh_tsdf_extract_count; blocking)."""
+        g = self.grid()
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.bh_tsdf_extract_count(self.ctx._h, C.byref(g), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def extract_mesh(self):
+        """(vertices [V,3] f32, colours [V,3] f32 or None, triangles [M,3] int32) on the device: marching tetrahedra at the zero level
+        over the cubes whose eight corners were observed; counter-clockwise seen from outside, deterministic."""
+        n_v, n_t = self.count()
+        dev = self.device
+        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        colours = torch.empty((n_v, 3), dtype=torch.float32, device=dev) if self.rgb is not None else None
+        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        g = self.grid()
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.bh_tsdf_extract(self.ctx._h, C.byref(g), _ptr(vertices), _ptr(colours) if colours is not None else None, _ptr(triangles),
+                                                    n_v, n_t, C.byref(nv), C.byref(nt)))
+        return vertices, colours, triangles
+
+    def to_ply(self) -> bytes:
+        vertices, colours, triangles = self.extract_mesh()
+        return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
+
+
+def fuse_views(splats: "Splats", cameras, img_size, volume: TsdfVolume, depth_mode="expected", pass_: "RasterPass" = None, depth_min=0.0,
+               depth_max=math.inf, alpha_min=0.5):
+    """Renders `splats` from every camera (a BH_FLAG_BWD_INFO forward on black), takes the depth map RenderNode.depth(depth_mode)
+    and the forward's image, and fuses them into `volume` in batches of 8 views (one pass over the volume per batch)."""
+    pass_ = RasterPass.Backward if pass_ is None else pass_
+    ctx = volume.ctx
+    w, h = int(img_size[0]), int(img_size[1])
+    cameras = list(cameras)
+    for first in range(0, len(cameras), _ffi.TSDF_MAX_BATCH):
+        cams, depths, images = [], [], []
+        for camera in cameras[first:first + _ffi.TSDF_MAX_BATCH]:
+            node = render_splats_diff(splats, camera, (w, h), (0.0, 0.0, 0.0), pass_, ctx=ctx)
+            depths.append(node.depth(depth_mode))
+            images.append(node.img.clone())   # (the node's image aliases ctx memory the next forward overwrites)
+            cams.append(camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((w, h)))
+        volume.integrate(depths, cams, images, depth_min=depth_min, depth_max=depth_max, alpha_min=alpha_min)
+    return volume
+
+
 @dataclass
 class SceneBatch:
     """brush-dataset/src/scene.rs:139-147: packed rgba8 GT [H,W] + camera."""

@@ -49,6 +49,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -71,6 +72,7 @@
 #include "brush_hip_normal_loss.h"
 #include "brush_hip_distortion.h"
 #include "brush_hip_bilagrid.h"
+#include "brush_hip_mesh.h"
 
 namespace brush_hip {
 
@@ -1349,6 +1351,96 @@ private:
 inline void train_set_bilagrid(const Context& ctx, const BilateralGridTable* table, float tv_weight = 10.0f) {
     ctx.check(bh_train_set_bilagrid(ctx.get(), table ? table->get() : nullptr, tv_weight));
 }
+
+// ---- mesh extraction (brush_hip_mesh.h; not in the reference) -----------------------------------------------------------------------
+static_assert(sizeof(BhTsdfGrid) == 56 && offsetof(BhTsdfGrid, voxel_size) == 12 && offsetof(BhTsdfGrid, nx) == 16 && offsetof(BhTsdfGrid, trunc) == 28 &&
+                  offsetof(BhTsdfGrid, max_weight) == 32 && offsetof(BhTsdfGrid, tw) == 40 && offsetof(BhTsdfGrid, rgb) == 48,
+              "BhTsdfGrid layout");
+static_assert(sizeof(BhTsdfIntegrateConfig) == 16 && offsetof(BhTsdfIntegrateConfig, depth_max) == 4 && offsetof(BhTsdfIntegrateConfig, alpha_min) == 8,
+              "BhTsdfIntegrateConfig layout");
+// A triangle mesh on the device: vertices [V,3] f32, colours [V,3] f32 (empty: none), triangles [M,3] u32.
+struct Mesh {
+    DeviceBuffer<float> vertices, colours;
+    DeviceBuffer<uint32_t> triangles;
+    uint32_t n_vertices = 0, n_triangles = 0;
+};
+// bh_mesh_to_ply: the mesh as a binary little-endian PLY file (rows packed on the device, one copy)
+inline std::vector<uint8_t> mesh_to_ply(const Context& ctx, const float* vertices, const float* colours /*or nullptr*/, uint32_t n_v, const uint32_t* triangles,
+                                        uint32_t n_t) {
+    uint64_t need = 0;
+    ctx.check(bh_mesh_to_ply(ctx.get(), vertices, colours, n_v, triangles, n_t, nullptr, 0, &need));
+    std::vector<uint8_t> out(need);
+    ctx.check(bh_mesh_to_ply(ctx.get(), vertices, colours, n_v, triangles, n_t, out.data(), need, &need));
+    return out;
+}
+// A dense TSDF volume that owns its device memory: nx x ny x nz samples at origin + voxel_size * (i, j, k), x fastest; tw holds
+// { tsdf in units of trunc, weight }, rgb the mean colour.  integrate() fuses depth maps (KinectFusion's running mean, up to
+// BH_TSDF_MAX_BATCH views per pass over the volume), extract() is marching tetrahedra at the zero level.  Move-only.
+class TsdfVolume {
+public:
+    TsdfVolume(const Context& ctx, const std::array<float, 3>& origin, float voxel_size, const std::array<uint32_t, 3>& dims, float trunc = 0.0f /*0: 4 voxels*/,
+               float max_weight = 64.0f, bool colour = true)
+        : ctx_(&ctx) {
+        g_ = BhTsdfGrid{};
+        for (int a = 0; a < 3; ++a) g_.origin[a] = origin[a];
+        g_.voxel_size = voxel_size;
+        g_.nx = dims[0]; g_.ny = dims[1]; g_.nz = dims[2];
+        g_.trunc = trunc > 0.0f ? trunc : 4.0f * voxel_size;
+        g_.max_weight = max_weight;
+        const uint64_t n = (uint64_t)dims[0] * dims[1] * dims[2];
+        if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2 || n > 0x7FFFFFFFull) throw Error(BH_ERR_INVALID_ARG, "TsdfVolume: dimensions of 2 or more, at most 2^31 - 1 samples");
+        tw_.resize((size_t)n * 2);
+        if (colour) rgb_.resize((size_t)n * 3);
+        g_.tw = tw_.data();
+        g_.rgb = colour ? rgb_.data() : nullptr;
+        clear();
+    }
+    TsdfVolume(const TsdfVolume&) = delete;
+    TsdfVolume& operator=(const TsdfVolume&) = delete;
+    TsdfVolume(TsdfVolume&&) noexcept = default;
+    const BhTsdfGrid& grid() const { return g_; }
+    size_t samples() const { return (size_t)g_.nx * g_.ny * g_.nz; }
+    std::vector<float> tw() const { ctx_->sync(); return tw_.download(); }     // [nz,ny,nx,2] on the host
+    std::vector<float> rgb() const { ctx_->sync(); return rgb_.download(); }   // [nz,ny,nx,3] on the host (empty without colour)
+    void set_tw(const std::vector<float>& host) {   // a field computed elsewhere, [nz,ny,nx,2]
+        if (host.size() != samples() * 2) throw Error(BH_ERR_INVALID_ARG, "TsdfVolume::set_tw: a field of another size");
+        ctx_->sync();
+        hip_check(hipMemcpy(tw_.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+    void clear() { ctx_->check(bh_tsdf_clear(ctx_->get(), &g_)); }
+    // depths[v] [H,W] and images[v] [H,W,4] (or an empty vector: no alpha test, no colour) are device pointers of cams[v]'s size
+    void integrate(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {},
+                   float depth_min = 0.0f, float depth_max = INFINITY, float alpha_min = 0.5f) {
+        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
+            throw Error(BH_ERR_INVALID_ARG, "TsdfVolume::integrate: as many depth maps (and images) as cameras");
+        const BhTsdfIntegrateConfig cfg{depth_min, depth_max, alpha_min, 0u};
+        ctx_->check(bh_tsdf_integrate(ctx_->get(), &g_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
+    }
+    std::pair<uint32_t, uint32_t> count() const {   // (vertices, triangles); blocking
+        uint32_t nv = 0, nt = 0;
+        ctx_->check(bh_tsdf_extract_count(ctx_->get(), &g_, &nv, &nt));
+        return {nv, nt};
+    }
+    Mesh extract() const {
+        Mesh m;
+        const auto [nv, nt] = count();
+        m.vertices.resize((size_t)nv * 3);
+        if (g_.rgb) m.colours.resize((size_t)nv * 3);
+        m.triangles.resize((size_t)nt * 3);
+        ctx_->check(bh_tsdf_extract(ctx_->get(), &g_, m.vertices.data(), g_.rgb ? m.colours.data() : nullptr, m.triangles.data(), nv, nt, &m.n_vertices,
+                                    &m.n_triangles));
+        return m;
+    }
+    std::vector<uint8_t> to_ply() const {
+        const Mesh m = extract();
+        return mesh_to_ply(*ctx_, m.vertices.data(), g_.rgb ? m.colours.data() : nullptr, m.n_vertices, m.triangles.data(), m.n_triangles);
+    }
+
+private:
+    const Context* ctx_;
+    BhTsdfGrid g_;
+    DeviceBuffer<float> tw_, rgb_;
+};
 
 // ---- depth supervision (brush_hip_depth_loss.h; not in the reference) --------------------------------------------------------------
 // A target: gt [H,W] f32 on the device holds depth (BH_DEPTH_LOSS_L1) or inverse depth (BH_DEPTH_LOSS_DISPARITY); t = fma(scale, gt, offset).
