@@ -1114,24 +1114,21 @@ namespace bh {
 
 // The two backward kernels on the saved state `fs` (bwd/render_bwd.rs:21-171).  What the forward's kernels cleared on their way is
 // recorded in ctx->clears under that forward's generation: a backward of any other forward (a retained, older one) finds nothing
-// there and clears everything itself.  span_floats != 0 (the train step): the four gradient outputs are one span of that many
-// floats starting at v_transforms (its exchange buffer).  want_refine = false: nobody reads the refine weight.
-// depth (depth.hip): a depth term's raw sums join the accumulator between K17 and K18; K17 does not run without a v_output.
-// v_viewmat (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined.
-// normal (normal.hip): a normal term's raw sums join the accumulator like depth's; its Vn lands behind depth's v_z, on row marks too.
-// distortion (distortion.hip): its raw sums join the accumulator behind depth's and normal's; its v_z joins the depth term's vector (one
-// scatter serves both) or, without a depth term, goes through the same scatter from a vector of its own, on row marks too.
-int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
-                  const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth, float* v_viewmat, const NormalTerm* normal,
-                  const DistortionTerm* distortion) {
+// there and clears everything itself.  `call` (context.h BackwardCall) says what else: K17 does not run without a v_output; the
+// terms' raw sums join the accumulator between K17 and K18 and each hands the per-splat vector it filled (v_z, Vn) to its scatter
+// behind K18 — one v_z scatter serves the depth and the distortion term — on row marks too.
+int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const BackwardCall& call) {
+    const float *transforms = call.transforms, *sh_coeffs = call.sh_coeffs, *raw_opacities = call.raw_opacities;
+    float *v_transforms = call.v_transforms, *v_sh_coeffs = call.v_sh_coeffs, *v_raw_opacities = call.v_raw_opacities, *v_refine_weight = call.v_refine_weight;
+    const size_t span_floats = call.span_floats;
     const BhRenderOut& r = fs.out;
     const uint32_t n = fs.n, nv = r.num_listed_splats, C = (fs.sh_degree + 1) * (fs.sh_degree + 1);
     const size_t nvpad = nv ? nv : 1;
     auto* v_combined = (float*)ensure(ctx, SLOT_V_COMBINED, nvpad * 10 * 4 + 16);   // + room to clear whole float4s
     if (!v_combined) return BH_ERR_OOM;
     bool row_marks = false;
-    const float* scatter_v_z = nullptr;   // the v_z vector behind K18: NULL = the depth term's
+    float* v_z = nullptr;         // what the depth and distortion terms leave for the v_z scatter behind K18
+    const float* v_n = nullptr;   // ... and the normal term for the Vn scatter
     {
         ProfScope ps(ctx, "ZeroGradBuffers");
         // what the forward's kernels cleared on their way (K5: v_combined; K1: the train step's gradient span) is done
@@ -1173,24 +1170,23 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         if (r.num_intersections > 0 && v_output)
             BH_TRY(launch_rasterize_backward(ctx, fs.uniforms, fs.bg, fs.flags & BH_FLAG_SMOOTH_CUTOFF,
                                              r.compact_gid_from_isect, r.tile_offsets, r.projected, r.out_img, v_output, v_combined, fs.lpt,
-                                             r.tile_offsets_far, want_refine, &fs.jobs, nv));
-        if (depth) BH_TRY(launch_depth_backward(ctx, fs, *depth, v_combined));
-        if (normal) BH_TRY(launch_normal_backward(ctx, fs, *normal, transforms, v_combined));
-        // (behind launch_depth_backward: SLOT_DEPTH has its final size and v_z is filled)
-        if (distortion) BH_TRY(launch_distortion_backward(ctx, fs, *distortion, v_combined, depth ? (float*)ctx->slots[SLOT_DEPTH].ptr : nullptr, &scatter_v_z));
+                                             r.tile_offsets_far, call.want_refine, &fs.jobs, nv));
+        if (call.depth) BH_TRY(launch_depth_backward(ctx, fs, *call.depth, v_combined, &v_z));
+        if (call.normal) BH_TRY(launch_normal_backward(ctx, fs, *call.normal, transforms, v_combined, &v_n));
+        if (call.distortion) BH_TRY(launch_distortion_backward(ctx, fs, *call.distortion, v_combined, &v_z));   // (behind the depth term: it adds to a filled v_z)
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
         BH_TRY(launch_project_backward(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs,
                                        raw_opacities, r.global_from_compact_gid, v_combined, v_transforms, v_sh_coeffs,
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
-        if (depth || distortion) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight, scatter_v_z));
-        if (normal) BH_TRY(launch_normal_vn_scatter(ctx, fs, transforms, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
+        if (v_z) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_z, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
+        if (v_n) BH_TRY(launch_normal_vn_scatter(ctx, fs, v_n, transforms, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
     }
-    if (v_viewmat) {   // (brush_hip_pose.h: only when asked for)
+    if (call.v_viewmat) {   // (brush_hip_pose.h: only when asked for)
         ProfScope ps(ctx, "PoseGrad");
         BH_TRY(launch_pose_grad(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs, r.global_from_compact_gid,
-                                v_combined, v_viewmat));
+                                v_combined, call.v_viewmat));
     }
     return 0;
 }
@@ -1208,6 +1204,31 @@ int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_co
     return set_error(ctx, BH_ERR_STATE, msg);
 }
 
+int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t required, const BhRenderOut* saved, const float* v_output, BackwardCall call) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    const std::string name(who);
+    const float* v_depth = call.depth ? call.depth->v_depth : nullptr;
+    const float* v_normal = call.normal ? call.normal->v_normal : nullptr;
+    const float* v_distortion = call.distortion ? call.distortion->v_distortion : nullptr;
+    const bool takes_normal = call.normal != nullptr;
+    if (!saved || !call.v_transforms || !call.v_sh_coeffs || !call.v_raw_opacities || !call.v_refine_weight || ((required & NEED_V_OUTPUT) && !v_output) ||
+        ((required & NEED_V_DEPTH) && !v_depth) || ((required & NEED_V_NORMAL) && !v_normal) || ((required & NEED_V_DISTORTION) && !v_distortion) ||
+        ((required & NEED_V_VIEWMAT) && !call.v_viewmat))
+        return set_error(ctx, BH_ERR_INVALID_ARG, name + ": null argument");
+    // an optional cotangent the caller left out: no term, and its mode is not looked at
+    if (!v_depth) call.depth = nullptr;
+    if (!v_normal) call.normal = nullptr;
+    if (!v_distortion) call.distortion = nullptr;
+    if (call.distortion) BH_TRY(check_distortion_kind(ctx, call.distortion->kind, call.distortion->near_z, call.distortion->far_z, who));
+    if (call.normal && call.normal->mode > BH_NORMAL_UNIT) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": unknown normal mode");
+    if (call.depth && call.depth->mode == BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": median depth has no gradient");
+    if (call.depth && call.depth->mode > BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": unknown depth mode");
+    const ForwardState* fs = nullptr;
+    BH_TRY(find_saved_bwd_forward(ctx, saved, not_bwd_code, who, &fs));
+    if (takes_normal && fs->n > 0 && !call.transforms) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": null transforms");
+    return backward_impl(ctx, *fs, v_output, call);
+}
+
 // the arena slots a BhRenderOut points into (everything a retained forward must keep alive)
 static const Slot kRetainSlots[RETAIN_SLOTS] = {SLOT_OUT_IMG, SLOT_VISIBLE, SLOT_MAX_RADIUS, SLOT_TILE_OFFSETS, SLOT_PROJECTED, SLOT_ISECT_GIDS_SORTED,
                                                 SLOT_TILE_IDS_SORTED, SLOT_GLOBAL_FROM_COMPACT, SLOT_CUM_TILES_HIT, SLOT_ISECT_COUNTS, SLOT_DEPTHS_SORTED,
@@ -1223,25 +1244,17 @@ int bh_render_backward(bh_ctx* ctx, const float* v_output, const float* transfor
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!ctx->have_forward || !(ctx->latest.flags & BH_FLAG_BWD_INFO))
         return set_error(ctx, BH_ERR_STATE, "render_backward needs a preceding BH_FLAG_BWD_INFO forward on this context");
-    if (!v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
-        return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward: null argument");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
-    return backward_impl(ctx, ctx->latest, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities,
-                         v_refine_weight, /*span_floats=*/0, /*want_refine=*/true);
+    // (the ctx's own record of that forward is the saved one: it is found again, and cannot be stale)
+    BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    return backward_entry(ctx, "render_backward", BH_ERR_STATE, NEED_V_OUTPUT, &ctx->latest.out, v_output, call);
 }
 
 // SplatBwdOps::{rasterize_bwd, project_bwd} take the forward's saved tensors explicitly (bwd/burn_glue.rs:62-92, 336-371): so does this.
 int bh_render_backward_saved(bh_ctx* ctx, const BhRenderOut* saved, const float* v_output, const float* transforms, const float* sh_coeffs,
                              const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities,
                              float* v_refine_weight) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!saved || !v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
-        return set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_saved: null argument");
-    const ForwardState* fs = nullptr;
-    BH_TRY(find_saved_bwd_forward(ctx, saved, BH_ERR_STATE, "render_backward_saved", &fs));
-    return backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
-                         /*span_floats=*/0, /*want_refine=*/true);
+    BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    return backward_entry(ctx, "render_backward_saved", BH_ERR_STATE, NEED_V_OUTPUT, saved, v_output, call);
 }
 
 int bh_render_retain(bh_ctx* ctx, const BhRenderOut* out) {
@@ -1720,6 +1733,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // ---- normal term (brush_hip_normal_loss.h): on the same final frame, with the same expected-depth map (rendered once).  N and
     // v_normal live in a slot of their own too (SLOT_NORMAL is the normal backward's scratch).  The fused operator adds its v_depth to
     // the depth loss's, or writes it where there is none; loss += the term's, in f32, behind the depth term's.
+    BackwardCall bwd;
     DepthTerm depth_term;
     NormalTerm normal_term;
     const bool frame_listed = ctx->latest.out.num_intersections > 0 && n > 0;   // (an empty frame has no valid pixel)
@@ -1734,6 +1748,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (depth_on) BH_TRY(launch_depth_loss(ctx, e_map, *depth_target, v_depth + hw, v_depth, loss_dev, loss_host));
         depth_term.v_depth = v_depth;
         depth_term.mode = BH_DEPTH_EXPECTED;
+        bwd.depth = &depth_term;
         if (normal_on) {
             ProfScope pn(ctx, "NormalTerm");
             auto* n_map = (float*)ensure(ctx, SLOT_NORMAL_TERM, (hw * 6 + 4) * 4);
@@ -1744,6 +1759,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
                                       v_normal + hw * 3, v_normal, v_depth, loss_dev, loss_host));
             normal_term.v_normal = v_normal;
             normal_term.mode = BH_NORMAL_ACCUMULATED;
+            bwd.normal = &normal_term;
         }
     }
     // ---- distortion term (brush_hip_distortion.h): on the same final frame, behind the normal term.  The moment map lives in a slot of
@@ -1763,6 +1779,7 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         BH_TRY(launch_distortion_map(ctx, ctx->latest, distortion_term, /*moments=*/true, moments));
         BH_TRY(launch_distortion_loss(ctx, moments, H, W, 4u, dc.weight, moments + hw * 4, loss_dev, loss_host));
         distortion_term.moments = moments;
+        bwd.distortion = &distortion_term;
     }
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
@@ -1818,9 +1835,12 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
     // runs without it (refine_weight_norm stays as refine() zeroed it).  g_tr .. the end of the exchange buffer is one span
     // (padding included): one zero-fill, if the forward's K1 did not clear it.
     const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
-    BH_TRY(backward_impl(ctx, ctx->latest, v_output, r_transforms, st->sh_coeffs, r_raw_opac, g_tr, g_sh, g_op, s_refine,
-                         /*span_floats=*/exch_count - o_tr, /*want_refine=*/!skip_refine, (depth_on || normal_on) ? &depth_term : nullptr, ctx->pose_grad,
-                         normal_on ? &normal_term : nullptr, distortion_on ? &distortion_term : nullptr));
+    bwd.transforms = r_transforms; bwd.sh_coeffs = st->sh_coeffs; bwd.raw_opacities = r_raw_opac;
+    bwd.v_transforms = g_tr; bwd.v_sh_coeffs = g_sh; bwd.v_raw_opacities = g_op; bwd.v_refine_weight = s_refine;
+    bwd.span_floats = exch_count - o_tr;
+    bwd.want_refine = !skip_refine;
+    bwd.v_viewmat = ctx->pose_grad;
+    BH_TRY(backward_impl(ctx, ctx->latest, v_output, bwd));
     if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");
         BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));

@@ -82,17 +82,15 @@ enum Slot : int {
     SLOT_LPIPS,              // bh_lpips_*: f64 partials | normalised inputs | scratch pair | activations of both images (lpips.hip)
     SLOT_PLY_COMPRESS,       // bh_splat_to_compressed_ply: box partials | box | Morton keys [N] | sorted keys [N] | row order [N] (ply_compress.hip)
     SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
-    SLOT_DEPTH,              // bh_render_backward_depth_saved: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip)
+    SLOT_DEPTH,              // launch_depth_backward: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip; nobody else looks inside: the backward hands v_z on)
     SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
     SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
     SLOT_CORRECTED,          // bh_train_step with an exposure or a bilateral-grid table (never both): [H,W,4] the exposed / sliced frame the loss reads (out_img stays as rendered)
-    SLOT_DEPTH_LOSS,         // bh_depth_loss_value_and_grad / bh_eval_depth_metrics: one f64 row of 4 per block (depth_loss.hip)
+    SLOT_PIXEL_LOSS,         // the pixel losses' partial sums, one f64 row of 4 per block (depth_loss.hip loss_partials): depth loss and metrics, normal consistency, distortion loss — one after another on the ctx stream, each followed at once by its final block
     SLOT_DEPTH_TERM,         // bh_train_step with a depth target or a normal term: expected depth [H,W] | v_depth [H,W] | the depth term's loss pair (4 floats)
-    SLOT_NORMAL,             // bh_render_normal / bh_render_backward_normal_saved: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip)
-    SLOT_NORMAL_LOSS,        // bh_normal_consistency_value_and_grad: one f64 row of 4 per block, 2 used (normal_loss.hip)
+    SLOT_NORMAL,             // bh_render_normal / launch_normal_backward: compact splat normals [Nv,3] | Vn [Nv,3] | the frame's accumulated normals [H,W,3] (normal.hip; the backward hands Vn on)
     SLOT_NORMAL_TERM,        // bh_train_step with a normal term: accumulated normals [H,W,3] | v_normal [H,W,3] | the term's loss pair (4 floats)
-    SLOT_DISTORTION,         // bh_render_distortion / bh_render_backward_distortion_saved: NDC depths m [Nv] | v_m (the term's own v_z) [Nv] | the frame's moment map [H,W,4] (distortion.hip)
-    SLOT_DISTORTION_LOSS,    // bh_distortion_loss: one f64 row of 4 per block, 2 used (distortion.hip)
+    SLOT_DISTORTION,         // bh_render_distortion / launch_distortion_backward: NDC depths m [Nv] | v_m (the term's own v_z) [Nv] | the frame's moment map [H,W,4] (distortion.hip)
     SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
     SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
     SLOT_TSDF,               // bh_tsdf_extract[_count]: per sample the edge mask / triangle count / corner bits [n] | the vertex scan [n] | the triangle scan [n] (tsdf.hip)
@@ -388,6 +386,24 @@ struct DistortionTerm {
     const float* moments = nullptr;        // [H,W,4] the frame's moment map if the caller has rendered it (the train step), or NULL
 };
 
+// One backward on a saved forward (api.hip backward_impl): the parameters the forward rendered, where the gradients go, and the
+// terms beside the colour term's <v_output, image>.
+struct BackwardCall {
+    const float* transforms = nullptr;
+    const float* sh_coeffs = nullptr;
+    const float* raw_opacities = nullptr;
+    float* v_transforms = nullptr;
+    float* v_sh_coeffs = nullptr;
+    float* v_raw_opacities = nullptr;
+    float* v_refine_weight = nullptr;
+    size_t span_floats = 0;        // != 0 (the train step): the four outputs are one span of that many floats from v_transforms on
+    bool want_refine = true;       // false: nobody reads the refine weight
+    const DepthTerm* depth = nullptr;             // its raw sums join the accumulator between K17 and K18, its v_z lands behind K18
+    const NormalTerm* normal = nullptr;           // likewise, behind depth's; its Vn lands behind depth's v_z
+    const DistortionTerm* distortion = nullptr;   // likewise, behind normal's; its v_z joins depth's or goes through the same scatter
+    float* v_viewmat = nullptr;    // [12] (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined
+};
+
 }  // namespace bh
 
 // The blend backward accumulates RAW per-splat sums into v_combined and the projection backward maps them to the reference's
@@ -532,32 +548,37 @@ int wait_host_tag(bh_ctx* ctx, const volatile uint32_t* word, uint32_t want, con
 // (the ctx's own record either way, no copy); anything else is BH_ERR_STATE under `who`'s name (a pending far slice is finished
 // first).  Valid until the next call that retains, releases or renders on the ctx.
 int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_code, const char* who, const ForwardState** fs);
-// api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when there is a depth or a normal term (then K17
-// does not run)
-int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const float* transforms, const float* sh_coeffs,
-                  const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight,
-                  size_t span_floats, bool want_refine, const DepthTerm* depth = nullptr, float* v_viewmat = nullptr,
-                  const NormalTerm* normal = nullptr, const DistortionTerm* distortion = nullptr);
-// depth.hip: the depth term between K17 and K18 (raw sums into v_combined, v_z into SLOT_DEPTH), and v_z -> v_mean behind K18
-int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined);
-// mark_rows (the single-GPU train step's ROW_MARKS span): a row K18 did not write is stored whole (zeros but the mean) and marked
-int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows = false, float* v_sh_coeffs = nullptr,
-                            float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr, const float* v_z = nullptr);
+// api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when the call has another term (then K17 does not
+// run)
+int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const BackwardCall& call);
+// api.hip: what the bh_render_backward*_saved entry points share.  `required`: the cotangents that entry refuses to do without;
+// a term of `call` whose cotangent is NULL is an optional one the caller left out.  In this order: the null-argument refusal, the
+// distortion-kind, normal-mode and depth-mode refusals, find_saved_bwd_forward(not_bwd_code), the null-transforms refusal (an
+// entry that accepts a normal term has it), backward_impl.  Every text carries `who`.
+enum : uint32_t { NEED_V_OUTPUT = 1u, NEED_V_DEPTH = 2u, NEED_V_NORMAL = 4u, NEED_V_DISTORTION = 8u, NEED_V_VIEWMAT = 16u };
+int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t required, const BhRenderOut* saved, const float* v_output, BackwardCall call);
+// depth.hip: the depth term between K17 and K18 (raw sums into v_combined; *v_z = the per-splat vector it filled), and a v_z ->
+// v_mean behind K18 (the depth term's vector, the distortion term's, or the one both filled)
+int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined, float** v_z);
+// mark_rows (the single-GPU train step's ROW_MARKS span): device_map_blend.h claim_grad_row
+int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, const float* v_z, float* v_transforms, bool mark_rows, float* v_sh_coeffs,
+                            float* v_raw_opacities, float* v_refine_weight);
 int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, float* out_depth);
-// normal.hip: the normal term between K17 and K18 (raw sums into v_combined, Vn into SLOT_NORMAL), and Vn -> v_quat behind K18 and
-// depth's scatter; mark_rows as launch_depth_vz_scatter's
-int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined);
-int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms, bool mark_rows = false,
-                             float* v_sh_coeffs = nullptr, float* v_raw_opacities = nullptr, float* v_refine_weight = nullptr);
+// normal.hip: the normal term between K17 and K18 (raw sums into v_combined; *v_n = the per-splat [Nv,3] vector it filled), and
+// Vn -> v_quat behind K18 and depth's scatter; mark_rows as launch_depth_vz_scatter's
+int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined, const float** v_n);
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* v_n, const float* transforms, float* v_transforms, bool mark_rows,
+                             float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight);
 // ... and the normal map `mode` of a saved forward with something listed (bh_render_normal, the train step's normal term)
 int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transforms, uint32_t mode, float* out);
 // normal_loss.hip: the fused normal-consistency operator on the ctx stream (arguments already checked; weight > 0).  accum != NULL (train
 // step): loss[0] is added to accum[0] in f32 and the total copied to accum_host
 int launch_normal_loss(bh_ctx* ctx, const BhCamera& cam, const float* normal, const float* depth, const float* image, uint32_t h, uint32_t w, float weight,
                        bool accumulate_v_depth, float* loss, float* v_normal, float* v_depth, float* accum, float* accum_host);
-// distortion.hip: the distortion term between K17 and K18, behind the depth term's replay (raw sums into v_combined; its v_z added into
-// depth_v_z, the depth term's filled vector, or stored in a vector of its own in SLOT_DISTORTION: *v_z_out is the one the scatter reads)
-int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& term, float* v_combined, float* depth_v_z, const float** v_z_out);
+// distortion.hip: the distortion term between K17 and K18, behind the depth term's replay (raw sums into v_combined).  *v_z in: the
+// depth term's filled vector, or NULL without one; out: the vector the ONE scatter behind K18 reads — the same with this term's v_z
+// added, or a vector of the term's own
+int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& term, float* v_combined, float** v_z);
 // ... the distortion map (moments: the moment map [H,W,4]) of a saved forward with something listed, the kind's check and the loss
 // (accum as launch_depth_loss's)
 int launch_distortion_map(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& term, bool moments, float* out);
@@ -567,7 +588,10 @@ int launch_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);
-// ... and its final block alone, for normal_loss.hip: loss = { f32(c * column 0 of the f64 rows), column 1 }, accum as above
+// ... what the pixel losses share (depth, normal consistency, distortion): the partial rows of a map of `pixels` pixels
+// (SLOT_PIXEL_LOSS; NULL: out of memory) with *blocks = the grid that fills them (DL_WG threads each, at most DL_MAX_BLOCKS), and
+// the final block: loss = { f32(c * column 0 of the f64 rows), column 1 }, accum as above
+double* loss_partials(bh_ctx* ctx, uint64_t pixels, uint32_t* blocks);
 int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, float c, float* loss, float* accum, float* accum_host);
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,

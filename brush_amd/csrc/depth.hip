@@ -83,50 +83,35 @@ struct DepthMap {
     static BH_DEV float vg(const Rec&, const Pix& px, int i) { return px.g[i]; }
 };
 
-// v_mean += (row 2 of the view matrix) * v_z, behind K18: a row K18 skipped (its ten sums are zero) is zero in the dense output
-__global__ __launch_bounds__(256) void depth_vz_scatter_kernel(uint32_t nv, float r0, float r1, float r2, const uint32_t* __restrict__ global_from_compact,
-                                                               const float* __restrict__ v_z, float* __restrict__ v_transforms) {
-    const uint32_t cg = blockIdx.x * 256u + threadIdx.x;
-    if (cg >= nv) return;
-    const float vz = v_z[cg];
-    if (vz == 0.0f) return;
-    float* vt = v_transforms + (size_t)global_from_compact[cg] * 10;
-    vt[0] = __builtin_fmaf(r0, vz, vt[0]);
-    vt[1] = __builtin_fmaf(r1, vz, vt[1]);
-    vt[2] = __builtin_fmaf(r2, vz, vt[2]);
-}
-
-// The same behind a K18 in marking mode (the single-GPU train step: only the refine-weight vector was cleared, K18 marked the rows
-// it wrote in that vector's sign bits and the update reads marked rows only).  K18 skips a splat whose ten sums are all zero — one
-// whose every pair sat at the alpha clamp still has a v_z — so a row that receives v_z may hold last step's bytes and carry no
-// mark: such a row is STORED whole (what a zero-filled row would hold after the accumulate above, bit for bit) and marked.  The
-// mark is the sign of a zero: the refine weight itself is not touched.
-__global__ __launch_bounds__(256) void depth_vz_scatter_marking_kernel(uint32_t nv, float r0, float r1, float r2, uint32_t sh_floats,
-                                                                       const uint32_t* __restrict__ global_from_compact, const float* __restrict__ v_z,
-                                                                       float* __restrict__ v_transforms, float* __restrict__ v_sh, float* __restrict__ v_raw_opac,
-                                                                       float* __restrict__ v_refine) {
+// v_mean += (row 2 of the view matrix) * v_z, behind K18 in its dense mode: a row K18 skipped (its ten sums are zero) is zero in the
+// zero-filled dense output.  MARK (behind a K18 in marking mode, the single-GPU train step): K18 skips a splat whose ten sums are
+// all zero — one whose every pair sat at the alpha clamp still has a v_z — so the row is claimed first (claim_grad_row).
+template <bool MARK>
+BH_DEV void vz_scatter_row(uint32_t nv, float r0, float r1, float r2, uint32_t sh_floats, const uint32_t* __restrict__ global_from_compact,
+                           const float* __restrict__ v_z, float* __restrict__ v_transforms, float* __restrict__ v_sh, float* __restrict__ v_raw_opac,
+                           float* __restrict__ v_refine) {
     const uint32_t cg = blockIdx.x * 256u + threadIdx.x;
     if (cg >= nv) return;
     const float vz = v_z[cg];
     if (vz == 0.0f) return;
     const uint32_t gid = global_from_compact[cg];
     float* vt = v_transforms + (size_t)gid * 10;
-    const uint32_t mark = f2u(v_refine[gid]);
-    if (mark >> 31) {
-        vt[0] = __builtin_fmaf(r0, vz, vt[0]);
-        vt[1] = __builtin_fmaf(r1, vz, vt[1]);
-        vt[2] = __builtin_fmaf(r2, vz, vt[2]);
-        return;
-    }
-    vt[0] = __builtin_fmaf(r0, vz, 0.0f);
-    vt[1] = __builtin_fmaf(r1, vz, 0.0f);
-    vt[2] = __builtin_fmaf(r2, vz, 0.0f);
-#pragma unroll
-    for (int k = 3; k < 10; ++k) vt[k] = 0.0f;
-    float* sh = v_sh + (size_t)gid * sh_floats;
-    for (uint32_t k = 0; k < sh_floats; ++k) sh[k] = 0.0f;
-    v_raw_opac[gid] = 0.0f;
-    v_refine[gid] = u2f(mark | 0x80000000u);
+    if (MARK) claim_grad_row(gid, sh_floats, vt, v_sh, v_raw_opac, v_refine);
+    vt[0] = __builtin_fmaf(r0, vz, vt[0]);
+    vt[1] = __builtin_fmaf(r1, vz, vt[1]);
+    vt[2] = __builtin_fmaf(r2, vz, vt[2]);
+}
+
+__global__ __launch_bounds__(256) void depth_vz_scatter_kernel(uint32_t nv, float r0, float r1, float r2, const uint32_t* __restrict__ global_from_compact,
+                                                               const float* __restrict__ v_z, float* __restrict__ v_transforms) {
+    vz_scatter_row<false>(nv, r0, r1, r2, 0u, global_from_compact, v_z, v_transforms, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void depth_vz_scatter_marking_kernel(uint32_t nv, float r0, float r1, float r2, uint32_t sh_floats,
+                                                                       const uint32_t* __restrict__ global_from_compact, const float* __restrict__ v_z,
+                                                                       float* __restrict__ v_transforms, float* __restrict__ v_sh, float* __restrict__ v_raw_opac,
+                                                                       float* __restrict__ v_refine) {
+    vz_scatter_row<true>(nv, r0, r1, r2, sh_floats, global_from_compact, v_z, v_transforms, v_sh, v_raw_opac, v_refine);
 }
 
 }  // namespace
@@ -146,16 +131,17 @@ int launch_depth_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t mode, flo
     return 0;
 }
 
-// The depth term of a backward, between K17 and K18: v_combined += its raw sums, v_z (SLOT_DEPTH) = sum of v_D * w.
-int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined) {
+// The depth term of a backward, between K17 and K18: v_combined += its raw sums, *v_z_out = v_z = sum of v_D * w.
+int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& term, float* v_combined, float** v_z_out) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     // SLOT_DEPTH: v_z [Nv] (padded to a multiple of 64 floats) | the frame's accumulated depth [H,W]
-    const size_t vz_floats = ((size_t)(nv ? nv : 1u) + 63u) & ~(size_t)63u;
+    const size_t vz_floats = splat_vec_floats(nv, 1);
     const size_t pixels = (size_t)u.img_w * u.img_h;
     auto* v_z = (float*)ensure(ctx, SLOT_DEPTH, (vz_floats + pixels) * 4);
     if (!v_z) return BH_ERR_OOM;
+    *v_z_out = v_z;
     float* depth_acc = v_z + vz_floats;
     BH_HIP(ctx, hipMemsetAsync(v_z, 0, vz_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || u.num_tiles == 0) return 0;
@@ -167,13 +153,11 @@ int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& 
     return 0;
 }
 
-// v_z: the vector to scatter (the distortion term's own, where no depth term runs); NULL: the depth term's (SLOT_DEPTH)
-int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, float* v_transforms, bool mark_rows, float* v_sh_coeffs, float* v_raw_opacities,
-                            float* v_refine_weight, const float* v_z) {
+int launch_depth_vz_scatter(bh_ctx* ctx, const ForwardState& fs, const float* v_z, float* v_transforms, bool mark_rows, float* v_sh_coeffs,
+                            float* v_raw_opacities, float* v_refine_weight) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     if (nv == 0 || r.num_intersections == 0) return 0;
-    if (!v_z) v_z = (const float*)ctx->slots[SLOT_DEPTH].ptr;
     const float* vm = fs.uniforms.vm;   // column-major rotation: row 2 = (vm[2], vm[5], vm[8])
     if (mark_rows) {
         const uint32_t sh_floats = (fs.sh_degree + 1) * (fs.sh_degree + 1) * 3;
@@ -207,19 +191,12 @@ int bh_render_depth(bh_ctx* ctx, const BhRenderOut* saved, uint32_t mode, float*
 int bh_render_backward_depth_saved(bh_ctx* ctx, const BhRenderOut* saved, const float* v_output, const float* v_depth, uint32_t mode,
                                    const float* transforms, const float* sh_coeffs, const float* raw_opacities, float* v_transforms,
                                    float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!saved || !v_depth || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
-        return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_depth_saved: null argument");
-    if (mode == BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_depth_saved: median depth has no gradient");
-    if (mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_depth_saved: unknown depth mode");
-    const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_INVALID_ARG, "render_backward_depth_saved", &found));
-    const bh::ForwardState& fs = *found;
-    bh::DepthTerm term;
-    term.v_depth = v_depth;
-    term.mode = mode;
-    return bh::backward_impl(ctx, fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
-                             /*span_floats=*/0, /*want_refine=*/true, &term);
+    bh::DepthTerm depth;
+    depth.v_depth = v_depth;
+    depth.mode = mode;
+    bh::BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    call.depth = &depth;
+    return bh::backward_entry(ctx, "render_backward_depth_saved", BH_ERR_INVALID_ARG, bh::NEED_V_DEPTH, saved, v_output, call);
 }
 
 }  // extern "C"

@@ -122,11 +122,6 @@ __global__ __launch_bounds__(DL_FINAL_WG) void depth_metrics_final_kernel(uint32
     }
 }
 
-uint32_t dl_grid(uint64_t pixels) {
-    const uint64_t blocks = (pixels + DL_WG - 1) / DL_WG;
-    return (uint32_t)(blocks < DL_MAX_BLOCKS ? blocks : DL_MAX_BLOCKS);
-}
-
 DepthLossArgs dl_args(const BhDepthTarget& t) {
     DepthLossArgs a;
     a.pixels = (uint64_t)t.h * t.w;
@@ -146,6 +141,12 @@ int check_target(bh_ctx* ctx, const BhDepthTarget* t, const char* who) {
 
 }  // namespace
 
+double* loss_partials(bh_ctx* ctx, uint64_t pixels, uint32_t* blocks) {
+    const uint64_t want = (pixels + DL_WG - 1) / DL_WG;
+    *blocks = (uint32_t)(want < DL_MAX_BLOCKS ? want : DL_MAX_BLOCKS);
+    return (double*)ensure(ctx, SLOT_PIXEL_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
+}
+
 int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, float c, float* loss, float* accum, float* accum_host) {
     hipLaunchKernelGGL(depth_loss_final_kernel, dim3(1), dim3(DL_FINAL_WG), 0, ctx->stream, rows, partials, c, loss, accum, accum_host);
     BH_LAUNCH_CHECK(ctx, "depth_loss_final_kernel");
@@ -154,9 +155,10 @@ int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, f
 
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host) {
     const DepthLossArgs a = dl_args(t);
-    auto* partials = (double*)ensure(ctx, SLOT_DEPTH_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
+    uint32_t blocks = 0;
+    double* partials = loss_partials(ctx, a.pixels, &blocks);
     if (!partials) return BH_ERR_OOM;
-    const dim3 grid(dl_grid(a.pixels)), block(DL_WG);
+    const dim3 grid(blocks), block(DL_WG);
 #define BH_DL(K, G) hipLaunchKernelGGL((depth_loss_kernel<K, G>), grid, block, 0, ctx->stream, a, depth, t.gt, v_depth, partials)
     if (t.kind == BH_DEPTH_LOSS_L1) { if (v_depth) BH_DL(BH_DEPTH_LOSS_L1, true); else BH_DL(BH_DEPTH_LOSS_L1, false); }
     else { if (v_depth) BH_DL(BH_DEPTH_LOSS_DISPARITY, true); else BH_DL(BH_DEPTH_LOSS_DISPARITY, false); }
@@ -198,10 +200,10 @@ int bh_eval_depth_metrics(bh_ctx* ctx, const float* depth, const BhDepthTarget* 
     BH_TRY(check_target(ctx, target, "eval_depth_metrics"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const DepthLossArgs a = dl_args(*target);
-    auto* partials = (double*)ensure(ctx, SLOT_DEPTH_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
+    uint32_t rows = 0;
+    double* partials = loss_partials(ctx, a.pixels, &rows);
     if (!partials) return BH_ERR_OOM;
     ProfScope ps(ctx, "DepthMetrics");
-    const uint32_t rows = dl_grid(a.pixels);
     hipLaunchKernelGGL(depth_metrics_kernel, dim3(rows), dim3(DL_WG), 0, ctx->stream, a, depth, target->gt, partials);
     BH_LAUNCH_CHECK(ctx, "depth_metrics_kernel");
     hipLaunchKernelGGL(depth_metrics_final_kernel, dim3(1), dim3(DL_FINAL_WG), 0, ctx->stream, rows, partials, metrics);

@@ -50,6 +50,28 @@ inline int clear_map_window(bh_ctx* ctx, const ViewUniforms& vu, float* out, siz
     return 0;
 }
 
+// floats of a per-splat vector of a term's backward (v_z: 1 per splat, Vn: 3), padded to a multiple of 64 so that whatever follows it
+// in the slot stays 256-byte aligned; never empty
+inline size_t splat_vec_floats(uint32_t nv, uint32_t per_splat) { return ((size_t)(nv ? nv : 1u) * per_splat + 63u) & ~(size_t)63u; }
+
+// The row-marking contract of the scatters behind K18 (depth.hip: v_z -> the mean, normal.hip: Vn -> the quaternion).  In the
+// single-GPU train step only the refine-weight vector was cleared; K18 marked the rows it wrote in that vector's sign bits and the
+// update reads marked rows only.  K18 skips a splat whose ten sums are all zero, so a row a scatter adds to may hold last step's
+// bytes and carry no mark.  Such a row is claimed: stored whole as zeros (the ten transform floats at vt, its sh_floats SH floats,
+// its raw opacity) and marked, so that the scatter's accumulate leaves what a zero-filled row would hold, bit for bit.  The mark is
+// the sign of a zero: the refine weight itself is not touched.  A marked row (K18's, or an earlier scatter's) is left as it is.
+BH_DEV void claim_grad_row(uint32_t gid, uint32_t sh_floats, float* __restrict__ vt, float* __restrict__ v_sh, float* __restrict__ v_raw_opac,
+                           float* __restrict__ v_refine) {
+    const uint32_t mark = f2u(v_refine[gid]);
+    if (mark >> 31) return;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) vt[k] = 0.0f;
+    float* sh = v_sh + (size_t)gid * sh_floats;
+    for (uint32_t k = 0; k < sh_floats; ++k) sh[k] = 0.0f;
+    v_raw_opac[gid] = 0.0f;
+    v_refine[gid] = u2f(mark | 0x80000000u);
+}
+
 // lane i stages splat i of the batch; the diagonal of the conic halved as in K16 (bit-identical sigma, rasterize.hip stage_batch)
 template <bool SMOOTH, class P>
 BH_DEV uint32_t stage_map_batch(const uint32_t* __restrict__ isect_gids, const float* __restrict__ projected, const float* __restrict__ attr,

@@ -131,7 +131,7 @@ struct DistortionScratch {
 };
 
 int distortion_scratch(bh_ctx* ctx, uint32_t nv, size_t moment_pixels, bool backward, DistortionScratch* s) {
-    const size_t vec_floats = ((size_t)(nv ? nv : 1u) + 63u) & ~(size_t)63u;
+    const size_t vec_floats = splat_vec_floats(nv, 1);
     const size_t floats = backward ? 2 * vec_floats + moment_pixels * 4 : vec_floats;
     auto* base = (float*)ensure(ctx, SLOT_DISTORTION, floats * 4);
     if (!base) return BH_ERR_OOM;
@@ -181,20 +181,20 @@ int launch_distortion_map(bh_ctx* ctx, const ForwardState& fs, const DistortionT
 }
 
 // The distortion term of a backward, between K17 and K18 and behind the depth term's replay: v_combined += its raw sums; its v_z is
-// added into depth_v_z (the depth term's vector, already filled) or, depth_v_z == NULL, stored in a vector of its own.  *v_z_out: the
+// added into *v_z (the depth term's vector, already filled) or, *v_z == NULL, stored in a vector of its own.  *v_z on return: the
 // vector the ONE scatter behind K18 reads.
-int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& t, float* v_combined, float* depth_v_z, const float** v_z_out) {
+int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& t, float* v_combined, float** v_z) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     const size_t pixels = (size_t)u.img_w * u.img_h;
     DistortionScratch s;
     BH_TRY(distortion_scratch(ctx, nv, t.moments ? 0 : pixels, /*backward=*/true, &s));
-    const size_t vec_floats = ((size_t)(nv ? nv : 1u) + 63u) & ~(size_t)63u;
+    float* const depth_v_z = *v_z;
     // Z with a depth term: the replay's atomics go straight into the depth term's v_z; every other case starts from a zeroed v_m
     const bool direct = depth_v_z && t.kind == BH_DISTORTION_Z;
-    if (!direct) BH_HIP(ctx, hipMemsetAsync(s.v_m, 0, vec_floats * 4, ctx->stream));
-    *v_z_out = depth_v_z ? depth_v_z : s.v_m;
+    if (!direct) BH_HIP(ctx, hipMemsetAsync(s.v_m, 0, splat_vec_floats(nv, 1) * 4, ctx->stream));
+    if (!depth_v_z) *v_z = s.v_m;
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
     const float* m_of = nullptr;
     BH_TRY(launch_distortion_depths(ctx, fs, t, s.m, &m_of));
@@ -221,10 +221,10 @@ int launch_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w
                            float* accum_host) {
     const uint64_t pixels = (uint64_t)h * w;
     const float c = (float)((double)weight / (double)pixels);
-    auto* partials = (double*)ensure(ctx, SLOT_DISTORTION_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
+    uint32_t blocks = 0;
+    double* partials = loss_partials(ctx, pixels, &blocks);
     if (!partials) return BH_ERR_OOM;
-    const uint64_t blocks = (pixels + DL_WG - 1) / DL_WG;
-    const dim3 grid((uint32_t)(blocks < DL_MAX_BLOCKS ? blocks : DL_MAX_BLOCKS)), block(DL_WG);
+    const dim3 grid(blocks), block(DL_WG);
     if (channels == 4) hipLaunchKernelGGL(distortion_loss_kernel<4>, grid, block, 0, ctx->stream, pixels, map, partials);
     else hipLaunchKernelGGL(distortion_loss_kernel<1>, grid, block, 0, ctx->stream, pixels, map, partials);
     BH_LAUNCH_CHECK(ctx, "distortion_loss_kernel");
@@ -273,28 +273,19 @@ int bh_render_backward_distortion_saved(bh_ctx* ctx, const BhRenderOut* saved, c
                                         const float* v_normal, uint32_t normal_mode, const float* v_distortion, const BhDistortionConfig* cfg,
                                         const float* transforms, const float* sh_coeffs, const float* raw_opacities, float* v_transforms,
                                         float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight) {
-    const char* who = "render_backward_distortion_saved";
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!saved || !v_distortion || !cfg || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
-        return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    BH_TRY(check_distortion_kind(ctx, cfg->kind, cfg->near_z, cfg->far_z, who));
-    if (v_normal && normal_mode > BH_NORMAL_UNIT) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": unknown normal mode");
-    if (v_depth && depth_mode == BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": median depth has no gradient");
-    if (v_depth && depth_mode > BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": unknown depth mode");
-    const ForwardState* found = nullptr;
-    BH_TRY(find_saved_bwd_forward(ctx, saved, BH_ERR_INVALID_ARG, who, &found));
-    const ForwardState& fs = *found;
-    if (fs.n > 0 && !transforms) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": null transforms");
     DepthTerm depth;
     depth.v_depth = v_depth;
     depth.mode = depth_mode;
     NormalTerm normal;
     normal.v_normal = v_normal;
     normal.mode = normal_mode;
-    DistortionTerm dist = term_of(*cfg);
+    DistortionTerm dist = cfg ? term_of(*cfg) : DistortionTerm{};
     dist.v_distortion = v_distortion;
-    return backward_impl(ctx, fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
-                         /*span_floats=*/0, /*want_refine=*/true, v_depth ? &depth : nullptr, /*v_viewmat=*/nullptr, v_normal ? &normal : nullptr, &dist);
+    BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    call.depth = &depth;
+    call.normal = &normal;
+    call.distortion = cfg ? &dist : nullptr;   // (no configuration: no term, and the term is required)
+    return backward_entry(ctx, "render_backward_distortion_saved", BH_ERR_INVALID_ARG, NEED_V_DISTORTION, saved, v_output, call);
 }
 
 int bh_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w, uint32_t channels, float weight, float* loss) {

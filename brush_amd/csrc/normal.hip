@@ -142,10 +142,9 @@ struct NormalMap {
 // v_quat += the chain of Vn through the sign, R_view^T, column k of the rotation matrix and the quaternion's normalisation, behind
 // K18 in its dense mode: a row K18 skipped (its ten sums are zero) is zero in the zero-filled dense output, so a splat that
 // received only Vn is still written
-// MARK (behind a K18 in marking mode: the single-GPU train step; depth.hip's depth_vz_scatter_marking_kernel has the contract): a splat
-// with a non-zero Vn may sit in a row K18 skipped, which holds last step's bytes and carries no mark.  Such a row is first cleared
-// whole and marked in the sign bit of its refine weight, so that the accumulate below leaves what a zero-filled row would hold, bit
-// for bit; a marked row (K18's, or depth's scatter, which runs in front of this one) is accumulated into as it is.
+// MARK (behind a K18 in marking mode: the single-GPU train step): a splat with a non-zero Vn may sit in a row K18 skipped, so the
+// row is claimed first (device_map_blend.h claim_grad_row); a marked row (K18's, or depth's scatter, which runs in front of this one)
+// is accumulated into as it is.
 template <bool MARK>
 BH_DEV void vn_scatter_row(uint32_t nv, const NormalView& v, uint32_t sh_floats, const uint32_t* __restrict__ global_from_compact,
                            const float* __restrict__ transforms, const float* __restrict__ v_n, float* __restrict__ v_transforms,
@@ -179,17 +178,7 @@ BH_DEV void vn_scatter_row(uint32_t nv, const NormalView& v, uint32_t sh_floats,
     // qn = q / |q|: v_q = (d - qn (qn . d)) / |q|
     const float along = qdot(f.qn, d);
     float* vt = v_transforms + (size_t)gid * 10;
-    if (MARK) {
-        const uint32_t mark = f2u(v_refine[gid]);
-        if (!(mark >> 31)) {
-#pragma unroll
-            for (int k = 0; k < 10; ++k) vt[k] = 0.0f;
-            float* sh = v_sh + (size_t)gid * sh_floats;
-            for (uint32_t k = 0; k < sh_floats; ++k) sh[k] = 0.0f;
-            v_raw_opac[gid] = 0.0f;
-            v_refine[gid] = u2f(mark | 0x80000000u);
-        }
-    }
+    if (MARK) claim_grad_row(gid, sh_floats, vt, v_sh, v_raw_opac, v_refine);
     vt[3] += (d.w - w * along) * f.inv_len;
     vt[4] += (d.x - x * along) * f.inv_len;
     vt[5] += (d.y - y * along) * f.inv_len;
@@ -259,7 +248,7 @@ struct NormalScratch {
 };
 
 int normal_scratch(bh_ctx* ctx, uint32_t nv, size_t pixels, bool backward, NormalScratch* s) {
-    s->vec_floats = ((size_t)(nv ? nv : 1u) * 3u + 63u) & ~(size_t)63u;
+    s->vec_floats = splat_vec_floats(nv, 3);
     const size_t floats = backward ? 2 * s->vec_floats + pixels * 3 : s->vec_floats;
     auto* base = (float*)ensure(ctx, SLOT_NORMAL, floats * 4);
     if (!base) return BH_ERR_OOM;
@@ -310,13 +299,14 @@ int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transfor
     return launch_normal_forward(ctx, fs, s.normals, mode, out);
 }
 
-// The normal term of a backward, between K17 and K18: v_combined += its raw sums, Vn (SLOT_NORMAL) = sum of vis * g.
-int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined) {
+// The normal term of a backward, between K17 and K18: v_combined += its raw sums, *v_n_out = Vn = sum of vis * g.
+int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm& term, const float* transforms, float* v_combined, const float** v_n_out) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     NormalScratch s;
     BH_TRY(normal_scratch(ctx, nv, (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
+    *v_n_out = s.v_n;
     BH_HIP(ctx, hipMemsetAsync(s.v_n, 0, s.vec_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
     BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
@@ -330,13 +320,11 @@ int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm
 
 // Vn -> the quaternion columns of v_transforms, behind K18 (and behind depth's scatter): dense and zero-filled, or (mark_rows, the
 // single-GPU train step) row-marked
-int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* v_transforms, bool mark_rows, float* v_sh_coeffs,
-                             float* v_raw_opacities, float* v_refine_weight) {
+int launch_normal_vn_scatter(bh_ctx* ctx, const ForwardState& fs, const float* v_n, const float* transforms, float* v_transforms, bool mark_rows,
+                             float* v_sh_coeffs, float* v_raw_opacities, float* v_refine_weight) {
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     if (nv == 0 || r.num_intersections == 0) return 0;
-    const size_t vec_floats = ((size_t)nv * 3u + 63u) & ~(size_t)63u;
-    const float* v_n = (const float*)ctx->slots[SLOT_NORMAL].ptr + vec_floats;
     if (mark_rows) {
         const uint32_t sh_floats = (fs.sh_degree + 1) * (fs.sh_degree + 1) * 3;
         hipLaunchKernelGGL(normal_vn_scatter_marking_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, ctx->stream, nv, normal_view(fs.uniforms.vm), sh_floats,
@@ -385,24 +373,16 @@ int bh_render_backward_normal_saved(bh_ctx* ctx, const BhRenderOut* saved, const
                                     const float* v_normal, uint32_t normal_mode, const float* transforms, const float* sh_coeffs,
                                     const float* raw_opacities, float* v_transforms, float* v_sh_coeffs, float* v_raw_opacities,
                                     float* v_refine_weight) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!saved || !v_normal || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight)
-        return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: null argument");
-    if (normal_mode > BH_NORMAL_UNIT) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown normal mode");
-    if (v_depth && depth_mode == BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: median depth has no gradient");
-    if (v_depth && depth_mode > BH_DEPTH_MEDIAN) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: unknown depth mode");
-    const bh::ForwardState* found = nullptr;
-    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_INVALID_ARG, "render_backward_normal_saved", &found));
-    const bh::ForwardState& fs = *found;
-    if (fs.n > 0 && !transforms) return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_normal_saved: null transforms");
     bh::DepthTerm depth;
     depth.v_depth = v_depth;
     depth.mode = depth_mode;
     bh::NormalTerm normal;
     normal.v_normal = v_normal;
     normal.mode = normal_mode;
-    return bh::backward_impl(ctx, fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
-                             /*span_floats=*/0, /*want_refine=*/true, v_depth ? &depth : nullptr, /*v_viewmat=*/nullptr, &normal);
+    bh::BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    call.depth = &depth;
+    call.normal = &normal;
+    return bh::backward_entry(ctx, "render_backward_normal_saved", BH_ERR_INVALID_ARG, bh::NEED_V_NORMAL, saved, v_output, call);
 }
 
 int bh_depth_to_normal(bh_ctx* ctx, const BhCamera* cam, const float* depth, uint32_t h, uint32_t w, float* out) {

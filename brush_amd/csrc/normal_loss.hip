@@ -92,10 +92,10 @@ int launch_normal_loss(bh_ctx* ctx, const BhCamera& cam, const float* normal, co
     a.k.w = w; a.k.h = h;
     a.pixels = (uint64_t)h * w;
     a.c = (float)((double)weight / (double)a.pixels);
-    auto* partials = (double*)ensure(ctx, SLOT_NORMAL_LOSS, (size_t)DL_MAX_BLOCKS * DL_ROW * 8);
+    uint32_t blocks = 0;
+    double* partials = loss_partials(ctx, a.pixels, &blocks);
     if (!partials) return BH_ERR_OOM;
-    const uint64_t blocks = (a.pixels + DL_WG - 1) / DL_WG;
-    const dim3 grid((uint32_t)(blocks < DL_MAX_BLOCKS ? blocks : DL_MAX_BLOCKS)), block(DL_WG);
+    const dim3 grid(blocks), block(DL_WG);
     if (accumulate_v_depth) hipLaunchKernelGGL(normal_consistency_kernel<true>, grid, block, 0, ctx->stream, a, normal, depth, image, v_normal, v_depth, partials);
     else hipLaunchKernelGGL(normal_consistency_kernel<false>, grid, block, 0, ctx->stream, a, normal, depth, image, v_normal, v_depth, partials);
     BH_LAUNCH_CHECK(ctx, "normal_consistency_kernel");

@@ -29,13 +29,9 @@ extern "C" {
 int bh_render_backward_pose_saved(bh_ctx* ctx, const BhRenderOut* saved, const float* v_output, const float* transforms,
                                   const float* sh_coeffs, const float* raw_opacities, float* v_transforms, float* v_sh_coeffs,
                                   float* v_raw_opacities, float* v_refine_weight, float* v_viewmat) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!saved || !v_output || !v_transforms || !v_sh_coeffs || !v_raw_opacities || !v_refine_weight || !v_viewmat)
-        return bh::set_error(ctx, BH_ERR_INVALID_ARG, "render_backward_pose_saved: null argument");
-    const bh::ForwardState* fs = nullptr;
-    BH_TRY(bh::find_saved_bwd_forward(ctx, saved, BH_ERR_STATE, "render_backward_pose_saved", &fs));
-    return bh::backward_impl(ctx, *fs, v_output, transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight,
-                             /*span_floats=*/0, /*want_refine=*/true, /*depth=*/nullptr, v_viewmat);
+    bh::BackwardCall call{transforms, sh_coeffs, raw_opacities, v_transforms, v_sh_coeffs, v_raw_opacities, v_refine_weight};
+    call.v_viewmat = v_viewmat;
+    return bh::backward_entry(ctx, "render_backward_pose_saved", BH_ERR_STATE, bh::NEED_V_OUTPUT | bh::NEED_V_VIEWMAT, saved, v_output, call);
 }
 
 int bh_train_set_pose_grad(bh_ctx* ctx, float* v_viewmat) {

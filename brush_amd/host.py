@@ -589,52 +589,40 @@ class RenderNode:
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
         if v_output is None and v_depth is None and v_normal is None and v_distortion is None:
             raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
-        if v_output is not None:
-            v_output = _f32c(v_output, dev).reshape(h, w, 4)
+        # the pose gradient is the colour term's: refused without v_output or with another cotangent (named: the one whose entry
+        # point the call would have taken)
+        other = "v_distortion" if v_distortion is not None else "v_normal" if v_normal is not None else "v_depth"
+        if pose and (v_output is None or v_depth is not None or v_normal is not None or v_distortion is not None):
+            raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no %s)" % other)
+
+        def cot(t, *shape):
+            return None if t is None else _f32c(t, dev).reshape(*shape)
+        v_output, v_depth, v_normal, v_distortion = cot(v_output, h, w, 4), cot(v_depth, h, w), cot(v_normal, h, w, 3), cot(v_distortion, h, w)
+        # (NULL for a cotangent that was not given)
+        p_output, p_depth, p_normal, p_distortion = (None if t is None else _ptr(t) for t in (v_output, v_depth, v_normal, v_distortion))
         r_t, r_o = self._folded
         v_t = torch.empty((n, 10), dtype=torch.float32, device=dev)
         v_sh = torch.empty((n, c, 3), dtype=torch.float32, device=dev)
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
-        v_vm = None
-        if v_distortion is not None:
-            if pose:
-                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_distortion)")
-            v_distortion = _f32c(v_distortion, dev).reshape(h, w)
-            if v_depth is not None:
-                v_depth = _f32c(v_depth, dev).reshape(h, w)
-            if v_normal is not None:
-                v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
-            cfg = _distortion_config(distortion, distortion_near, distortion_far)
-            ctx.check(ctx.lib.bh_render_backward_distortion_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
-                                                                  _ptr(v_depth) if v_depth is not None else None, _depth_mode(depth_mode),
-                                                                  _ptr(v_normal) if v_normal is not None else None, _normal_mode(normal_mode),
-                                                                  _ptr(v_distortion), C.byref(cfg), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                                  _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
-        elif v_normal is not None:
-            if pose:
-                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_normal)")
-            v_normal = _f32c(v_normal, dev).reshape(h, w, 3)
-            if v_depth is not None:
-                v_depth = _f32c(v_depth, dev).reshape(h, w)
-            ctx.check(ctx.lib.bh_render_backward_normal_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
-                                                              _ptr(v_depth) if v_depth is not None else None, _depth_mode(depth_mode),
-                                                              _ptr(v_normal), _normal_mode(normal_mode), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                              _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+        v_vm = torch.empty((12,), dtype=torch.float32, device=dev) if pose else None
+        tail = (_ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o), _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf))
+        # the narrowest entry point that takes every cotangent given
+        lib = ctx.lib
+        if p_distortion is not None or p_normal is not None:
+            maps = (p_depth, _depth_mode(depth_mode), p_normal, _normal_mode(normal_mode))
+            if p_distortion is not None:
+                cfg = _distortion_config(distortion, distortion_near, distortion_far)
+                entry, args = lib.bh_render_backward_distortion_saved, maps + (p_distortion, C.byref(cfg)) + tail
+            else:
+                entry, args = lib.bh_render_backward_normal_saved, maps + tail
         elif pose:
-            if v_depth is not None or v_output is None:
-                raise BrushHipError("RenderNode.backward: the pose gradient is that of the colour term alone (v_output, no v_depth)")
-            v_vm = torch.empty((12,), dtype=torch.float32, device=dev)
-            ctx.check(ctx.lib.bh_render_backward_pose_saved(ctx._h, C.byref(self.out), _ptr(v_output), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                            _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf), _ptr(v_vm)))
-        elif v_depth is not None:
-            v_depth = _f32c(v_depth, dev).reshape(h, w)
-            ctx.check(ctx.lib.bh_render_backward_depth_saved(ctx._h, C.byref(self.out), _ptr(v_output) if v_output is not None else None,
-                                                             _ptr(v_depth), _depth_mode(depth_mode), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                             _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+            entry, args = lib.bh_render_backward_pose_saved, tail + (_ptr(v_vm),)
+        elif p_depth is not None:
+            entry, args = lib.bh_render_backward_depth_saved, (p_depth, _depth_mode(depth_mode)) + tail
         else:
-            ctx.check(ctx.lib.bh_render_backward_saved(ctx._h, C.byref(self.out), _ptr(v_output), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o),
-                                                       _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf)))
+            entry, args = lib.bh_render_backward_saved, tail
+        ctx.check(entry(ctx._h, C.byref(self.out), p_output, *args))
         if splats.min_scale is not None:
             ctx.check(ctx.lib.bh_fold_min_scale_backward(ctx._h, _ptr(splats.transforms), _ptr(splats.raw_opacities), _ptr(splats.min_scale), n,
                                                          _ptr(v_t), _ptr(v_op)))

@@ -420,19 +420,9 @@ class RenderNode {
     RenderNode& operator=(const RenderNode&) = delete;
     ~RenderNode() { if (retained_) (void)bh_render_release(ctx_.get(), &aux.raw); }
     SplatGrads backward(const float* v_output) const {
-        const uint32_t n = splats_.num_splats();
-        SplatGrads g;
-        g.v_transforms.resize((size_t)n * 10);
-        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
-        g.v_raw_opacities.resize(n);
-        g.v_refine_weight.resize(n);
-        ctx_.check(bh_render_backward_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(),
-                                            g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
-        if (splats_.min_scale)
-            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
-                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
-        ctx_.sync();
-        return g;
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf);
+        });
     }
     // The node's depth map [H,W] f32 (brush_hip_depth.h): BH_DEPTH_ACCUMULATED, BH_DEPTH_EXPECTED or BH_DEPTH_MEDIAN.  Rows outside a
     // tile-row window stay 0.
@@ -447,19 +437,10 @@ class RenderNode {
     }
     // gradients of <v_output, image> + <v_depth, depth(mode)>; v_output may be nullptr (the depth term alone)
     SplatGrads backward(const float* v_output, const float* v_depth, uint32_t mode = BH_DEPTH_EXPECTED) const {
-        const uint32_t n = splats_.num_splats();
-        SplatGrads g;
-        g.v_transforms.resize((size_t)n * 10);
-        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
-        g.v_raw_opacities.resize(n);
-        g.v_refine_weight.resize(n);
-        ctx_.check(bh_render_backward_depth_saved(ctx_.get(), &aux.raw, v_output, v_depth, mode, folded_.t, splats_.sh_coeffs.data(), folded_.o,
-                                                  g.v_transforms.data(), g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
-        if (splats_.min_scale)
-            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
-                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
-        ctx_.sync();
-        return g;
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_depth_saved(ctx_.get(), &aux.raw, v_output, v_depth, mode, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh,
+                                                  v_op, v_rf);
+        });
     }
     // The node's normal map [H,W,3] f32 in camera space (brush_hip_normal.h): BH_NORMAL_ACCUMULATED or BH_NORMAL_UNIT.  Rows outside a
     // tile-row window stay 0.
@@ -476,20 +457,10 @@ class RenderNode {
     // v_depth may be nullptr
     SplatGrads backward_normal(const float* v_output, const float* v_depth, uint32_t depth_mode, const float* v_normal,
                                uint32_t normal_mode = BH_NORMAL_ACCUMULATED) const {
-        const uint32_t n = splats_.num_splats();
-        SplatGrads g;
-        g.v_transforms.resize((size_t)n * 10);
-        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
-        g.v_raw_opacities.resize(n);
-        g.v_refine_weight.resize(n);
-        ctx_.check(bh_render_backward_normal_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, folded_.t,
-                                                   splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(), g.v_sh_coeffs.data(),
-                                                   g.v_raw_opacities.data(), g.v_refine_weight.data()));
-        if (splats_.min_scale)
-            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
-                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
-        ctx_.sync();
-        return g;
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_normal_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, folded_.t,
+                                                   splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf);
+        });
     }
     SplatGrads backward_normal(const float* v_normal, uint32_t normal_mode = BH_NORMAL_ACCUMULATED) const {
         return backward_normal(nullptr, nullptr, BH_DEPTH_EXPECTED, v_normal, normal_mode);
@@ -511,20 +482,10 @@ class RenderNode {
     // in one backward; every cotangent but v_distortion may be nullptr
     SplatGrads backward_distortion(const float* v_output, const float* v_depth, uint32_t depth_mode, const float* v_normal, uint32_t normal_mode,
                                    const float* v_distortion, const BhDistortionConfig& cfg = BhDistortionConfig{}) const {
-        const uint32_t n = splats_.num_splats();
-        SplatGrads g;
-        g.v_transforms.resize((size_t)n * 10);
-        g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
-        g.v_raw_opacities.resize(n);
-        g.v_refine_weight.resize(n);
-        ctx_.check(bh_render_backward_distortion_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, v_distortion, &cfg,
-                                                       folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(), g.v_sh_coeffs.data(),
-                                                       g.v_raw_opacities.data(), g.v_refine_weight.data()));
-        if (splats_.min_scale)
-            ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
-                                                  g.v_transforms.data(), g.v_raw_opacities.data()));
-        ctx_.sync();
-        return g;
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_distortion_saved(ctx_.get(), &aux.raw, v_output, v_depth, depth_mode, v_normal, normal_mode, v_distortion, &cfg,
+                                                       folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf);
+        });
     }
     SplatGrads backward_distortion(const float* v_distortion, const BhDistortionConfig& cfg = BhDistortionConfig{}) const {
         return backward_distortion(nullptr, nullptr, BH_DEPTH_EXPECTED, nullptr, BH_NORMAL_ACCUMULATED, v_distortion, cfg);
@@ -532,23 +493,32 @@ class RenderNode {
     // gradients of <v_output, image> and, into v_viewmat (device, 12 floats in the layout of BhCamera.vm), its gradient with respect
     // to the camera's view matrix (brush_hip_pose.h); the four splat outputs are backward(v_output)'s
     SplatGrads backward_pose(const float* v_output, float* v_viewmat) const {
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_pose_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf,
+                                                 v_viewmat);
+        });
+    }
+    RenderAux aux;
+
+  private:
+    // what every backward shares: the four gradient buffers, ONE C entry point on them (entry(v_transforms, v_sh_coeffs,
+    // v_raw_opacities, v_refine_weight) -> status), the chain through the fold (the autodiff of bwd/burn_glue.rs:260-270), the sync
+    template <class Entry>
+    SplatGrads run_backward(Entry entry) const {
         const uint32_t n = splats_.num_splats();
         SplatGrads g;
         g.v_transforms.resize((size_t)n * 10);
         g.v_sh_coeffs.resize(splats_.sh_coeffs.size());
         g.v_raw_opacities.resize(n);
         g.v_refine_weight.resize(n);
-        ctx_.check(bh_render_backward_pose_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, g.v_transforms.data(),
-                                                 g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data(), v_viewmat));
+        ctx_.check(entry(g.v_transforms.data(), g.v_sh_coeffs.data(), g.v_raw_opacities.data(), g.v_refine_weight.data()));
         if (splats_.min_scale)
             ctx_.check(bh_fold_min_scale_backward(ctx_.get(), splats_.transforms.data(), splats_.raw_opacities.data(), splats_.min_scale->data(), n,
                                                   g.v_transforms.data(), g.v_raw_opacities.data()));
         ctx_.sync();
         return g;
     }
-    RenderAux aux;
 
-  private:
     const Context& ctx_;
     const Splats& splats_;
     detail::Folded folded_;
