@@ -50,6 +50,10 @@ Names and argument meaning follow the reference (paths under
     TsdfVolume / fuse_views / mesh_to_ply    mesh extraction: rendered depth maps fused into a TSDF volume (8 views per pass over the
                                          volume), its zero level set by marching tetrahedra, a triangle-mesh PLY (not in the
                                          reference; include/brush_hip_mesh.h)
+    render_features / RenderNode.features / RenderNode.backward(v_features=, features=) / feature_loss_value_and_grad / FeatureField
+                                         feature maps: caller-owned per-splat vectors of 1 .. 256 channels blended with the colour
+                                         blend's weights, the gradient into them and the splats, fused L1 / cross-entropy losses (not
+                                         in the reference; gsplat's colors [N, D]; include/brush_hip_features.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -66,5 +70,6 @@ from .host import (  # noqa: F401
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
     render_distortion, distortion_loss, BilateralGridTable,
     TsdfVolume, mesh_to_ply, fuse_views,
+    render_features, feature_loss_value_and_grad, FeatureField,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -365,6 +365,22 @@ MESH_SYMBOLS = {
     "bh_mesh_to_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
+# every symbol include/brush_hip_features.h declares (feature maps: N-channel splat features, their backward and the fused losses)
+FEATURE_MAX_CHANNELS = 256   # BH_FEATURE_MAX_CHANNELS
+FEATURE_LOSS_L1, FEATURE_LOSS_CROSS_ENTROPY = 0, 1   # BH_FEATURE_LOSS_*
+
+
+class BhFeatureTarget(C.Structure):
+    _fields_ = [("target", C.c_void_p), ("h", C.c_uint32), ("w", C.c_uint32), ("channels", C.c_uint32), ("kind", C.c_uint32),
+                ("weight", C.c_float), ("reserved", C.c_uint32)]
+
+
+FEATURE_SYMBOLS = {
+    "bh_render_features": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bh_render_backward_features_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 9),
+    "bh_feature_loss_value_and_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhFeatureTarget), C.c_void_p, C.c_void_p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -404,7 +420,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS))
     return _lib
 
 
@@ -413,6 +429,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -431,6 +431,8 @@ const Option kOptions[] = {
      [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "ring") { c->knob_direct_allreduce = false; return true; } if (w == "direct") { c->knob_direct_allreduce = true; return true; } return false; }},
     {"update_sparse", "0..256: an update block with at most this many non-dormant rows fetches them in one round trip (0: never; 256: every block that may skip dormant rows; default 64 at SH degree 0, else 0)",
      [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 256, &u)) return false; c->knob_update_sparse = (int)u; return true; }},
+    {"feature_chunk", "0|4|8|16: channels per pass over the lists of the feature-map blends (0 = chosen per channel count)",
+     [](bh_ctx* c, const char* v) { uint32_t u = 0; if (!parse_u32(v, 0, 16, &u) || !(u == 0 || u == 4 || u == 8 || u == 16)) return false; c->feature_chunk = u; return true; }},
 };
 constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
 }  // namespace
@@ -1129,6 +1131,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
     bool row_marks = false;
     float* v_z = nullptr;         // what the depth and distortion terms leave for the v_z scatter behind K18
     const float* v_n = nullptr;   // ... and the normal term for the Vn scatter
+    const float* v_f = nullptr;   // ... and the feature term for the copy into the dense v_features
     {
         ProfScope ps(ctx, "ZeroGradBuffers");
         // what the forward's kernels cleared on their way (K5: v_combined; K1: the train step's gradient span) is done
@@ -1174,6 +1177,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         if (call.depth) BH_TRY(launch_depth_backward(ctx, fs, *call.depth, v_combined, &v_z));
         if (call.normal) BH_TRY(launch_normal_backward(ctx, fs, *call.normal, transforms, v_combined, &v_n));
         if (call.distortion) BH_TRY(launch_distortion_backward(ctx, fs, *call.distortion, v_combined, &v_z));   // (behind the depth term: it adds to a filled v_z)
+        if (call.feature) BH_TRY(launch_feature_backward(ctx, fs, *call.feature, v_combined, &v_f));
     }
     {
         ProfScope ps(ctx, "ProjectBackwards");
@@ -1182,6 +1186,7 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
                                        v_raw_opacities, v_refine_weight, row_marks, r.projected));
         if (v_z) BH_TRY(launch_depth_vz_scatter(ctx, fs, v_z, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
         if (v_n) BH_TRY(launch_normal_vn_scatter(ctx, fs, v_n, transforms, v_transforms, row_marks, v_sh_coeffs, v_raw_opacities, v_refine_weight));
+        if (v_f) BH_TRY(launch_feature_scatter(ctx, fs, *call.feature, v_f));
     }
     if (call.v_viewmat) {   // (brush_hip_pose.h: only when asked for)
         ProfScope ps(ctx, "PoseGrad");
@@ -1213,7 +1218,8 @@ int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t requ
     const bool takes_normal = call.normal != nullptr;
     if (!saved || !call.v_transforms || !call.v_sh_coeffs || !call.v_raw_opacities || !call.v_refine_weight || ((required & NEED_V_OUTPUT) && !v_output) ||
         ((required & NEED_V_DEPTH) && !v_depth) || ((required & NEED_V_NORMAL) && !v_normal) || ((required & NEED_V_DISTORTION) && !v_distortion) ||
-        ((required & NEED_V_VIEWMAT) && !call.v_viewmat))
+        ((required & NEED_V_VIEWMAT) && !call.v_viewmat) ||
+        ((required & NEED_V_FEATURES) && (!call.feature || !call.feature->features || !call.feature->v_map || !call.feature->v_features)))
         return set_error(ctx, BH_ERR_INVALID_ARG, name + ": null argument");
     // an optional cotangent the caller left out: no term, and its mode is not looked at
     if (!v_depth) call.depth = nullptr;
@@ -1223,6 +1229,8 @@ int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t requ
     if (call.normal && call.normal->mode > BH_NORMAL_UNIT) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": unknown normal mode");
     if (call.depth && call.depth->mode == BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": median depth has no gradient");
     if (call.depth && call.depth->mode > BH_DEPTH_MEDIAN) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": unknown depth mode");
+    if (call.feature && (call.feature->channels == 0 || call.feature->channels > BH_FEATURE_MAX_CHANNELS))
+        return set_error(ctx, BH_ERR_INVALID_ARG, name + ": channels must be 1 .. 256");
     const ForwardState* fs = nullptr;
     BH_TRY(find_saved_bwd_forward(ctx, saved, not_bwd_code, who, &fs));
     if (takes_normal && fs->n > 0 && !call.transforms) return set_error(ctx, BH_ERR_INVALID_ARG, name + ": null transforms");

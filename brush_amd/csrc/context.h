@@ -18,6 +18,7 @@
 #include "../../include/brush_hip_normal_loss.h"
 #include "../../include/brush_hip_distortion.h"
 #include "../../include/brush_hip_mesh.h"
+#include "../../include/brush_hip_features.h"
 #include "device_math.h"
 
 namespace bh {
@@ -94,6 +95,7 @@ enum Slot : int {
     SLOT_DISTORTION_TERM,    // bh_train_step with a distortion term: the moment map [H,W,4] | the term's loss pair (4 floats)
     SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
     SLOT_TSDF,               // bh_tsdf_extract[_count]: per sample the edge mask / triangle count / corner bits [n] | the vertex scan [n] | the triangle scan [n] (tsdf.hip)
+    SLOT_FEATURES,           // bh_render_features / launch_feature_backward: compact features [Nv,C] | V [Nv,C] | the frame's accumulated feature map [H,W,C] (features.hip)
     SLOT_COUNT
 };
 
@@ -386,6 +388,14 @@ struct DistortionTerm {
     const float* moments = nullptr;        // [H,W,4] the frame's moment map if the caller has rendered it (the train step), or NULL
 };
 
+// The feature term of a backward (features.hip, brush_hip_features.h): <v_map, feature map of `features`>
+struct FeatureTerm {
+    const float* features = nullptr;   // [N,C] by global splat id
+    uint32_t channels = 0;             // 1 .. BH_FEATURE_MAX_CHANNELS
+    const float* v_map = nullptr;      // [H,W,C]
+    float* v_features = nullptr;       // [N,C] out: dense, fully overwritten
+};
+
 // One backward on a saved forward (api.hip backward_impl): the parameters the forward rendered, where the gradients go, and the
 // terms beside the colour term's <v_output, image>.
 struct BackwardCall {
@@ -401,6 +411,7 @@ struct BackwardCall {
     const DepthTerm* depth = nullptr;             // its raw sums join the accumulator between K17 and K18, its v_z lands behind K18
     const NormalTerm* normal = nullptr;           // likewise, behind depth's; its Vn lands behind depth's v_z
     const DistortionTerm* distortion = nullptr;   // likewise, behind normal's; its v_z joins depth's or goes through the same scatter
+    const FeatureTerm* feature = nullptr;         // likewise, behind distortion's; its V lands in v_features behind the other scatters
     float* v_viewmat = nullptr;    // [12] (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined
 };
 
@@ -489,6 +500,7 @@ struct bh_ctx {
     bool knob_no_view_hash = false;       // BH_NO_VIEW_HASH (A/B): frames without a view id share ONE table (rounds 4's behaviour) instead of being keyed by their camera
     bool knob_fixed_margin = false;       // BH_CUT_MARGIN_FIXED (A/B): the margin is BH_CUT_MARGIN_PCT for every frame (rounds 4's behaviour), not adaptive
     bool knob_cut_sort_all = false;       // BH_CUT_SORT_ALL (A/B): with per-tile cuts, still sort every visible splat
+    uint32_t feature_chunk = 0;           // option feature_chunk: channels per pass of the feature-map blends (features.hip); 0: feature_chunk(C)
     uint32_t knob_band_mode = 1;          // XCD bands of the blend kernels: 0 contiguous eighths of the tile range, 1 dealt in chunks of 8 tiles
     uint32_t knob_k16_waves = 0;          // forward blend: resident waves per SIMD (0 / 8: all eight; fewer: later tiles are dispatched as earlier ones finish)
     uint32_t knob_k16_split = 250;        // forward blend: split tiles at >= max(SPLIT_MIN_WORK, this / 100 x the band's mean forecast work); 0: never
@@ -554,8 +566,9 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
 // api.hip: what the bh_render_backward*_saved entry points share.  `required`: the cotangents that entry refuses to do without;
 // a term of `call` whose cotangent is NULL is an optional one the caller left out.  In this order: the null-argument refusal, the
 // distortion-kind, normal-mode and depth-mode refusals, find_saved_bwd_forward(not_bwd_code), the null-transforms refusal (an
-// entry that accepts a normal term has it), backward_impl.  Every text carries `who`.
-enum : uint32_t { NEED_V_OUTPUT = 1u, NEED_V_DEPTH = 2u, NEED_V_NORMAL = 4u, NEED_V_DISTORTION = 8u, NEED_V_VIEWMAT = 16u };
+// entry that accepts a normal term has it), backward_impl.  Every text carries `who`.  NEED_V_FEATURES: the feature term's four
+// pointers join the null-argument refusal, and its channel count is refused behind the depth-mode refusals.
+enum : uint32_t { NEED_V_OUTPUT = 1u, NEED_V_DEPTH = 2u, NEED_V_NORMAL = 4u, NEED_V_DISTORTION = 8u, NEED_V_VIEWMAT = 16u, NEED_V_FEATURES = 32u };
 int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t required, const BhRenderOut* saved, const float* v_output, BackwardCall call);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined; *v_z = the per-splat vector it filled), and a v_z ->
 // v_mean behind K18 (the depth term's vector, the distortion term's, or the one both filled)
@@ -585,6 +598,10 @@ int launch_distortion_map(bh_ctx* ctx, const ForwardState& fs, const DistortionT
 int check_distortion_kind(bh_ctx* ctx, uint32_t kind, float near_z, float far_z, const char* who);
 int launch_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w, uint32_t channels, float weight, float* loss, float* accum,
                            float* accum_host);
+// features.hip: the feature term between K17 and K18 (raw sums into v_combined; *v_compact = the compact [Nv,C] vector it filled;
+// the dense v_features is cleared), and the compact vector -> the rows of v_features behind K18
+int launch_feature_backward(bh_ctx* ctx, const ForwardState& fs, const FeatureTerm& term, float* v_combined, const float** v_compact);
+int launch_feature_scatter(bh_ctx* ctx, const ForwardState& fs, const FeatureTerm& term, const float* v_compact);
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);

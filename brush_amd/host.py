@@ -578,15 +578,27 @@ class RenderNode:
         2DGS's far (z - near) / ((far - near) z) ("ndc"); a forward of a tile-row window writes its rows, the rest is 0."""
         return render_distortion(self, kind, near, far)
 
+    def features(self, features):
+        """The node's feature map [H,W,C] f32 (bh_render_features): the blend of the caller's per-splat vectors `features` [N,C],
+        1 <= C <= 256, with the colour blend's own weights; a forward of a tile-row window writes its rows, the rest is 0."""
+        return render_features(self, features)
+
     def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False, v_normal=None, normal_mode="accumulated", v_distortion=None,
-                 distortion="z", distortion_near=0.2, distortion_far=1000.0):
+                 distortion="z", distortion_near=0.2, distortion_far=1000.0, v_features=None, features=None):
         """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>] [+ <v_normal, normal(normal_mode)>] [+ <v_distortion,
         distortion(kind `distortion`, distortion_near, distortion_far)>]; v_output may be None when another cotangent is given.
         pose=True (bh_render_backward_pose_saved): also "v_viewmat", the twelve f32 of the gradient with respect to the camera's
-        view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only."""
+        view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only.
+        v_features [H,W,C] with features [N,C] (bh_render_backward_features_saved): + <v_features, features(features)>, and
+        "v_features" [N,C] in the result, the gradient with respect to `features`; not together with v_depth / v_normal /
+        v_distortion / pose."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
+        if v_features is not None or features is not None:
+            if v_depth is not None or v_normal is not None or v_distortion is not None or pose:
+                raise BrushHipError("RenderNode.backward: the feature term does not combine with v_depth / v_normal / v_distortion / pose")
+            return self._backward_features(v_output, v_features, features)
         if v_output is None and v_depth is None and v_normal is None and v_distortion is None:
             raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
         # the pose gradient is the colour term's: refused without v_output or with another cotangent (named: the one whose entry
@@ -630,6 +642,32 @@ class RenderNode:
         if v_vm is not None:
             res["v_viewmat"] = v_vm
         return res
+
+    def _backward_features(self, v_output, v_map, features):
+        ctx, splats, dev = self.ctx, self.splats, self.splats.device
+        w, h = self.img_size
+        n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
+        if v_map is None or features is None:
+            raise BrushHipError("RenderNode.backward: v_features and features go together")
+        features = _feature_rows(features, n, dev, "RenderNode.backward")
+        ch = int(features.shape[1])
+        v_map = _f32c(v_map, dev)
+        if tuple(v_map.shape) != (h, w, ch):
+            raise BrushHipError("RenderNode.backward: v_features must be [%d, %d, %d]" % (h, w, ch))
+        v_output = None if v_output is None else _f32c(v_output, dev).reshape(h, w, 4)
+        r_t, r_o = self._folded
+        v_t = torch.empty((n, 10), dtype=torch.float32, device=dev)
+        v_sh = torch.empty((n, c, 3), dtype=torch.float32, device=dev)
+        v_op = torch.empty((n,), dtype=torch.float32, device=dev)
+        v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
+        v_f = torch.empty((n, ch), dtype=torch.float32, device=dev)
+        ctx.check(ctx.lib.bh_render_backward_features_saved(ctx._h, C.byref(self.out), None if v_output is None else _ptr(v_output), _ptr(features), ch,
+                                                            _ptr(v_map), _ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o), _ptr(v_t), _ptr(v_sh), _ptr(v_op),
+                                                            _ptr(v_rf), _ptr(v_f)))
+        if splats.min_scale is not None:
+            ctx.check(ctx.lib.bh_fold_min_scale_backward(ctx._h, _ptr(splats.transforms), _ptr(splats.raw_opacities), _ptr(splats.min_scale), n,
+                                                         _ptr(v_t), _ptr(v_op)))
+        return dict(v_transforms=v_t, v_sh_coeffs=v_sh, v_raw_opacities=v_op, v_refine_weight=v_rf, v_features=v_f)
 
     def release(self):
         if self.retained:
@@ -698,6 +736,91 @@ def render_normal(saved: "RenderNode", mode="accumulated", out=None):
         raise BrushHipError("render_normal: `out` must be a contiguous float32 [%d, %d, 3] tensor on %s" % (h, w, dev))
     ctx.check(ctx.lib.bh_render_normal(ctx._h, C.byref(saved.out), _ptr(saved._folded[0]), _normal_mode(mode), _ptr(out)))
     return out
+
+
+FEATURE_MAX_CHANNELS = _ffi.FEATURE_MAX_CHANNELS
+FEATURE_LOSS_KINDS = {"l1": _ffi.FEATURE_LOSS_L1, "cross_entropy": _ffi.FEATURE_LOSS_CROSS_ENTROPY}
+
+
+def _feature_rows(features, n, dev, who):
+    features = _f32c(features, dev)
+    if features.dim() != 2 or features.shape[0] != n:
+        raise BrushHipError("%s: features must be [%d, C]" % (who, n))
+    return features
+
+
+def render_features(saved: "RenderNode", features, out=None):
+    """Feature map [H,W,C] f32 of a differentiable render's saved state (bh_render_features; include/brush_hip_features.h): the
+    blend of `features` [N,C] (one row per splat, 1 <= C <= 256) with the colour blend's own weights, nothing clamped, no
+    background.  The node must be the ctx's most recent forward or a retained one.  `out`: a contiguous f32 [H,W,C] tensor to write
+    into (rows outside a tile-row window are left as they are); otherwise a zero-filled one is returned."""
+    ctx, dev = saved.ctx, saved.splats.device
+    w, h = saved.img_size
+    features = _feature_rows(features, saved.splats.num_splats(), dev, "render_features")
+    ch = int(features.shape[1])
+    if out is None:
+        out = torch.zeros((h, w, ch), dtype=torch.float32, device=dev)
+    if not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (h, w, ch)
+            and out.device == torch.device(dev)):
+        raise BrushHipError("render_features: `out` must be a contiguous float32 [%d, %d, %d] tensor on %s" % (h, w, ch, dev))
+    ctx.check(ctx.lib.bh_render_features(ctx._h, C.byref(saved.out), _ptr(features), ch, _ptr(out)))
+    return out
+
+
+def feature_loss_value_and_grad(map, target, kind="l1", weight=1.0, want_grad=True, ctx: Optional[Context] = None):
+    """The fused feature losses (bh_feature_loss_value_and_grad; include/brush_hip_features.h) of a feature map [H,W,C]: "l1"
+    against an f32 target [H,W,C] (a pixel counts when all its target values are finite; the mean over H W C), or "cross_entropy"
+    against uint8 labels [H,W] (a pixel counts when label < C, 255 = ignore; the mean over H W) -> (loss [2] device f32 = (weight *
+    the mean, valid pixels), v_map [H,W,C] or None).  Queued on the ctx stream: nothing is read back."""
+    dev = map.device
+    ctx = ctx or get_context(dev)
+    map = _f32c(map, dev)
+    if map.dim() != 3:
+        raise ValueError("the feature map must be [H, W, C]")
+    h, w, ch = (int(s) for s in map.shape)
+    k = int(FEATURE_LOSS_KINDS[kind]) if isinstance(kind, str) else int(kind)
+    if k == _ffi.FEATURE_LOSS_CROSS_ENTROPY:
+        target = torch.as_tensor(target, dtype=torch.uint8, device=dev).contiguous()
+        want = (h, w)
+    else:
+        target = _f32c(target, dev)
+        want = (h, w, ch)
+    if tuple(target.shape) != want:
+        raise ValueError("the feature target must be %s" % (want,))
+    t = _ffi.BhFeatureTarget()
+    t.target, t.h, t.w, t.channels, t.kind, t.weight = target.data_ptr(), h, w, ch, k, float(weight)
+    loss = torch.empty((2,), dtype=torch.float32, device=dev)
+    v_map = torch.empty_like(map) if want_grad else None
+    ctx.check(ctx.lib.bh_feature_loss_value_and_grad(ctx._h, _ptr(map), C.byref(t), _ptr(loss), _ptr(v_map) if want_grad else None))
+    return loss, v_map
+
+
+class FeatureField:
+    """Caller-owned per-splat feature vectors [N,C] with their Adam state, trained on a fixed set of splats (the second stage of
+    LangSplat and Gaussian Grouping): zero-initialised features, `render(node)` the map, `backward(node, v_map)` the gradients,
+    `step(v_features)` one Adam step (adam_step with row_len = C)."""
+
+    def __init__(self, n, channels, lr=1e-2, device=None, ctx: Optional[Context] = None, beta1=0.9, beta2=0.999, eps=1e-15):
+        if not 1 <= int(channels) <= FEATURE_MAX_CHANNELS:
+            raise BrushHipError("FeatureField: channels must be 1 .. %d" % FEATURE_MAX_CHANNELS)
+        self.ctx = ctx or get_context(device)
+        dev = device if device is not None else "cuda:%d" % torch.cuda.current_device()
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), beta1, beta2, eps
+        self.features = torch.zeros((int(n), int(channels)), dtype=torch.float32, device=dev)
+        self.m1 = torch.zeros_like(self.features)
+        self.m2 = torch.zeros_like(self.features)
+        self.t = 0
+
+    def render(self, node: "RenderNode"):
+        return render_features(node, self.features)
+
+    def backward(self, node: "RenderNode", v_map, v_output=None):
+        return node.backward(v_output, v_features=v_map, features=self.features)
+
+    def step(self, v_features):
+        self.t += 1
+        adam_step(self.features, _f32c(v_features, self.features.device), self.m1, self.m2, self.lr, self.t, beta1=self.beta1, beta2=self.beta2,
+                  eps=self.eps, ctx=self.ctx)
 
 
 DISTORTION_KINDS = {"z": _ffi.DISTORTION_Z, "ndc": _ffi.DISTORTION_NDC}

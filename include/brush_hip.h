@@ -186,7 +186,8 @@ const char* bh_version(void);
  *   tile_sort auto|bucket|lsd | spec_k5 0|1 | event_waits 0|1 | readback_copy 0|1 | force_exchange 0|1 | zero_grads 0|1 | loss_bands 0|1 |
  *   update_rows 0|64|128|256 | no_dormant 0|1 | sort_kpt 0|4|8|16 | grad_allreduce ring|direct |
  *   update_sparse 0..256 (an update block with at most this many non-dormant splats fetches them in one round trip; 0 = never,
- *   256 = every block that may skip dormant splats; read at every step; default 64 at SH degree 0, 0 at higher degrees)
+ *   256 = every block that may skip dormant splats; read at every step; default 64 at SH degree 0, 0 at higher degrees) |
+ *   feature_chunk 0|4|8|16 (channels per pass of the feature-map blends, brush_hip_features.h; 0 = chosen per channel count)
  * bh_option_count / bh_option_name / bh_option_help enumerate them with one line of documentation each (host strings). */
 int bh_set_option(bh_ctx* ctx, const char* key /*host*/, const char* value /*host*/);
 int bh_option_count(void);

@@ -38,6 +38,9 @@
 //   brush_hip::BilateralGridTable / train_set_bilagrid   not in the reference: per-view bilateral grids (a grid of affine colour
 //                                                   transforms per training view, sliced at (x, y, luminance), TV term, Adam on the
 //                                                   device; gsplat's lib_bilagrid; brush_hip_bilagrid.h)
+//   RenderNode::features / backward_features, brush_hip::feature_loss_value_and_grad   not in the reference: feature maps (caller-owned
+//                                                   per-splat vectors of 1 .. 256 channels, gsplat's colors [N, D]), their gradient
+//                                                   and the fused L1 / cross-entropy losses (brush_hip_features.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -73,6 +76,7 @@
 #include "brush_hip_distortion.h"
 #include "brush_hip_bilagrid.h"
 #include "brush_hip_mesh.h"
+#include "brush_hip_features.h"
 
 namespace brush_hip {
 
@@ -489,6 +493,27 @@ class RenderNode {
     }
     SplatGrads backward_distortion(const float* v_distortion, const BhDistortionConfig& cfg = BhDistortionConfig{}) const {
         return backward_distortion(nullptr, nullptr, BH_DEPTH_EXPECTED, nullptr, BH_NORMAL_ACCUMULATED, v_distortion, cfg);
+    }
+    // The node's feature map [H,W,C] f32 (brush_hip_features.h): the blend of `features` [N,C] (device, 1 <= C <= 256) with the colour
+    // blend's own weights.  Rows outside a tile-row window stay 0.
+    DeviceBuffer<float> features(const float* features, uint32_t channels) const {
+        DeviceBuffer<float> d;
+        d.resize((size_t)aux.img_w * aux.img_h * channels);
+        d.zero();
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the fill is ordered before the ctx stream's kernel
+        ctx_.check(bh_render_features(ctx_.get(), &aux.raw, features, channels, d.data()));
+        ctx_.sync();
+        return d;
+    }
+    // gradients of <v_output, image> + <v_map, features(features)>; v_output may be nullptr.  v_features: [N,C] = the gradient with
+    // respect to `features` (dense, rows of unlisted splats 0)
+    SplatGrads backward_features(const float* v_output, const float* features, uint32_t channels, const float* v_map,
+                                 DeviceBuffer<float>& v_features) const {
+        v_features.resize((size_t)splats_.num_splats() * channels);
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_features_saved(ctx_.get(), &aux.raw, v_output, features, channels, v_map, folded_.t, splats_.sh_coeffs.data(),
+                                                     folded_.o, v_t, v_sh, v_op, v_rf, v_features.data());
+        });
     }
     // gradients of <v_output, image> and, into v_viewmat (device, 12 floats in the layout of BhCamera.vm), its gradient with respect
     // to the camera's view matrix (brush_hip_pose.h); the four splat outputs are backward(v_output)'s
@@ -1431,6 +1456,19 @@ inline void eval_depth_metrics(const Context& ctx, const float* depth, const BhD
 }
 // bh_train_step on this ctx adds the depth term of `target` (copied; its gt must outlive the steps); nullptr detaches
 inline void train_set_depth(const Context& ctx, const BhDepthTarget* target) { ctx.check(bh_train_set_depth(ctx.get(), target)); }
+
+// ---- feature maps (brush_hip_features.h; not in the reference) ------------------------------------------------------------------------
+// A target of the fused feature losses: f32 [H,W,C] on the device (BH_FEATURE_LOSS_L1) or uint8 labels [H,W] (BH_FEATURE_LOSS_CROSS_ENTROPY)
+inline BhFeatureTarget feature_target(const void* target, uint32_t h, uint32_t w, uint32_t channels, uint32_t kind = BH_FEATURE_LOSS_L1, float weight = 1.0f) {
+    static_assert(BH_FEATURE_LOSS_L1 == 0u && BH_FEATURE_LOSS_CROSS_ENTROPY == 1u && BH_FEATURE_MAX_CHANNELS == 256u, "feature loss kinds");
+    BhFeatureTarget t{};
+    t.target = target; t.h = h; t.w = w; t.channels = channels; t.kind = kind; t.weight = weight;
+    return t;
+}
+// loss [2] (device) = (weight * the mean, valid pixels), v_map [H,W,C] or nullptr = dloss / d map; nothing is read back
+inline void feature_loss_value_and_grad(const Context& ctx, const float* map, const BhFeatureTarget& target, float* loss, float* v_map) {
+    ctx.check(bh_feature_loss_value_and_grad(ctx.get(), map, &target, loss, v_map));
+}
 
 // ---- normal maps (brush_hip_normal.h; not in the reference) ---------------------------------------------------------------------------
 // the camera-space normal [N,3] of every splat: the axis of the smallest scale of the rendered (folded) transforms, facing the camera
