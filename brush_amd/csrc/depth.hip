@@ -28,12 +28,12 @@ namespace {
 // (accumulated: g = v_D, e = 0; expected: g = v_D / A, e = E, 0 where A == 0) — the chain through 1/A, which is a gradient on the
 // alpha channel, is the offset.  S = g * (remaining sum of w_j (z_j - e)).
 template <uint32_t MODE>
-struct DepthMap {
-    static constexpr int STRIDE = 8, NACC = 1, NV = 1;
+struct DepthMap : SinglePassMap<1> {
+    static constexpr int STRIDE = 8, NACC = 1;
     struct Rec { float4 s0, s1; };   // x y c00/2 c01 | c11/2 a z sigma_cut
     static BH_DEV Rec load(const float* p) { return Rec{*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4)}; }
     static BH_DEV float cut(const Rec& r) { return r.s1.w; }
-    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, const float* __restrict__ depths, uint32_t cg) {
+    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, Attr depths, uint32_t cg) {
         const float z = depths[cg];
         d[0] = make_float4(v[0], v[1], 0.5f * v[2], v[3]);
         d[1] = make_float4(0.5f * v[4], v[5], z, sigma_cut);
@@ -52,7 +52,7 @@ struct DepthMap {
             T = ok ? (sat ? -T : next_t) : T;
         }
     }
-    static BH_DEV void store(float* __restrict__ out, size_t pix, const float* acc, float T) {
+    static BH_DEV void store(float* __restrict__ out, Attr, size_t pix, const float* acc, float T) {
         float v = acc[0];
         if (MODE == BH_DEPTH_EXPECTED) {
             const float a = 1.0f - __builtin_fabsf(T);   // the colour image's alpha, bit for bit (rasterize.hip store_pixels)
@@ -136,19 +136,16 @@ int launch_depth_backward(bh_ctx* ctx, const ForwardState& fs, const DepthTerm& 
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
-    // SLOT_DEPTH: v_z [Nv] (padded to a multiple of 64 floats) | the frame's accumulated depth [H,W]
-    const size_t vz_floats = splat_vec_floats(nv, 1);
-    const size_t pixels = (size_t)u.img_w * u.img_h;
-    auto* v_z = (float*)ensure(ctx, SLOT_DEPTH, (vz_floats + pixels) * 4);
-    if (!v_z) return BH_ERR_OOM;
-    *v_z_out = v_z;
-    float* depth_acc = v_z + vz_floats;
-    BH_HIP(ctx, hipMemsetAsync(v_z, 0, vz_floats * 4, ctx->stream));
+    // SLOT_DEPTH: no input vector (depths_sorted is staged as it is) | v_z [Nv] | the frame's accumulated depth [H,W]
+    MapScratch s;
+    BH_TRY(map_scratch(ctx, SLOT_DEPTH, nv, 1, /*has_input=*/false, /*backward=*/true, (size_t)u.img_w * u.img_h, &s));
+    *v_z_out = s.v;
+    BH_HIP(ctx, hipMemsetAsync(s.v, 0, s.vec_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || u.num_tiles == 0) return 0;
-    BH_TRY(launch_depth_forward(ctx, fs, BH_DEPTH_ACCUMULATED, depth_acc));
+    BH_TRY(launch_depth_forward(ctx, fs, BH_DEPTH_ACCUMULATED, s.acc));
     using P = DepthMap<BH_DEPTH_ACCUMULATED>;
-    const P::BwdMaps maps{r.out_img, depth_acc, term.v_depth, term.mode == BH_DEPTH_EXPECTED ? 1u : 0u};
-    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, r.depths_sorted, maps, v_combined, v_z);
+    const P::BwdMaps maps{r.out_img, s.acc, term.v_depth, term.mode == BH_DEPTH_EXPECTED ? 1u : 0u};
+    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, r.depths_sorted, maps, v_combined, s.v);
     BH_LAUNCH_CHECK(ctx, "depth_backward_kernel");
     return 0;
 }

@@ -35,12 +35,12 @@ namespace {
 
 // What a distortion map adds to the map skeleton.  MOMENTS: the store writes { A, M1', M2', r } instead of dist.
 template <bool MOMENTS>
-struct DistortionMap {
-    static constexpr int STRIDE = 8, NACC = 4, NV = 1;   // acc: r, M1', M2', seen (0 until the pixel's first contributor)
+struct DistortionMap : SinglePassMap<1> {
+    static constexpr int STRIDE = 8, NACC = 4;   // acc: r, M1', M2', seen (0 until the pixel's first contributor)
     struct Rec { float4 s0, s1; };   // x y c00/2 c01 | c11/2 a m sigma_cut
     static BH_DEV Rec load(const float* p) { return Rec{*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4)}; }
     static BH_DEV float cut(const Rec& r) { return r.s1.w; }
-    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, const float* __restrict__ m_of, uint32_t cg) {
+    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, Attr m_of, uint32_t cg) {
         const float m = m_of[cg];
         d[0] = make_float4(v[0], v[1], 0.5f * v[2], v[3]);
         d[1] = make_float4(0.5f * v[4], v[5], m, sigma_cut);
@@ -56,7 +56,7 @@ struct DistortionMap {
         acc[2] = __builtin_fmaf(vis * d, d, acc[2]);
         T = ok ? (sat ? -T : next_t) : T;
     }
-    static BH_DEV void store(float* __restrict__ out, size_t pix, const float* acc, float T) {
+    static BH_DEV void store(float* __restrict__ out, Attr, size_t pix, const float* acc, float T) {
         const float a = 1.0f - __builtin_fabsf(T);   // the colour image's alpha, bit for bit (rasterize.hip store_pixels)
         if (MOMENTS) reinterpret_cast<float4*>(out)[pix] = make_float4(a, acc[1], acc[2], acc[0]);
         else out[pix] = __builtin_fmaf(a, acc[2], -(acc[1] * acc[1]));
@@ -123,24 +123,6 @@ __global__ __launch_bounds__(DL_WG) void distortion_loss_kernel(uint64_t pixels,
 
 float ndc_factor(const DistortionTerm& t) { return (float)((double)t.far_z * (double)t.near_z / ((double)t.far_z - (double)t.near_z)); }
 
-// SLOT_DISTORTION: m [Nv] | v_m [Nv] (each padded to a multiple of 64 floats) | the frame's moment map [H,W,4]
-struct DistortionScratch {
-    float* m = nullptr;
-    float* v_m = nullptr;
-    float* moments = nullptr;
-};
-
-int distortion_scratch(bh_ctx* ctx, uint32_t nv, size_t moment_pixels, bool backward, DistortionScratch* s) {
-    const size_t vec_floats = splat_vec_floats(nv, 1);
-    const size_t floats = backward ? 2 * vec_floats + moment_pixels * 4 : vec_floats;
-    auto* base = (float*)ensure(ctx, SLOT_DISTORTION, floats * 4);
-    if (!base) return BH_ERR_OOM;
-    s->m = base;
-    s->v_m = base + vec_floats;
-    s->moments = base + 2 * vec_floats;   // (16-byte aligned: vec_floats is a multiple of 64)
-    return 0;
-}
-
 // the per-splat depth the blends stage: depths_sorted itself, or the NDC vector in `scratch_m`
 int launch_distortion_depths(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& t, float* scratch_m, const float** m_of) {
     const uint32_t nv = fs.out.num_listed_splats;
@@ -173,10 +155,10 @@ int check_distortion_kind(bh_ctx* ctx, uint32_t kind, float near_z, float far_z,
 
 // The distortion map (moments: the moment map) of the saved forward `fs` (something is listed); the NDC depths go through SLOT_DISTORTION.
 int launch_distortion_map(bh_ctx* ctx, const ForwardState& fs, const DistortionTerm& t, bool moments, float* out) {
-    DistortionScratch s;
+    MapScratch s;
     const float* m_of = nullptr;
-    if (t.kind != BH_DISTORTION_Z) BH_TRY(distortion_scratch(ctx, fs.out.num_listed_splats, 0, /*backward=*/false, &s));
-    BH_TRY(launch_distortion_depths(ctx, fs, t, s.m, &m_of));
+    if (t.kind != BH_DISTORTION_Z) BH_TRY(map_scratch(ctx, SLOT_DISTORTION, fs.out.num_listed_splats, 1, /*has_input=*/true, /*backward=*/false, 0, &s));
+    BH_TRY(launch_distortion_depths(ctx, fs, t, s.in, &m_of));
     return launch_distortion_blend(ctx, fs, m_of, moments, out);
 }
 
@@ -188,29 +170,30 @@ int launch_distortion_backward(bh_ctx* ctx, const ForwardState& fs, const Distor
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
     const size_t pixels = (size_t)u.img_w * u.img_h;
-    DistortionScratch s;
-    BH_TRY(distortion_scratch(ctx, nv, t.moments ? 0 : pixels, /*backward=*/true, &s));
+    // SLOT_DISTORTION: m [Nv] | v_m [Nv] | the frame's moment map [H,W,4] (none where the caller brings its own)
+    MapScratch s;
+    BH_TRY(map_scratch(ctx, SLOT_DISTORTION, nv, 1, /*has_input=*/true, /*backward=*/true, t.moments ? 0 : pixels * 4, &s));
     float* const depth_v_z = *v_z;
     // Z with a depth term: the replay's atomics go straight into the depth term's v_z; every other case starts from a zeroed v_m
     const bool direct = depth_v_z && t.kind == BH_DISTORTION_Z;
-    if (!direct) BH_HIP(ctx, hipMemsetAsync(s.v_m, 0, splat_vec_floats(nv, 1) * 4, ctx->stream));
-    if (!depth_v_z) *v_z = s.v_m;
+    if (!direct) BH_HIP(ctx, hipMemsetAsync(s.v, 0, s.vec_floats * 4, ctx->stream));
+    if (!depth_v_z) *v_z = s.v;
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
     const float* m_of = nullptr;
-    BH_TRY(launch_distortion_depths(ctx, fs, t, s.m, &m_of));
+    BH_TRY(launch_distortion_depths(ctx, fs, t, s.in, &m_of));
     const float* moments = t.moments;
     if (!moments) {
-        BH_TRY(launch_distortion_blend(ctx, fs, m_of, /*moments=*/true, s.moments));
-        moments = s.moments;
+        BH_TRY(launch_distortion_blend(ctx, fs, m_of, /*moments=*/true, s.acc));
+        moments = s.acc;
     }
     using P = DistortionMap<true>;
     const P::BwdMaps maps{moments, t.v_distortion, t.gain};
-    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, m_of, maps, v_combined, direct ? depth_v_z : s.v_m);
+    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, m_of, maps, v_combined, direct ? depth_v_z : s.v);
     BH_LAUNCH_CHECK(ctx, "distortion_backward_kernel");
     if (t.kind == BH_DISTORTION_NDC) {
         const dim3 grid((nv + 255u) / 256u), block(256);
-        if (depth_v_z) hipLaunchKernelGGL(distortion_ndc_chain_kernel<true>, grid, block, 0, ctx->stream, nv, ndc_factor(t), r.depths_sorted, s.v_m, depth_v_z);
-        else hipLaunchKernelGGL(distortion_ndc_chain_kernel<false>, grid, block, 0, ctx->stream, nv, ndc_factor(t), r.depths_sorted, s.v_m, s.v_m);
+        if (depth_v_z) hipLaunchKernelGGL(distortion_ndc_chain_kernel<true>, grid, block, 0, ctx->stream, nv, ndc_factor(t), r.depths_sorted, s.v, depth_v_z);
+        else hipLaunchKernelGGL(distortion_ndc_chain_kernel<false>, grid, block, 0, ctx->stream, nv, ndc_factor(t), r.depths_sorted, s.v, s.v);
         BH_LAUNCH_CHECK(ctx, "distortion_ndc_chain_kernel");
     }
     return 0;

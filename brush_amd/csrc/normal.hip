@@ -81,14 +81,14 @@ __global__ __launch_bounds__(256) void splat_normals_kernel(uint64_t n, NormalVi
 // (accumulated: g = v; unit: g = (v - (v . u) u) / |N|, 0 where |N| == 0).  The "colour" of splat i at the pixel is cv = g . n_i and
 // S = the remaining sum of w_j (g . n_j): it starts at g . N.
 template <uint32_t MODE>
-struct NormalMap {
-    static constexpr int STRIDE = 12, NACC = 3, NV = 3;
+struct NormalMap : SinglePassMap<3> {
+    static constexpr int STRIDE = 12, NACC = 3;
     struct Rec { float4 s0, s1, s2; };   // x y c00/2 c01 | c11/2 a sigma_cut nx | ny nz - -
     static BH_DEV Rec load(const float* p) {
         return Rec{*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), *reinterpret_cast<const float4*>(p + 8)};
     }
     static BH_DEV float cut(const Rec& r) { return r.s1.z; }
-    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, const float* __restrict__ normals, uint32_t cg) {
+    static BH_DEV void stage(float4* d, const float* v, float sigma_cut, Attr normals, uint32_t cg) {
         const float* nn = normals + (size_t)cg * 3;
         const float nx = nn[0], ny = nn[1], nz = nn[2];
         d[0] = make_float4(v[0], v[1], 0.5f * v[2], v[3]);
@@ -102,7 +102,7 @@ struct NormalMap {
         acc[2] = __builtin_fmaf(r.s2.y, vis, acc[2]);
         T = ok ? (sat ? -T : next_t) : T;
     }
-    static BH_DEV void store(float* __restrict__ out, size_t pix, const float* acc, float T) {
+    static BH_DEV void store(float* __restrict__ out, Attr, size_t pix, const float* acc, float T) {
         float x = acc[0], y = acc[1], z = acc[2];
         if (MODE == BH_NORMAL_UNIT) {
             const float len = __builtin_sqrtf(__builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
@@ -239,25 +239,6 @@ NormalView normal_view(const float* vm) {
     return v;
 }
 
-// SLOT_NORMAL: compact splat normals [Nv,3] | Vn [Nv,3] (each padded to a multiple of 64 floats) | the accumulated map [H,W,3]
-struct NormalScratch {
-    float* normals = nullptr;
-    float* v_n = nullptr;
-    float* acc = nullptr;
-    size_t vec_floats = 0;
-};
-
-int normal_scratch(bh_ctx* ctx, uint32_t nv, size_t pixels, bool backward, NormalScratch* s) {
-    s->vec_floats = splat_vec_floats(nv, 3);
-    const size_t floats = backward ? 2 * s->vec_floats + pixels * 3 : s->vec_floats;
-    auto* base = (float*)ensure(ctx, SLOT_NORMAL, floats * 4);
-    if (!base) return BH_ERR_OOM;
-    s->normals = base;
-    s->v_n = base + s->vec_floats;
-    s->acc = base + 2 * s->vec_floats;
-    return 0;
-}
-
 int launch_compact_normals(bh_ctx* ctx, const ForwardState& fs, const float* transforms, float* normals) {
     const uint32_t nv = fs.out.num_listed_splats;
     if (nv == 0) return 0;
@@ -293,10 +274,10 @@ PinholeK pinhole_of(const BhCamera* cam, uint32_t h, uint32_t w) {
 
 // The normal map `mode` of the saved forward `fs` (something is listed); the compact splat normals go through SLOT_NORMAL.
 int launch_normal_map(bh_ctx* ctx, const ForwardState& fs, const float* transforms, uint32_t mode, float* out) {
-    NormalScratch s;
-    BH_TRY(normal_scratch(ctx, fs.out.num_listed_splats, 0, /*backward=*/false, &s));
-    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
-    return launch_normal_forward(ctx, fs, s.normals, mode, out);
+    MapScratch s;
+    BH_TRY(map_scratch(ctx, SLOT_NORMAL, fs.out.num_listed_splats, 3, /*has_input=*/true, /*backward=*/false, 0, &s));
+    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.in));
+    return launch_normal_forward(ctx, fs, s.in, mode, out);
 }
 
 // The normal term of a backward, between K17 and K18: v_combined += its raw sums, *v_n_out = Vn = sum of vis * g.
@@ -304,16 +285,17 @@ int launch_normal_backward(bh_ctx* ctx, const ForwardState& fs, const NormalTerm
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
-    NormalScratch s;
-    BH_TRY(normal_scratch(ctx, nv, (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
-    *v_n_out = s.v_n;
-    BH_HIP(ctx, hipMemsetAsync(s.v_n, 0, s.vec_floats * 4, ctx->stream));
+    // SLOT_NORMAL: compact splat normals [Nv,3] | Vn [Nv,3] | the accumulated map [H,W,3]
+    MapScratch s;
+    BH_TRY(map_scratch(ctx, SLOT_NORMAL, nv, 3, /*has_input=*/true, /*backward=*/true, (size_t)u.img_w * u.img_h * 3, &s));
+    *v_n_out = s.v;
+    BH_HIP(ctx, hipMemsetAsync(s.v, 0, s.vec_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
-    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.normals));
-    BH_TRY(launch_normal_forward(ctx, fs, s.normals, BH_NORMAL_ACCUMULATED, s.acc));
+    BH_TRY(launch_compact_normals(ctx, fs, transforms, s.in));
+    BH_TRY(launch_normal_forward(ctx, fs, s.in, BH_NORMAL_ACCUMULATED, s.acc));
     using P = NormalMap<BH_NORMAL_ACCUMULATED>;
     const P::BwdMaps maps{s.acc, term.v_normal, term.mode == BH_NORMAL_UNIT ? 1u : 0u};
-    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, s.normals, maps, v_combined, s.v_n);
+    launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, s.in, maps, v_combined, s.v);
     BH_LAUNCH_CHECK(ctx, "normal_backward_kernel");
     return 0;
 }

@@ -1,5 +1,5 @@
 """Feature maps on the GPU (include/brush_hip_features.h): bit identity with the colour image whose blend they
-restate, the map and its gradients against the float64 restatement tests/feature_ref.py, the feature-only backward against the
+restate and with the accumulated normal map (the map skeleton's other three-channel traits struct), the map and its gradients against the float64 restatement tests/feature_ref.py, the feature-only backward against the
 oracle-pinned colour backward, bit identity across list policies / calls / retained forwards / tile-row windows, the two fused
 losses against their numpy restatements, and the edges.
 
@@ -128,6 +128,35 @@ def test_rgb_features_are_the_colour_image_bit_for_bit(dev, n, w, h, seed):
             ctx.set_option("feature_chunk", width)
             assert torch.equal(node.features(f3), rgb), ("forced chunk", width)
             assert torch.equal(node.features(f)[..., :3], rgb), ("forced chunk, 19 channels", width)
+        ctx.set_option("feature_chunk", 0)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("extra", [0, 16], ids=["C3", "C19"])
+@pytest.mark.parametrize("smooth", [False, True], ids=["hard", "smooth"])
+def test_normal_features_are_the_normal_map_bit_for_bit(dev, smooth, extra):
+    """Features whose first three columns are the dense splat normals give the accumulated normal map with torch.equal, at the
+    default chunk width and at every forced one (C = 19: two chunks at width 16, five at width 4): FeatureMap and NormalMap are two
+    traits structs of one skeleton, and this holds them to each other through the arithmetic they share."""
+    import brush_amd as ba
+    n, w, h = 3000, 123, 82
+    sc, cp = _scene(n, w, h, 0xD2)
+    spl = ba.Splats(sc["transforms"], sc["sh"], sc["raw_opac"], device=dev)
+    cam = util.hip_camera(ba, cp)
+    ctx = ba.Context(dev)
+    try:
+        node = ba.render_splats_diff(spl, cam, (w, h), pass_=_pass(ba, smooth), ctx=ctx)
+        want = ba.render_normal(node, "accumulated").clone()
+        assert float(want.abs().max()) > 0.1
+        f = torch.randn((n, 3 + extra), generator=torch.Generator().manual_seed(11)).to(dev)
+        f[:, :3] = ba.splat_normals(spl, cam, ctx=ctx)
+        f = f.contiguous()
+        for width in (0,) + CHUNKS:
+            ctx.set_option("feature_chunk", width)
+            got = node.features(f)
+            assert torch.equal(got[..., :3], want), ("chunk width", width)
+            assert extra == 0 or float(got[..., 3:].abs().max()) > 0.0
         ctx.set_option("feature_chunk", 0)
     finally:
         ctx.close()
