@@ -54,6 +54,10 @@ Names and argument meaning follow the reference (paths under
                                          feature maps: caller-owned per-splat vectors of 1 .. 256 channels blended with the colour
                                          blend's weights, the gradient into them and the splats, fused L1 / cross-entropy losses (not
                                          in the reference; gsplat's colors [N, D]; include/brush_hip_features.h)
+    SplatTrainer(feature_field=) / SceneBatch.features / TrainConfig.feature_loss_weight / FeatureField.carry / .gather
+                                         feature fields trained jointly with the splats: the feature term inside the step, the
+                                         field's Adam update on the device, its rows carried through refine (not in the reference;
+                                         Feature-3DGS, Gaussian Grouping; include/brush_hip_feature_train.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.

@@ -1563,6 +1563,18 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         if (!whole_frame) return refuse_partial_frame(ctx, "distortion term");
         if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a distortion term", "distortion term");
     }
+    // a feature term (brush_hip_feature_train.h): refused before anything is queued; no field, no target or a weight <= 0 (or not a
+    // number) is no term at all
+    const bool feature_wanted = ctx->feature_attached && ctx->feature_target.weight > 0.0f;
+    if (feature_wanted) {
+        if (!whole_frame) return refuse_partial_frame(ctx, "feature term");
+        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a feature term", "feature term");
+        if (ctx->feature_field.n != st->n)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the feature term's field has " + std::to_string(ctx->feature_field.n) + " rows, the state " +
+                                                          std::to_string(st->n) + " splats (a refine re-rows the splats: carry the field with bh_refine_carry_rows)");
+        if (ctx->feature_target.h != batch->camera.img_h || ctx->feature_target.w != batch->camera.img_w)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the feature term's target size differs from the camera's");
+    }
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
     const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
@@ -1789,6 +1801,37 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         distortion_term.moments = moments;
         bwd.distortion = &distortion_term;
     }
+    // ---- feature term (brush_hip_feature_train.h): on the same final frame, behind the distortion term.  The map is blended ONCE:
+    // it and the compact rows behind it go to the backward, which then skips its own gather and forward; the map and v_map live in a
+    // slot of their own, the dense v_features in another until the field's update.  loss += the term's, in f32, behind the distortion
+    // term's.  A frame that lists nothing: the map is all +0, the loss is still evaluated, the backward leaves v_features all +0.
+    FeatureTerm feature_term;
+    float* v_features = nullptr;
+    if (feature_wanted) {
+        ProfScope pf(ctx, "FeatureTerm");
+        const BhFeatureField& ff = ctx->feature_field;
+        const size_t map_floats = hw * ff.channels;
+        auto* f_map = (float*)ensure(ctx, SLOT_FEATURE_TERM, (map_floats * 2 + 4) * 4);
+        v_features = (float*)ensure(ctx, SLOT_FEATURE_GRAD, (size_t)(n ? n : 1) * ff.channels * 4);
+        if (!f_map || !v_features) return BH_ERR_OOM;
+        float* v_map = f_map + map_floats;
+        float* rows = nullptr;
+        BH_TRY(feature_term_rows(ctx, ctx->latest, ff.channels, &rows));
+        if (frame_listed && ctx->latest.out.num_listed_splats > 0) {
+            BH_TRY(launch_feature_gather(ctx, ctx->latest, ff.features, ff.channels, rows));
+            BH_TRY(launch_feature_forward(ctx, ctx->latest, ff.channels, rows, f_map));
+        } else {
+            BH_HIP(ctx, hipMemsetAsync(f_map, 0, map_floats * 4, ctx->stream));
+        }
+        BH_TRY(launch_feature_loss(ctx, f_map, ctx->feature_target, v_map + map_floats, v_map, loss_dev, loss_host));
+        feature_term.features = ff.features;
+        feature_term.channels = ff.channels;
+        feature_term.v_map = v_map;
+        feature_term.v_features = v_features;
+        feature_term.map_acc = f_map;
+        feature_term.compact = rows;
+        bwd.feature = &feature_term;
+    }
 
     // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
     // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling
@@ -1884,6 +1927,11 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
             BH_TRY(sum_over_ranks(exch, (uint64_t)o_ref));
         }
     }
+    // ... and the feature term's v_features by one more sum of the same kind: N C floats, dense (brush_hip_feature_train.h)
+    if (feature_wanted && exchanging && n > 0) {
+        ProfScope ps(ctx, "FeatureExchange");
+        BH_TRY(sum_over_ranks(v_features, (uint64_t)n * ctx->feature_field.channels));
+    }
     // ---- refine statistics (train.rs:280-298) + optimizer (train.rs:300-381): one launch
     const double decay = std::pow(cfg->lr_mean_end / cfg->lr_mean, 1.0 / (double)cfg->total_train_iters);
     const double lr_mean = cfg->lr_mean * std::pow(decay, (double)((int)step - 1)) * (double)cfg->median_scene_scale;
@@ -1907,6 +1955,11 @@ static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* 
         uc.t = step; uc.beta1 = 0.9f; uc.beta2 = 0.999f; uc.eps = 1e-15f;
         uc.noise = noise_fused ? &na : nullptr; uc.masked_rows = masked_grads;
         BH_TRY(launch_train_update(ctx, st, uc));
+        if (feature_wanted && n > 0) {   // the field's Adam step on grad_scale * v_features (launch_adam's arithmetic, full second moment); no rows, no update to count
+            BhFeatureField& ff = ctx->feature_field;
+            BH_TRY(launch_adam(ctx, ff.features, v_features, ff.m1, ff.m2, n, ff.channels, nullptr, ff.lr, ff.step + 1, false, ff.beta1, ff.beta2, ff.eps, grad_scale));
+            ff.step += 1;
+        }
     }
     st->step_count = step;   // the update is queued: the step counts
     if (noise_on && !noise_fused) {

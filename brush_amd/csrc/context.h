@@ -19,6 +19,7 @@
 #include "../../include/brush_hip_distortion.h"
 #include "../../include/brush_hip_mesh.h"
 #include "../../include/brush_hip_features.h"
+#include "../../include/brush_hip_feature_train.h"
 #include "device_math.h"
 
 namespace bh {
@@ -96,6 +97,8 @@ enum Slot : int {
     SLOT_BILAGRID,           // bh_bilagrid_backward: the train step's TV scalar (16 bytes) | the f64 gradient sums of the row | one f64 row of 48 per (unit, level) of the v_g pass (bilagrid.hip)
     SLOT_TSDF,               // bh_tsdf_extract[_count]: per sample the edge mask / triangle count / corner bits [n] | the vertex scan [n] | the triangle scan [n] (tsdf.hip)
     SLOT_FEATURES,           // bh_render_features / launch_feature_backward: compact features [Nv,C] | V [Nv,C] | the frame's accumulated feature map [H,W,C] (features.hip)
+    SLOT_FEATURE_TERM,       // bh_train_step with a feature term: the feature map [H,W,C] | v_map [H,W,C] | the term's loss pair (4 floats)
+    SLOT_FEATURE_GRAD,       // ... and its dense v_features [N,C], from the backward to the field's update
     SLOT_COUNT
 };
 
@@ -394,6 +397,9 @@ struct FeatureTerm {
     uint32_t channels = 0;             // 1 .. BH_FEATURE_MAX_CHANNELS
     const float* v_map = nullptr;      // [H,W,C]
     float* v_features = nullptr;       // [N,C] out: dense, fully overwritten
+    // what the caller has already produced for this frame (the train step), or NULL: the backward gathers and blends its own
+    const float* map_acc = nullptr;    // [H,W,C] the frame's accumulated feature map
+    const float* compact = nullptr;    // [Nv,C] the compact rows behind it, at feature_term_rows' address
 };
 
 // One backward on a saved forward (api.hip backward_impl): the parameters the forward rendered, where the gradients go, and the
@@ -454,6 +460,9 @@ struct bh_ctx {
     BhNormalTermConfig normal_term{};
     bool distortion_attached = false; // bh_train_set_distortion: the step adds the distortion term (brush_hip_distortion.h); only ever true with a weight > 0
     BhDistortionTermConfig distortion_term{};
+    bool feature_attached = false;    // bh_train_set_features: a field is attached (brush_hip_feature_train.h); feature_field.step counts its updates
+    BhFeatureField feature_field{};
+    BhFeatureTarget feature_target{}; // ... and the target of the next steps; weight <= 0 (or not a number, or no target): no term
     std::vector<bh::ViewTable*> view_tables;   // every per-view table of this ctx, of either kind (view_table.h): bh_destroy frees what is left
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
@@ -602,6 +611,13 @@ int launch_distortion_loss(bh_ctx* ctx, const float* map, uint32_t h, uint32_t w
 // the dense v_features is cleared), and the compact vector -> the rows of v_features behind K18
 int launch_feature_backward(bh_ctx* ctx, const ForwardState& fs, const FeatureTerm& term, float* v_combined, const float** v_compact);
 int launch_feature_scatter(bh_ctx* ctx, const ForwardState& fs, const FeatureTerm& term, const float* v_compact);
+// ... the pieces of a feature map of a saved forward with something listed: features[gid, :] -> the compact rows `feat` [Nv,C], and
+// their blend into out [H,W,C]; feature_term_rows: the address of the compact rows a FeatureTerm::compact must have (SLOT_FEATURES,
+// sized for the backward); the fused loss (the target is already checked; accum as launch_depth_loss's)
+int launch_feature_gather(bh_ctx* ctx, const ForwardState& fs, const float* features, uint32_t channels, float* feat);
+int launch_feature_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t channels, const float* feat, float* out);
+int feature_term_rows(bh_ctx* ctx, const ForwardState& fs, uint32_t channels, float** feat);
+int launch_feature_loss(bh_ctx* ctx, const float* map, const BhFeatureTarget& t, float* loss, float* v_map, float* accum, float* accum_host);
 // depth_loss.hip: the fused depth loss on the ctx stream (the target is already checked; weight > 0).  accum != NULL (train step):
 // accum[0] += loss[0], and the sum is stored to accum_host too
 int launch_depth_loss(bh_ctx* ctx, const float* depth, const BhDepthTarget& t, float* loss, float* v_depth, float* accum, float* accum_host);
@@ -819,7 +835,8 @@ int launch_image_loss_backward(bh_ctx* ctx, const float* pred, const uint32_t* g
                                float* dl_dpred);
 // optim.hip
 int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
-                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps);
+                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps, float gscale = 1.0f);
+// (gscale: a factor on every gradient, full second moment only — the feature field's update under data parallelism)
 // statistics + the three Adam updates of a train step in one launch (tab_t: per-column lr of `transforms`)
 // noise != NULL: the visibility-gated mean noise of train.rs:389-416, drawn on the device (device_rng.h), rides on the same launch
 struct NoiseArgs { uint64_t seed; uint32_t step; float scale, clamp_abs; };

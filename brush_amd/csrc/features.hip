@@ -141,6 +141,8 @@ void with_feature_map(const bh_ctx* ctx, uint32_t channels, F&& f) {
     }
 }
 
+}  // namespace
+
 // the blend of the compact rows `feat` into `out`
 int launch_feature_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t channels, const float* feat, float* out) {
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
@@ -153,10 +155,14 @@ int launch_feature_forward(bh_ctx* ctx, const ForwardState& fs, uint32_t channel
     return 0;
 }
 
+namespace {
+
 // SLOT_FEATURES: compact features [Nv,C] | V [Nv,C] | the accumulated map [H,W,C]
 int feature_scratch(bh_ctx* ctx, uint32_t nv, uint32_t channels, size_t pixels, bool backward, MapScratch* s) {
     return map_scratch(ctx, SLOT_FEATURES, nv, channels, /*has_input=*/true, backward, pixels * channels, s);
 }
+
+}  // namespace
 
 int launch_feature_gather(bh_ctx* ctx, const ForwardState& fs, const float* features, uint32_t channels, float* feat) {
     const uint64_t total = (uint64_t)fs.out.num_listed_splats * channels;
@@ -166,6 +172,17 @@ int launch_feature_gather(bh_ctx* ctx, const ForwardState& fs, const float* feat
     BH_LAUNCH_CHECK(ctx, "feature_gather_kernel");
     return 0;
 }
+
+// the train step's compact rows: where launch_feature_backward will look for them (the slot is sized for that backward here, so
+// it does not move in between)
+int feature_term_rows(bh_ctx* ctx, const ForwardState& fs, uint32_t channels, float** feat) {
+    MapScratch s;
+    BH_TRY(feature_scratch(ctx, fs.out.num_listed_splats, channels, 0, /*backward=*/true, &s));
+    *feat = s.in;
+    return 0;
+}
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // losses
@@ -236,17 +253,24 @@ int launch_feature_backward(bh_ctx* ctx, const ForwardState& fs, const FeatureTe
     const BhRenderOut& r = fs.out;
     const uint32_t nv = r.num_listed_splats, C = term.channels;
     const MapUniforms u = map_uniforms(ctx, fs.uniforms);
+    const bool rendered = term.map_acc != nullptr;   // the train step: the map and the compact rows exist (feature_term_rows' layout)
     MapScratch s;
-    BH_TRY(feature_scratch(ctx, nv, C, (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
+    BH_TRY(feature_scratch(ctx, nv, C, rendered ? 0 : (size_t)u.img_w * u.img_h, /*backward=*/true, &s));
     *v_compact = s.v;
     if (fs.n > 0) BH_HIP(ctx, hipMemsetAsync(term.v_features, 0, (size_t)fs.n * C * 4, ctx->stream));
     BH_HIP(ctx, hipMemsetAsync(s.v, 0, s.vec_floats * 4, ctx->stream));
     if (r.num_intersections == 0 || nv == 0 || u.num_tiles == 0) return 0;
-    BH_TRY(launch_feature_gather(ctx, fs, term.features, C, s.in));
-    BH_TRY(launch_feature_forward(ctx, fs, C, s.in, s.acc));
+    const float* map_acc = term.map_acc;
+    if (!rendered) {
+        BH_TRY(launch_feature_gather(ctx, fs, term.features, C, s.in));
+        BH_TRY(launch_feature_forward(ctx, fs, C, s.in, s.acc));
+        map_acc = s.acc;
+    } else if (term.compact != s.in) {
+        return set_error(ctx, BH_ERR_STATE, "internal: the feature term's compact rows are not where the backward's scratch has them");
+    }
     with_feature_map(ctx, C, [&](auto p) {
         using P = decltype(p);
-        launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, typename P::Attr{s.in, C}, typename P::BwdMaps{s.acc, term.v_map, C}, v_combined, s.v);
+        launch_map_backward<P>(ctx, u, fs.flags & BH_FLAG_SMOOTH_CUTOFF, r, typename P::Attr{s.in, C}, typename P::BwdMaps{map_acc, term.v_map, C}, v_combined, s.v);
     });
     BH_LAUNCH_CHECK(ctx, "feature_backward_kernel");
     return 0;
@@ -306,6 +330,35 @@ int bh_feature_loss_value_and_grad(bh_ctx* ctx, const float* map, const BhFeatur
         return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": channels must be 1 .. 256");
     if (target->kind > BH_FEATURE_LOSS_CROSS_ENTROPY) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": unknown feature loss kind");
     BH_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_feature_loss(ctx, map, *target, loss, v_map, nullptr, nullptr);
+}
+
+// brush_hip_feature_train.h: the field and the target of the ctx's next train steps (api.hip train_step_impl applies them)
+int bh_train_set_features(bh_ctx* ctx, const BhFeatureField* field, const BhFeatureTarget* target) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    const char* who = "train_set_features";
+    if (field) {
+        if (!field->features || !field->m1 || !field->m2) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": null pointer in the field");
+        if (field->channels == 0 || field->channels > BH_FEATURE_MAX_CHANNELS)
+            return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": channels must be 1 .. 256");
+        if (target) {
+            if (target->channels != field->channels) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": the target's channels differ from the field's");
+            if (target->kind > BH_FEATURE_LOSS_CROSS_ENTROPY) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": unknown feature loss kind");
+            if (target->weight > 0.0f && !target->target) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": the target has no target map");
+        }
+    }
+    ctx->feature_attached = field != nullptr;
+    ctx->feature_field = field ? *field : BhFeatureField{};
+    ctx->feature_target = (field && target) ? *target : BhFeatureTarget{};
+    return 0;
+}
+
+}  // extern "C"
+
+namespace bh {
+
+int launch_feature_loss(bh_ctx* ctx, const float* map, const BhFeatureTarget& t, float* loss, float* v_map, float* accum, float* accum_host) {
+    const BhFeatureTarget* target = &t;
     FeatureLossArgs a;
     a.pixels = (uint64_t)target->h * target->w;
     a.channels = target->channels;
@@ -326,7 +379,7 @@ int bh_feature_loss_value_and_grad(bh_ctx* ctx, const float* map, const BhFeatur
     else { if (v_map) BH_FL(BH_FEATURE_LOSS_CROSS_ENTROPY, true); else BH_FL(BH_FEATURE_LOSS_CROSS_ENTROPY, false); }
 #undef BH_FL
     BH_LAUNCH_CHECK(ctx, "feature_loss_kernel");
-    return launch_loss_pair_final(ctx, grid.x, partials, a.c, loss, nullptr, nullptr);
+    return launch_loss_pair_final(ctx, grid.x, partials, a.c, loss, accum, accum_host);
 }
 
-}  // extern "C"
+}  // namespace bh

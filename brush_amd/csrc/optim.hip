@@ -49,10 +49,10 @@ BH_DEV uint32_t row10(uint32_t e) { return (e * 52429u) >> 19; }   // e / 10, ex
 // full second moment: one thread per element
 __global__ __launch_bounds__(OPT_WG) void adam_full_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                           float* __restrict__ m1, float* __restrict__ m2, uint64_t count,
-                                                          uint32_t row_len, const float* __restrict__ col_scale, AdamArgs a) {
+                                                          uint32_t row_len, const float* __restrict__ col_scale, AdamArgs a, float gscale) {
     const uint64_t i = (uint64_t)blockIdx.x * OPT_WG + threadIdx.x;
     if (i >= count) return;
-    const float g = grad[i];
+    const float g = grad[i] * gscale;   // (gscale 1: the gradient's own bits)
     const float mm1 = moment1_step(a, &m1[i], g);
     const float mm2 = moment2_step(a, &m2[i], g * g);
     m1[i] = mm1;
@@ -146,9 +146,10 @@ static size_t max_dynamic_lds(bh_ctx* ctx) {
 }
 
 int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
-                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps) {
+                const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps, float gscale) {
     if (rows == 0 || row_len == 0) return 0;
     if (t == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "adam: t is 1-based");
+    if (reduce_m2 && gscale != 1.0f) return set_error(ctx, BH_ERR_UNSUPPORTED, "adam (reduced second moment): no gradient scale");
     const AdamArgs a = make_adam_args(beta1, beta2, eps, lr, t);
     if (reduce_m2) {
         // 256 rows of row_len + 1 floats and the rows' second moments in LDS: what fits is the device's word (the opt-in limit of
@@ -169,7 +170,7 @@ int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* 
     } else {
         const uint64_t count = rows * row_len;
         const uint64_t nb = (count + OPT_WG - 1) / OPT_WG;
-        hipLaunchKernelGGL(adam_full_kernel, dim3((unsigned)nb), dim3(OPT_WG), 0, ctx->stream, param, grad, m1, m2, count, row_len, col_scale, a);
+        hipLaunchKernelGGL(adam_full_kernel, dim3((unsigned)nb), dim3(OPT_WG), 0, ctx->stream, param, grad, m1, m2, count, row_len, col_scale, a, gscale);
         BH_LAUNCH_CHECK(ctx, "adam_full_kernel");
     }
     return 0;

@@ -272,6 +272,24 @@ __global__ __launch_bounds__(RF_WG) void refine_apply_kernel(
     op[j] = decay_opacity(raw, a.minus_opac);
 }
 
+// ---- any other per-splat table through the plan (brush_hip_feature_train.h) --------------------
+// One thread per float of the OLD table: consecutive lanes take consecutive channels of a row, so the load and both stores
+// coalesce.  A kept row goes to its new row, a split parent's row to its child's as well (zero_split: both are +0, what the apply
+// kernel does to the Adam moments).  Every new row has exactly one source: no row is written twice.
+__global__ __launch_bounds__(RF_WG) void refine_carry_rows_kernel(uint64_t total, uint32_t channels, int zero_split, const uint32_t* __restrict__ ctl,
+                                                                 const uint32_t* __restrict__ keep, const uint32_t* __restrict__ keep_excl,
+                                                                 const uint32_t* __restrict__ split, const uint32_t* __restrict__ split_excl,
+                                                                 const float* __restrict__ in, float* __restrict__ out) {
+    const uint64_t idx = (uint64_t)blockIdx.x * RF_WG + threadIdx.x;
+    if (idx >= total) return;
+    const uint64_t i = idx / channels, c = idx - i * channels;
+    if (!keep[i]) return;
+    const bool is_split = split[i] != 0u;
+    const float v = (is_split && zero_split) ? 0.0f : in[idx];
+    out[(uint64_t)keep_excl[i] * channels + c] = v;
+    if (is_split) out[((uint64_t)ctl[C_NKEEP] + split_excl[i]) * channels + c] = v;
+}
+
 // ---- percentile bounds (splat_init.rs:130-160) ------------------------------------------------
 // float -> u32 whose unsigned order is f32::total_cmp order; non-finite values go last
 BH_DEV uint32_t total_order_key(float v) {
@@ -437,6 +455,26 @@ int bh_refine_apply(bh_ctx* ctx, const BhRefineConfig* cfg, const BhTrainState* 
     BH_HIP(ctx, hipMemsetAsync(out->max_screen_size, 0, nb, ctx->stream));
     out->step_count = in->step_count;
     ctx->refine_n = 0;
+    return 0;
+}
+
+int bh_refine_carry_rows(bh_ctx* ctx, const float* in, float* out, uint32_t channels, uint32_t mode) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!in || !out) return set_error(ctx, BH_ERR_INVALID_ARG, "refine_carry_rows: null argument");
+    if (channels == 0 || channels > BH_CARRY_MAX_CHANNELS) return set_error(ctx, BH_ERR_INVALID_ARG, "refine_carry_rows: channels must be 1 .. 4096");
+    if (mode > BH_CARRY_ZERO_SPLIT) return set_error(ctx, BH_ERR_INVALID_ARG, "refine_carry_rows: unknown carry mode");
+    if (ctx->refine_n == 0 || !ctx->slots[SLOT_REFINE].ptr)
+        return set_error(ctx, BH_ERR_STATE, "refine_carry_rows needs a pending plan: call it between bh_refine_plan and bh_refine_apply");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = ctx->refine_n;
+    const uint64_t total = (uint64_t)n * channels;
+    const uint64_t blocks = (total + RF_WG - 1) / RF_WG;
+    if (blocks > 0x7FFFFFFFull) return set_error(ctx, BH_ERR_UNSUPPORTED, "refine_carry_rows: the table is too large for one launch");
+    const uint32_t* ctl = (const uint32_t*)ctx->slots[SLOT_REFINE].ptr;
+    const uint32_t* keep = ctl + C_COUNT;
+    hipLaunchKernelGGL(refine_carry_rows_kernel, dim3((uint32_t)blocks), dim3(RF_WG), 0, ctx->stream, total, channels, mode == BH_CARRY_ZERO_SPLIT ? 1 : 0, ctl,
+                       keep, keep + n, keep + 2 * n, keep + 3 * n, in, out);
+    BH_LAUNCH_CHECK(ctx, "refine_carry_rows_kernel");
     return 0;
 }
 

@@ -796,9 +796,11 @@ def feature_loss_value_and_grad(map, target, kind="l1", weight=1.0, want_grad=Tr
 
 
 class FeatureField:
-    """Caller-owned per-splat feature vectors [N,C] with their Adam state, trained on a fixed set of splats (the second stage of
-    LangSplat and Gaussian Grouping): zero-initialised features, `render(node)` the map, `backward(node, v_map)` the gradients,
-    `step(v_features)` one Adam step (adam_step with row_len = C)."""
+    """Caller-owned per-splat feature vectors [N,C] with their Adam state.  On a fixed set of splats (the second stage of LangSplat
+    and Gaussian Grouping): zero-initialised features, `render(node)` the map, `backward(node, v_map)` the gradients,
+    `step(v_features)` one Adam step (adam_step with row_len = C).  Jointly with the splats (Feature-3DGS, gsplat's colors [N, D]):
+    SplatTrainer(..., feature_field=field) trains it inside the step against SceneBatch.features and carries it through refine
+    (`carry`); `gather` follows a decimation.  `t` counts the Adam updates applied so far, whoever applied them."""
 
     def __init__(self, n, channels, lr=1e-2, device=None, ctx: Optional[Context] = None, beta1=0.9, beta2=0.999, eps=1e-15):
         if not 1 <= int(channels) <= FEATURE_MAX_CHANNELS:
@@ -821,6 +823,45 @@ class FeatureField:
         self.t += 1
         adam_step(self.features, _f32c(v_features, self.features.device), self.m1, self.m2, self.lr, self.t, beta1=self.beta1, beta2=self.beta2,
                   eps=self.eps, ctx=self.ctx)
+
+    def as_struct(self) -> "_ffi.BhFeatureField":
+        """The field as bh_train_set_features takes it (include/brush_hip_feature_train.h): the three tensors, the counters and the
+        Adam constants; `step` = the updates applied so far (self.t)."""
+        f = _ffi.BhFeatureField()
+        f.features, f.m1, f.m2 = self.features.data_ptr(), self.m1.data_ptr(), self.m2.data_ptr()
+        f.n, f.channels, f.step = int(self.features.shape[0]), int(self.features.shape[1]), int(self.t)
+        f.lr, f.beta1, f.beta2, f.eps = float(self.lr), float(self.beta1), float(self.beta2), float(self.eps)
+        return f
+
+    def carry(self, ctx: Optional[Context] = None, total_splats: Optional[int] = None):
+        """Takes the field through the ctx's pending refine plan (bh_refine_carry_rows; valid between bh_refine_plan and
+        bh_refine_apply — SplatTrainer.refine calls it there): the features follow their splats, a split parent's row goes to both
+        halves; the moments of both halves of a split start at zero, as refine leaves the splats' own.  Replaces the three tensors.
+        total_splats: the plan's BhRefineStats.total_splats if the caller has it (refine does); None reads it from the plan's flags (one
+        synchronising readback)."""
+        ctx = ctx or self.ctx
+        dev = self.features.device
+        n, ch = (int(v) for v in self.features.shape)
+        flags = ctx.lib.bh_refine_plan_flags(ctx._h, 0)
+        if not flags:
+            raise BrushHipError("FeatureField.carry: no refine plan is pending (call it between bh_refine_plan and bh_refine_apply)")
+        if total_splats is None:
+            ctx.sync()
+            total_splats = int(_view(flags, (n,), torch.int32, dev).sum().item()) + int(_view(ctx.lib.bh_refine_plan_flags(ctx._h, 2), (n,), torch.int32, dev).sum().item())
+        new = [torch.empty((int(total_splats), ch), dtype=torch.float32, device=dev) for _ in range(3)]
+        if not ctx.uses_torch_stream:
+            torch.cuda.current_stream(dev).synchronize()
+        for src, dst, mode in ((self.features, new[0], _ffi.CARRY_COPY), (self.m1, new[1], _ffi.CARRY_ZERO_SPLIT), (self.m2, new[2], _ffi.CARRY_ZERO_SPLIT)):
+            ctx.check(ctx.lib.bh_refine_carry_rows(ctx._h, _ptr(src), _ptr(dst), ch, mode))
+        if not ctx.uses_torch_stream:
+            ctx.sync()   # the old tables are released below: on torch's own stream its allocator orders that, on the ctx's nothing does
+        self.features, self.m1, self.m2 = new
+
+    def gather(self, indices):
+        """Keeps the rows `indices` (what decimate_to_count(..., return_indices=True) returns), in that order: plain indexing of the
+        three tensors."""
+        idx = torch.as_tensor(indices, device=self.features.device).long()
+        self.features, self.m1, self.m2 = (t[idx].contiguous() for t in (self.features, self.m1, self.m2))
 
 
 DISTORTION_KINDS = {"z": _ffi.DISTORTION_Z, "ndc": _ffi.DISTORTION_NDC}
@@ -1542,6 +1583,11 @@ class TrainConfig:
     distortion_kind: str = "z"
     distortion_near: float = 0.2
     distortion_far: float = 1000.0
+    # not in the reference: > 0 adds the feature term (brush_hip_feature_train.h) from step feature_loss_from_iter on, for batches that
+    # carry a feature target; needs SplatTrainer(..., feature_field=FeatureField); kind "l1" or "cross_entropy"
+    feature_loss_weight: float = 0.0
+    feature_loss_kind: str = "l1"
+    feature_loss_from_iter: int = 0
 
     def depth_weight_at(self, step: int) -> float:
         """The depth term's weight at step `step` (from 1): w0 * (w1 / w0) ** ((step - 1) / total_train_iters)."""
@@ -1764,6 +1810,9 @@ class SceneBatch:
     depth: Optional[torch.Tensor] = None
     depth_scale: float = 1.0
     depth_offset: float = 0.0
+    # feature supervision (TrainConfig.feature_loss_weight, SplatTrainer(feature_field=)): the view's target, f32 [H,W,C] for
+    # feature_loss_kind "l1" or uint8 labels [H,W] (255 = ignore) for "cross_entropy".  None: no feature term this step
+    features: Optional[torch.Tensor] = None
 
     def img_size(self):
         return tuple(self.img_packed.shape)  # (h, w)
@@ -2049,7 +2098,7 @@ class SplatTrainer:
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
                  allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None,
                  exposure: Optional["ExposureTable"] = None, exposure_lr=None, bilagrid: Optional["BilateralGridTable"] = None, bilagrid_lr=None,
-                 bilagrid_tv_weight: float = 10.0):
+                 bilagrid_tv_weight: float = 10.0, feature_field: Optional["FeatureField"] = None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -2077,13 +2126,24 @@ class SplatTrainer:
         the frame or with brightness: every step slices its frame with the grid of the batch's view_id before the loss, adds
         bilagrid_tv_weight times the grid's total variation to the loss (10 is gsplat's weight) and updates that grid on the
         device.  bilagrid_lr: an optional callable of the step number (from 1), as exposure_lr.  Not with partition "tiles" and
-        not together with `exposure`."""
+        not together with `exposure`.
+
+        feature_field: a FeatureField (bh_train_set_features) trained beside the splats: a step whose batch carries a feature target
+        (SceneBatch.features), at config.feature_loss_weight > 0 and from config.feature_loss_from_iter on, blends the field's
+        map, adds the fused feature loss, backpropagates it into the field AND the splats and updates the field on the device
+        (no readback); `refine` carries the field's rows through the plan.  Not with partition "tiles" and not together with
+        `pose_optimizer`."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if pose_optimizer is not None and partition == "tiles":
             raise ValueError("pose_optimizer is not available with partition 'tiles'")
         if exposure is not None and partition == "tiles":
             raise ValueError("exposure is not available with partition 'tiles'")
+        if feature_field is not None and partition == "tiles":
+            raise ValueError("feature_field is not available with partition 'tiles'")
+        if feature_field is not None and pose_optimizer is not None:
+            raise ValueError("feature_field and pose_optimizer cannot be combined (the pose pass does not carry the feature term's gradient)")
+        self.feature_field = feature_field
         self.pose_optimizer = pose_optimizer
         self._pose_buf = None
         self.exposure, self.exposure_lr = exposure, exposure_lr
@@ -2307,6 +2367,33 @@ class SplatTrainer:
             if self._hook is None:
                 self._hook = self._make_hook(dev)
             hook, scale = self._hook, (1.0 if tiles else 1.0 / self._world)
+        # what this step cannot do is said before anything is attached to the ctx (the terms below are detached behind the call only)
+        lw = float(getattr(c, "lpips_loss_weight", 0.0))
+        if lw > 0.0 and self.lpips is None:
+            raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
+        # the feature target of this batch (TrainConfig.feature_loss_weight, from feature_loss_from_iter on): checked and converted here
+        ff, ft, ftgt = self.feature_field, None, None
+        ftarget = getattr(batch, "features", None)
+        fw = float(getattr(c, "feature_loss_weight", 0.0)) if ftarget is not None else 0.0
+        if ff is None:
+            if fw > 0.0:
+                raise ValueError("feature_loss_weight > 0 and a batch with a feature target need SplatTrainer(..., feature_field=FeatureField(...))")
+        elif fw > 0.0 and self.step_count + 1 >= int(getattr(c, "feature_loss_from_iter", 0)):
+            fk = getattr(c, "feature_loss_kind", "l1")
+            fk = int(FEATURE_LOSS_KINDS[fk]) if isinstance(fk, str) else int(fk)
+            ch = int(ff.features.shape[1])
+            if fk == _ffi.FEATURE_LOSS_CROSS_ENTROPY:
+                ftgt = torch.as_tensor(ftarget, dtype=torch.uint8, device=dev).contiguous()
+                if ftgt.dim() != 2:
+                    raise ValueError("SceneBatch.features: cross-entropy labels must be uint8 [H, W]")
+            else:
+                ftgt = _f32c(ftarget, dev)
+                if ftgt.dim() != 3 or int(ftgt.shape[2]) != ch:
+                    raise ValueError("SceneBatch.features: an l1 target must be float32 [H, W, %d]" % ch)
+            if ftgt is not ftarget and not ctx.uses_torch_stream:
+                torch.cuda.current_stream(dev).synchronize()   # the conversion ran on torch's stream, the step runs on the ctx's own
+            ft = _ffi.BhFeatureTarget()
+            ft.target, ft.h, ft.w, ft.channels, ft.kind, ft.weight = ftgt.data_ptr(), int(ftgt.shape[0]), int(ftgt.shape[1]), ch, fk, fw
         # the depth term is ctx state (bh_train_set_depth): attached for a batch that has a depth map — at this step's weight, and a
         # weight of 0 is no term — and detached for one that has none; detached again behind the step, like the pose buffer
         dgt = None
@@ -2330,11 +2417,16 @@ class SplatTrainer:
             ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, C.byref(xt)))
         else:
             ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, None))
+        # ... and the feature term (bh_train_set_features): the field and this batch's target (checked above) are attached before every
+        # step — the target changes per batch — and detached for a batch without one or while the weight is off.  (A trainer
+        # without a field makes none of these calls: every trainer detaches behind its own step, so there is nothing of another's
+        # to clear.)
+        if ft is not None:
+            ctx.check(ctx.lib.bh_train_set_features(ctx._h, C.byref(ff.as_struct()), C.byref(ft)))
+        elif ff is not None:
+            ctx.check(ctx.lib.bh_train_set_features(ctx._h, None, None))
         if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
             self.batch_patch(b)
-        lw = float(getattr(c, "lpips_loss_weight", 0.0))
-        if lw > 0.0 and self.lpips is None:
-            raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
         # the term is ctx state (bh_train_set_lpips): set it for THIS trainer's step, whatever another trainer on the ctx left
         ctx.check(ctx.lib.bh_train_set_lpips(ctx._h, self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0))
         if po is not None:
@@ -2356,6 +2448,8 @@ class SplatTrainer:
             ctx.lib.bh_train_set_depth(ctx._h, None)
             ctx.lib.bh_train_set_normal(ctx._h, None)
             ctx.lib.bh_train_set_distortion(ctx._h, None)
+            if ff is not None:
+                ctx.lib.bh_train_set_features(ctx._h, None, None)
             if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
                 ctx.lib.bh_train_set_pose_grad(ctx._h, None)
             if ex is not None:
@@ -2364,9 +2458,11 @@ class SplatTrainer:
                 ctx.lib.bh_train_set_bilagrid(ctx._h, None, 0.0)
         if po is not None:
             po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
+        if ft is not None:   # the step succeeded with the term: the library applied one Adam update to the field
+            ff.t += 1
         self.step_count = st.step_count
         self._last_stats = stats
-        self._keep = (gt, ns, dgt)
+        self._keep = (gt, ns, dgt, ftgt)
         if tiles and self.rebalance_every > 0:
             if self.step_count % self.rebalance_every == 0:
                 self._measure_row_weights(ctx, (h + 15) // 16, (w + 15) // 16, dev)
@@ -2459,6 +2555,9 @@ class SplatTrainer:
             cfg.bounds_center[k], cfg.bounds_extent[k] = self.bounds[0][k], self.bounds[1][k]
         cfg.seed = int(seed) if seed is not None else (0x5EED0000 + int(iter))
         st_in = self._train_state(splats, self.state)
+        ff = self.feature_field
+        if ff is not None and int(ff.features.shape[0]) != st_in.n:
+            raise BrushHipError("refine: the feature field has %d rows, the splats %d" % (int(ff.features.shape[0]), st_in.n))
         rs = _ffi.BhRefineStats()
         ctx.check(ctx.lib.bh_refine_plan(ctx._h, C.byref(cfg), C.byref(st_in), C.byref(rs)))
         n2 = rs.total_splats
@@ -2470,6 +2569,8 @@ class SplatTrainer:
         st_out = self._train_state(new, ns)
         self.last_refine_plan = {k: _view(ctx.lib.bh_refine_plan_flags(ctx._h, i), (st_in.n,), torch.int32, dev).clone()
                                  for i, k in enumerate(("keep", "new_row", "split", "child_slot"))}
+        if ff is not None:   # between plan and apply: the field's rows follow the plan (bh_refine_carry_rows)
+            ff.carry(ctx, total_splats=n2)
         ctx.check(ctx.lib.bh_refine_apply(ctx._h, C.byref(cfg), C.byref(st_in), C.byref(st_out)))
         self.state = ns
         self.set_bounds(*splat_bounds(new, ctx=ctx))  # train.rs:634

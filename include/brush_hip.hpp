@@ -41,6 +41,9 @@
 //   RenderNode::features / backward_features, brush_hip::feature_loss_value_and_grad   not in the reference: feature maps (caller-owned
 //                                                   per-splat vectors of 1 .. 256 channels, gsplat's colors [N, D]), their gradient
 //                                                   and the fused L1 / cross-entropy losses (brush_hip_features.h)
+//   brush_hip::FeatureField / train_set_features / refine_carry_rows, SplatTrainer::refine(.., FeatureField*)   not in the reference:
+//                                                   feature fields trained jointly with the splats (the step's feature term, Adam on
+//                                                   the device, rows carried through refine; brush_hip_feature_train.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -77,6 +80,7 @@
 #include "brush_hip_bilagrid.h"
 #include "brush_hip_mesh.h"
 #include "brush_hip_features.h"
+#include "brush_hip_feature_train.h"
 
 namespace brush_hip {
 
@@ -895,6 +899,55 @@ class SceneLoader {
     uint32_t last_index_ = 0;
 };
 
+// ---- feature fields trained with the splats (brush_hip_feature_train.h; not in the reference) ---------------------------------------
+// Carries a per-splat table [N,channels] through the ctx's pending refine plan (between bh_refine_plan and bh_refine_apply): `out` has
+// the plan's total_splats rows.  BH_CARRY_COPY: rows follow their splats, a split parent's row goes to both halves;
+// BH_CARRY_ZERO_SPLIT: both halves of a split are +0
+inline void refine_carry_rows(const Context& ctx, const float* in, float* out, uint32_t channels, uint32_t mode = BH_CARRY_COPY) {
+    static_assert(BH_CARRY_COPY == 0u && BH_CARRY_ZERO_SPLIT == 1u && BH_CARRY_MAX_CHANNELS == 4096u, "carry modes");
+    ctx.check(bh_refine_carry_rows(ctx.get(), in, out, channels, mode));
+}
+
+// Per-splat feature vectors [n,channels] with their Adam moments, zero-initialised: what bh_train_step trains beside the splats once
+// train_set_features has attached it.  `step` counts the Adam updates applied so far: the caller adds one after every successful
+// step that carried the term (the library counts in its own copy, which the next train_set_features replaces).
+struct FeatureField {
+    DeviceBuffer<float> features, m1, m2;
+    uint32_t n = 0, channels = 0, step = 0;
+    float lr = 1e-2f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f;
+
+    FeatureField() = default;
+    FeatureField(uint32_t n_, uint32_t channels_, float lr_ = 1e-2f) : n(n_), channels(channels_), lr(lr_) {
+        for (auto* b : {&features, &m1, &m2}) { b->resize((size_t)n * channels); b->zero(); }
+    }
+    BhFeatureField as_struct() {
+        BhFeatureField f{};
+        f.features = features.data(); f.m1 = m1.data(); f.m2 = m2.data();
+        f.n = n; f.channels = channels; f.step = step;
+        f.lr = lr; f.beta1 = beta1; f.beta2 = beta2; f.eps = eps;
+        return f;
+    }
+    // between bh_refine_plan and bh_refine_apply: the features follow the plan, the moments of both halves of a split start at zero
+    void carry(const Context& ctx, uint32_t total_splats) {
+        DeviceBuffer<float> f2((size_t)total_splats * channels), a2((size_t)total_splats * channels), b2((size_t)total_splats * channels);
+        refine_carry_rows(ctx, features.data(), f2.data(), channels, BH_CARRY_COPY);
+        refine_carry_rows(ctx, m1.data(), a2.data(), channels, BH_CARRY_ZERO_SPLIT);
+        refine_carry_rows(ctx, m2.data(), b2.data(), channels, BH_CARRY_ZERO_SPLIT);
+        ctx.sync();   // the old tables are freed below
+        features = std::move(f2); m1 = std::move(a2); m2 = std::move(b2);
+        n = total_splats;
+    }
+};
+
+// bh_train_step on this ctx trains `field` against `target` (both copied; nullptr field detaches; a nullptr target or a weight <= 0
+// is no term).  Call it before every step — the target changes per batch — and add one to field->step after a step that succeeded
+// with the term.
+inline void train_set_features(const Context& ctx, FeatureField* field, const BhFeatureTarget* target) {
+    if (!field) { ctx.check(bh_train_set_features(ctx.get(), nullptr, nullptr)); return; }
+    const BhFeatureField f = field->as_struct();
+    ctx.check(bh_train_set_features(ctx.get(), &f, target));
+}
+
 class SplatTrainer {
   public:
     SplatTrainer(const Context& ctx, TrainConfig config, float median_scene_scale = 1.0f) : ctx_(ctx), cfg_(config), median_(median_scene_scale) {}
@@ -930,8 +983,9 @@ class SplatTrainer {
         return {stats.num_visible, stats.num_intersections, stats.lr_mean, stats.loss};
     }
 
-    // SplatTrainer::refine (train.rs:431-663); `seed` replaces rand::rng().  Replaces `splats` and the optimizer state.
-    BhRefineStats refine(uint32_t iter, Splats& splats, uint64_t seed) {
+    // SplatTrainer::refine (train.rs:431-663); `seed` replaces rand::rng().  Replaces `splats` and the optimizer state; a feature
+    // field trained beside the splats is carried through the plan (brush_hip_feature_train.h).
+    BhRefineStats refine(uint32_t iter, Splats& splats, uint64_t seed, FeatureField* feature_field = nullptr) {
         if (!have_state_) throw Error(BH_ERR_STATE, "Can only refine if refine stats are initialized");  // train.rs:445
         splats.bake_min_scale(ctx_);
         if (!have_bounds_) update_bounds(splats);
@@ -947,6 +1001,7 @@ class SplatTrainer {
         for (int k = 0; k < 3; ++k) { rc.bounds_center[k] = center_[k]; rc.bounds_extent[k] = extent_[k]; }
         rc.seed = seed;
         BhTrainState in = c_state(splats);
+        if (feature_field && feature_field->n != in.n) throw Error(BH_ERR_INVALID_ARG, "refine: the feature field's rows differ from the splats'");
         BhRefineStats rs{};
         ctx_.check(bh_refine_plan(ctx_.get(), &rc, &in, &rs));
         const size_t n2 = rs.total_splats, c3 = (size_t)splats.num_coeffs() * 3;
@@ -962,6 +1017,7 @@ class SplatTrainer {
         o.transforms = out.transforms.data(); o.sh_coeffs = out.sh_coeffs.data(); o.raw_opacities = out.raw_opacities.data();
         ns.fill(o);
         o.min_scale = nullptr;
+        if (feature_field) feature_field->carry(ctx_, rs.total_splats);
         ctx_.check(bh_refine_apply(ctx_.get(), &rc, &in, &o));
         ctx_.sync();
         splats = std::move(out);

@@ -13,8 +13,10 @@
  * of a degree-0 scene over a black background IS the colour image, bit for bit, whatever the other channels hold.  Nothing is
  * clamped (features may be negative), the background contributes nothing.
  *
- * Not built: a feature term combined with a depth / normal / distortion cotangent or with the pose gradient in one backward;
- * carrying features through bh_refine_apply; a feature term inside bh_train_step; a normalised F / A mode.
+ * A feature term inside bh_train_step and the row carry through a refine are brush_hip_feature_train.h.
+ *
+ * Not built: a feature term combined with a depth / normal / distortion cotangent or with the pose gradient in one backward ENTRY
+ * POINT (the train step's own backward carries the depth, normal, distortion and feature terms together); a normalised F / A mode.
  */
 #ifndef BRUSH_HIP_FEATURES_H
 #define BRUSH_HIP_FEATURES_H
