@@ -58,6 +58,10 @@ Names and argument meaning follow the reference (paths under
                                          feature fields trained jointly with the splats: the feature term inside the step, the
                                          field's Adam update on the device, its rows carried through refine (not in the reference;
                                          Feature-3DGS, Gaussian Grouping; include/brush_hip_feature_train.h)
+    SceneTransform / Splats.transformed / .transform_ / Camera.transformed / SceneRegion / select_region / crop_splats
+                                         scene editing: a similarity transform of a scene with the rotation of its SH bands, the
+                                         same transform of a camera, a box / ellipsoid / opacity crop (not in the reference;
+                                         include/brush_hip_scene.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -75,5 +79,6 @@ from .host import (  # noqa: F401
     render_distortion, distortion_loss, BilateralGridTable,
     TsdfVolume, mesh_to_ply, fuse_views,
     render_features, feature_loss_value_and_grad, FeatureField,
+    SceneTransform, SceneRegion, select_region, crop_splats,
 )
 from ._ffi import BrushHipError  # noqa: F401

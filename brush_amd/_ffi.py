@@ -398,6 +398,31 @@ FEATURE_TRAIN_SYMBOLS = {
     "bh_refine_carry_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
 }
 
+# every symbol include/brush_hip_scene.h declares (scene editing: a similarity transform of the splats with their SH rotation, the same
+# transform of a camera, a region select)
+REGION_BOX, REGION_ELLIPSOID = 0, 1   # BH_REGION_*
+
+
+class BhSceneTransform(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("rot", C.c_float * 9), ("quat", C.c_float * 4),
+                ("trans", C.c_float * 3), ("scale", C.c_float), ("log_scale", C.c_float), ("sh_rot", C.c_float * 164),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class BhSceneRegion(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("invert", C.c_uint32), ("center", C.c_float * 3), ("half_extent", C.c_float * 3),
+                ("rot", C.c_float * 9), ("min_raw_opacity", C.c_float), ("reserved", C.c_uint32)]
+
+
+SCENE_SYMBOLS = {
+    "bh_scene_transform_make": (C.c_int, [dp, dp, C.c_double, C.POINTER(BhSceneTransform)]),
+    "bh_scene_transform_compose": (C.c_int, [C.POINTER(BhSceneTransform), C.POINTER(BhSceneTransform), C.POINTER(BhSceneTransform)]),
+    "bh_scene_transform_invert": (C.c_int, [C.POINTER(BhSceneTransform), C.POINTER(BhSceneTransform)]),
+    "bh_camera_apply_scene_transform": (C.c_int, [C.POINTER(BhCamera), C.POINTER(BhSceneTransform), C.POINTER(BhCamera)]),
+    "bh_splats_transform": (C.c_int, [C.c_void_p, C.POINTER(BhSceneTransform), C.c_uint32, C.c_uint32] + [C.c_void_p] * 6),
+    "bh_splats_select_region": (C.c_int, [C.c_void_p, C.POINTER(BhSceneRegion), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, u32p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -437,7 +462,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS))
     return _lib
 
 
@@ -446,6 +471,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

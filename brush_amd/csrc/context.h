@@ -99,6 +99,7 @@ enum Slot : int {
     SLOT_FEATURES,           // bh_render_features / launch_feature_backward: compact features [Nv,C] | V [Nv,C] | the frame's accumulated feature map [H,W,C] (features.hip)
     SLOT_FEATURE_TERM,       // bh_train_step with a feature term: the feature map [H,W,C] | v_map [H,W,C] | the term's loss pair (4 floats)
     SLOT_FEATURE_GRAD,       // ... and its dense v_features [N,C], from the backward to the field's update
+    SLOT_SCENE,              // bh_splats_select_region with a count: one u32 per block of the select | the total (scene_edit.hip)
     SLOT_COUNT
 };
 

@@ -285,8 +285,20 @@ class Camera:
         """The camera moved by the twist (omega, tau): W <- exp([omega]x) W, t <- exp([omega]x) t + tau on its world-to-camera
         pose, by bh_camera_apply_twist on its uniforms (include/brush_hip_pose.h); position and rotation are read back from the
         moved view matrix.  Returns a new Camera."""
+        return self._with_pose_of(_uniforms_apply_twist(self.uniforms((16, 16)), twist))   # (vm and cam_pos do not depend on the image size)
+
+    def transformed(self, T: "SceneTransform") -> "Camera":
+        """The camera that sees a scene moved by T (Splats.transformed) as this one saw the original: position s R p + t, orientation
+        R times its own, by bh_camera_apply_scene_transform on its uniforms (include/brush_hip_scene.h).  Returns a new Camera."""
+        cam = self.uniforms((16, 16))
+        out = _ffi.BhCamera()
+        if _ffi.load().bh_camera_apply_scene_transform(C.byref(cam), C.byref(T.as_struct()), C.byref(out)) != 0:
+            raise BrushHipError("bh_camera_apply_scene_transform failed")
+        return self._with_pose_of(out)
+
+    def _with_pose_of(self, cam: "_ffi.BhCamera") -> "Camera":
+        """This camera with the position and rotation read back from the view matrix of `cam`."""
         import dataclasses
-        cam = _uniforms_apply_twist(self.uniforms((16, 16)), twist)   # (vm and cam_pos do not depend on the image size)
         r = [[float(cam.vm[3 * i + j]) for j in range(3)] for i in range(3)]   # camera-to-world = W^T: r[i][j] = W[j][i] = vm[3 i + j]
         q = [1 + r[0][0] - r[1][1] - r[2][2], 1 - r[0][0] + r[1][1] - r[2][2], 1 - r[0][0] - r[1][1] + r[2][2], 1 + r[0][0] + r[1][1] + r[2][2]]
         k = q.index(max(q))   # the best-conditioned of the four quaternion extractions
@@ -356,6 +368,27 @@ class Splats:
     def clone(self):
         return Splats(self.transforms.clone(), self.sh_coeffs.clone(), self.raw_opacities.clone(), self.render_mip, self.device,
                       None if self.min_scale is None else self.min_scale.clone())
+
+    # ---- scene editing (include/brush_hip_scene.h) ----
+    def _transform(self, T, ctx, ot, osh, oms):
+        ctx = ctx or get_context(self.device)
+        ms = self.min_scale
+        ctx.check(ctx.lib.bh_splats_transform(ctx._h, C.byref(T.as_struct()), self.num_splats(), self.sh_coeffs.shape[1], _ptr(self.transforms),
+                                              _ptr(self.sh_coeffs), _ptr(ms) if ms is not None else None, _ptr(ot), _ptr(osh),
+                                              _ptr(oms) if oms is not None else None))
+
+    def transformed(self, T: "SceneTransform", ctx=None) -> "Splats":
+        """New Splats moved by x' = s R x + t (bh_splats_transform): means, rotations, log-scales, the SH bands of degree >= 1 and
+        min_scale; opacities do not change (a copy).  Render them from Camera.transformed(T) for the image of the original."""
+        ot, osh = torch.empty_like(self.transforms), torch.empty_like(self.sh_coeffs)
+        oms = None if self.min_scale is None else torch.empty_like(self.min_scale)
+        self._transform(T, ctx, ot, osh, oms)
+        return Splats(ot, osh, self.raw_opacities.clone(), self.render_mip, self.device, oms)
+
+    def transform_(self, T: "SceneTransform", ctx=None) -> "Splats":
+        """transformed(T) in place."""
+        self._transform(T, ctx, self.transforms, self.sh_coeffs, self.min_scale)
+        return self
 
     # ---- Mip-Splatting 3D filter (gaussian_splats.rs:188-256) ----
     def with_min_scale(self, f):
@@ -2730,6 +2763,156 @@ def decimate_to_count(splats: "Splats", scores, target_count: int, ctx: Optional
                                            _ptr(oms) if oms is not None else None, _ptr(idx)))
     out = Splats(ot, osh, oo, splats.render_mip, dev, oms)
     return (out, idx) if return_indices else out
+
+
+# ---------------------------------------------------------------------------
+# scene editing: similarity transform with SH rotation, region crop (include/brush_hip_scene.h)
+# ---------------------------------------------------------------------------
+class SceneTransform:
+    """The similarity x' = s R x + t (R a proper rotation, s > 0) as the library's record: f64 (q, t, s) and everything the kernel reads,
+    the rotation matrices of the SH bands 1..4 included.  Every operation is one of the C functions of include/brush_hip_scene.h."""
+
+    def __init__(self, record: Optional["_ffi.BhSceneTransform"] = None):
+        if record is None:
+            record = SceneTransform.from_quat()._rec
+        self._rec = record
+
+    @staticmethod
+    def from_quat(q_wxyz=(1.0, 0.0, 0.0, 0.0), t=(0.0, 0.0, 0.0), s=1.0) -> "SceneTransform":
+        """R from the quaternion (w, x, y, z) — normalised by the library — translation t, scale s."""
+        rec = _ffi.BhSceneTransform()
+        q = (C.c_double * 4)(*[float(v) for v in q_wxyz])
+        tt = (C.c_double * 3)(*[float(v) for v in t])
+        if _ffi.load().bh_scene_transform_make(q, tt, float(s), C.byref(rec)) != 0:
+            raise BrushHipError("bh_scene_transform_make: the quaternion must be finite and not zero, the translation finite, the scale a finite number > 0")
+        return SceneTransform(rec)
+
+    @staticmethod
+    def from_matrix(m, tol=1e-6) -> "SceneTransform":
+        """From a 4x4 matrix [[s R, t], [0, 0, 0, 1]].  Refused (ValueError): a last row that differs from (0, 0, 0, 1) by more than
+        `tol`; a 3x3 block A whose determinant is not > 0 (a reflection); shear or non-uniform scale, i.e. an entry of
+        A^T A / s^2 - I above `tol` with s = det(A)^(1/3).  The default 1e-6 admits a matrix that was stored in f32."""
+        import numpy as np
+        m = np.asarray(m.detach().cpu().numpy() if torch.is_tensor(m) else m, np.float64)
+        if m.shape != (4, 4) or not np.isfinite(m).all():
+            raise ValueError("from_matrix: a finite 4x4 matrix")
+        if np.abs(m[3] - np.array([0.0, 0.0, 0.0, 1.0])).max() > tol:
+            raise ValueError("from_matrix: the last row must be (0, 0, 0, 1)")
+        a = m[:3, :3]
+        det = float(np.linalg.det(a))
+        if not det > 0.0:
+            raise ValueError("from_matrix: the determinant must be > 0 (no reflections)")
+        s = det ** (1.0 / 3.0)
+        r = a / s
+        if np.abs(r.T @ r - np.eye(3)).max() > tol:
+            raise ValueError("from_matrix: shear or non-uniform scale (A^T A / s^2 differs from I by more than %g)" % tol)
+        q = [1 + r[0, 0] + r[1, 1] + r[2, 2], 1 + r[0, 0] - r[1, 1] - r[2, 2], 1 - r[0, 0] + r[1, 1] - r[2, 2], 1 - r[0, 0] - r[1, 1] + r[2, 2]]
+        k = q.index(max(q))   # the best-conditioned of the four quaternion extractions, (w, x, y, z)
+        if k == 0:
+            quat = (q[0], r[2, 1] - r[1, 2], r[0, 2] - r[2, 0], r[1, 0] - r[0, 1])
+        elif k == 1:
+            quat = (r[2, 1] - r[1, 2], q[1], r[1, 0] + r[0, 1], r[0, 2] + r[2, 0])
+        elif k == 2:
+            quat = (r[0, 2] - r[2, 0], r[1, 0] + r[0, 1], q[2], r[2, 1] + r[1, 2])
+        else:
+            quat = (r[1, 0] - r[0, 1], r[0, 2] + r[2, 0], r[2, 1] + r[1, 2], q[3])
+        return SceneTransform.from_quat(quat, m[:3, 3], s)
+
+    def as_struct(self) -> "_ffi.BhSceneTransform":
+        return self._rec
+
+    @property
+    def quat(self):
+        return tuple(self._rec.q)
+
+    @property
+    def translation(self):
+        return tuple(self._rec.t)
+
+    @property
+    def scale(self):
+        return float(self._rec.s)
+
+    def inverse(self) -> "SceneTransform":
+        rec = _ffi.BhSceneTransform()
+        if _ffi.load().bh_scene_transform_invert(C.byref(self._rec), C.byref(rec)) != 0:
+            raise BrushHipError("bh_scene_transform_invert failed")
+        return SceneTransform(rec)
+
+    def __matmul__(self, other: "SceneTransform") -> "SceneTransform":
+        """self @ other applies `other` first."""
+        rec = _ffi.BhSceneTransform()
+        if _ffi.load().bh_scene_transform_compose(C.byref(self._rec), C.byref(other._rec), C.byref(rec)) != 0:
+            raise BrushHipError("bh_scene_transform_compose failed: the product is no transform (scale out of range?)")
+        return SceneTransform(rec)
+
+    def matrix(self):
+        """[[s R, t], [0, 0, 0, 1]] as a 4x4 float64 numpy array, from the record's f64 fields."""
+        import numpy as np
+        w, x, y, z = self._rec.q
+        r = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], np.float64)
+        m = np.eye(4)
+        m[:3, :3] = self._rec.s * r
+        m[:3, 3] = list(self._rec.t)
+        return m
+
+    def sh_rotation(self, l: int):
+        """D_l, the (2l+1) x (2l+1) float32 matrix that turns the SH coefficients of band l (1..4) with the scene."""
+        import numpy as np
+        l = int(l)
+        if not 1 <= l <= 4:
+            raise ValueError("sh_rotation: band 1..4")
+        first = (0, 0, 9, 34, 83)[l]
+        m = 2 * l + 1
+        return np.array(self._rec.sh_rot[first:first + m * m], np.float32).reshape(m, m)
+
+
+@dataclass
+class SceneRegion:
+    """An oriented box or an ellipsoid, and an opacity floor (BhSceneRegion): `rotation` is 3x3 row-major with the region's axes in
+    world coordinates as its columns; invert keeps the outside; min_raw_opacity drops splats whose raw opacity (logit) is below it."""
+    kind: str = "box"   # "box" | "ellipsoid"
+    center: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    half_extent: Tuple[float, float, float] = (1.0, 1.0, 1.0)
+    rotation: Tuple[float, ...] = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+    invert: bool = False
+    min_raw_opacity: float = -math.inf
+
+    def as_struct(self) -> "_ffi.BhSceneRegion":
+        kinds = {"box": _ffi.REGION_BOX, "ellipsoid": _ffi.REGION_ELLIPSOID}
+        if self.kind not in kinds:
+            raise ValueError("SceneRegion.kind: 'box' or 'ellipsoid'")
+        rot = [float(v) for row in self.rotation for v in (row if hasattr(row, "__len__") else (row,))]
+        if len(rot) != 9 or len(self.center) != 3 or len(self.half_extent) != 3:
+            raise ValueError("SceneRegion: center [3], half_extent [3], rotation 3x3")
+        g = _ffi.BhSceneRegion(kind=kinds[self.kind], invert=int(bool(self.invert)), min_raw_opacity=float(self.min_raw_opacity))
+        g.center[:] = [float(v) for v in self.center]
+        g.half_extent[:] = [float(v) for v in self.half_extent]
+        g.rot[:] = rot
+        return g
+
+
+def select_region(splats: "Splats", region: SceneRegion, ctx: Optional[Context] = None, return_count=False):
+    """keep [N] f32 device: 1.0 where the splat's mean lies in the region (outside with invert) and its raw opacity is not below the
+    floor, 0.0 elsewhere (bh_splats_select_region).  return_count: also the number kept (one blocking readback)."""
+    dev = splats.device
+    ctx = ctx or get_context(dev)
+    n = splats.num_splats()
+    keep = torch.empty((n,), dtype=torch.float32, device=dev)
+    count = C.c_uint32(0)
+    ctx.check(ctx.lib.bh_splats_select_region(ctx._h, C.byref(region.as_struct()), _ptr(splats.transforms), _ptr(splats.raw_opacities), n, _ptr(keep),
+                                              C.byref(count) if return_count else None))
+    return (keep, int(count.value)) if return_count else keep
+
+
+def crop_splats(splats: "Splats", region: SceneRegion, return_indices=False, ctx: Optional[Context] = None):
+    """New Splats of the rows select_region keeps, in source order: select, count, decimate_to_count (whose ties keep ascending
+    index).  return_indices: also the kept source rows (int32 [K] device)."""
+    ctx = ctx or get_context(splats.device)
+    keep, count = select_region(splats, region, ctx=ctx, return_count=True)
+    return decimate_to_count(splats, keep, count, ctx=ctx, return_indices=return_indices)
 
 
 # ---------------------------------------------------------------------------

@@ -44,6 +44,9 @@
 //   brush_hip::FeatureField / train_set_features / refine_carry_rows, SplatTrainer::refine(.., FeatureField*)   not in the reference:
 //                                                   feature fields trained jointly with the splats (the step's feature term, Adam on
 //                                                   the device, rows carried through refine; brush_hip_feature_train.h)
+//   brush_hip::SceneTransform / transform_splats / transformed_splats / select_region / crop_splats   not in the reference: scene
+//                                                   editing (a similarity transform with the rotation of the SH bands, the same
+//                                                   transform of a camera, a box / ellipsoid / opacity crop; brush_hip_scene.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -81,6 +84,7 @@
 #include "brush_hip_mesh.h"
 #include "brush_hip_features.h"
 #include "brush_hip_feature_train.h"
+#include "brush_hip_scene.h"
 
 namespace brush_hip {
 
@@ -1145,6 +1149,78 @@ inline Splats decimate_to_count(const Context& ctx, const Splats& splats, const 
     ctx.sync();
     if (keep_idx) *keep_idx = idx.download();
     return out;
+}
+
+// ---- scene editing (include/brush_hip_scene.h; not in the reference) ---------------------------------------------
+// The similarity x' = s R x + t as the library's record.  Nothing is computed here: every operator is one C call.
+struct SceneTransform {
+    BhSceneTransform rec;
+
+    SceneTransform() : SceneTransform(std::array<double, 4>{1.0, 0.0, 0.0, 0.0}) {}
+    explicit SceneTransform(const std::array<double, 4>& quat_wxyz, const std::array<double, 3>& trans = {0.0, 0.0, 0.0}, double scale = 1.0) {
+        static_assert(sizeof(BhSceneTransform) == 800 && offsetof(BhSceneTransform, rot) == 64 && offsetof(BhSceneTransform, sh_rot) == 136, "BhSceneTransform layout");
+        if (bh_scene_transform_make(quat_wxyz.data(), trans.data(), scale, &rec) != 0)
+            throw Error(BH_ERR_INVALID_ARG, "SceneTransform: the quaternion must be finite and not zero, the translation finite, the scale a finite number > 0");
+    }
+    SceneTransform inverse() const {
+        SceneTransform out;
+        if (bh_scene_transform_invert(&rec, &out.rec) != 0) throw Error(BH_ERR_INVALID_ARG, "SceneTransform::inverse: not a transform");
+        return out;
+    }
+    // (*this) * other applies `other` first
+    SceneTransform operator*(const SceneTransform& other) const {
+        SceneTransform out;
+        if (bh_scene_transform_compose(&rec, &other.rec, &out.rec) != 0) throw Error(BH_ERR_INVALID_ARG, "SceneTransform: the product is no transform");
+        return out;
+    }
+    // D_l (band 1..4), (2l+1) x (2l+1) row-major, inside the record
+    const float* sh_rotation(uint32_t l) const {
+        if (l < 1 || l > 4) throw Error(BH_ERR_INVALID_ARG, "SceneTransform::sh_rotation: band 1..4");
+        const uint32_t first[5] = {0, 0, 9, 34, 83};
+        return rec.sh_rot + first[l];
+    }
+    // the uniforms of the camera that sees the moved scene as `cam` saw the original
+    BhCamera apply(const BhCamera& cam) const {
+        BhCamera out{};
+        if (bh_camera_apply_scene_transform(&cam, &rec, &out) != 0) throw Error(BH_ERR_INVALID_ARG, "camera_apply_scene_transform: not a transform");
+        return out;
+    }
+};
+
+// Splats moved by T in place (means, rotations, log-scales, SH bands >= 1, min_scale); queued on the ctx stream
+inline void transform_splats(const Context& ctx, Splats& s, const SceneTransform& T) {
+    float* ms = s.min_scale ? s.min_scale->data() : nullptr;
+    ctx.check(bh_splats_transform(ctx.get(), &T.rec, s.num_splats(), s.num_coeffs(), s.transforms.data(), s.sh_coeffs.data(), ms, s.transforms.data(),
+                                  s.sh_coeffs.data(), ms));
+}
+// ... and into new Splats
+inline Splats transformed_splats(const Context& ctx, const Splats& s, const SceneTransform& T) {
+    const uint32_t n = s.num_splats();
+    Splats out;
+    out.render_mip = s.render_mip;
+    out.transforms.resize(s.transforms.size());
+    out.sh_coeffs.resize(s.sh_coeffs.size());
+    out.raw_opacities.resize(n);
+    if (n) hip_check(hipMemcpy(out.raw_opacities.data(), s.raw_opacities.data(), (size_t)n * 4, hipMemcpyDeviceToDevice), "hipMemcpy D2D");
+    if (s.min_scale) out.min_scale.emplace(n);
+    ctx.check(bh_splats_transform(ctx.get(), &T.rec, n, s.num_coeffs(), s.transforms.data(), s.sh_coeffs.data(), s.min_scale ? s.min_scale->data() : nullptr,
+                                  out.transforms.data(), out.sh_coeffs.data(), out.min_scale ? out.min_scale->data() : nullptr));
+    ctx.sync();
+    return out;
+}
+
+// keep [N] = 1 / 0 per splat (bh_splats_select_region); count (optional): the number kept, which makes the call blocking
+inline DeviceBuffer<float> select_region(const Context& ctx, const Splats& s, const BhSceneRegion& region, uint32_t* count = nullptr) {
+    static_assert(sizeof(BhSceneRegion) == 76 && BH_REGION_BOX == 0u && BH_REGION_ELLIPSOID == 1u, "BhSceneRegion layout");
+    DeviceBuffer<float> keep(s.num_splats());
+    ctx.check(bh_splats_select_region(ctx.get(), &region, s.transforms.data(), s.raw_opacities.data(), s.num_splats(), keep.data(), count));
+    return keep;
+}
+// the kept rows in source order: select, count, decimate_to_count (ties keep ascending index)
+inline Splats crop_splats(const Context& ctx, const Splats& s, const BhSceneRegion& region, std::vector<uint32_t>* keep_idx = nullptr) {
+    uint32_t count = 0;
+    const DeviceBuffer<float> keep = select_region(ctx, s, region, &count);
+    return decimate_to_count(ctx, s, keep.data(), count, keep_idx);
 }
 
 // ---- held-out evaluation (brush-train/src/eval.rs:23-63; run_eval of brush-process/src/train_stream.rs:506-566) ----------------
