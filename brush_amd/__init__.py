@@ -62,6 +62,10 @@ Names and argument meaning follow the reference (paths under
                                          scene editing: a similarity transform of a scene with the rotation of its SH bands, the
                                          same transform of a camera, a box / ellipsoid / opacity crop (not in the reference;
                                          include/brush_hip_scene.h)
+    LiftAccumulator / lift_labels / compact_splats
+                                         mask lifting: per-splat blend-weight votes from 2-D label maps over any number of views, the
+                                         largest weight and the pixel count of each splat, argmax / threshold, compaction (not in
+                                         the reference; SAGA, Gaussian Grouping, FlashSplat; include/brush_hip_lift.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -80,5 +84,6 @@ from .host import (  # noqa: F401
     TsdfVolume, mesh_to_ply, fuse_views,
     render_features, feature_loss_value_and_grad, FeatureField,
     SceneTransform, SceneRegion, select_region, crop_splats,
+    LiftAccumulator, lift_labels, compact_splats,
 )
 from ._ffi import BrushHipError  # noqa: F401

@@ -75,6 +75,36 @@ BH_DEV float row_allreduce(float x) {
     x = dpp_rot_add<0x121>(x);  // row_ror:1
     return x;
 }
+// The butterfly's integer kin (lift.hip: four u32 sums per register; the same lanes end up with the same components), and the
+// wave-wide unsigned maximum: the row's by four DPP rotates, the four rows' through scalar registers.
+BH_DEV uint32_t swap32_add_u32(uint32_t a, uint32_t b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    return r[0] + r[1];
+}
+BH_DEV uint32_t swap16_add_u32(uint32_t a, uint32_t b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    return r[0] + r[1];
+}
+template <int CTRL>
+BH_DEV uint32_t dpp_rot_u32(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0u, x, CTRL, 0xF, 0xF, false);
+}
+BH_DEV uint32_t row_allreduce_u32(uint32_t x) {
+    x += dpp_rot_u32<0x128>(x);  // row_ror:8
+    x += dpp_rot_u32<0x124>(x);  // row_ror:4
+    x += dpp_rot_u32<0x122>(x);  // row_ror:2
+    x += dpp_rot_u32<0x121>(x);  // row_ror:1
+    return x;
+}
+BH_DEV uint32_t wave_max_u32(uint32_t x) {
+    x = max(x, dpp_rot_u32<0x128>(x));
+    x = max(x, dpp_rot_u32<0x124>(x));
+    x = max(x, dpp_rot_u32<0x122>(x));
+    x = max(x, dpp_rot_u32<0x121>(x));
+    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
+    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
+    return max(max(r0, r1), max(r2, r3));
+}
 // The same three row sums, FOLDED into one register while they are reduced (seven DPP adds instead of twelve): a DPP add with a
 // partial bank_mask writes only some 4-lane banks of its destination, so b's row_ror:8 sums go into banks 2-3 of a's, the
 // merged row_ror:4 step is kept where it is right (row_ror:4 feeds bank n from bank n-1: banks 1 and 3), c's row_ror:4 sums take

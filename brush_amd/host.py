@@ -2916,6 +2916,99 @@ def crop_splats(splats: "Splats", region: SceneRegion, return_indices=False, ctx
 
 
 # ---------------------------------------------------------------------------
+# mask lifting: per-splat blend-weight votes from 2-D label maps (include/brush_hip_lift.h)
+# ---------------------------------------------------------------------------
+class LiftAccumulator:
+    """The tables of a mask lifting over any number of views (include/brush_hip_lift.h): `votes` int64 [N,L] — the library's u64,
+    the same bits while below 2^63 — with votes[i, l] = the sum over views and pixels of label l of the blend weight of splat i in
+    units of 2^-24, and with stats=True `max_weight` f32 [N] (the largest weight the splat had at a pixel) and `pixel_count` int32 [N]
+    (the number of pixels it reached).  Integer sums: the same bits whatever the order of views, tiles or calls."""
+
+    def __init__(self, n, num_labels, device=None, stats=True, ctx: Optional[Context] = None):
+        n, num_labels = int(n), int(num_labels)
+        if not 1 <= num_labels <= _ffi.LIFT_MAX_LABELS:
+            raise BrushHipError("LiftAccumulator: num_labels must be 1 .. %d" % _ffi.LIFT_MAX_LABELS)
+        self.ctx = ctx or get_context(device)
+        self.device = self.ctx.device if device is None else device
+        self.n, self.num_labels = n, num_labels
+        self.votes = torch.zeros((n, num_labels), dtype=torch.int64, device=self.device)
+        self.max_weight = torch.zeros((n,), dtype=torch.float32, device=self.device) if stats else None
+        self.pixel_count = torch.zeros((n,), dtype=torch.int32, device=self.device) if stats else None
+
+    def clear(self):
+        for t in (self.votes, self.max_weight, self.pixel_count):
+            if t is not None:
+                t.zero_()
+        return self
+
+    def add(self, node: "RenderNode", labels=None):
+        """One view's votes (bh_lift_accumulate): `node` a BH_FLAG_BWD_INFO forward of the accumulator's splats, the ctx's most recent or
+        a retained one; `labels` uint8 [H,W] (a value >= num_labels, 255 by convention, votes nowhere) or None: label 0 everywhere."""
+        if node.splats.num_splats() != self.n:
+            raise BrushHipError("LiftAccumulator.add: the node renders %d splats, the tables hold %d" % (node.splats.num_splats(), self.n))
+        w, h = node.img_size
+        if labels is not None:
+            labels = torch.as_tensor(labels, device=self.device)
+            if labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
+                raise BrushHipError("LiftAccumulator.add: labels must be uint8 [%d, %d]" % (h, w))
+            labels = labels.contiguous()
+        ctx = node.ctx
+        ctx.check(ctx.lib.bh_lift_accumulate(ctx._h, C.byref(node.out), _ptr(labels) if labels is not None else None, self.num_labels,
+                                             _ptr(self.votes), _ptr(self.max_weight) if self.max_weight is not None else None,
+                                             _ptr(self.pixel_count) if self.pixel_count is not None else None))
+        return self
+
+    def weights(self):
+        """f32 [N,L] = votes / 2^24: the summed blend weights (exact in f64 below 2^53 raw units, then rounded once)."""
+        return (self.votes.to(torch.float64) * (1.0 / _ffi.LIFT_VOTE_ONE)).to(torch.float32)
+
+    def assign(self, min_weight=0.0, return_share=False):
+        """uint8 [N]: the label with the most votes per splat, ties to the lowest (bh_lift_assign); 255 where the splat's summed weight is
+        0 or below min_weight.  return_share: also f32 [N], the winning label's share of the row's total (+0 where unassigned)."""
+        out = torch.empty((self.n,), dtype=torch.uint8, device=self.device)
+        share = torch.empty((self.n,), dtype=torch.float32, device=self.device) if return_share else None
+        self.ctx.check(self.ctx.lib.bh_lift_assign(self.ctx._h, _ptr(self.votes), self.n, self.num_labels, float(min_weight), _ptr(out),
+                                                   _ptr(share) if share is not None else None))
+        return (out, share) if return_share else out
+
+    def select(self, label=None, min_share=0.5, min_weight=0.0, min_max_weight=0.0, min_pixels=0, invert=False):
+        """keep f32 [N], 1.0 / 0.0 (bh_lift_select), what compact_splats and decimate_to_count take: the splat got a vote and at least
+        min_weight in all; with a `label`, that label holds at least min_share of the splat's votes; min_max_weight / min_pixels > 0
+        test the two statistics (stats=True).  Every test asked for must pass; invert flips the result."""
+        sel = _ffi.BhLiftSelect(label=_ffi.LIFT_ANY_LABEL if label is None else int(label), min_share=float(min_share), min_weight=float(min_weight),
+                                min_max_weight=float(min_max_weight), min_pixels=int(min_pixels), invert=1 if invert else 0)
+        keep = torch.empty((self.n,), dtype=torch.float32, device=self.device)
+        self.ctx.check(self.ctx.lib.bh_lift_select(self.ctx._h, _ptr(self.votes), _ptr(self.max_weight) if self.max_weight is not None else None,
+                                                   _ptr(self.pixel_count) if self.pixel_count is not None else None, self.n, self.num_labels,
+                                                   C.byref(sel), _ptr(keep)))
+        return keep
+
+
+def lift_labels(splats: "Splats", views, num_labels, img_size, pass_: "RasterPass" = None, ctx: Optional[Context] = None, stats=True):
+    """Lifts 2-D label maps onto `splats`: `views` yields (camera, labels uint8 [H,W] or None); each view is a BH_FLAG_BWD_INFO
+    forward on black (as fuse_views renders its views) whose votes join one LiftAccumulator, which is returned."""
+    pass_ = RasterPass.Backward if pass_ is None else pass_
+    ctx = ctx or get_context(splats.device)
+    w, h = int(img_size[0]), int(img_size[1])
+    acc = LiftAccumulator(splats.num_splats(), num_labels, splats.device, stats=stats, ctx=ctx)
+    for camera, labels in views:
+        acc.add(render_splats_diff(splats, camera, (w, h), (0.0, 0.0, 0.0), pass_, ctx=ctx), labels)
+    return acc
+
+
+def compact_splats(splats: "Splats", keep, return_indices=False, ctx: Optional[Context] = None):
+    """New Splats of the rows where keep [N] (1.0 / 0.0: LiftAccumulator.select, select_region) is not 0, in source order: count
+    (one blocking readback of keep), then decimate_to_count, whose ties keep ascending index.  return_indices: also the kept source
+    rows (int32 [K] device), which serve FeatureField.gather."""
+    ctx = ctx or get_context(splats.device)
+    keep = _f32c(keep, splats.device).reshape(-1)
+    if keep.numel() != splats.num_splats():
+        raise ValueError("one keep value per splat")
+    count = int(torch.count_nonzero(keep).item())
+    return decimate_to_count(splats, keep, count, ctx=ctx, return_indices=return_indices)
+
+
+# ---------------------------------------------------------------------------
 # held-out evaluation (brush-train/src/eval.rs:23-63, run_eval of brush-process/src/train_stream.rs:506-566)
 # ---------------------------------------------------------------------------
 @dataclass

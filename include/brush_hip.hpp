@@ -47,6 +47,9 @@
 //   brush_hip::SceneTransform / transform_splats / transformed_splats / select_region / crop_splats   not in the reference: scene
 //                                                   editing (a similarity transform with the rotation of the SH bands, the same
 //                                                   transform of a camera, a box / ellipsoid / opacity crop; brush_hip_scene.h)
+//   brush_hip::LiftAccumulator / compact_splats      not in the reference: mask lifting (per-splat blend-weight votes from 2-D label
+//                                                   maps, the largest weight and the pixel count, argmax / threshold, compaction;
+//                                                   brush_hip_lift.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -85,6 +88,7 @@
 #include "brush_hip_features.h"
 #include "brush_hip_feature_train.h"
 #include "brush_hip_scene.h"
+#include "brush_hip_lift.h"
 
 namespace brush_hip {
 
@@ -1222,6 +1226,73 @@ inline Splats crop_splats(const Context& ctx, const Splats& s, const BhSceneRegi
     const DeviceBuffer<float> keep = select_region(ctx, s, region, &count);
     return decimate_to_count(ctx, s, keep.data(), count, keep_idx);
 }
+
+// ---- mask lifting (include/brush_hip_lift.h; not in the reference) -----------------------------------------------
+// The rows where keep [N] (device, 1 / 0: LiftAccumulator::select, select_region) is not 0, in source order: count (one readback of
+// keep), then decimate_to_count, whose ties keep ascending index.  keep_idx serves FeatureField::gather.
+inline Splats compact_splats(const Context& ctx, const Splats& s, const DeviceBuffer<float>& keep, std::vector<uint32_t>* keep_idx = nullptr) {
+    if (keep.size() != s.num_splats()) throw Error(BH_ERR_INVALID_ARG, "compact_splats: one keep value per splat");
+    ctx.sync();
+    const std::vector<float> host = keep.download();
+    const uint32_t count = (uint32_t)std::count_if(host.begin(), host.end(), [](float k) { return k != 0.0f; });
+    return decimate_to_count(ctx, s, keep.data(), count, keep_idx);
+}
+
+// The tables of a mask lifting over any number of views: votes u64 [N,L] (votes[i, l] = the summed blend weight of splat i at the
+// pixels of label l, in units of 2^-24) and, with stats, max_weight f32 [N] and pixel_count u32 [N].  Nothing is computed here.
+class LiftAccumulator {
+  public:
+    LiftAccumulator(const Context& ctx, uint32_t n, uint32_t num_labels, bool stats = true) : ctx_(ctx), n_(n), num_labels_(num_labels), stats_(stats) {
+        static_assert(sizeof(BhLiftSelect) == 24 && offsetof(BhLiftSelect, min_pixels) == 16 && BH_LIFT_MAX_LABELS == 256u && BH_LIFT_ANY_LABEL == 0xFFFFFFFFu,
+                      "BhLiftSelect layout");
+        if (num_labels == 0 || num_labels > BH_LIFT_MAX_LABELS) throw Error(BH_ERR_INVALID_ARG, "LiftAccumulator: num_labels must be 1 .. 256");
+        votes.resize((size_t)n * num_labels);
+        if (stats) {
+            max_weight.resize(n);
+            pixel_count.resize(n);
+        }
+        clear();
+    }
+    void clear() {
+        votes.zero();
+        max_weight.zero();
+        pixel_count.zero();
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // the fills are ordered before the ctx stream's kernels
+    }
+    // one view's votes (bh_lift_accumulate): labels uint8 [H,W] on the device, or nullptr: label 0 everywhere
+    void add(const RenderNode& node, const uint8_t* labels) {
+        if (node.aux.num_splats != n_) throw Error(BH_ERR_INVALID_ARG, "LiftAccumulator::add: the node renders another number of splats");
+        ctx_.check(bh_lift_accumulate(ctx_.get(), &node.aux.raw, labels, num_labels_, votes.data(), stats_ ? max_weight.data() : nullptr,
+                                      stats_ ? pixel_count.data() : nullptr));
+    }
+    // the label with the most votes per splat, ties to the lowest; BH_LIFT_UNASSIGNED below min_weight (bh_lift_assign)
+    DeviceBuffer<uint8_t> assign(float min_weight = 0.0f, DeviceBuffer<float>* share = nullptr) const {
+        DeviceBuffer<uint8_t> out(n_);
+        if (share) share->resize(n_);
+        ctx_.check(bh_lift_assign(ctx_.get(), votes.data(), n_, num_labels_, min_weight, out.data(), share ? share->data() : nullptr));
+        ctx_.sync();
+        return out;
+    }
+    // keep [N] = 1 / 0 (bh_lift_select), what compact_splats takes
+    DeviceBuffer<float> select(const BhLiftSelect& sel) const {
+        DeviceBuffer<float> keep(n_);
+        ctx_.check(bh_lift_select(ctx_.get(), votes.data(), stats_ ? max_weight.data() : nullptr, stats_ ? pixel_count.data() : nullptr, n_, num_labels_, &sel,
+                                  keep.data()));
+        ctx_.sync();
+        return keep;
+    }
+    uint32_t num_splats() const { return n_; }
+    uint32_t num_labels() const { return num_labels_; }
+
+    DeviceBuffer<uint64_t> votes;
+    DeviceBuffer<float> max_weight;
+    DeviceBuffer<uint32_t> pixel_count;
+
+  private:
+    const Context& ctx_;
+    uint32_t n_, num_labels_;
+    bool stats_;
+};
 
 // ---- held-out evaluation (brush-train/src/eval.rs:23-63; run_eval of brush-process/src/train_stream.rs:506-566) ----------------
 // eval_stats' metrics of a rendered [h,w,4] f32 image against gt_packed ([h,w] rgba8 device): metrics (device float[3]) = mse, psnr,
