@@ -1,7 +1,7 @@
 // api.hip — the extern "C" surface of libbrush_hip.so (include/brush_hip.h):
 // context / arena / error plumbing and the host-side orchestration of the
-// forward pipeline (render.rs:37-314), the backward (bwd/render_bwd.rs:21-171)
-// and SplatTrainer::step (brush-train/src/train.rs:176-429).
+// forward pipeline (render.rs:37-314) and the backward (bwd/render_bwd.rs:21-171).
+// (SplatTrainer::step, brush-train/src/train.rs:176-429, is train.hip.)
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -14,13 +14,6 @@
 #include "view_table.h"
 
 namespace bh {
-
-int launch_image_loss_fused(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt, uint32_t h, uint32_t w, const BhLossConfig& cfg,
-                            bool alpha_match, float dl_rgb, float dl_alpha, float* loss_out, float* v_output, float* loss_host = nullptr,
-                            uint32_t* started_host = nullptr, uint32_t started_tag = 0);
-int launch_image_loss_fused_window(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt, uint32_t h, uint32_t w, const BhLossConfig& cfg,
-                                   bool alpha_match, float dl_rgb, float dl_alpha, uint32_t tile_y0, uint32_t tile_y1, float* loss_out,
-                                   float* v_output, float* loss_host = nullptr, uint32_t* started_host = nullptr, uint32_t started_tag = 0);
 
 // grid-stride clear of two float4 spans in one launch
 __global__ __launch_bounds__(256) void zero_two_kernel(float4* __restrict__ a, size_t na, float4* __restrict__ b, size_t nb) {
@@ -605,7 +598,7 @@ int bh_camera_setup(const float* pos, const float* rot_xyzw, double fov_x, doubl
 }  // extern "C"
 
 // bh_render_forward and the train step: the request's checks, a deferred far-slice decision collected, then the pipeline
-static int render_forward(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
+int bh::render_forward(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     const BhCamera& cam = req.cam;
     if (cam.img_w == 0 || cam.img_h == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "Can't render images with 0 size.");  // render.rs:50-53
     if (req.sh_degree > 4) return set_error(ctx, BH_ERR_INVALID_ARG, "sh_degree must be 0..4");
@@ -1003,13 +996,13 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
         if (by_cut) j.req = req;   // what a second attempt with complete lists needs (finish_far_slice)
         if (ctx->knob_readback_copy)
             BH_HIP(ctx, hipMemcpyAsync(ctx->host_counters + HOST_GATE_WORD, f.slice_info + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-        // (per-tile cuts: the forecast is expected to hold — the host decides every time, bh_train_step hides the wait behind its
+        // (per-tile cuts: the forecast is expected to hold — the host decides every time, the train step (train.hip) hides the wait behind its
         //  loss kernels)
         if (ctx->far_direct && !by_cut) {
             BH_TRY(enqueue_far_slice(ctx, j));
             ctx->gate_learn = true;
         } else {
-            // bh_train_step (req.defer_decision) queues its loss kernels next and lets the first of them signal "the blend is done" through a
+            // the train step (req.defer_decision) queues its loss kernels next and lets the first of them signal "the blend is done" through a
             // tag word: no event behind the blend (finish_far_slice records one late if nobody queued the signal)
             if (++ctx->gate_tag == 0u) ctx->gate_tag = 1u;
             j.gate_tag = ctx->gate_tag;
@@ -1476,511 +1469,4 @@ extern "C" int bh_debug_split_counts(bh_ctx* ctx, uint32_t* out) {
     BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 1;
 }
-extern "C" int bh_debug_fill_train_scratch(bh_ctx* ctx, uint32_t pattern) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    const Buffer& s = ctx->slots[SLOT_GRADS];
-    if (!s.ptr || s.cap < 4) return set_error(ctx, BH_ERR_STATE, "debug_fill_train_scratch: no train step on this context yet");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s.ptr), (int)pattern, s.cap / 4, ctx->stream));
-    return 0;
-}
 #endif
-
-// ---- training step -------------------------------------------------------------
-static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* st, const BhTrainBatch* batch,
-                           bh_grad_hook hook, void* hook_user, float grad_scale, BhTrainStats* stats);
-
-extern "C" int bh_train_step(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* st, const BhTrainBatch* batch,
-                             bh_grad_hook hook, void* hook_user, float grad_scale, BhTrainStats* stats) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    const int rc = train_step_impl(ctx, cfg, st, batch, hook, hook_user, grad_scale, stats);
-    if (rc != 0) {   // (the frame is incomplete: nothing may be replayed or backpropagated from it)
-        drop_far_job(ctx);
-        ctx->have_forward = false;
-        ctx->clears.begin_forward();
-    }
-    return rc;
-}
-
-// the two families of refusals a term of the step can meet, by the term's noun
-static int refuse_partial_frame(bh_ctx* ctx, const char* term) {
-    return set_error(ctx, BH_ERR_INVALID_ARG, std::string("train_step: the ") + term + " needs the whole frame on this rank (no tile-row partition)");
-}
-static int refuse_with_pose_grad(bh_ctx* ctx, const char* a_term, const char* the_term) {
-    return set_error(ctx, BH_ERR_INVALID_ARG, std::string("train_step: ") + a_term + " and a pose-gradient buffer cannot be attached together (the pose pass does not carry the " +
-                                                  the_term + "'s gradient)");
-}
-
-static int train_step_impl(bh_ctx* ctx, const BhTrainConfig* cfg, BhTrainState* st, const BhTrainBatch* batch,
-                           bh_grad_hook hook, void* hook_user, float grad_scale, BhTrainStats* stats) {
-    if (!cfg || !st || !batch || !stats) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null argument");
-    if (!st->transforms || !st->sh_coeffs || !st->raw_opacities || !st->m1_transforms || !st->m2_transforms || !st->m1_sh ||
-        !st->m2_sh || !st->m1_opac || !st->m2_opac || !st->refine_weight_norm || !st->vis_weight || !st->max_screen_size ||
-        !batch->gt_packed)
-        return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null state tensor");
-    // the camera's tile-row window, and whether this rank has the whole frame to itself: every term below but the image loss needs that
-    const ViewUniforms win_u = make_uniforms(batch->camera);
-    const bool whole_frame = !batch->image_hook && win_u.tile_y0 == 0u && win_u.tile_y1 == win_u.tile_bh;
-    // an exposure table (brush_hip_exposure.h): the batch's view names the row
-    bh_exposure* const exposure = ctx->exposure;
-    if (exposure) {
-        if (batch->view_id == 0u || batch->view_id > exposure->n_views)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with an exposure table the batch's view_id must be 1 .. n_views");
-        if (!whole_frame) return refuse_partial_frame(ctx, "exposure term");
-    }
-    // a bilateral-grid table (brush_hip_bilagrid.h): the exposure table's rules, and the two are alternatives
-    bh_bilagrid* const bilagrid = ctx->bilagrid;
-    if (bilagrid) {
-        if (exposure)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: an exposure table and a bilateral-grid table cannot be attached together (they are alternatives: detach one)");
-        if (batch->view_id == 0u || batch->view_id > bilagrid->n_views)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table the batch's view_id must be 1 .. n_views");
-        if (!whole_frame) return refuse_partial_frame(ctx, "bilateral-grid term");
-        if ((uint64_t)batch->camera.img_w * batch->camera.img_h > 0x7FFFFFFFull)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table h * w must stay below 2^31");
-    }
-    // a depth target (brush_hip_depth_loss.h): refused before anything is queued; weight <= 0 is no term at all
-    const BhDepthTarget* const depth_target = (ctx->depth_attached && ctx->depth_target.weight > 0.0f) ? &ctx->depth_target : nullptr;
-    if (depth_target) {
-        if (!depth_target->gt) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth target has no depth map");
-        if (depth_target->h != batch->camera.img_h || depth_target->w != batch->camera.img_w)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the depth target's size differs from the camera's");
-        if (depth_target->kind > BH_DEPTH_LOSS_DISPARITY) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: unknown depth loss kind");
-        if (!whole_frame) return refuse_partial_frame(ctx, "depth term");
-        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a depth target", "depth term");
-    }
-    // a normal-consistency term (brush_hip_normal_loss.h): refused before anything is queued; weight <= 0 is no term at all
-    const bool normal_wanted = ctx->normal_attached && ctx->normal_term.weight > 0.0f;
-    if (normal_wanted) {
-        if (batch->camera.model != BH_CAMERA_PINHOLE)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs a pinhole camera (the normals of a depth map are defined for it alone)");
-        if (!whole_frame) return refuse_partial_frame(ctx, "normal term");
-        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a normal term", "normal term");
-    }
-    // a distortion term (brush_hip_distortion.h): refused before anything is queued; attached only with a weight > 0 and a checked kind
-    const bool distortion_wanted = ctx->distortion_attached;
-    if (distortion_wanted) {
-        if (!whole_frame) return refuse_partial_frame(ctx, "distortion term");
-        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a distortion term", "distortion term");
-    }
-    // a feature term (brush_hip_feature_train.h): refused before anything is queued; no field, no target or a weight <= 0 (or not a
-    // number) is no term at all
-    const bool feature_wanted = ctx->feature_attached && ctx->feature_target.weight > 0.0f;
-    if (feature_wanted) {
-        if (!whole_frame) return refuse_partial_frame(ctx, "feature term");
-        if (ctx->pose_grad) return refuse_with_pose_grad(ctx, "a feature term", "feature term");
-        if (ctx->feature_field.n != st->n)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the feature term's field has " + std::to_string(ctx->feature_field.n) + " rows, the state " +
-                                                          std::to_string(st->n) + " splats (a refine re-rows the splats: carry the field with bh_refine_carry_rows)");
-        if (ctx->feature_target.h != batch->camera.img_h || ctx->feature_target.w != batch->camera.img_w)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the feature term's target size differs from the camera's");
-    }
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t n = st->n, C = (st->sh_degree + 1) * (st->sh_degree + 1);
-    const uint32_t W = batch->camera.img_w, H = batch->camera.img_h;
-    // train.rs:183 — committed to `st` only once the update is queued: a step that fails half-way (OOM, hook / RCCL error)
-    // applied no update, so Adam's t and the lr_mean schedule must not have advanced for the retry
-    const uint32_t step = st->step_count + 1;
-
-    // ---- the exchange buffer: visible[N] | v_transforms[10N] | v_sh[3CN] | v_raw_opac[N] | v_refine[N], every section
-    // starting on a 16-byte boundary (padded to a multiple of 4 floats; the padding stays zero) so the update kernel
-    // can move it with 128-bit accesses whatever N is.  One buffer = one collective per step for a multi-GPU caller.
-    auto pad4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
-    const size_t o_tr = pad4(n), o_sh = o_tr + pad4((size_t)n * 10), o_op = o_sh + pad4((size_t)n * 3 * C), o_ref = o_op + pad4(n);
-    const size_t exch_count = o_ref + pad4(n);
-    auto* exch = (float*)ensure(ctx, SLOT_GRADS, (exch_count ? exch_count : 4) * 4);
-    auto* s_radius = (float*)ensure(ctx, SLOT_STATS, (size_t)(n ? n : 1) * 4);
-    if (!exch || !s_radius) return BH_ERR_OOM;
-    float* s_visible = exch;
-    float* s_refine = exch + o_ref;
-
-    // ---- Mip-Splatting 3D filter: render fold_min_scale(params) (bwd/burn_glue.rs:260-270)
-    const float* r_transforms = st->transforms;
-    const float* r_raw_opac = st->raw_opacities;
-    if (st->min_scale && n > 0) {
-        ProfScope ps(ctx, "FoldMinScale");
-        auto* ft = (float*)ensure(ctx, SLOT_FOLDED_TRANSFORMS, (size_t)n * 10 * 4);
-        auto* fo = (float*)ensure(ctx, SLOT_FOLDED_RAW_OPAC, (size_t)n * 4);
-        if (!ft || !fo) return BH_ERR_OOM;
-        BH_TRY(launch_fold_min_scale(ctx, st->transforms, st->raw_opacities, st->min_scale, n, ft, fo));
-        r_transforms = ft;
-        r_raw_opac = fo;
-    }
-
-    // ---- forward (train.rs:211-215); `visible` lands directly in the exchange buffer
-    BhRenderOut ro;
-    ForwardRequest fwd;
-    fwd.cam = batch->camera;
-    fwd.n = n; fwd.sh_degree = st->sh_degree;
-    fwd.flags = BH_FLAG_BWD_INFO | (cfg->render_mip ? BH_FLAG_MIP : 0) | (cfg->exact_lists ? 0 : BH_FLAG_SLICED_LISTS);
-    fwd.transforms = r_transforms; fwd.sh_coeffs = st->sh_coeffs; fwd.raw_opacities = r_raw_opac;
-    fwd.bg[0] = batch->background[0]; fwd.bg[1] = batch->background[1]; fwd.bg[2] = batch->background[2];
-    fwd.view_id = batch->view_id;
-    fwd.visible = s_visible;
-    fwd.visible_floats = o_tr;  // the forward clears the section incl. its padding
-    fwd.max_radius = s_radius;
-    fwd.grad_begin = exch + o_tr;       // ... and the whole gradient span (padding included): K1 does both on its way
-    fwd.grad_floats = exch_count - o_tr;
-    // ... unless nobody but this step's own update reads the gradients (one GPU, no hook): then only the refine-weight vector
-    // (N floats, the span's last section) is cleared.  K18 writes the rows of the splats that received a gradient and marks them in
-    // that vector's sign bit, the update kernel takes every unmarked row as zero — at SH degree 3 the zero-fill was most of K1's
-    // HBM traffic (236 of 330 MB per step at 1 M splats).
-    // (knob_force_exchange: a one-rank communicator still walks the whole exchange path — its kernels, readback and host logic —
-    // with the collectives themselves degenerate: the one-GPU measurement of what the path costs per step)
-    const bool exchanging = hook || (ctx->comm && (ctx->comm_world > 1 || ctx->knob_force_exchange));
-    // one frame split over the ranks by strips of tile rows: the caller's image hook moves the strips / halos, or — no hook, a
-    // communicator on the ctx, a proper tile-row window in the camera — the library exchanges the halos itself (comm.hip)
-    const bool window_partial = win_u.tile_y0 != 0u || win_u.tile_y1 != win_u.tile_bh;
-    // (a one-rank communicator has no neighbours: a window without strip_loss then runs as it does without a communicator)
-    const bool native_tiles = !batch->image_hook && window_partial && ctx->comm != nullptr && !hook && (batch->strip_loss || ctx->comm_world > 1);
-    if (native_tiles && !batch->strip_loss)
-        return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: a tile-row window without an image hook needs strip_loss = 1 (the library exchanges the strips' halos, not whole frames)");
-    const bool tile_mode = batch->image_hook != nullptr || native_tiles;
-    const bool lpips_on = ctx->lpips != nullptr && ctx->lpips_weight > 0.0f;
-    if (lpips_on && !whole_frame) return refuse_partial_frame(ctx, "LPIPS term");
-    const bool masked_grads = !exchanging && !tile_mode && !ctx->knob_zero_grads && n > 0;
-    if (masked_grads) {
-        fwd.grad_begin = exch + o_ref;
-        fwd.grad_floats = exch_count - o_ref;
-    }
-    // depth-sliced lists: whether the far slice has to run is known once the near slice's blend has; a single-GPU step does not
-    // wait for that — the loss kernels are queued behind the near slice first (below) and the host reads the answer while they run
-    // (a tile-partitioned frame hands the image to its hook right after the forward: there the forward waits itself)
-    fwd.defer_decision = !tile_mode;
-    BH_TRY(render_forward(ctx, fwd, &ro));
-
-    // ---- tile-partitioned frame: fetch the other ranks' strips (not in the reference: SURVEY.md §8e)
-    if (tile_mode) {
-        ProfScope ps(ctx, "ImageExchange");
-        const uint32_t r0 = win_u.tile_y0 * TILE_WIDTH, r1 = win_u.tile_y1 * TILE_WIDTH < H ? win_u.tile_y1 * TILE_WIDTH : H;
-        if (native_tiles) BH_TRY(comm_exchange_strip_halos(ctx, ro.out_img, H, W, r0, r1));
-        else if (batch->image_hook(batch->image_hook_user, ro.out_img, H, W, r0, r1) != 0) return set_error(ctx, BH_ERR_STATE, "image hook failed");
-    }
-
-    // ---- loss (train.rs:227-260)
-    const bool ssim_on = cfg->ssim_weight > 0.0f;
-    BhLossConfig lc{};
-    lc.l1_weight = ssim_on ? 1.0f - cfg->ssim_weight : 1.0f;
-    lc.ssim_weight = ssim_on ? -cfg->ssim_weight : 0.0f;
-    const bool bg_nonzero = batch->background[0] != 0.0f || batch->background[1] != 0.0f || batch->background[2] != 0.0f;
-    lc.composite_bg = (batch->has_alpha && bg_nonzero) ? 1 : 0;
-    lc.bg[0] = batch->background[0]; lc.bg[1] = batch->background[1]; lc.bg[2] = batch->background[2];
-    lc.mask = batch->alpha_is_mask ? 1 : 0;
-    const bool alpha_match = batch->has_alpha && !batch->alpha_is_mask && cfg->match_alpha_weight > 0.0f;
-    const size_t hw = (size_t)W * H;
-    auto* v_output = (float*)ensure(ctx, SLOT_V_OUTPUT, hw * 16);
-    auto* loss_dev = (float*)ensure(ctx, SLOT_LOSS_SCALAR, 16);
-    if (!v_output || !loss_dev) return BH_ERR_OOM;
-    // with an exposure or a bilateral-grid table the loss reads the exposed / sliced frame from a slot of its own: out_img is what
-    // K17 replays from
-    float* corrected = nullptr;
-    if ((exposure || bilagrid) && !(corrected = (float*)ensure(ctx, SLOT_CORRECTED, hw * 16))) return BH_ERR_OOM;
-    // the loss scalar goes straight into pinned host memory (bh_sync hands it to stats->loss): no copy launch
-    float* loss_host = reinterpret_cast<float*>(ctx->host_counters) + HOST_LOSS_WORD;
-    const float dl_rgb = 1.0f / (float)(hw * 3);
-    const float dl_alpha = alpha_match ? cfg->match_alpha_weight / (float)hw : 0.0f;
-    // fused forward + backward of the loss on the rasterizer's [H,W,4] image (loss_fused.hip)
-    auto queue_loss = [&]() -> int {
-        // a deferred far-slice decision without an event behind the blend: this loss kernel tells the host when it starts
-        uint32_t* started_host = nullptr;
-        uint32_t started_tag = 0u;
-        if (ctx->far_job.pending && !ctx->far_job.gate_event_recorded && !ctx->gate_signal_queued) {
-            started_host = ctx->host_counters + HOST_GATE_TAG_WORD;
-            started_tag = ctx->far_job.gate_tag;
-            ctx->gate_signal_queued = true;
-        }
-        if (tile_mode && batch->strip_loss) {
-            // one frame over several ranks: the hook delivered only the 21-px halos; loss and dL/dimg for this rank's strip
-            // (stats->loss is the strip's share of the mean: the ranks' shares add up to the frame's loss)
-            return launch_image_loss_fused_window(ctx, ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, win_u.tile_y0, win_u.tile_y1,
-                                                  loss_dev, v_output, loss_host, started_host, started_tag);
-        }
-        if (exposure) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
-            ProfScope ps(ctx, "Exposure");
-            BH_TRY(launch_exposure_apply(ctx, exposure, batch->view_id, ro.out_img, H, W, corrected));
-        }
-        if (bilagrid) {   // (likewise)
-            ProfScope ps(ctx, "Bilagrid");
-            BH_TRY(launch_bilagrid_slice(ctx, bilagrid, batch->view_id, ro.out_img, H, W, corrected));
-        }
-        return launch_image_loss_fused(ctx, corrected ? corrected : ro.out_img, batch->gt_packed, H, W, lc, alpha_match, dl_rgb, dl_alpha, loss_dev, v_output, loss_host, started_host,
-                                       started_tag);
-    };
-#ifdef BH_TEST_HOOKS
-    if (ctx->knob_fail_loss_at && ++ctx->train_steps_seen == ctx->knob_fail_loss_at)   // (the forward is queued, a deferred far slice may be pending)
-        return set_error(ctx, BH_ERR_OOM, "train_step: injected failure between the forward and the loss (BH_TEST_FAIL_LOSS_AT)");
-#endif
-    if (far_job_decides_first(ctx)) {   // (a view whose forecast keeps missing: lists.hip)
-        BH_TRY(finish_far_slice(ctx, nullptr));
-        ro = ctx->latest.out;   // (a second attempt replaces the frame's outputs)
-    }
-    BH_TRY(queue_loss());
-    if (ctx->far_job.pending) {
-        // The loss above ran on the near slice's image, which is the frame's image unless some tile was left unsaturated — the
-        // host finds out while it runs.  Then (rare: the near lists carry a margin over what the view needed last time)
-        // the far slice is queued and the loss is evaluated again on the finished image.
-        bool far_ran = false;
-        BH_TRY(finish_far_slice(ctx, &far_ran));
-        if (far_ran) {
-            ro = ctx->latest.out;
-            BH_TRY(queue_loss());
-        }
-    }
-    // ---- LPIPS (train.rs:265-273): on the frame's final image, GT composited as the loss above does it; loss and dL/dimg grow
-    // in place on the device (no host wait)
-    if (lpips_on) BH_TRY(lpips_train_term(ctx, corrected ? corrected : ro.out_img, batch->gt_packed, H, W, lc.composite_bg ? lc.bg : nullptr, v_output, loss_dev, loss_host));
-    // ---- exposure backward: v_output becomes A^T v' in place (x = the frame as rendered), the view's row takes its Adam step
-    if (exposure) {
-        ProfScope ps(ctx, "Exposure");
-        BH_TRY(launch_exposure_backward(ctx, exposure, batch->view_id, ro.out_img, v_output, H, W, v_output, /*update=*/true));
-    }
-    // ---- bilateral grid: loss += tv_weight TV(grid) in f32 (no launch at weight 0), then v_output becomes v_img in place and the
-    // view's grid takes its Adam step on v_g + tv_weight dTV
-    if (bilagrid) {
-        ProfScope ps(ctx, "Bilagrid");
-        const float tvw = ctx->bilagrid_tv_weight;
-        if (tvw != 0.0f) {
-            float* tv_value = bilagrid_tv_scratch(ctx);
-            if (!tv_value) return BH_ERR_OOM;
-            BH_TRY(launch_bilagrid_tv(ctx, bilagrid, batch->view_id, tv_value, tvw, loss_dev, loss_host));
-        }
-        BH_TRY(launch_bilagrid_backward(ctx, bilagrid, batch->view_id, ro.out_img, v_output, H, W, v_output, tvw, /*update=*/true));
-    }
-
-    // ---- depth term (brush_hip_depth_loss.h): the frame is final here — a second attempt with complete lists has replaced it, if
-    // there was one — so the expected depth is that of the state the backward replays.  E and v_depth live in a slot of their own
-    // until the backward (SLOT_DEPTH is the depth backward's scratch and may move).  loss += the term's, in f32, behind LPIPS.
-    // ---- normal term (brush_hip_normal_loss.h): on the same final frame, with the same expected-depth map (rendered once).  N and
-    // v_normal live in a slot of their own too (SLOT_NORMAL is the normal backward's scratch).  The fused operator adds its v_depth to
-    // the depth loss's, or writes it where there is none; loss += the term's, in f32, behind the depth term's.
-    BackwardCall bwd;
-    DepthTerm depth_term;
-    NormalTerm normal_term;
-    const bool frame_listed = ctx->latest.out.num_intersections > 0 && n > 0;   // (an empty frame has no valid pixel)
-    const bool depth_on = depth_target != nullptr && frame_listed;
-    const bool normal_on = normal_wanted && frame_listed;
-    if (depth_on || normal_on) {
-        ProfScope ps(ctx, "DepthTerm");
-        auto* e_map = (float*)ensure(ctx, SLOT_DEPTH_TERM, (hw * 2 + 4) * 4);
-        if (!e_map) return BH_ERR_OOM;
-        float* v_depth = e_map + hw;
-        BH_TRY(launch_depth_forward(ctx, ctx->latest, BH_DEPTH_EXPECTED, e_map));
-        if (depth_on) BH_TRY(launch_depth_loss(ctx, e_map, *depth_target, v_depth + hw, v_depth, loss_dev, loss_host));
-        depth_term.v_depth = v_depth;
-        depth_term.mode = BH_DEPTH_EXPECTED;
-        bwd.depth = &depth_term;
-        if (normal_on) {
-            ProfScope pn(ctx, "NormalTerm");
-            auto* n_map = (float*)ensure(ctx, SLOT_NORMAL_TERM, (hw * 6 + 4) * 4);
-            if (!n_map) return BH_ERR_OOM;
-            float* v_normal = n_map + hw * 3;
-            BH_TRY(launch_normal_map(ctx, ctx->latest, r_transforms, BH_NORMAL_ACCUMULATED, n_map));
-            BH_TRY(launch_normal_loss(ctx, batch->camera, n_map, e_map, ctx->latest.out.out_img, H, W, ctx->normal_term.weight, /*accumulate_v_depth=*/depth_on,
-                                      v_normal + hw * 3, v_normal, v_depth, loss_dev, loss_host));
-            normal_term.v_normal = v_normal;
-            normal_term.mode = BH_NORMAL_ACCUMULATED;
-            bwd.normal = &normal_term;
-        }
-    }
-    // ---- distortion term (brush_hip_distortion.h): on the same final frame, behind the normal term.  The moment map lives in a slot of
-    // its own until the backward, which reads it instead of rendering it again; the cotangent is the constant weight / (H W), so no
-    // [H,W] map of it exists.  loss += the term's, in f32, behind the normal term's.
-    DistortionTerm distortion_term;
-    const bool distortion_on = distortion_wanted && frame_listed && ctx->latest.out.num_listed_splats > 0;
-    if (distortion_on) {
-        ProfScope pd(ctx, "DistortionTerm");
-        auto* moments = (float*)ensure(ctx, SLOT_DISTORTION_TERM, (hw * 4 + 4) * 4);
-        if (!moments) return BH_ERR_OOM;
-        const BhDistortionTermConfig& dc = ctx->distortion_term;
-        distortion_term.kind = dc.kind;
-        distortion_term.near_z = dc.near_z;
-        distortion_term.far_z = dc.far_z;
-        distortion_term.gain = (float)((double)dc.weight / (double)hw);
-        BH_TRY(launch_distortion_map(ctx, ctx->latest, distortion_term, /*moments=*/true, moments));
-        BH_TRY(launch_distortion_loss(ctx, moments, H, W, 4u, dc.weight, moments + hw * 4, loss_dev, loss_host));
-        distortion_term.moments = moments;
-        bwd.distortion = &distortion_term;
-    }
-    // ---- feature term (brush_hip_feature_train.h): on the same final frame, behind the distortion term.  The map is blended ONCE:
-    // it and the compact rows behind it go to the backward, which then skips its own gather and forward; the map and v_map live in a
-    // slot of their own, the dense v_features in another until the field's update.  loss += the term's, in f32, behind the distortion
-    // term's.  A frame that lists nothing: the map is all +0, the loss is still evaluated, the backward leaves v_features all +0.
-    FeatureTerm feature_term;
-    float* v_features = nullptr;
-    if (feature_wanted) {
-        ProfScope pf(ctx, "FeatureTerm");
-        const BhFeatureField& ff = ctx->feature_field;
-        const size_t map_floats = hw * ff.channels;
-        auto* f_map = (float*)ensure(ctx, SLOT_FEATURE_TERM, (map_floats * 2 + 4) * 4);
-        v_features = (float*)ensure(ctx, SLOT_FEATURE_GRAD, (size_t)(n ? n : 1) * ff.channels * 4);
-        if (!f_map || !v_features) return BH_ERR_OOM;
-        float* v_map = f_map + map_floats;
-        float* rows = nullptr;
-        BH_TRY(feature_term_rows(ctx, ctx->latest, ff.channels, &rows));
-        if (frame_listed && ctx->latest.out.num_listed_splats > 0) {
-            BH_TRY(launch_feature_gather(ctx, ctx->latest, ff.features, ff.channels, rows));
-            BH_TRY(launch_feature_forward(ctx, ctx->latest, ff.channels, rows, f_map));
-        } else {
-            BH_HIP(ctx, hipMemsetAsync(f_map, 0, map_floats * 4, ctx->stream));
-        }
-        BH_TRY(launch_feature_loss(ctx, f_map, ctx->feature_target, v_map + map_floats, v_map, loss_dev, loss_host));
-        feature_term.features = ff.features;
-        feature_term.channels = ff.channels;
-        feature_term.v_map = v_map;
-        feature_term.v_features = v_features;
-        feature_term.map_acc = f_map;
-        feature_term.compact = rows;
-        bwd.feature = &feature_term;
-    }
-
-    // ---- multi-GPU exchange, part 1 (mask-keyed mode, exchange.hip): the visible flags are final once the forward (incl. a far
-    // slice, if it had to run) is, so they are summed, the union of contributing splats is listed and its size starts travelling
-    // to the host NOW — the backward hides the collective's latency and the readback, and the host finds the count ready
-    // "sum `cnt` floats at `p` over the ranks, in place": the caller's hook, or the library's communicator
-    auto sum_over_ranks = [&](float* p, uint64_t cnt) -> int {
-        if (hook) return hook(hook_user, p, cnt) == 0 ? 0 : set_error(ctx, BH_ERR_STATE, "gradient hook failed");
-        return comm_allreduce(ctx, p, cnt, false);
-    };
-    const bool keyed = exchanging && batch->exchange_mode == 1 && n > 0;
-    uint32_t* union_idx = nullptr;
-    float* compact = nullptr;
-    bool flags_on_side = false;
-    if (keyed) {
-        ProfScope ps(ctx, "FlagExchange");
-        const uint32_t nblk = (n + 4095u) / 4096u;
-        auto* blocks = (uint32_t*)ensure(ctx, SLOT_EXCH_BLOCKS, ((size_t)nblk + 2) * 4);   // [nblk] block offsets, then the total
-        union_idx = (uint32_t*)ensure(ctx, SLOT_EXCH_IDX, (size_t)n * 4);
-        if (!blocks || !union_idx) return BH_ERR_OOM;   // (the compact block is sized once the union's size is known, below)
-        // The library's communicator runs this on its own stream: the flag sum (4 B per splat over xGMI), the union listing and the
-        // count's way to the host then overlap the backward on the ctx stream instead of standing in front of it; nothing on the
-        // ctx stream touches the flag section before the update, which waits for the side stream below.  (A caller's hook decides
-        // its own streams.)
-        flags_on_side = !hook && ctx->comm_stream != nullptr;
-        hipStream_t main_stream = ctx->stream;
-        if (flags_on_side) {
-            BH_HIP(ctx, hipEventRecord(ctx->comm_ev, main_stream));
-            BH_HIP(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->comm_ev, 0));
-            ctx->stream = ctx->comm_stream;   // (single-threaded ctx: the launchers below take the stream from it)
-        }
-        int rc = sum_over_ranks(exch, (uint64_t)o_tr);
-        if (rc == 0) rc = launch_union_index(ctx, s_visible, n, blocks, blocks + nblk, union_idx);
-        if (rc == 0) rc = check_hip(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(ctx->host_counters) + 8, blocks + nblk, 4, hipMemcpyDeviceToHost, ctx->stream), "flag count readback");
-        if (rc == 0) rc = check_hip(ctx, hipEventRecord(ctx->readback_ev, ctx->stream), "flag count event");
-        ctx->stream = main_stream;
-        BH_TRY(rc);
-    }
-
-    // ---- backward (train.rs:278)
-    float* g_tr = exch + o_tr;
-    float* g_sh = exch + o_sh;
-    float* g_op = exch + o_op;
-    // masked gradients rely on last step's row marks (sign bits of the refine-weight vector) being gone: K1 of the frame's (last)
-    // forward clears the vector on its way when the span is float4-addressable (always, with the pad4 layout and hipMalloc's
-    // alignment) - not an implicit invariant: if it could not, clear it here.  Decided HERE, behind every second attempt a failed
-    // forecast may have caused: the record describes the forward the backward is about to replay.
-    if (masked_grads) {
-        if (ctx->clears.span != GradClears::ZEROED) BH_HIP(ctx, hipMemsetAsync(exch + o_ref, 0, (exch_count - o_ref) * sizeof(float), ctx->stream));
-        ctx->clears.mark_rows();   // this step's backward runs K18 in marking mode and fills nothing
-    }
-    // the refine weight's one consumer stops reading it at growth_stop_iter (train.rs:589-614): from then on the blend backward
-    // runs without it (refine_weight_norm stays as refine() zeroed it).  g_tr .. the end of the exchange buffer is one span
-    // (padding included): one zero-fill, if the forward's K1 did not clear it.
-    const bool skip_refine = cfg->growth_stop_iter != 0u && step >= cfg->growth_stop_iter;
-    bwd.transforms = r_transforms; bwd.sh_coeffs = st->sh_coeffs; bwd.raw_opacities = r_raw_opac;
-    bwd.v_transforms = g_tr; bwd.v_sh_coeffs = g_sh; bwd.v_raw_opacities = g_op; bwd.v_refine_weight = s_refine;
-    bwd.span_floats = exch_count - o_tr;
-    bwd.want_refine = !skip_refine;
-    bwd.v_viewmat = ctx->pose_grad;
-    BH_TRY(backward_impl(ctx, ctx->latest, v_output, bwd));
-    if (st->min_scale && n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
-        ProfScope ps(ctx, "FoldMinScaleBackward");
-        BH_TRY(launch_fold_min_scale_backward(ctx, st->transforms, st->raw_opacities, st->min_scale, n, g_tr, g_op));
-    }
-    // ---- multi-GPU exchange, part 2 (not in the reference: SURVEY.md §8e)
-    stats->exchange_rows = 0;
-    if (exchanging) {
-        ProfScope ps(ctx, "GradExchange");
-        if (keyed) {
-            // only the gradient rows of splats some rank saw (the count was requested right after the forward).  One frame
-            // split over the ranks: the strips' refine weights are partial sums too and travel as one more column.
-            float* g_ref = tile_mode ? s_refine : nullptr;
-            const uint32_t c3 = 3 * C, k = 11 + c3 + (tile_mode ? 1u : 0u);
-            BH_HIP(ctx, hipEventSynchronize(ctx->readback_ev));
-            if (flags_on_side) BH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->readback_ev, 0));   // the union list and the summed flags are the side stream's
-            const uint32_t rows = reinterpret_cast<uint32_t*>(ctx->host_counters)[8];
-            if (rows == 0) {
-                // no rank saw any splat: every gradient row is zero everywhere, nothing to send (same decision on all ranks)
-            } else if ((uint64_t)rows * 2 <= n) {
-                // sized by what this step sends (grow-only arena): megabytes for a view's worth of rows, not n / 2 rows up front
-                compact = (float*)ensure(ctx, SLOT_EXCH_COMPACT, (size_t)rows * k * 4);
-                if (!compact) return BH_ERR_OOM;
-                BH_TRY(launch_exchange_rows(ctx, true, union_idx, rows, c3, g_tr, g_sh, g_op, g_ref, compact));
-                BH_TRY(sum_over_ranks(compact, (uint64_t)rows * k));
-                BH_TRY(launch_exchange_rows(ctx, false, union_idx, rows, c3, g_tr, g_sh, g_op, g_ref, compact));
-                stats->exchange_rows = rows;
-            } else {
-                BH_TRY(sum_over_ranks(exch + o_tr, (uint64_t)((tile_mode ? exch_count : o_ref) - o_tr)));
-            }
-        } else if (tile_mode) {
-            BH_TRY(sum_over_ranks(exch, (uint64_t)exch_count));
-        } else {
-            BH_TRY(sum_over_ranks(exch, (uint64_t)o_ref));
-        }
-    }
-    // ... and the feature term's v_features by one more sum of the same kind: N C floats, dense (brush_hip_feature_train.h)
-    if (feature_wanted && exchanging && n > 0) {
-        ProfScope ps(ctx, "FeatureExchange");
-        BH_TRY(sum_over_ranks(v_features, (uint64_t)n * ctx->feature_field.channels));
-    }
-    // ---- refine statistics (train.rs:280-298) + optimizer (train.rs:300-381): one launch
-    const double decay = std::pow(cfg->lr_mean_end / cfg->lr_mean, 1.0 / (double)cfg->total_train_iters);
-    const double lr_mean = cfg->lr_mean * std::pow(decay, (double)((int)step - 1)) * (double)cfg->median_scene_scale;
-    // visibility-gated noise on the means (train.rs:389-416): injected samples, or drawn on the device (device_rng.h)
-    const bool noise_on = cfg->mean_noise_weight > 0.0f && n > 0 && (batch->noise_samples || batch->device_noise);
-    const float noise_scale = (float)lr_mean * cfg->mean_noise_weight;
-    // device-drawn noise without a 3D-filter floor rides on the update launch (the gate reads the opacity that launch just wrote)
-    const bool noise_fused = noise_on && !batch->noise_samples && !st->min_scale;
-    {
-        ProfScope ps(ctx, "OptimizerStep");
-        const NoiseArgs na{batch->noise_seed, step, noise_scale, cfg->median_scene_scale};
-        UpdateCall uc;
-        uc.g_transforms = g_tr; uc.g_sh = g_sh; uc.g_opac = g_op;
-        uc.refine_weight = s_refine; uc.visible = s_visible; uc.screen_radius = s_radius;
-        uc.gscale = grad_scale; uc.vis_clamp = tile_mode;
-        for (int i = 0; i < 3; ++i) uc.tab_t[i] = (float)lr_mean;
-        for (int i = 3; i < 7; ++i) uc.tab_t[i] = (float)cfg->lr_rotation;
-        for (int i = 7; i < 10; ++i) uc.tab_t[i] = (float)cfg->lr_scale;
-        // sh: DC at full lr, bands >= 1 scaled by 1/lr_coeffs_sh_scale
-        uc.lr_sh = (float)cfg->lr_coeffs_dc; uc.sh_rest_scale = 1.0f / cfg->lr_coeffs_sh_scale; uc.lr_opac = (float)cfg->lr_opac;
-        uc.t = step; uc.beta1 = 0.9f; uc.beta2 = 0.999f; uc.eps = 1e-15f;
-        uc.noise = noise_fused ? &na : nullptr; uc.masked_rows = masked_grads;
-        BH_TRY(launch_train_update(ctx, st, uc));
-        if (feature_wanted && n > 0) {   // the field's Adam step on grad_scale * v_features (launch_adam's arithmetic, full second moment); no rows, no update to count
-            BhFeatureField& ff = ctx->feature_field;
-            BH_TRY(launch_adam(ctx, ff.features, v_features, ff.m1, ff.m2, n, ff.channels, nullptr, ff.lr, ff.step + 1, false, ff.beta1, ff.beta2, ff.eps, grad_scale));
-            ff.step += 1;
-        }
-    }
-    st->step_count = step;   // the update is queued: the step counts
-    if (noise_on && !noise_fused) {
-        ProfScope ps(ctx, "MeanNoise");
-        // the gate reads splats.opacities() of the UPDATED parameters (train.rs:389), i.e. through the fold when a floor is set
-        const float* gate_opac = st->raw_opacities;
-        if (st->min_scale && n > 0) {
-            auto* ft = (float*)ctx->slots[SLOT_FOLDED_TRANSFORMS].ptr;
-            auto* fo = (float*)ctx->slots[SLOT_FOLDED_RAW_OPAC].ptr;
-            BH_TRY(launch_fold_min_scale(ctx, st->transforms, st->raw_opacities, st->min_scale, n, ft, fo));
-            gate_opac = fo;
-        }
-        BH_TRY(launch_mean_noise(ctx, st->transforms, gate_opac, s_visible, batch->noise_samples, n, noise_scale, cfg->median_scene_scale,
-                                 batch->noise_seed, step));
-    }
-    stats->num_visible = ro.num_visible;
-    stats->num_intersections = ro.num_intersections;
-    stats->lr_mean = lr_mean;
-    // the loss kernel wrote the scalar into pinned staging (a copy into the caller's pageable struct would
-    // stall the host until the whole step has run); bh_sync moves it into stats->loss
-    ctx->pending_loss_dst = &stats->loss;
-    stats->loss = 0.0f;
-    return 0;
-}

@@ -522,8 +522,8 @@ int bh_train_set_bilagrid(bh_ctx* ctx, bh_bilagrid* table, float tv_weight) {
     BH_TRY(view_table_attachable(ctx, VT_BILAGRID, table, "train_set_bilagrid"));
     if (table && (!(tv_weight >= 0.0f) || !std::isfinite(tv_weight)))
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_bilagrid: tv_weight must be finite and >= 0");
-    ctx->bilagrid = table;
-    ctx->bilagrid_tv_weight = table ? tv_weight : 0.0f;
+    ctx->terms.bilagrid = table;
+    ctx->terms.bilagrid_tv_weight = table ? tv_weight : 0.0f;
     return 0;
 }
 

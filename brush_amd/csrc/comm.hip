@@ -252,7 +252,7 @@ int bh_comm_init(bh_ctx* ctx, int rank, int world, const void* unique_id) {
     ctx->comm = comm;
     ctx->comm_rank = rank;
     ctx->comm_world = world;
-    // side stream for the flag exchange (api.hip); without it the exchange simply stays on the ctx stream
+    // side stream for the flag exchange (train.hip); without it the exchange simply stays on the ctx stream
     if (hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->comm_ev, hipEventDisableTiming) != hipSuccess) {
         (void)hipGetLastError();

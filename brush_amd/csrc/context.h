@@ -422,6 +422,32 @@ struct BackwardCall {
     float* v_viewmat = nullptr;    // [12] (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined
 };
 
+// What is attached to the train steps of a ctx: the bh_train_set_* calls write here, plan_step (train.hip) reads it.  A term counts for
+// a step when its accessor says so; everything else about it is the step's business.
+struct StepTerms {
+    const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
+    float lpips_weight = 0.0f;
+    float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
+    bool depth_attached = false;      // bh_train_set_depth: the step adds the depth term of depth_target (brush_hip_depth_loss.h); weight <= 0 = off
+    BhDepthTarget depth_target{};
+    bool normal_attached = false;     // bh_train_set_normal: the step adds the normal-consistency term (brush_hip_normal_loss.h); weight <= 0 = off
+    BhNormalTermConfig normal_term{};
+    bool distortion_attached = false; // bh_train_set_distortion: the step adds the distortion term (brush_hip_distortion.h); only ever true with a weight > 0
+    BhDistortionTermConfig distortion_term{};
+    bool feature_attached = false;    // bh_train_set_features: a field is attached (brush_hip_feature_train.h); feature_field.step counts its updates
+    BhFeatureField feature_field{};
+    BhFeatureTarget feature_target{}; // ... and the target of the next steps; weight <= 0 (or not a number, or no target): no term
+    bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
+    bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
+    float bilagrid_tv_weight = 0.0f;  // ... and adds this much of the grid's total variation to the loss
+
+    bool lpips_on() const { return lpips != nullptr && lpips_weight > 0.0f; }
+    bool depth_on() const { return depth_attached && depth_target.weight > 0.0f; }
+    bool normal_on() const { return normal_attached && normal_term.weight > 0.0f; }
+    bool distortion_on() const { return distortion_attached; }
+    bool feature_on() const { return feature_attached && feature_target.weight > 0.0f; }
+};
+
 }  // namespace bh
 
 // The blend backward accumulates RAW per-splat sums into v_combined and the projection backward maps them to the reference's
@@ -452,25 +478,11 @@ struct bh_ctx {
     void* image_tab_host = nullptr;   // bh_resize_u8: pinned staging of the weight tables (image.hip) ...
     size_t image_tab_cap = 0;
     hipEvent_t image_tab_ev = nullptr; // ... free again once this event (behind their copy) has completed
-    const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
-    float lpips_weight = 0.0f;
-    float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
-    bool depth_attached = false;      // bh_train_set_depth: the step adds the depth term of depth_target (brush_hip_depth_loss.h); weight <= 0 = off
-    BhDepthTarget depth_target{};
-    bool normal_attached = false;     // bh_train_set_normal: the step adds the normal-consistency term (brush_hip_normal_loss.h); weight <= 0 = off
-    BhNormalTermConfig normal_term{};
-    bool distortion_attached = false; // bh_train_set_distortion: the step adds the distortion term (brush_hip_distortion.h); only ever true with a weight > 0
-    BhDistortionTermConfig distortion_term{};
-    bool feature_attached = false;    // bh_train_set_features: a field is attached (brush_hip_feature_train.h); feature_field.step counts its updates
-    BhFeatureField feature_field{};
-    BhFeatureTarget feature_target{}; // ... and the target of the next steps; weight <= 0 (or not a number, or no target): no term
+    bh::StepTerms terms;              // what the bh_train_set_* calls attached to the next train steps (train.hip)
     std::vector<bh::ViewTable*> view_tables;   // every per-view table of this ctx, of either kind (view_table.h): bh_destroy frees what is left
-    bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
-    bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
-    float bilagrid_tv_weight = 0.0f;  // ... and adds this much of the grid's total variation to the loss
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
-    // beside the backward on the ctx stream (api.hip); comm_ev marks "the forward is done" for it
+    // beside the backward on the ctx stream (train.hip); comm_ev marks "the forward is done" for it
     hipStream_t comm_stream = nullptr;
     hipEvent_t comm_ev = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -573,6 +585,8 @@ int find_saved_bwd_forward(bh_ctx* ctx, const BhRenderOut* saved, int not_bwd_co
 // api.hip: the backward kernels on the saved state `fs`.  v_output may be NULL when the call has another term (then K17 does not
 // run)
 int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, const BackwardCall& call);
+// api.hip: bh_render_forward and the train step (train.hip): the request's checks, a deferred far-slice decision collected, then forward_impl
+int render_forward(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
 // api.hip: what the bh_render_backward*_saved entry points share.  `required`: the cotangents that entry refuses to do without;
 // a term of `call` whose cotangent is NULL is an optional one the caller left out.  In this order: the null-argument refusal, the
 // distortion-kind, normal-mode and depth-mode refusals, find_saved_bwd_forward(not_bwd_code), the null-transforms refusal (an
@@ -834,6 +848,13 @@ int launch_image_loss_forward(bh_ctx* ctx, const float* pred, const uint32_t* gt
 int launch_image_loss_backward(bh_ctx* ctx, const float* pred, const uint32_t* gt, const float* dl_dmap,
                                float dl_const, uint32_t channels, uint32_t h, uint32_t w, const BhLossConfig& cfg,
                                float* dl_dpred);
+// loss_fused.hip
+int launch_image_loss_fused(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt, uint32_t h, uint32_t w, const BhLossConfig& cfg,
+                            bool alpha_match, float dl_rgb, float dl_alpha, float* loss_out, float* v_output, float* loss_host = nullptr,
+                            uint32_t* started_host = nullptr, uint32_t started_tag = 0);
+int launch_image_loss_fused_window(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt, uint32_t h, uint32_t w, const BhLossConfig& cfg,
+                                   bool alpha_match, float dl_rgb, float dl_alpha, uint32_t tile_y0, uint32_t tile_y1, float* loss_out,
+                                   float* v_output, float* loss_host = nullptr, uint32_t* started_host = nullptr, uint32_t started_tag = 0);
 // optim.hip
 int launch_adam(bh_ctx* ctx, float* param, const float* grad, float* m1, float* m2, uint64_t rows, uint32_t row_len,
                 const float* col_scale, float lr, uint32_t t, bool reduce_m2, float beta1, float beta2, float eps, float gscale = 1.0f);

@@ -189,8 +189,8 @@ int bh_depth_loss_value_and_grad(bh_ctx* ctx, const float* depth, const BhDepthT
 
 int bh_train_set_depth(bh_ctx* ctx, const BhDepthTarget* target) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    ctx->depth_attached = target != nullptr;
-    ctx->depth_target = target ? *target : BhDepthTarget{};
+    ctx->terms.depth_attached = target != nullptr;
+    ctx->terms.depth_target = target ? *target : BhDepthTarget{};
     return 0;
 }
 

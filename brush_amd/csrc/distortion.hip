@@ -290,8 +290,8 @@ int bh_train_set_distortion(bh_ctx* ctx, const BhDistortionTermConfig* cfg) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     const bool on = cfg != nullptr && cfg->weight > 0.0f;   // (a NaN weight compares false: no term)
     if (on) BH_TRY(check_distortion_kind(ctx, cfg->kind, cfg->near_z, cfg->far_z, "train_set_distortion"));
-    ctx->distortion_attached = on;
-    ctx->distortion_term = on ? *cfg : BhDistortionTermConfig{};
+    ctx->terms.distortion_attached = on;
+    ctx->terms.distortion_term = on ? *cfg : BhDistortionTermConfig{};
     return 0;
 }
 

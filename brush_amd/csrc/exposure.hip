@@ -182,7 +182,7 @@ int bh_exposure_backward(bh_ctx* ctx, bh_exposure* table, uint32_t view, const f
 int bh_train_set_exposure(bh_ctx* ctx, bh_exposure* table) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     BH_TRY(view_table_attachable(ctx, VT_EXPOSURE, table, "train_set_exposure"));
-    ctx->exposure = table;
+    ctx->terms.exposure = table;
     return 0;
 }
 

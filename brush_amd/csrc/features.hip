@@ -333,7 +333,7 @@ int bh_feature_loss_value_and_grad(bh_ctx* ctx, const float* map, const BhFeatur
     return launch_feature_loss(ctx, map, *target, loss, v_map, nullptr, nullptr);
 }
 
-// brush_hip_feature_train.h: the field and the target of the ctx's next train steps (api.hip train_step_impl applies them)
+// brush_hip_feature_train.h: the field and the target of the ctx's next train steps (context.h StepTerms; train.hip applies them)
 int bh_train_set_features(bh_ctx* ctx, const BhFeatureField* field, const BhFeatureTarget* target) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     const char* who = "train_set_features";
@@ -347,9 +347,9 @@ int bh_train_set_features(bh_ctx* ctx, const BhFeatureField* field, const BhFeat
             if (target->weight > 0.0f && !target->target) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": the target has no target map");
         }
     }
-    ctx->feature_attached = field != nullptr;
-    ctx->feature_field = field ? *field : BhFeatureField{};
-    ctx->feature_target = (field && target) ? *target : BhFeatureTarget{};
+    ctx->terms.feature_attached = field != nullptr;
+    ctx->terms.feature_field = field ? *field : BhFeatureField{};
+    ctx->terms.feature_target = (field && target) ? *target : BhFeatureTarget{};
     return 0;
 }
 

@@ -633,12 +633,12 @@ static int lpips_check(bh_ctx* ctx, const bh_lpips* m, const float* img, const u
     return 0;
 }
 
-// the train step's term (api.hip): loss += weight * LPIPS, v_output.rgb += weight * dLPIPS/dimg
+// the train step's term (train.hip): loss += weight * LPIPS, v_output.rgb += weight * dLPIPS/dimg
 int lpips_train_term(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, const float* bg, float* v_output,
                      float* loss, float* loss_host) {
-    const bh_lpips* m = ctx->lpips;
+    const bh_lpips* m = ctx->terms.lpips;
     BH_TRY(lpips_check(ctx, m, img_hwc4, gt_packed, h, w, "train_step (LPIPS)"));
-    return lpips_run(ctx, m, img_hwc4, gt_packed, h, w, bg, ctx->lpips_weight, nullptr, v_output, loss, loss_host);
+    return lpips_run(ctx, m, img_hwc4, gt_packed, h, w, bg, ctx->terms.lpips_weight, nullptr, v_output, loss, loss_host);
 }
 
 }  // namespace bh
@@ -749,8 +749,8 @@ int bh_train_set_lpips(bh_ctx* ctx, const bh_lpips* m, float weight) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!(weight >= 0.0f) || !std::isfinite(weight)) return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_lpips: weight must be finite and >= 0");
     if (m && m->device != ctx->device) return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_lpips: the model lives on another device");
-    ctx->lpips = m;
-    ctx->lpips_weight = m ? weight : 0.0f;
+    ctx->terms.lpips = m;
+    ctx->terms.lpips_weight = m ? weight : 0.0f;
     return 0;
 }
 

@@ -137,8 +137,8 @@ int bh_normal_consistency_value_and_grad(bh_ctx* ctx, const BhCamera* cam, const
 
 int bh_train_set_normal(bh_ctx* ctx, const BhNormalTermConfig* cfg) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    ctx->normal_attached = cfg != nullptr;
-    ctx->normal_term = cfg ? *cfg : BhNormalTermConfig{};
+    ctx->terms.normal_attached = cfg != nullptr;
+    ctx->terms.normal_term = cfg ? *cfg : BhNormalTermConfig{};
     return 0;
 }
 

@@ -36,7 +36,7 @@ int bh_render_backward_pose_saved(bh_ctx* ctx, const BhRenderOut* saved, const f
 
 int bh_train_set_pose_grad(bh_ctx* ctx, float* v_viewmat) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    ctx->pose_grad = v_viewmat;
+    ctx->terms.pose_grad = v_viewmat;
     return 0;
 }
 

@@ -45,15 +45,15 @@ inline void view_table_free(ViewTable* tab) {
 }
 
 inline void view_table_detach(bh_ctx* ctx, const ViewTable* tab) {
-    if (ctx->exposure == tab) ctx->exposure = nullptr;
-    if (ctx->bilagrid == tab) ctx->bilagrid = nullptr;
+    if (ctx->terms.exposure == tab) ctx->terms.exposure = nullptr;
+    if (ctx->terms.bilagrid == tab) ctx->terms.bilagrid = nullptr;
 }
 
 inline void view_tables_free_all(bh_ctx* ctx) {   // bh_destroy
     for (ViewTable* tab : ctx->view_tables) view_table_free(tab);
     ctx->view_tables.clear();
-    ctx->exposure = nullptr;
-    ctx->bilagrid = nullptr;
+    ctx->terms.exposure = nullptr;
+    ctx->terms.bilagrid = nullptr;
 }
 
 // the handle is a table of this kind that the ctx owns (a handle of the other kind is refused like any stranger)

@@ -8,6 +8,7 @@ import ctypes as C
 import enum
 import math
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
@@ -2316,15 +2317,8 @@ class SplatTrainer:
                 return 1
         return _ffi.IMAGE_HOOK(hook)
 
-    def step(self, batch: SceneBatch, splats: Splats, background=None, noise_samples=None) -> Tuple[Splats, TrainStepStats]:
-        """One optimisation step, in place on `splats`. `background` / `noise_samples`
-        [N,3] inject the two stochastic terms; None = base colour / no noise."""
-        ctx = self.ctx or get_context(splats.device)
-        dev = splats.device
-        if self.state is None:
-            self._init_state(splats)
-        cfg = _ffi.BhTrainConfig()
-        c = self.config
+    def _train_config(self, splats):
+        c, cfg = self.config, _ffi.BhTrainConfig()
         cfg.lr_mean, cfg.lr_mean_end, cfg.total_train_iters = c.lr_mean, c.lr_mean_end, c.total_train_iters
         cfg.lr_coeffs_dc, cfg.lr_coeffs_sh_scale, cfg.lr_opac = c.lr_coeffs_dc, c.lr_coeffs_sh_scale, c.lr_opac
         cfg.lr_scale, cfg.lr_rotation, cfg.ssim_weight = c.lr_scale, c.lr_rotation, c.ssim_weight
@@ -2332,50 +2326,156 @@ class SplatTrainer:
         cfg.background[0], cfg.background[1], cfg.background[2] = c.background_color
         cfg.median_scene_scale = self.median_scene_scale
         cfg.render_mip = 1 if (c.render_mip or splats.render_mip) else 0
-        cfg.exact_lists = 1 if getattr(c, "exact_lists", False) else 0
+        cfg.exact_lists = 1 if c.exact_lists else 0
         cfg.growth_stop_iter = int(c.growth_stop_iter)   # from that step on nobody reads the refine weight (train.rs:589-614): the step stops computing it
-        s = self.state
-        st = _ffi.BhTrainState()
-        st.n, st.sh_degree = splats.num_splats(), splats.sh_degree()
-        st.transforms, st.sh_coeffs, st.raw_opacities = splats.transforms.data_ptr(), splats.sh_coeffs.data_ptr(), splats.raw_opacities.data_ptr()
-        st.m1_transforms, st.m2_transforms = s["m1_t"].data_ptr(), s["m2_t"].data_ptr()
-        st.m1_sh, st.m2_sh = s["m1_sh"].data_ptr(), s["m2_sh"].data_ptr()
-        st.m1_opac, st.m2_opac = s["m1_o"].data_ptr(), s["m2_o"].data_ptr()
-        st.refine_weight_norm, st.vis_weight, st.max_screen_size = s["refine_weight_norm"].data_ptr(), s["vis_weight"].data_ptr(), s["max_screen_size"].data_ptr()
-        st.step_count = self.step_count
+        return cfg
+
+    def _tile_window(self, ctx, b, h, dev):
+        """partition "tiles": this rank's strip of tile rows goes into b.camera, with the image hook that moves the strips or — native_comm —
+        the library's own halo exchange, and the strip-wise loss where the strips allow it.  -> whether the frame is split at all."""
+        native_tiles = self.native_comm and self.partition == "tiles" and ctx.comm_world() > 1
+        if not ((self.pg is not None and self.partition == "tiles") or native_tiles):
+            return False
+        if native_tiles:
+            t_rank, t_world = ctx.comm_rank(), ctx.comm_world()
+        else:
+            import torch.distributed as dist
+            t_rank, t_world = dist.get_rank(self.pg), dist.get_world_size(self.pg)
+        rows = tile_rows_for_rank((h + 15) // 16, t_rank, t_world, self._row_weights)
+        cam = _ffi.BhCamera()
+        C.memmove(C.byref(cam), C.byref(b.camera), C.sizeof(cam))
+        cam.tile_row_begin, cam.tile_row_end = rows
+        b.camera = cam
+        halo_ok = strips_allow_halo_loss(strip_spans_px(h, t_world, self._row_weights))
+        if native_tiles:
+            # no hook: the library exchanges the halos over its own communicator (strip-wise loss is the only native mode)
+            if not halo_ok:
+                raise BrushHipError("native tile partition needs every strip to be at least 21 pixel rows tall")
+            self._strip_loss_now = True
+        else:
+            if self._img_hook is None:
+                self._img_hook = self._make_image_hook(dev)
+            b.image_hook = C.cast(self._img_hook, C.c_void_p)
+            self._strip_loss_now = bool(self.strip_loss) and halo_ok
+        b.strip_loss = int(self._strip_loss_now)
+        return True
+
+    def _feature_target(self, ctx, batch, dev):
+        """The feature target of this batch (TrainConfig.feature_loss_weight, from feature_loss_from_iter on), checked and converted
+        -> (BhFeatureTarget, the tensor it points into), or (None, None): no feature term this step."""
+        c, ff, ftarget = self.config, self.feature_field, batch.features
+        fw = float(c.feature_loss_weight) if ftarget is not None else 0.0
+        if ff is None:
+            if fw > 0.0:
+                raise ValueError("feature_loss_weight > 0 and a batch with a feature target need SplatTrainer(..., feature_field=FeatureField(...))")
+            return None, None
+        if not (fw > 0.0 and self.step_count + 1 >= int(c.feature_loss_from_iter)):
+            return None, None
+        fk = c.feature_loss_kind
+        fk = int(FEATURE_LOSS_KINDS[fk]) if isinstance(fk, str) else int(fk)
+        ch = int(ff.features.shape[1])
+        if fk == _ffi.FEATURE_LOSS_CROSS_ENTROPY:
+            ftgt = torch.as_tensor(ftarget, dtype=torch.uint8, device=dev).contiguous()
+            if ftgt.dim() != 2:
+                raise ValueError("SceneBatch.features: cross-entropy labels must be uint8 [H, W]")
+        else:
+            ftgt = _f32c(ftarget, dev)
+            if ftgt.dim() != 3 or int(ftgt.shape[2]) != ch:
+                raise ValueError("SceneBatch.features: an l1 target must be float32 [H, W, %d]" % ch)
+        if ftgt is not ftarget and not ctx.uses_torch_stream:
+            torch.cuda.current_stream(dev).synchronize()   # the conversion ran on torch's stream, the step runs on the ctx's own
+        ft = _ffi.BhFeatureTarget()
+        ft.target, ft.h, ft.w, ft.channels, ft.kind, ft.weight = ftgt.data_ptr(), int(ftgt.shape[0]), int(ftgt.shape[1]), ch, fk, fw
+        return ft, ftgt
+
+    def _step_terms(self, ctx, batch, b, dev):
+        """What this step attaches to the ctx, in attach order, for `_attached`: (setter, the arguments that attach this step's term — or
+        say that there is none —, the arguments that detach it behind the step, or None: the term stays as set), or a plain callable that
+        has its turn at that place.  What the step cannot do is said here, before anything is attached.
+        -> (terms, (depth tensor, feature tensor) the terms point into, the BhFeatureTarget or None)."""
+        c, lib, step = self.config, ctx.lib, self.step_count + 1
+        lw = float(c.lpips_loss_weight)
+        if lw > 0.0 and self.lpips is None:
+            raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
+        ff = self.feature_field
+        ft, ftgt = self._feature_target(ctx, batch, dev)
+        off = (None,)
+        terms = []
+        # the terms of the batch.  Depth: for a batch that has a depth map, at this step's weight (a weight of 0 is no term)
+        dgt = None
+        if batch.depth is not None:
+            dt, dgt = _depth_target(batch.depth, dev, c.depth_loss_kind, c.depth_weight_at(step), batch.depth_scale, batch.depth_offset, shape=batch.img_size())
+            terms.append((lib.bh_train_set_depth, (C.byref(dt),), off))
+        else:
+            terms.append((lib.bh_train_set_depth, off, off))
+        # normal consistency and distortion: from their *_from_iter on
+        nw = float(c.normal_loss_weight)
+        if nw > 0.0 and step >= int(c.normal_loss_from_iter):
+            terms.append((lib.bh_train_set_normal, (C.byref(_ffi.BhNormalTermConfig(weight=nw)),), off))
+        else:
+            terms.append((lib.bh_train_set_normal, off, off))
+        xw = float(c.distortion_loss_weight)
+        if xw > 0.0 and step >= int(c.distortion_loss_from_iter):
+            xt = _ffi.BhDistortionTermConfig(weight=xw, kind=_distortion_kind(c.distortion_kind), near_z=float(c.distortion_near), far_z=float(c.distortion_far))
+            terms.append((lib.bh_train_set_distortion, (C.byref(xt),), off))
+        else:
+            terms.append((lib.bh_train_set_distortion, off, off))
+        # features: the field and this batch's target, or none for a batch without one or while the weight is off.  (A trainer without a
+        # field makes neither call: there is nothing of another trainer's to clear.)
+        if ff is not None:
+            terms.append((lib.bh_train_set_features, (C.byref(ff.as_struct()), C.byref(ft)) if ft is not None else (None, None), (None, None)))
+        if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
+            terms.append(lambda: self.batch_patch(b))
+        # the terms of the trainer.  LPIPS is set for THIS trainer's step, whatever another trainer on the ctx left, and stays
+        terms.append((lib.bh_train_set_lpips, (self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0), None))
+        if self.pose_optimizer is not None:
+            terms.append((lib.bh_train_set_pose_grad, (_ptr(self._pose_buf),), off))
+        ex, grid = self.exposure, self.bilagrid
+        if ex is not None:
+            if self.exposure_lr is not None:
+                terms.append(lambda: ex.set_lr(self.exposure_lr(step)))
+            terms.append((lib.bh_train_set_exposure, (ex._h,), off))
+        if grid is not None:
+            if self.bilagrid_lr is not None:
+                terms.append(lambda: grid.set_lr(self.bilagrid_lr(step)))
+            terms.append((lib.bh_train_set_bilagrid, (grid._h, self.bilagrid_tv_weight), (None, 0.0)))
+        return terms, (dgt, ftgt), ft
+
+    @staticmethod
+    @contextmanager
+    def _attached(ctx, terms):
+        """The terms of a step are ctx state (bh_train_set_*) and a ctx may serve several trainers: every trainer attaches what its own
+        step needs right before the step, in `terms`' order, and detaches it behind the step in the same order, whether or not the step
+        succeeded."""
+        try:
+            for t in terms:
+                if callable(t):
+                    t()
+                else:
+                    ctx.check(t[0](ctx._h, *t[1]))
+            yield
+        finally:
+            for t in terms:
+                if not callable(t) and t[2] is not None:
+                    t[0](ctx._h, *t[2])
+
+    def step(self, batch: SceneBatch, splats: Splats, background=None, noise_samples=None) -> Tuple[Splats, TrainStepStats]:
+        """One optimisation step, in place on `splats`. `background` / `noise_samples`
+        [N,3] inject the two stochastic terms; None = base colour / no noise."""
+        ctx = self.ctx or get_context(splats.device)
+        dev = splats.device
+        if self.state is None:
+            self._init_state(splats)
+        cfg, st = self._train_config(splats), self._train_state(splats, self.state)
         st.min_scale = splats.min_scale.data_ptr() if splats.min_scale is not None else None
         h, w = batch.img_size()
         b = _ffi.BhTrainBatch()
         b.camera = batch.camera if isinstance(batch.camera, _ffi.BhCamera) else batch.camera.uniforms((w, h))
-        native_tiles = self.native_comm and self.partition == "tiles" and ctx.comm_world() > 1
-        tiles = (self.pg is not None and self.partition == "tiles") or native_tiles
-        if tiles:
-            if native_tiles:
-                t_rank, t_world = ctx.comm_rank(), ctx.comm_world()
-            else:
-                import torch.distributed as dist
-                t_rank, t_world = dist.get_rank(self.pg), dist.get_world_size(self.pg)
-            rows = tile_rows_for_rank((h + 15) // 16, t_rank, t_world, self._row_weights)
-            cam = _ffi.BhCamera()
-            C.memmove(C.byref(cam), C.byref(b.camera), C.sizeof(cam))
-            cam.tile_row_begin, cam.tile_row_end = rows
-            b.camera = cam
-            halo_ok = strips_allow_halo_loss(strip_spans_px(h, t_world, self._row_weights))
-            if native_tiles:
-                # no hook: the library exchanges the halos over its own communicator (strip-wise loss is the only native mode)
-                if not halo_ok:
-                    raise BrushHipError("native tile partition needs every strip to be at least 21 pixel rows tall")
-                self._strip_loss_now = True
-            else:
-                if self._img_hook is None:
-                    self._img_hook = self._make_image_hook(dev)
-                b.image_hook = C.cast(self._img_hook, C.c_void_p)
-                self._strip_loss_now = bool(self.strip_loss) and halo_ok
-            b.strip_loss = int(self._strip_loss_now)
+        tiles = self._tile_window(ctx, b, h, dev)
         gt = _as_u32(batch.img_packed, dev)
         b.gt_packed = gt.data_ptr()
         b.has_alpha, b.alpha_is_mask = int(batch.has_alpha), int(batch.alpha_is_mask)
-        bg = background if background is not None else (self.sample_background() if self.seed is not None else c.background_color)
+        bg = background if background is not None else (self.sample_background() if self.seed is not None else self.config.background_color)
         b.background[0], b.background[1], b.background[2] = [float(v) for v in bg]
         ns = None
         if noise_samples is not None:
@@ -2385,7 +2485,7 @@ class SplatTrainer:
             b.device_noise, b.noise_seed = 1, self.seed
         stats = _ffi.BhTrainStats()
         b.exchange_mode = 1 if (self.sparse_exchange and (self.pg is not None or self.native_comm)) else 0
-        b.view_id = int(getattr(batch, "view_id", 0)) & 0xFFFFFFFF
+        b.view_id = int(batch.view_id) & 0xFFFFFFFF
         po = self.pose_optimizer
         if po is not None:   # the view at its current correction, named by its id (a moving camera's hash would mint a view table per step)
             b.camera = po.camera(b.view_id, b.camera)
@@ -2400,102 +2500,17 @@ class SplatTrainer:
             if self._hook is None:
                 self._hook = self._make_hook(dev)
             hook, scale = self._hook, (1.0 if tiles else 1.0 / self._world)
-        # what this step cannot do is said before anything is attached to the ctx (the terms below are detached behind the call only)
-        lw = float(getattr(c, "lpips_loss_weight", 0.0))
-        if lw > 0.0 and self.lpips is None:
-            raise ValueError("lpips_loss_weight > 0 needs SplatTrainer(..., lpips=Lpips.from_state_dict(...))")
-        # the feature target of this batch (TrainConfig.feature_loss_weight, from feature_loss_from_iter on): checked and converted here
-        ff, ft, ftgt = self.feature_field, None, None
-        ftarget = getattr(batch, "features", None)
-        fw = float(getattr(c, "feature_loss_weight", 0.0)) if ftarget is not None else 0.0
-        if ff is None:
-            if fw > 0.0:
-                raise ValueError("feature_loss_weight > 0 and a batch with a feature target need SplatTrainer(..., feature_field=FeatureField(...))")
-        elif fw > 0.0 and self.step_count + 1 >= int(getattr(c, "feature_loss_from_iter", 0)):
-            fk = getattr(c, "feature_loss_kind", "l1")
-            fk = int(FEATURE_LOSS_KINDS[fk]) if isinstance(fk, str) else int(fk)
-            ch = int(ff.features.shape[1])
-            if fk == _ffi.FEATURE_LOSS_CROSS_ENTROPY:
-                ftgt = torch.as_tensor(ftarget, dtype=torch.uint8, device=dev).contiguous()
-                if ftgt.dim() != 2:
-                    raise ValueError("SceneBatch.features: cross-entropy labels must be uint8 [H, W]")
-            else:
-                ftgt = _f32c(ftarget, dev)
-                if ftgt.dim() != 3 or int(ftgt.shape[2]) != ch:
-                    raise ValueError("SceneBatch.features: an l1 target must be float32 [H, W, %d]" % ch)
-            if ftgt is not ftarget and not ctx.uses_torch_stream:
-                torch.cuda.current_stream(dev).synchronize()   # the conversion ran on torch's stream, the step runs on the ctx's own
-            ft = _ffi.BhFeatureTarget()
-            ft.target, ft.h, ft.w, ft.channels, ft.kind, ft.weight = ftgt.data_ptr(), int(ftgt.shape[0]), int(ftgt.shape[1]), ch, fk, fw
-        # the depth term is ctx state (bh_train_set_depth): attached for a batch that has a depth map — at this step's weight, and a
-        # weight of 0 is no term — and detached for one that has none; detached again behind the step, like the pose buffer
-        dgt = None
-        if getattr(batch, "depth", None) is not None:
-            dt, dgt = _depth_target(batch.depth, dev, getattr(c, "depth_loss_kind", "l1"), c.depth_weight_at(self.step_count + 1),
-                                    batch.depth_scale, batch.depth_offset, shape=(h, w))
-            ctx.check(ctx.lib.bh_train_set_depth(ctx._h, C.byref(dt)))
-        else:
-            ctx.check(ctx.lib.bh_train_set_depth(ctx._h, None))
-        # the normal term is ctx state too (bh_train_set_normal): attached from normal_loss_from_iter on, detached otherwise and behind the step
-        nw = float(getattr(c, "normal_loss_weight", 0.0))
-        if nw > 0.0 and self.step_count + 1 >= int(getattr(c, "normal_loss_from_iter", 0)):
-            ctx.check(ctx.lib.bh_train_set_normal(ctx._h, C.byref(_ffi.BhNormalTermConfig(weight=nw))))
-        else:
-            ctx.check(ctx.lib.bh_train_set_normal(ctx._h, None))
-        # ... and so is the distortion term (bh_train_set_distortion), from distortion_loss_from_iter on
-        xw = float(getattr(c, "distortion_loss_weight", 0.0))
-        if xw > 0.0 and self.step_count + 1 >= int(getattr(c, "distortion_loss_from_iter", 0)):
-            xt = _ffi.BhDistortionTermConfig(weight=xw, kind=_distortion_kind(getattr(c, "distortion_kind", "z")),
-                                             near_z=float(getattr(c, "distortion_near", 0.2)), far_z=float(getattr(c, "distortion_far", 1000.0)))
-            ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, C.byref(xt)))
-        else:
-            ctx.check(ctx.lib.bh_train_set_distortion(ctx._h, None))
-        # ... and the feature term (bh_train_set_features): the field and this batch's target (checked above) are attached before every
-        # step — the target changes per batch — and detached for a batch without one or while the weight is off.  (A trainer
-        # without a field makes none of these calls: every trainer detaches behind its own step, so there is nothing of another's
-        # to clear.)
-        if ft is not None:
-            ctx.check(ctx.lib.bh_train_set_features(ctx._h, C.byref(ff.as_struct()), C.byref(ft)))
-        elif ff is not None:
-            ctx.check(ctx.lib.bh_train_set_features(ctx._h, None, None))
-        if self.batch_patch is not None:   # last word on the BhTrainBatch (callers that partition a frame themselves; tests)
-            self.batch_patch(b)
-        # the term is ctx state (bh_train_set_lpips): set it for THIS trainer's step, whatever another trainer on the ctx left
-        ctx.check(ctx.lib.bh_train_set_lpips(ctx._h, self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0))
-        if po is not None:
-            ctx.check(ctx.lib.bh_train_set_pose_grad(ctx._h, _ptr(self._pose_buf)))
-        ex = self.exposure
-        if ex is not None:
-            if self.exposure_lr is not None:
-                ex.set_lr(self.exposure_lr(self.step_count + 1))
-            ctx.check(ctx.lib.bh_train_set_exposure(ctx._h, ex._h))
-        bg = self.bilagrid
-        if bg is not None:
-            if self.bilagrid_lr is not None:
-                bg.set_lr(self.bilagrid_lr(self.step_count + 1))
-            ctx.check(ctx.lib.bh_train_set_bilagrid(ctx._h, bg._h, self.bilagrid_tv_weight))
-        try:
+        terms, kept, ft = self._step_terms(ctx, batch, b, dev)
+        with self._attached(ctx, terms):
             ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                             float(scale), C.byref(stats)))
-        finally:
-            ctx.lib.bh_train_set_depth(ctx._h, None)
-            ctx.lib.bh_train_set_normal(ctx._h, None)
-            ctx.lib.bh_train_set_distortion(ctx._h, None)
-            if ff is not None:
-                ctx.lib.bh_train_set_features(ctx._h, None, None)
-            if po is not None:   # ctx state, like the LPIPS term: this trainer's steps only, whether or not the step succeeded
-                ctx.lib.bh_train_set_pose_grad(ctx._h, None)
-            if ex is not None:
-                ctx.lib.bh_train_set_exposure(ctx._h, None)
-            if bg is not None:
-                ctx.lib.bh_train_set_bilagrid(ctx._h, None, 0.0)
         if po is not None:
             po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
         if ft is not None:   # the step succeeded with the term: the library applied one Adam update to the field
-            ff.t += 1
+            self.feature_field.t += 1
         self.step_count = st.step_count
         self._last_stats = stats
-        self._keep = (gt, ns, dgt, ftgt)
+        self._keep = (gt, ns) + kept
         if tiles and self.rebalance_every > 0:
             if self.step_count % self.rebalance_every == 0:
                 self._measure_row_weights(ctx, (h + 15) // 16, (w + 15) // 16, dev)

@@ -13,7 +13,7 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -munsafe-fp-atomics -fno-slp-vectorize -Wall -Wno-unused-function"
-UNITS="api project sort depth_sort scan rasterize loss loss_fused optim refine filter3d ply upload comm exchange"
+UNITS=$(sed -n 's/^SRCS := //p' "$ROOT/brush_amd/csrc/Makefile" | sed 's/\.hip//g')   # every unit of the library: the Makefile's list
 OUT=$ROOT/brush_amd/variants
 verb=$1; shift || true
 setup() {   # $1 = variant | default | ENV=VALUE  -> ENVV (an `env` argument)
