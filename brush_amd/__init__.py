@@ -66,6 +66,11 @@ Names and argument meaning follow the reference (paths under
                                          mask lifting: per-splat blend-weight votes from 2-D label maps over any number of views, the
                                          largest weight and the pixel count of each splat, argmax / threshold, compaction (not in
                                          the reference; SAGA, Gaussian Grouping, FlashSplat; include/brush_hip_lift.h)
+    EnvironmentMap / SplatTrainer(envmap=) / run_eval(envmap=)
+                                         environment maps: a learned cubemap behind the splats (sky, skyline, a bright window),
+                                         composited behind the frame before the loss, with an exact integer gradient and Adam on the
+                                         device (not in the reference; splatfacto-w's and Street Gaussians' sky, gsplat's
+                                         backgrounds; include/brush_hip_envmap.h)
 
 torch is used only for device memory, streams and torch.distributed; every
 computation runs in the hand-written HIP kernels. No CPU fallback exists.
@@ -85,5 +90,6 @@ from .host import (  # noqa: F401
     render_features, feature_loss_value_and_grad, FeatureField,
     SceneTransform, SceneRegion, select_region, crop_splats,
     LiftAccumulator, lift_labels, compact_splats,
+    EnvironmentMap,
 )
 from ._ffi import BrushHipError  # noqa: F401

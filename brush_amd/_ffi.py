@@ -439,6 +439,22 @@ LIFT_SYMBOLS = {
     "bh_lift_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BhLiftSelect), C.c_void_p]),
 }
 
+# every symbol include/brush_hip_envmap.h declares (environment maps: a learned cubemap behind the splats, trained in the step)
+ENVMAP_MAX_RESOLUTION = 1024   # BH_ENVMAP_MAX_RESOLUTION
+ENVMAP_SYMBOLS = {
+    "bh_envmap_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_envmap_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bh_envmap_set_params": (C.c_int, [C.c_void_p, C.c_void_p, fp]),
+    "bh_envmap_get_params": (C.c_int, [C.c_void_p, C.c_void_p, fp]),
+    "bh_envmap_get_grad": (C.c_int, [C.c_void_p, C.c_void_p, fp]),
+    "bh_envmap_get_state": (C.c_int, [C.c_void_p, C.c_void_p, fp, fp, u32p]),
+    "bh_envmap_set_state": (C.c_int, [C.c_void_p, C.c_void_p, fp, fp, C.c_uint32]),
+    "bh_envmap_set_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bh_envmap_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_envmap_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BhCamera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]),
+    "bh_train_set_envmap": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -478,7 +494,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS))
     return _lib
 
 
@@ -487,6 +503,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -20,6 +20,7 @@
 #include "../../include/brush_hip_mesh.h"
 #include "../../include/brush_hip_features.h"
 #include "../../include/brush_hip_feature_train.h"
+#include "../../include/brush_hip_envmap.h"
 #include "device_math.h"
 
 namespace bh {
@@ -99,6 +100,7 @@ enum Slot : int {
     SLOT_FEATURES,           // bh_render_features / launch_feature_backward: compact features [Nv,C] | V [Nv,C] | the frame's accumulated feature map [H,W,C] (features.hip)
     SLOT_FEATURE_TERM,       // bh_train_step with a feature term: the feature map [H,W,C] | v_map [H,W,C] | the term's loss pair (4 floats)
     SLOT_FEATURE_GRAD,       // ... and its dense v_features [N,C], from the backward to the field's update
+    SLOT_ENVMAP_FRAME,       // bh_train_step with an environment map: [H,W,4] the frame composited over the map (envmap.hip; out_img stays what K17 replays)
     SLOT_SCENE,              // bh_splats_select_region with a count: one u32 per block of the select | the total (scene_edit.hip)
     SLOT_COUNT
 };
@@ -440,6 +442,7 @@ struct StepTerms {
     bh_exposure* exposure = nullptr;  // bh_train_set_exposure: the step exposes its frame with the row of the batch's view and updates it; NULL = off
     bh_bilagrid* bilagrid = nullptr;  // bh_train_set_bilagrid: the step slices its frame with the grid of the batch's view and updates it; NULL = off
     float bilagrid_tv_weight = 0.0f;  // ... and adds this much of the grid's total variation to the loss
+    bh_envmap* envmap = nullptr;      // bh_train_set_envmap: the step composites its frame over the map before the loss and updates the map; NULL = off
 
     bool lpips_on() const { return lpips != nullptr && lpips_weight > 0.0f; }
     bool depth_on() const { return depth_attached && depth_target.weight > 0.0f; }
@@ -480,6 +483,7 @@ struct bh_ctx {
     hipEvent_t image_tab_ev = nullptr; // ... free again once this event (behind their copy) has completed
     bh::StepTerms terms;              // what the bh_train_set_* calls attached to the next train steps (train.hip)
     std::vector<bh::ViewTable*> view_tables;   // every per-view table of this ctx, of either kind (view_table.h): bh_destroy frees what is left
+    std::vector<bh_envmap*> envmaps;  // every environment map of this ctx (envmap.hip): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (train.hip); comm_ev marks "the forward is done" for it
@@ -657,6 +661,18 @@ int launch_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* tab, uint32_t view, const
                              float tv_weight, bool update);
 int launch_bilagrid_tv(bh_ctx* ctx, const bh_bilagrid* tab, uint32_t view, float* value, float weight, float* accum, float* accum_host);
 float* bilagrid_tv_scratch(bh_ctx* ctx);   // four floats of SLOT_BILAGRID for the train step's TV value
+// envmap.hip: out = img over the map seen through `cam`, and its backward: v_img (in place allowed), the map's gradient = v_E and — when
+// `update` — one Adam step of the table on gscale * v_E (brush_hip_envmap.h).  Camera and image size are already checked.  A
+// non-finite max |v_out|: check_host reads it back and refuses; otherwise the kernels behind the max pass do nothing.  launch_envmap_adam:
+// the step alone, on the gradient as it stands (the train step sums it over the ranks first).  envmaps_free_all: bh_destroy.
+int check_envmap_frame(bh_ctx* ctx, const BhCamera* cam, uint32_t h, uint32_t w, const char* who);
+int launch_envmap_composite(bh_ctx* ctx, const bh_envmap* map, const BhCamera& cam, const float* img, uint32_t h, uint32_t w, float* out);
+int launch_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera& cam, const float* img, const float* v_out, uint32_t h, uint32_t w, float* v_img,
+                           bool update, float gscale, bool check_host);
+int launch_envmap_adam(bh_ctx* ctx, bh_envmap* map, float gscale);
+uint64_t envmap_floats(const bh_envmap* map);
+float* envmap_grad(const bh_envmap* map);
+void envmaps_free_all(bh_ctx* ctx);
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view
 // id whose camera is new, or a failed allocation.  A second attempt (!req.allow_cut) leaves the view's gap and LRU stamp alone.

@@ -29,6 +29,7 @@ struct StepPlan {
     bool lpips = false, depth = false, normal = false, distortion = false, feature = false;
     bh_exposure* exposure = nullptr;
     bh_bilagrid* bilagrid = nullptr;
+    bh_envmap* envmap = nullptr;
     // the camera's tile-row window, and whether this rank has the whole frame to itself: every term but the image loss needs that
     uint32_t tile_y0 = 0, tile_y1 = 0;
     bool whole_frame = true, window_partial = false;
@@ -57,6 +58,7 @@ struct StepWork {
     float* v_output = nullptr;    // dL/dimg [H,W,4]
     float* loss_dev = nullptr;
     float* loss_host = nullptr;   // the loss scalar goes straight into pinned host memory (bh_sync hands it to stats->loss): no copy launch
+    float* composited = nullptr;  // with an environment map the frame over the map lives in a slot of its own too: the loss, LPIPS and the colour tables read it
     float* corrected = nullptr;   // with an exposure or a bilateral-grid table the loss reads the exposed / sliced frame from a slot of its own: out_img is what K17 replays from
     BackwardCall bwd;
     DepthTerm depth_term;
@@ -67,6 +69,8 @@ struct StepWork {
     uint32_t* union_idx = nullptr;
     bool flags_on_side = false;
     float* visible() const { return exch; }
+    // what the image terms see of the frame: the rasterizer's image, or that image over the environment map
+    float* frame() const { return composited ? composited : ro.out_img; }
 };
 
 // the image loss of one attempt: queue_loss runs once, or twice when a far slice had to follow
@@ -91,7 +95,7 @@ int check_frame_and_pose(bh_ctx* ctx, const StepPlan& p, const char* the_term, c
     return 0;
 }
 
-// Every refusal of the step, in this order: null arguments, exposure, bilagrid, depth (map, size, kind, frame, pose), normal (camera,
+// Every refusal of the step, in this order: null arguments, exposure, bilagrid, environment map (camera, frame, pose, alpha), depth (map, size, kind, frame, pose), normal (camera,
 // frame, pose), distortion, feature (frame, pose, rows, size), strip_loss, LPIPS.  Nothing is queued, no device is touched.
 int plan_step(bh_ctx* ctx, const BhTrainConfig* cfg, const BhTrainState* st, const BhTrainBatch* batch, bh_grad_hook hook, const BhTrainStats* stats, StepPlan* plan) {
     if (!cfg || !st || !batch || !stats) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null argument");
@@ -122,6 +126,17 @@ int plan_step(bh_ctx* ctx, const BhTrainConfig* cfg, const BhTrainState* st, con
         BH_TRY(check_frame_and_pose(ctx, p, "bilateral-grid term", nullptr));
         if ((uint64_t)cam.img_w * cam.img_h > 0x7FFFFFFFull)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with a bilateral-grid table h * w must stay below 2^31");
+    }
+    // an environment map (brush_hip_envmap.h): rays exist for a pinhole alone, the pose pass does not carry the lookup's dependence on
+    // the rotation, and a target with real alpha says what lies behind the splats itself
+    if ((p.envmap = t.envmap)) {
+        if (cam.model != BH_CAMERA_PINHOLE)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the environment map needs a pinhole camera (no other model can be unprojected to a ray)");
+        BH_TRY(check_frame_and_pose(ctx, p, "environment map", "an environment map"));
+        if (batch->has_alpha && !batch->alpha_is_mask)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: an environment map and a target with real alpha cannot be combined (a mask is fine)");
+        if ((uint64_t)cam.img_w * cam.img_h > 0x7FFFFFFFull)
+            return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: with an environment map h * w must stay below 2^31");
     }
     // a depth target (brush_hip_depth_loss.h); weight <= 0 is no term at all
     if ((p.depth = t.depth_on())) {
@@ -255,20 +270,24 @@ int queue_loss(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, const StepWork
         return launch_image_loss_fused_window(ctx, w.ro.out_img, batch->gt_packed, p.H, p.W, l.lc, l.alpha_match, l.dl_rgb, l.dl_alpha, p.tile_y0, p.tile_y1,
                                               w.loss_dev, w.v_output, w.loss_host, started_host, started_tag);
     }
-    if (p.exposure) {   // (inside queue_loss: a second attempt after a failed forecast exposes the finished image again)
+    if (p.envmap) {   // (inside queue_loss: a second attempt after a failed forecast composites the finished image again)
+        ProfScope ps(ctx, "EnvMap");
+        BH_TRY(launch_envmap_composite(ctx, p.envmap, batch->camera, w.ro.out_img, p.H, p.W, w.composited));
+    }
+    if (p.exposure) {   // (likewise; the map is part of the scene, the colour model part of the camera: it acts on the composited frame)
         ProfScope ps(ctx, "Exposure");
-        BH_TRY(launch_exposure_apply(ctx, p.exposure, batch->view_id, w.ro.out_img, p.H, p.W, w.corrected));
+        BH_TRY(launch_exposure_apply(ctx, p.exposure, batch->view_id, w.frame(), p.H, p.W, w.corrected));
     }
     if (p.bilagrid) {   // (likewise)
         ProfScope ps(ctx, "Bilagrid");
-        BH_TRY(launch_bilagrid_slice(ctx, p.bilagrid, batch->view_id, w.ro.out_img, p.H, p.W, w.corrected));
+        BH_TRY(launch_bilagrid_slice(ctx, p.bilagrid, batch->view_id, w.frame(), p.H, p.W, w.corrected));
     }
-    return launch_image_loss_fused(ctx, w.corrected ? w.corrected : w.ro.out_img, batch->gt_packed, p.H, p.W, l.lc, l.alpha_match, l.dl_rgb, l.dl_alpha, w.loss_dev, w.v_output,
+    return launch_image_loss_fused(ctx, w.corrected ? w.corrected : w.frame(), batch->gt_packed, p.H, p.W, l.lc, l.alpha_match, l.dl_rgb, l.dl_alpha, w.loss_dev, w.v_output,
                                    w.loss_host, started_host, started_tag);
 }
 
-// ---- loss (train.rs:227-260), with the far slice's decision behind it, and the terms that act on the image: LPIPS, and the backward
-// of the exposure table or the bilateral grid
+// ---- loss (train.rs:227-260), with the far slice's decision behind it, and the terms that act on the image: LPIPS, the backward
+// of the exposure table or the bilateral grid, and the backward of the environment map
 int step_image_loss(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork& w) {
     const BhTrainConfig* cfg = a.cfg;
     const BhTrainBatch* batch = a.batch;
@@ -286,6 +305,7 @@ int step_image_loss(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork&
     w.v_output = (float*)ensure(ctx, SLOT_V_OUTPUT, hw * 16);
     w.loss_dev = (float*)ensure(ctx, SLOT_LOSS_SCALAR, 16);
     if (!w.v_output || !w.loss_dev) return BH_ERR_OOM;
+    if (p.envmap && !(w.composited = (float*)ensure(ctx, SLOT_ENVMAP_FRAME, hw * 16))) return BH_ERR_OOM;
     if ((p.exposure || p.bilagrid) && !(w.corrected = (float*)ensure(ctx, SLOT_CORRECTED, hw * 16))) return BH_ERR_OOM;
     w.loss_host = reinterpret_cast<float*>(ctx->host_counters) + HOST_LOSS_WORD;
     l.dl_rgb = 1.0f / (float)(hw * 3);
@@ -310,14 +330,14 @@ int step_image_loss(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork&
             BH_TRY(queue_loss(ctx, a, p, w, l));
         }
     }
-    float* const final_img = w.corrected ? w.corrected : w.ro.out_img;
+    float* const final_img = w.corrected ? w.corrected : w.frame();
     // LPIPS (train.rs:265-273): on the frame's final image, GT composited as the loss above does it; loss and dL/dimg grow in place
     // on the device (no host wait)
     if (p.lpips) BH_TRY(lpips_train_term(ctx, final_img, batch->gt_packed, p.H, p.W, lc.composite_bg ? lc.bg : nullptr, w.v_output, w.loss_dev, w.loss_host));
-    // exposure backward: v_output becomes A^T v' in place (x = the frame as rendered), the view's row takes its Adam step
+    // exposure backward: v_output becomes A^T v' in place (x = the frame as rendered, or over the map), the view's row takes its Adam step
     if (p.exposure) {
         ProfScope ps(ctx, "Exposure");
-        BH_TRY(launch_exposure_backward(ctx, p.exposure, batch->view_id, w.ro.out_img, w.v_output, p.H, p.W, w.v_output, /*update=*/true));
+        BH_TRY(launch_exposure_backward(ctx, p.exposure, batch->view_id, w.frame(), w.v_output, p.H, p.W, w.v_output, /*update=*/true));
     }
     // bilateral grid: loss += tv_weight TV(grid) in f32 (no launch at weight 0), then v_output becomes v_img in place and the view's
     // grid takes its Adam step on v_g + tv_weight dTV
@@ -329,7 +349,15 @@ int step_image_loss(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork&
             if (!tv_value) return BH_ERR_OOM;
             BH_TRY(launch_bilagrid_tv(ctx, p.bilagrid, batch->view_id, tv_value, tvw, w.loss_dev, w.loss_host));
         }
-        BH_TRY(launch_bilagrid_backward(ctx, p.bilagrid, batch->view_id, w.ro.out_img, w.v_output, p.H, p.W, w.v_output, tvw, /*update=*/true));
+        BH_TRY(launch_bilagrid_backward(ctx, p.bilagrid, batch->view_id, w.frame(), w.v_output, p.H, p.W, w.v_output, tvw, /*update=*/true));
+    }
+    // environment map, behind the colour tables' backward: v_output's alpha takes the sky's term in place (the render backward then pulls
+    // alpha down where the sky explains the pixel), v_E is left in the map and — unless it has to be summed over the ranks first
+    // (step_grad_exchange, step_update) — the table takes its Adam step
+    if (p.envmap) {
+        ProfScope ps(ctx, "EnvMap");
+        BH_TRY(launch_envmap_backward(ctx, p.envmap, batch->camera, w.ro.out_img, w.v_output, p.H, p.W, w.v_output, /*update=*/!p.exchanging, a.grad_scale,
+                                      /*check_host=*/false));
     }
     return 0;
 }
@@ -516,6 +544,11 @@ int step_grad_exchange(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWo
         ProfScope ps(ctx, "FeatureExchange");
         BH_TRY(sum_over_ranks(ctx, a, w.v_features, (uint64_t)p.n * ctx->terms.feature_field.channels));
     }
+    // ... and the environment map's v_E by one more: 6 R R 3 floats (brush_hip_envmap.h)
+    if (p.envmap && p.exchanging) {
+        ProfScope ps(ctx, "EnvMapExchange");
+        BH_TRY(sum_over_ranks(ctx, a, envmap_grad(p.envmap), envmap_floats(p.envmap)));
+    }
     return 0;
 }
 
@@ -553,6 +586,7 @@ int step_update(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork& w) 
             BH_TRY(launch_adam(ctx, ff.features, w.v_features, ff.m1, ff.m2, n, ff.channels, nullptr, ff.lr, ff.step + 1, false, ff.beta1, ff.beta2, ff.eps, a.grad_scale));
             ff.step += 1;
         }
+        if (p.envmap && p.exchanging) BH_TRY(launch_envmap_adam(ctx, p.envmap, a.grad_scale));   // the map's step on grad_scale * the summed v_E
     }
     st->step_count = p.step;   // the update is queued: the step counts
     if (noise_on && !noise_fused) {

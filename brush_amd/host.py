@@ -1282,6 +1282,109 @@ class ExposureTable(_ViewTable):
         return out
 
 
+class EnvironmentMap:
+    """A learned cubemap E[6,R,R,3] f32 behind the splats (include/brush_hip_envmap.h): what the splats leave
+    uncovered shows the map along the pixel's world ray, out = img + (1 - alpha) E(d), with the exact integer gradient to the table, its
+    Adam moments (f32) and the update on the device.  Faces are +X, -X, +Y, -Y, +Z, -Z in world axes, the library's own table (no
+    OpenGL flips); pinhole cameras only.  A new map is black.  Nothing here reads back except the getters (`params`, `grads`
+    [6,R,R,3] f32, `state` (m1, m2 [6,R,R,3] f32, t)) and `backward`, which fetches four bytes to refuse a cotangent that is not
+    finite.  SplatTrainer(envmap=map) attaches it to the train step."""
+
+    def __init__(self, resolution=64, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15, ctx: Optional[Context] = None):
+        ctx = ctx or get_context()
+        self.ctx, self.lib, self.resolution = ctx, ctx.lib, int(resolution)
+        self.shape = (6, self.resolution, self.resolution, 3)
+        h = C.c_void_p()
+        ctx.check(self.lib.bh_envmap_create(ctx._h, self.resolution, C.byref(h)))
+        self._h = h
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
+        self.set_lr(lr)
+
+    def set_lr(self, lr):
+        """The learning rate of every following update (bh_envmap_set_adam); 0 freezes the table while its moments still move."""
+        self.ctx.check(self.lib.bh_envmap_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
+        self.lr = float(lr)
+
+    def _get(self, fn):
+        import numpy as np
+        out = np.empty(self.shape, np.float32)
+        self.ctx.check(fn(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def _cells(self, a, what):
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        if a.shape != self.shape:
+            raise ValueError("%s must be [6, %d, %d, 3]" % (what, self.resolution, self.resolution))
+        return a
+
+    @property
+    def params(self):
+        """[6,R,R,3] f32 numpy copy of the table (one synchronisation); assign an array of the same shape to set it."""
+        return self._get(self.lib.bh_envmap_get_params)
+
+    @params.setter
+    def params(self, value):
+        a = self._cells(value, "params")
+        self.ctx.check(self.lib.bh_envmap_set_params(self.ctx._h, self._h, a.ctypes.data_as(C.POINTER(C.c_float))))
+
+    @property
+    def grads(self):
+        """[6,R,R,3] f32: v_E of the last backward (or train step) on the map; zeros before the first."""
+        return self._get(self.lib.bh_envmap_get_grad)
+
+    def state(self):
+        """(m1, m2 [6,R,R,3] f32, t): the Adam moments and the step count."""
+        import numpy as np
+        m1, m2, t = np.empty(self.shape, np.float32), np.empty(self.shape, np.float32), C.c_uint32()
+        p = C.POINTER(C.c_float)
+        self.ctx.check(self.lib.bh_envmap_get_state(self.ctx._h, self._h, m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
+        return m1, m2, int(t.value)
+
+    def set_state(self, m1, m2, t):
+        """Puts the Adam state back (resuming from a checkpoint)."""
+        a, b = self._cells(m1, "m1"), self._cells(m2, "m2")
+        p = C.POINTER(C.c_float)
+        self.ctx.check(self.lib.bh_envmap_set_state(self.ctx._h, self._h, a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+
+    @staticmethod
+    def _camera(camera, img):
+        return camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((int(img.shape[1]), int(img.shape[0])))
+
+    def composite(self, img, camera, out=None):
+        """`img` [H,W,4] f32 (rendered on black) over the map as `camera` (a Camera or a BhCamera) sees it; `out` may be `img`."""
+        img = _aligned_hwc4(img, img.device)
+        out = _hwc4_out(img, out)
+        cam = self._camera(camera, img)
+        self.ctx.check(self.lib.bh_envmap_composite(self.ctx._h, self._h, C.byref(cam), _ptr(img), int(img.shape[0]), int(img.shape[1]), _ptr(out)))
+        return out
+
+    def backward(self, img, camera, v, update=False, out=None):
+        """The gradient to the frame of the cotangent `v` on composite(img, camera) (`out` may be `v`), grads = v_E, and with
+        `update` one Adam step of the table on it.  A `v` whose rgb holds a NaN or an infinity is refused and nothing is written."""
+        img = _aligned_hwc4(img, img.device)
+        v = _aligned_hwc4(v, img.device)
+        if v.shape != img.shape:
+            raise ValueError("v must have the shape of img")
+        out = _hwc4_out(img, out)
+        cam = self._camera(camera, img)
+        self.ctx.check(self.lib.bh_envmap_backward(self.ctx._h, self._h, C.byref(cam), _ptr(img), _ptr(v), int(img.shape[0]), int(img.shape[1]), _ptr(out),
+                                                   1 if update else 0))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):   # (a closed context has freed its maps)
+                self.lib.bh_envmap_destroy(self.ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class BilateralGridTable(_ViewTable):
     """A device table of one bilateral grid per training view: g[Hg,Wg,L,12] f32, a grid of row-major 3x4 colour matrices looked up
     by trilinear interpolation at (x, y, luminance) and applied to the rasterizer's image before the loss, with its Adam moments
@@ -2132,7 +2235,8 @@ class SplatTrainer:
                  partition: str = "cameras", native_comm: bool = False, sparse_exchange: bool = True, seed: Optional[int] = None,
                  allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None,
                  exposure: Optional["ExposureTable"] = None, exposure_lr=None, bilagrid: Optional["BilateralGridTable"] = None, bilagrid_lr=None,
-                 bilagrid_tv_weight: float = 10.0, feature_field: Optional["FeatureField"] = None):
+                 bilagrid_tv_weight: float = 10.0, envmap: Optional["EnvironmentMap"] = None, envmap_lr=None,
+                 feature_field: Optional["FeatureField"] = None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -2166,7 +2270,12 @@ class SplatTrainer:
         (SceneBatch.features), at config.feature_loss_weight > 0 and from config.feature_loss_from_iter on, blends the field's
         map, adds the fused feature loss, backpropagates it into the field AND the splats and updates the field on the device
         (no readback); `refine` carries the field's rows through the plan.  Not with partition "tiles" and not together with
-        `pose_optimizer`."""
+        `pose_optimizer`.
+
+        envmap: an EnvironmentMap (bh_train_set_envmap): every step composites its frame over the map before the loss (an exposure
+        table or a bilateral grid then act on the composited frame) and updates the map on the device.  The frame is rendered on
+        black: config.background_color must be (0, 0, 0) and the background jitter is not drawn.  envmap_lr: an optional callable of
+        the step number (from 1), as exposure_lr.  Not with partition "tiles" and not together with `pose_optimizer`."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if pose_optimizer is not None and partition == "tiles":
@@ -2177,6 +2286,13 @@ class SplatTrainer:
             raise ValueError("feature_field is not available with partition 'tiles'")
         if feature_field is not None and pose_optimizer is not None:
             raise ValueError("feature_field and pose_optimizer cannot be combined (the pose pass does not carry the feature term's gradient)")
+        if envmap is not None and partition == "tiles":
+            raise ValueError("envmap is not available with partition 'tiles'")
+        if envmap is not None and any(float(b) != 0.0 for b in config.background_color):
+            raise ValueError("envmap needs background_color (0, 0, 0): the map is what lies behind the splats")
+        if envmap is not None and pose_optimizer is not None:
+            raise ValueError("envmap and pose_optimizer cannot be combined (the pose pass does not carry the lookup's dependence on the rotation)")
+        self.envmap, self.envmap_lr = envmap, envmap_lr
         self.feature_field = feature_field
         self.pose_optimizer = pose_optimizer
         self._pose_buf = None
@@ -2439,6 +2555,11 @@ class SplatTrainer:
             if self.bilagrid_lr is not None:
                 terms.append(lambda: grid.set_lr(self.bilagrid_lr(step)))
             terms.append((lib.bh_train_set_bilagrid, (grid._h, self.bilagrid_tv_weight), (None, 0.0)))
+        env = self.envmap
+        if env is not None:
+            if self.envmap_lr is not None:
+                terms.append(lambda: env.set_lr(self.envmap_lr(step)))
+            terms.append((lib.bh_train_set_envmap, (env._h,), off))
         return terms, (dgt, ftgt), ft
 
     @staticmethod
@@ -2475,7 +2596,9 @@ class SplatTrainer:
         gt = _as_u32(batch.img_packed, dev)
         b.gt_packed = gt.data_ptr()
         b.has_alpha, b.alpha_is_mask = int(batch.has_alpha), int(batch.alpha_is_mask)
-        bg = background if background is not None else (self.sample_background() if self.seed is not None else self.config.background_color)
+        # (an environment map is what lies behind the splats: its trainer's base colour is black and the jitter is not drawn)
+        jitter = self.seed is not None and self.envmap is None
+        bg = background if background is not None else (self.sample_background() if jitter else self.config.background_color)
         b.background[0], b.background[1], b.background[2] = [float(v) for v in bg]
         ns = None
         if noise_samples is not None:
@@ -3099,12 +3222,14 @@ def eval_stats(splats: "Splats", camera, gt_packed, ctx: Optional[Context] = Non
     return EvalSample(mse=mse, psnr=psnr, ssim=ssim, metrics=metrics, image=rgb8)
 
 
-def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images=False) -> EvalResult:
+def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images=False, envmap: Optional["EnvironmentMap"] = None) -> EvalResult:
     """run_eval (train_stream.rs:506-566): eval_stats of every held-out view, the per-view PSNR and SSIM averaged in f32 (not the
     PSNR of a mean MSE).  `views` has compute_pup_scores' shape: (image uint8 [H,W,3|4] or a callable returning one, Camera[,
     alpha_is_mask[, depth]]), packed through a BatchUploader.  Every view's metrics go to its row of one device table; one readback at
     the end.  `depth`: the view's depth map [H,W] f32, or a dict(depth=, kind="l1", scale=1.0, offset=0.0): such a view is also
-    rendered differentiably for its expected depth and scored by eval_depth_metrics (EvalResult.depth_per_view)."""
+    rendered differentiably for its expected depth and scored by eval_depth_metrics (EvalResult.depth_per_view).  `envmap`: the scene's
+    EnvironmentMap: every view is then rendered on black (render_splats), composited over the map and scored by eval_metrics; the
+    3D-filter floor bh_eval_view folds in is not applied on that path."""
     import numpy as np
     dev = splats.device
     ctx = ctx or get_context(dev)
@@ -3127,7 +3252,12 @@ def run_eval(splats: "Splats", views, ctx: Optional[Context] = None, keep_images
             slot = up.submit(img, premultiply=not mask)
             gt, _ = up.acquire(slot)
             rgb8 = torch.empty(tuple(gt.shape), dtype=torch.int32, device=dev) if keep_images else None
-            _eval_view(ctx, splats, view[1], gt, table[i], rgb8)
+            if envmap is None:
+                _eval_view(ctx, splats, view[1], gt, table[i], rgb8)
+            else:
+                frame, _ = render_splats(splats, view[1], (img.shape[1], img.shape[0]), (0.0, 0.0, 0.0), RasterPass.Backward, ctx=ctx)
+                scored = eval_metrics(envmap.composite(frame, view[1], out=frame), gt, ctx=ctx, keep_image=keep_images, out=table[i])
+                rgb8 = scored[1] if keep_images else None
             up.release(slot)
             if keep_images:
                 images.append(rgb8)

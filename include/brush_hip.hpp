@@ -50,6 +50,9 @@
 //   brush_hip::LiftAccumulator / compact_splats      not in the reference: mask lifting (per-splat blend-weight votes from 2-D label
 //                                                   maps, the largest weight and the pixel count, argmax / threshold, compaction;
 //                                                   brush_hip_lift.h)
+//   brush_hip::EnvironmentMap / train_set_envmap  not in the reference: environment maps (a learned cubemap behind the splats,
+//                                                   composited behind the frame before the loss, Adam on the device;
+//                                                   brush_hip_envmap.h)
 //   Context::comm_* / allreduce_* / exchange_strip_halos   not in the reference: RCCL behind the C ABI
 //
 // Errors are exceptions (brush_hip::Error carrying bh_last_error) where the reference panics.  Device memory is
@@ -89,6 +92,7 @@
 #include "brush_hip_feature_train.h"
 #include "brush_hip_scene.h"
 #include "brush_hip_lift.h"
+#include "brush_hip_envmap.h"
 
 namespace brush_hip {
 
@@ -1472,6 +1476,72 @@ private:
 // bh_train_step on this ctx exposes its frame with the row of the batch's view_id and updates that row; nullptr detaches
 inline void train_set_exposure(const Context& ctx, const ExposureTable* table) {
     ctx.check(bh_train_set_exposure(ctx.get(), table ? table->get() : nullptr));
+}
+
+// ---- environment maps (brush_hip_envmap.h; not in the reference) ------------------------------------------------------
+// A device cubemap E[6][R][R][3] behind the splats with Adam on the device (bh_envmap_*): faces +X -X +Y -Y +Z -Z in world axes, pinhole
+// cameras only, black when new.  Move-only; destroy it before its Context (a Context that dies first frees the map itself, and this
+// handle must then not be used).  Only the getters read back, and backward (four bytes, to refuse a cotangent that is not finite).
+class EnvironmentMap {
+public:
+    EnvironmentMap(const Context& ctx, uint32_t resolution = 64, double lr = 1e-3, double beta1 = 0.9, double beta2 = 0.999, double eps = 1e-15)
+        : ctx_(&ctx), res_(resolution), beta1_(beta1), beta2_(beta2), eps_(eps) {
+        ctx.check(bh_envmap_create(ctx.get(), resolution, &h_));
+        set_lr(lr);
+    }
+    EnvironmentMap(const EnvironmentMap&) = delete;
+    EnvironmentMap& operator=(const EnvironmentMap&) = delete;
+    EnvironmentMap(EnvironmentMap&& o) noexcept : ctx_(o.ctx_), h_(o.h_), res_(o.res_), beta1_(o.beta1_), beta2_(o.beta2_), eps_(o.eps_) { o.h_ = nullptr; }
+    ~EnvironmentMap() { if (h_) (void)bh_envmap_destroy(ctx_->get(), h_); }
+    bh_envmap* get() const { return h_; }
+    uint32_t resolution() const { return res_; }
+    size_t floats() const { return (size_t)6 * res_ * res_ * 3; }
+    void set_lr(double lr) { ctx_->check(bh_envmap_set_adam(ctx_->get(), h_, lr, beta1_, beta2_, eps_)); }
+    // the table and its last gradient, [6,R,R,3] on the host (one synchronisation each)
+    std::vector<float> params() const {
+        std::vector<float> out(floats());
+        ctx_->check(bh_envmap_get_params(ctx_->get(), h_, out.data()));
+        return out;
+    }
+    std::vector<float> grads() const {
+        std::vector<float> out(floats());
+        ctx_->check(bh_envmap_get_grad(ctx_->get(), h_, out.data()));
+        return out;
+    }
+    void set_params(const std::vector<float>& table) {
+        if (table.size() != floats()) throw Error(BH_ERR_INVALID_ARG, "EnvironmentMap::set_params: the table must hold 6 R R 3 floats");
+        ctx_->check(bh_envmap_set_params(ctx_->get(), h_, table.data()));
+    }
+    struct State { std::vector<float> m1, m2; uint32_t t = 0; };
+    State state() const {
+        State s;
+        s.m1.resize(floats());
+        s.m2.resize(floats());
+        ctx_->check(bh_envmap_get_state(ctx_->get(), h_, s.m1.data(), s.m2.data(), &s.t));
+        return s;
+    }
+    void set_state(const State& s) {
+        if (s.m1.size() != floats() || s.m2.size() != floats()) throw Error(BH_ERR_INVALID_ARG, "EnvironmentMap::set_state: the moments must hold 6 R R 3 floats");
+        ctx_->check(bh_envmap_set_state(ctx_->get(), h_, s.m1.data(), s.m2.data(), s.t));
+    }
+    // out = img [h,w,4] (device, rendered on black) over the map as `cam` sees it; out may be img
+    void composite(const BhCamera& cam, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) const {
+        ctx_->check(bh_envmap_composite(ctx_->get(), h_, &cam, img_hwc4, h, w, out_hwc4));
+    }
+    // v_img = the gradient to the frame (may be in place), grads = v_E, and with `update` one Adam step of the table
+    void backward(const BhCamera& cam, const float* img_hwc4, const float* v_out, uint32_t h, uint32_t w, float* v_img, bool update = false) {
+        ctx_->check(bh_envmap_backward(ctx_->get(), h_, &cam, img_hwc4, v_out, h, w, v_img, update ? 1 : 0));
+    }
+
+private:
+    const Context* ctx_;
+    bh_envmap* h_ = nullptr;
+    uint32_t res_;
+    double beta1_, beta2_, eps_;
+};
+// bh_train_step on this ctx composites its frame over the map before the loss and updates the map; nullptr detaches
+inline void train_set_envmap(const Context& ctx, const EnvironmentMap* map) {
+    ctx.check(bh_train_set_envmap(ctx.get(), map ? map->get() : nullptr));
 }
 
 // ---- per-view bilateral grids (brush_hip_bilagrid.h; not in the reference) ----------------------------------------------------------
