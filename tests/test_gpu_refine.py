@@ -13,6 +13,8 @@ import torch
 from brush_amd import synth
 from oracle import refine as orf
 
+import refine_ref as rr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -72,11 +74,15 @@ def test_refine_matches_oracle_given_the_same_choices(dev, deg, iter_, max_splat
     assert int(stage1.sum()) == k1 and not (stage1 & ~split).any()
     assert rs.num_split_oversized == min(budget, int((bc["oversized"] & ~stage1).sum()))
     growing = iter_ < min(tr.config.growth_stop_iter, tr.config.total_train_iters)
+    # for a given seed the sample itself is specified (tests/refine_ref.py): the stage-3 counts are equalities, not only bounded
+    rp = rr.plan(dict(transforms=sc["transforms"], sh=sc["sh"], raw_opac=sc["raw_opac"], **{k: host[k] for k in ("refine_weight_norm", "vis_weight", "max_screen_size")}),
+                 dict(rcfg, bounds_center=bounds[0], bounds_extent=bounds[1], max_splats=max_splats,
+                      growth_stop_iter=min(tr.config.growth_stop_iter, tr.config.total_train_iters)), 1234)
     if growing:
         headroom = max(0, max_splats - (bc["n_keep"] + k1 + rs.num_split_oversized))
         k3 = min(max(0, bc["grow_count"] - bc["pruned"]), headroom, int(bc["above"].sum()))
-        assert rs.num_split_high_grad <= k3
-        assert rs.num_added >= max(k1, rs.num_split_oversized) and rs.num_added <= k1 + rs.num_split_oversized + k3
+        assert rs.num_split_high_grad == rp["stats"]["num_split_high_grad"] <= k3 == rp["k3"]
+        assert rs.num_added >= max(k1, rs.num_split_oversized) and rs.num_added == rp["stats"]["num_added"] <= k1 + rs.num_split_oversized + k3
     else:
         assert rs.num_split_high_grad == 0
     assert rs.num_added == int(split.sum()) and rs.total_splats == bc["n_keep"] + rs.num_added == new.num_splats()
