@@ -11,7 +11,7 @@
 
 #include "context.h"
 #include "device_rng.h"
-#include "view_table.h"
+#include "param_table.h"
 
 namespace bh {
 
@@ -289,8 +289,7 @@ void bh_destroy(bh_ctx* ctx) {
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
     if (ctx->image_tab_host) (void)hipHostFree(ctx->image_tab_host);
     if (ctx->image_tab_ev) (void)hipEventDestroy(ctx->image_tab_ev);
-    bh::view_tables_free_all(ctx);
-    bh::envmaps_free_all(ctx);
+    bh::param_tables_free_all(ctx);
     if (ctx->comm) (void)bh_comm_destroy(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

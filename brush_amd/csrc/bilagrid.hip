@@ -8,11 +8,11 @@
 //   bilagrid_final_kernel     per grid element: the units' partial rows in index order + the TV gradient -> grad and the f64 sum
 //   bilagrid_step_kernel      Adam on the f64 sum (a launch of its own: the TV gradient above reads neighbouring parameters)
 //   bilagrid_tv_kernel        TV of a row, one block, f64
-// The table itself — a bh_bilagrid is a ViewTable of rows of gh gw gl 12 with f32 moments, plus the grid's sides — and every entry
-// point that only manages it are view_table.h's; the wave butterfly and the Adam step are device_f64_sum.h's.
+// The table itself — a bh_bilagrid is a ParamTable of rows of gh gw gl 12 with f32 moments, plus the grid's sides — and every entry
+// point that only manages it are param_table.h's, shared with exposure.hip and envmap.hip; the wave butterfly and the Adam step are device_f64_sum.h's.
 #include "../../include/brush_hip_bilagrid.h"
 #include "device_f64_sum.h"
-#include "view_table.h"
+#include "param_table.h"
 
 namespace bh {
 
@@ -429,12 +429,6 @@ int launch_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* tab, uint32_t view, const
     return 0;
 }
 
-static int check_image(bh_ctx* ctx, uint32_t h, uint32_t w, const char* who) {
-    if (h == 0 || w == 0) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": an image of zero size");
-    if ((uint64_t)h * w > 0x7FFFFFFFull) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": h * w must stay below 2^31");
-    return 0;
-}
-
 }  // namespace bh
 
 using namespace bh;
@@ -442,22 +436,22 @@ using namespace bh;
 extern "C" {
 
 int bh_bilagrid_create(bh_ctx* ctx, uint32_t n_views, uint32_t grid_w, uint32_t grid_h, uint32_t grid_l, bh_bilagrid** table) {
-    BH_TRY(view_table_create_args(ctx, table, n_views, "bilagrid_create"));
+    BH_TRY(param_table_create_args(ctx, table, n_views, "bilagrid_create"));
     if (grid_w == 0 || grid_h == 0 || grid_l == 0 || grid_w > 1024u || grid_h > 1024u || grid_l > 1024u ||
         (uint64_t)grid_w * grid_h * grid_l * 12u > (1ull << 22))
         return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_create: grid sides must be 1 .. 1024 and a view at most 2^22 floats");
-    ViewTable* tab = nullptr;
-    BH_TRY(view_table_create(ctx, VT_BILAGRID, n_views, (size_t)grid_w * grid_h * grid_l * 12, "bilagrid_create", &tab));
-    *table = static_cast<bh_bilagrid*>(tab);
-    (*table)->gw = grid_w; (*table)->gh = grid_h; (*table)->gl = grid_l;
+    bh_bilagrid* tab = new bh_bilagrid;
+    BH_TRY(param_table_create(ctx, tab, n_views, (size_t)grid_w * grid_h * grid_l * 12, 0, &COLOUR_IDENTITY, "bilagrid_create"));
+    tab->gw = grid_w; tab->gh = grid_h; tab->gl = grid_l;
+    *table = tab;
     return 0;
 }
 
-int bh_bilagrid_destroy(bh_ctx* ctx, bh_bilagrid* table) { return view_table_destroy(ctx, VT_BILAGRID, table, "bilagrid_destroy"); }
+int bh_bilagrid_destroy(bh_ctx* ctx, bh_bilagrid* table) { return param_table_destroy(ctx, PT_BILAGRID, table, "bilagrid_destroy"); }
 
 int bh_bilagrid_dims(bh_ctx* ctx, bh_bilagrid* table, uint32_t* n_views, uint32_t* grid_w, uint32_t* grid_h, uint32_t* grid_l) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(check_rows(ctx, VT_BILAGRID, table, 1, 1, "bilagrid_dims"));
+    BH_TRY(check_rows(ctx, PT_BILAGRID, table, 1, 1, "bilagrid_dims"));
     if (n_views) *n_views = table->n_views;
     if (grid_w) *grid_w = table->gw;
     if (grid_h) *grid_h = table->gh;
@@ -466,34 +460,34 @@ int bh_bilagrid_dims(bh_ctx* ctx, bh_bilagrid* table, uint32_t* n_views, uint32_
 }
 
 int bh_bilagrid_set_params(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, const float* host) {
-    return view_table_set_params(ctx, VT_BILAGRID, table, first_view, count, host, "bilagrid_set_params");
+    return param_table_set_params(ctx, PT_BILAGRID, table, first_view, count, host, "bilagrid_set_params");
 }
 
 int bh_bilagrid_get_params(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, float* host) {
-    return view_table_get_rows(ctx, VT_BILAGRID, table, &ViewTable::param, first_view, count, host, "bilagrid_get_params");
+    return param_table_get_rows(ctx, PT_BILAGRID, table, &ParamTable::param, first_view, count, host, "bilagrid_get_params");
 }
 
 int bh_bilagrid_get_grad(bh_ctx* ctx, bh_bilagrid* table, uint32_t first_view, uint32_t count, float* host) {
-    return view_table_get_rows(ctx, VT_BILAGRID, table, &ViewTable::grad, first_view, count, host, "bilagrid_get_grad");
+    return param_table_get_rows(ctx, PT_BILAGRID, table, &ParamTable::grad, first_view, count, host, "bilagrid_get_grad");
 }
 
 int bh_bilagrid_get_state(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, float* m1, float* m2, uint32_t* t) {
-    return view_table_get_state(ctx, VT_BILAGRID, table, view, m1, m2, t, "bilagrid_get_state");
+    return param_table_get_state(ctx, PT_BILAGRID, table, view, m1, m2, t, "bilagrid_get_state");
 }
 
 int bh_bilagrid_set_state(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const float* m1, const float* m2, uint32_t t) {
-    return view_table_set_state(ctx, VT_BILAGRID, table, view, m1, m2, t, "bilagrid_set_state");
+    return param_table_set_state(ctx, PT_BILAGRID, table, view, m1, m2, t, "bilagrid_set_state");
 }
 
 int bh_bilagrid_set_adam(bh_ctx* ctx, bh_bilagrid* table, double lr, double beta1, double beta2, double eps) {
-    return view_table_set_adam(ctx, VT_BILAGRID, table, lr, beta1, beta2, eps, "bilagrid_set_adam");
+    return param_table_set_adam(ctx, PT_BILAGRID, table, lr, beta1, beta2, eps, "bilagrid_set_adam");
 }
 
 int bh_bilagrid_slice(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !out_hwc4) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_slice: null argument");
-    BH_TRY(check_image(ctx, h, w, "bilagrid_slice"));
-    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_slice"));
+    BH_TRY(check_image(ctx, h, w, /*below_2_31=*/true, "bilagrid_slice"));
+    BH_TRY(check_rows(ctx, PT_BILAGRID, table, view, 1, "bilagrid_slice"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_slice(ctx, table, view, img_hwc4, h, w, out_hwc4);
 }
@@ -502,9 +496,9 @@ int bh_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const f
                          float* v_img, float tv_weight, int update) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !v_sliced || !v_img) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_backward: null argument");
-    BH_TRY(check_image(ctx, h, w, "bilagrid_backward"));
+    BH_TRY(check_image(ctx, h, w, /*below_2_31=*/true, "bilagrid_backward"));
     if (!(tv_weight >= 0.0f) || !std::isfinite(tv_weight)) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_backward: tv_weight must be finite and >= 0");
-    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_backward"));
+    BH_TRY(check_rows(ctx, PT_BILAGRID, table, view, 1, "bilagrid_backward"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_backward(ctx, table, view, img_hwc4, v_sliced, h, w, v_img, tv_weight, update != 0);
 }
@@ -512,14 +506,14 @@ int bh_bilagrid_backward(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, const f
 int bh_bilagrid_tv(bh_ctx* ctx, bh_bilagrid* table, uint32_t view, float* value_dev) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!value_dev) return set_error(ctx, BH_ERR_INVALID_ARG, "bilagrid_tv: null argument");
-    BH_TRY(check_rows(ctx, VT_BILAGRID, table, view, 1, "bilagrid_tv"));
+    BH_TRY(check_rows(ctx, PT_BILAGRID, table, view, 1, "bilagrid_tv"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_bilagrid_tv(ctx, table, view, value_dev, 0.0f, nullptr, nullptr);
 }
 
 int bh_train_set_bilagrid(bh_ctx* ctx, bh_bilagrid* table, float tv_weight) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(view_table_attachable(ctx, VT_BILAGRID, table, "train_set_bilagrid"));
+    BH_TRY(param_table_attachable(ctx, PT_BILAGRID, table, "train_set_bilagrid"));
     if (table && (!(tv_weight >= 0.0f) || !std::isfinite(tv_weight)))
         return set_error(ctx, BH_ERR_INVALID_ARG, "train_set_bilagrid: tv_weight must be finite and >= 0");
     ctx->terms.bilagrid = table;

@@ -383,9 +383,9 @@ struct NormalTerm {
     uint32_t mode = 0;                 // BH_NORMAL_ACCUMULATED or BH_NORMAL_UNIT
 };
 
-// The distortion term of a backward (distortion.hip, brush_hip_distortion.h): <v_distortion, dist of the forward>
-struct ViewTable;   // view_table.h: the host core of bh_exposure and bh_bilagrid
+struct ParamTable;   // param_table.h: the host core of bh_exposure, bh_bilagrid and bh_envmap
 
+// The distortion term of a backward (distortion.hip, brush_hip_distortion.h): <v_distortion, dist of the forward>
 struct DistortionTerm {
     const float* v_distortion = nullptr;   // [H,W], or NULL: the uniform cotangent `gain` at every pixel
     float gain = 0.0f;
@@ -482,8 +482,7 @@ struct bh_ctx {
     size_t image_tab_cap = 0;
     hipEvent_t image_tab_ev = nullptr; // ... free again once this event (behind their copy) has completed
     bh::StepTerms terms;              // what the bh_train_set_* calls attached to the next train steps (train.hip)
-    std::vector<bh::ViewTable*> view_tables;   // every per-view table of this ctx, of either kind (view_table.h): bh_destroy frees what is left
-    std::vector<bh_envmap*> envmaps;  // every environment map of this ctx (envmap.hip): bh_destroy frees what is left
+    std::vector<bh::ParamTable*> param_tables;   // every learned table of this ctx, of any kind (param_table.h): bh_destroy frees what is left
     void* comm = nullptr;             // RCCL communicator (comm.hip), or NULL
     // the library communicator's side stream: the mask-keyed exchange sums the visible flags and lists their union there,
     // beside the backward on the ctx stream (train.hip); comm_ev marks "the forward is done" for it
@@ -664,15 +663,12 @@ float* bilagrid_tv_scratch(bh_ctx* ctx);   // four floats of SLOT_BILAGRID for t
 // envmap.hip: out = img over the map seen through `cam`, and its backward: v_img (in place allowed), the map's gradient = v_E and — when
 // `update` — one Adam step of the table on gscale * v_E (brush_hip_envmap.h).  Camera and image size are already checked.  A
 // non-finite max |v_out|: check_host reads it back and refuses; otherwise the kernels behind the max pass do nothing.  launch_envmap_adam:
-// the step alone, on the gradient as it stands (the train step sums it over the ranks first).  envmaps_free_all: bh_destroy.
+// the step alone, on the gradient as it stands (the train step sums it over the ranks first).
 int check_envmap_frame(bh_ctx* ctx, const BhCamera* cam, uint32_t h, uint32_t w, const char* who);
 int launch_envmap_composite(bh_ctx* ctx, const bh_envmap* map, const BhCamera& cam, const float* img, uint32_t h, uint32_t w, float* out);
 int launch_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera& cam, const float* img, const float* v_out, uint32_t h, uint32_t w, float* v_img,
                            bool update, float gscale, bool check_host);
 int launch_envmap_adam(bh_ctx* ctx, bh_envmap* map, float gscale);
-uint64_t envmap_floats(const bh_envmap* map);
-float* envmap_grad(const bh_envmap* map);
-void envmaps_free_all(bh_ctx* ctx);
 // lists.hip — the per-tile cut-list policy (BH_FLAG_SLICED_LISTS, automatic mode) and the far job
 // The state of the view a frame of `req` renders (created on first use), or nullptr: a forward-only frame (casual) without a view
 // id whose camera is new, or a failed allocation.  A second attempt (!req.allow_cut) leaves the view's gap and LRU stamp alone.

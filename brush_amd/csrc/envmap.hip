@@ -19,26 +19,9 @@
 //                             the rest straight to memory.
 //   envmap_final_kernel       v_E = the integer sums / S, and the Adam step of every texel
 // Integer sums and an unsigned maximum: nothing depends on the order in which lanes, waves or blocks arrive.
-#include <algorithm>
-#include <cmath>
-#include <string>
-
-#include "context.h"
-
-struct bh_envmap {
-    uint32_t res = 0;
-    size_t cells = 0;                  // 6 R R 3
-    void* mem = nullptr;               // one allocation: acc | ctl | param | grad | m1 | m2 | t_dev (acc and ctl are cleared by one fill)
-    unsigned long long* acc = nullptr; // [cells] the quantised sums of the backward in flight
-    float* param = nullptr;            // [cells]
-    float* grad = nullptr;             // [cells]
-    float* m1 = nullptr;               // [cells]
-    float* m2 = nullptr;               // [cells]
-    uint32_t* ctl = nullptr;           // [4]: [0] the bits of m of the backward in flight
-    uint32_t* t_dev = nullptr;         // [4]: [0] t, as of the last update queued
-    uint32_t t = 0;                    // the step count (the host's copy is the one the updates are computed from)
-    double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, eps = 1e-15;   // passed to the update by value
-};
+// The table itself — a bh_envmap is a ParamTable of one row of 6 R R 3 with f32 moments, plus the sums and the maximum's word of the
+// backward in flight — and every entry point that only manages it are param_table.h's, shared with exposure.hip and bilagrid.hip.
+#include "param_table.h"
 
 namespace bh {
 
@@ -307,11 +290,11 @@ double pow_by_squaring(double b, uint32_t t) {
     return p;
 }
 
-// the update of step map->t + 1 on the gradient as it stands (dequant: as the sums say); the map counts it once it is queued
+// the update of step map->t_host + 1 on the gradient as it stands (dequant: as the sums say); the map counts it once it is queued
 int launch_final(bh_ctx* ctx, bh_envmap* map, uint32_t log_pixels, bool dequant, bool adam, float gscale) {
     EnvAdam a{};
     if (adam) {
-        a.t = map->t + 1u;
+        a.t = map->t_host + 1u;
         a.lr = (float)map->lr; a.beta1 = (float)map->beta1; a.beta2 = (float)map->beta2;
         a.omb1 = (float)(1.0 - map->beta1); a.omb2 = (float)(1.0 - map->beta2);
         a.eps = (float)map->eps;
@@ -319,46 +302,18 @@ int launch_final(bh_ctx* ctx, bh_envmap* map, uint32_t log_pixels, bool dequant,
         a.c2 = (float)(1.0 - pow_by_squaring(map->beta2, a.t));
         a.gscale = gscale;
     }
-    hipLaunchKernelGGL(envmap_final_kernel, dim3(stream_grid(map->cells)), dim3(ENV_WG), 0, ctx->stream, (uint32_t)map->cells, log_pixels, dequant ? 1 : 0,
-                       adam ? 1 : 0, a, map->ctl, map->t_dev, map->acc, map->grad, map->param, map->m1, map->m2);
+    hipLaunchKernelGGL(envmap_final_kernel, dim3(stream_grid(map->row)), dim3(ENV_WG), 0, ctx->stream, (uint32_t)map->row, log_pixels, dequant ? 1 : 0,
+                       adam ? 1 : 0, a, map->ctl, map->t, map->acc, map->grad, map->param, static_cast<float*>(map->m1), static_cast<float*>(map->m2));
     BH_LAUNCH_CHECK(ctx, "envmap_final_kernel");
-    if (adam) map->t = a.t;
+    if (adam) map->t_host = a.t;
     return 0;
-}
-
-int envmap_owned(bh_ctx* ctx, const bh_envmap* map, const char* who) {
-    if (!map || std::find(ctx->envmaps.begin(), ctx->envmaps.end(), map) == ctx->envmaps.end())
-        return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": not an environment map of this context");
-    return 0;
-}
-
-void envmap_free(bh_envmap* map) {
-    if (map->mem) (void)hipFree(map->mem);
-    delete map;
-}
-
-int settle(bh_ctx* ctx) {
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    deliver_pending_loss(ctx);
-    return 0;
-}
-
-// get_params / get_grad: `which` is &bh_envmap::param or &bh_envmap::grad
-int read_cells(bh_ctx* ctx, const bh_envmap* map, float* bh_envmap::*which, float* host, const char* who) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!host) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    BH_TRY(envmap_owned(ctx, map, who));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemcpyAsync(host, map->*which, map->cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return settle(ctx);
 }
 
 }  // namespace
 
 int check_envmap_frame(bh_ctx* ctx, const BhCamera* cam, uint32_t h, uint32_t w, const char* who) {
     if (!cam) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (h == 0 || w == 0) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": an image of zero size");
-    if ((uint64_t)h * w > 0x7FFFFFFFull) return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": h * w must stay below 2^31");
+    BH_TRY(check_image(ctx, h, w, /*below_2_31=*/true, who));
     if (cam->model != BH_CAMERA_PINHOLE)
         return set_error(ctx, BH_ERR_INVALID_ARG, std::string(who) + ": an environment map needs a pinhole camera (no other model can be unprojected to a ray)");
     return 0;
@@ -374,13 +329,12 @@ int launch_envmap_composite(bh_ctx* ctx, const bh_envmap* map, const BhCamera& c
 int launch_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera& cam, const float* img, const float* v_out, uint32_t h, uint32_t w, float* v_img,
                            bool update, float gscale, bool check_host) {
     const uint32_t pixels = h * w, log_pixels = ceil_log2(pixels);
-    BH_HIP(ctx, hipMemsetAsync(map->acc, 0, map->cells * 8 + 16, ctx->stream));   // the sums and, behind them, the maximum's word
+    BH_HIP(ctx, hipMemsetAsync(map->acc, 0, map->row * 8 + 16, ctx->stream));   // the sums and, behind them, the maximum's word
     hipLaunchKernelGGL(envmap_max_kernel, dim3(std::min(stream_grid(pixels), ENV_MAX_BLOCKS)), dim3(ENV_WG), 0, ctx->stream, reinterpret_cast<const float4*>(v_out), pixels, map->ctl);
     BH_LAUNCH_CHECK(ctx, "envmap_max_kernel");
     if (check_host) {
         uint32_t m_bits = 0;
-        BH_HIP(ctx, hipMemcpyAsync(&m_bits, map->ctl, 4, hipMemcpyDeviceToHost, ctx->stream));
-        BH_TRY(settle(ctx));
+        BH_TRY(read_back(ctx, &m_bits, map->ctl, 4));
         if (m_bits >= 0x7F800000u) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_backward: v_out holds a NaN or an infinity (nothing was written)");
     }
     const uint32_t tiles_x = (w + ENV_TILE - 1) / ENV_TILE, tiles_y = (h + ENV_TILE - 1) / ENV_TILE;
@@ -393,15 +347,6 @@ int launch_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera& cam, con
 
 int launch_envmap_adam(bh_ctx* ctx, bh_envmap* map, float gscale) { return launch_final(ctx, map, 0u, false, true, gscale); }
 
-uint64_t envmap_floats(const bh_envmap* map) { return map->cells; }
-float* envmap_grad(const bh_envmap* map) { return map->grad; }
-
-void envmaps_free_all(bh_ctx* ctx) {
-    for (bh_envmap* map : ctx->envmaps) envmap_free(map);
-    ctx->envmaps.clear();
-    ctx->terms.envmap = nullptr;
-}
-
 }  // namespace bh
 
 using namespace bh;
@@ -409,101 +354,49 @@ using namespace bh;
 extern "C" {
 
 int bh_envmap_create(bh_ctx* ctx, uint32_t resolution, bh_envmap** map) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!map) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_create: null argument");
-    *map = nullptr;
+    BH_TRY(param_table_create_args(ctx, map, 1, "envmap_create"));
     if (resolution == 0 || resolution > BH_ENVMAP_MAX_RESOLUTION) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_create: the resolution must be 1 .. 1024");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)6 * resolution * resolution * 3;
     bh_envmap* m = new bh_envmap;
+    BH_TRY(param_table_create(ctx, m, 1, cells, cells * 8 + 16, /*pattern=*/nullptr, "envmap_create"));   // (a new map is black)
     m->res = resolution;
-    m->cells = (size_t)6 * resolution * resolution * 3;
-    const size_t bytes = m->cells * (8 + 4 * 4) + 32;
-    hipError_t e = hipMalloc(&m->mem, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(m->mem, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        envmap_free(m);
-        return check_hip(ctx, e, "envmap_create");
-    }
-    deliver_pending_loss(ctx);
     m->acc = static_cast<unsigned long long*>(m->mem);
-    m->ctl = reinterpret_cast<uint32_t*>(m->acc + m->cells);
-    m->param = reinterpret_cast<float*>(m->ctl + 4);
-    m->grad = m->param + m->cells;
-    m->m1 = m->grad + m->cells;
-    m->m2 = m->m1 + m->cells;
-    m->t_dev = reinterpret_cast<uint32_t*>(m->m2 + m->cells);
-    ctx->envmaps.push_back(m);
+    m->ctl = reinterpret_cast<uint32_t*>(m->acc + cells);
     *map = m;
     return 0;
 }
 
-int bh_envmap_destroy(bh_ctx* ctx, bh_envmap* map) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(envmap_owned(ctx, map, "envmap_destroy"));
-    if (ctx->terms.envmap == map) ctx->terms.envmap = nullptr;   // an attached map is detached first
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);   // kernels queued on the map have run
-    deliver_pending_loss(ctx);
-    ctx->envmaps.erase(std::find(ctx->envmaps.begin(), ctx->envmaps.end(), map));
-    envmap_free(map);
-    return 0;
+int bh_envmap_destroy(bh_ctx* ctx, bh_envmap* map) { return param_table_destroy(ctx, PT_ENVMAP, map, "envmap_destroy"); }
+
+int bh_envmap_set_params(bh_ctx* ctx, bh_envmap* map, const float* host) { return param_table_set_params(ctx, PT_ENVMAP, map, 1, 1, host, "envmap_set_params"); }
+
+int bh_envmap_get_params(bh_ctx* ctx, bh_envmap* map, float* host) {
+    return param_table_get_rows(ctx, PT_ENVMAP, map, &ParamTable::param, 1, 1, host, "envmap_get_params");
 }
 
-int bh_envmap_set_params(bh_ctx* ctx, bh_envmap* map, const float* host) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!host) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_set_params: null argument");
-    BH_TRY(envmap_owned(ctx, map, "envmap_set_params"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemcpyAsync(map->param, host, map->cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    return settle(ctx);   // (the caller's array may die on return)
+int bh_envmap_get_grad(bh_ctx* ctx, bh_envmap* map, float* host) {
+    return param_table_get_rows(ctx, PT_ENVMAP, map, &ParamTable::grad, 1, 1, host, "envmap_get_grad");
 }
-
-int bh_envmap_get_params(bh_ctx* ctx, bh_envmap* map, float* host) { return read_cells(ctx, map, &bh_envmap::param, host, "envmap_get_params"); }
-
-int bh_envmap_get_grad(bh_ctx* ctx, bh_envmap* map, float* host) { return read_cells(ctx, map, &bh_envmap::grad, host, "envmap_get_grad"); }
 
 int bh_envmap_get_state(bh_ctx* ctx, bh_envmap* map, float* m1, float* m2, uint32_t* t) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!m1 || !m2 || !t) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_get_state: null argument");
-    BH_TRY(envmap_owned(ctx, map, "envmap_get_state"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemcpyAsync(m1, map->m1, map->cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(m2, map->m2, map->cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(t, map->t_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-    return settle(ctx);
+    return param_table_get_state(ctx, PT_ENVMAP, map, 1, m1, m2, t, "envmap_get_state");
 }
 
 int bh_envmap_set_state(bh_ctx* ctx, bh_envmap* map, const float* m1, const float* m2, uint32_t t) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    if (!m1 || !m2) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_set_state: null argument");
-    BH_TRY(envmap_owned(ctx, map, "envmap_set_state"));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    BH_HIP(ctx, hipMemcpyAsync(map->m1, m1, map->cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(map->m2, m2, map->cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(map->t_dev, &t, 4, hipMemcpyHostToDevice, ctx->stream));
-    BH_TRY(settle(ctx));
-    map->t = t;
+    BH_TRY(param_table_set_state(ctx, PT_ENVMAP, map, 1, m1, m2, t, "envmap_set_state"));
+    map->t_host = t;
     return 0;
 }
 
 int bh_envmap_set_adam(bh_ctx* ctx, bh_envmap* map, double lr, double beta1, double beta2, double eps) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(envmap_owned(ctx, map, "envmap_set_adam"));
-    if (!(lr >= 0.0) || !std::isfinite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps > 0.0) || !std::isfinite(eps))
-        return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_set_adam: needs lr >= 0, 0 <= beta < 1 and eps > 0, all finite");
-    map->lr = lr;
-    map->beta1 = beta1;
-    map->beta2 = beta2;
-    map->eps = eps;
-    return 0;
+    return param_table_set_adam(ctx, PT_ENVMAP, map, lr, beta1, beta2, eps, "envmap_set_adam");
 }
 
 int bh_envmap_composite(bh_ctx* ctx, bh_envmap* map, const BhCamera* cam, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !out_hwc4) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_composite: null argument");
     BH_TRY(check_envmap_frame(ctx, cam, h, w, "envmap_composite"));
-    BH_TRY(envmap_owned(ctx, map, "envmap_composite"));
+    BH_TRY(param_table_owned(ctx, PT_ENVMAP, map, "envmap_composite"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     ProfScope ps(ctx, "EnvMap");
     return launch_envmap_composite(ctx, map, *cam, img_hwc4, h, w, out_hwc4);
@@ -514,7 +407,7 @@ int bh_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera* cam, const f
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !v_out || !v_img) return set_error(ctx, BH_ERR_INVALID_ARG, "envmap_backward: null argument");
     BH_TRY(check_envmap_frame(ctx, cam, h, w, "envmap_backward"));
-    BH_TRY(envmap_owned(ctx, map, "envmap_backward"));
+    BH_TRY(param_table_owned(ctx, PT_ENVMAP, map, "envmap_backward"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     ProfScope ps(ctx, "EnvMap");
     return launch_envmap_backward(ctx, map, *cam, img_hwc4, v_out, h, w, v_img, update != 0, 1.0f, /*check_host=*/true);
@@ -522,7 +415,7 @@ int bh_envmap_backward(bh_ctx* ctx, bh_envmap* map, const BhCamera* cam, const f
 
 int bh_train_set_envmap(bh_ctx* ctx, bh_envmap* map) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    if (map) BH_TRY(envmap_owned(ctx, map, "train_set_envmap"));
+    BH_TRY(param_table_attachable(ctx, PT_ENVMAP, map, "train_set_envmap"));
     ctx->terms.envmap = map;
     return 0;
 }

@@ -1,11 +1,11 @@
 // exposure.hip — per-view exposure compensation (brush_hip_exposure.h): the affine colour transform of a view on
 // the rasterizer's image, its backward, and Adam on the twelve parameters of the view, all on the device.  Three kernels, all
 // streaming or tiny: the point is to stay at HBM speed and to keep the order of the f64 reduction fixed.  The table itself — a
-// bh_exposure is a ViewTable of rows of 12 with f64 moments — and every entry point that only manages it are view_table.h's; the f64
-// reductions and the Adam step are device_f64_sum.h's.
+// bh_exposure is a ParamTable of rows of 12 with f64 moments — and every entry point that only manages it are param_table.h's, shared
+// with bilagrid.hip and envmap.hip; the f64 reductions and the Adam step are device_f64_sum.h's.
 #include "../../include/brush_hip_exposure.h"
 #include "device_f64_sum.h"
-#include "view_table.h"
+#include "param_table.h"
 
 namespace bh {
 
@@ -127,44 +127,44 @@ using namespace bh;
 extern "C" {
 
 int bh_exposure_create(bh_ctx* ctx, uint32_t n_views, bh_exposure** table) {
-    BH_TRY(view_table_create_args(ctx, table, n_views, "exposure_create"));
-    ViewTable* tab = nullptr;
-    BH_TRY(view_table_create(ctx, VT_EXPOSURE, n_views, 12, "exposure_create", &tab));
-    *table = static_cast<bh_exposure*>(tab);
+    BH_TRY(param_table_create_args(ctx, table, n_views, "exposure_create"));
+    bh_exposure* tab = new bh_exposure;
+    BH_TRY(param_table_create(ctx, tab, n_views, 12, 0, &COLOUR_IDENTITY, "exposure_create"));
+    *table = tab;
     return 0;
 }
 
-int bh_exposure_destroy(bh_ctx* ctx, bh_exposure* table) { return view_table_destroy(ctx, VT_EXPOSURE, table, "exposure_destroy"); }
+int bh_exposure_destroy(bh_ctx* ctx, bh_exposure* table) { return param_table_destroy(ctx, PT_EXPOSURE, table, "exposure_destroy"); }
 
 int bh_exposure_set_params(bh_ctx* ctx, bh_exposure* table, uint32_t first_view, uint32_t count, const float* host) {
-    return view_table_set_params(ctx, VT_EXPOSURE, table, first_view, count, host, "exposure_set_params");
+    return param_table_set_params(ctx, PT_EXPOSURE, table, first_view, count, host, "exposure_set_params");
 }
 
 int bh_exposure_get_params(bh_ctx* ctx, bh_exposure* table, uint32_t first_view, uint32_t count, float* host) {
-    return view_table_get_rows(ctx, VT_EXPOSURE, table, &ViewTable::param, first_view, count, host, "exposure_get_params");
+    return param_table_get_rows(ctx, PT_EXPOSURE, table, &ParamTable::param, first_view, count, host, "exposure_get_params");
 }
 
 int bh_exposure_get_grad(bh_ctx* ctx, bh_exposure* table, uint32_t first_view, uint32_t count, float* host) {
-    return view_table_get_rows(ctx, VT_EXPOSURE, table, &ViewTable::grad, first_view, count, host, "exposure_get_grad");
+    return param_table_get_rows(ctx, PT_EXPOSURE, table, &ParamTable::grad, first_view, count, host, "exposure_get_grad");
 }
 
 int bh_exposure_get_state(bh_ctx* ctx, bh_exposure* table, uint32_t view, double* m1, double* m2, uint32_t* t) {
-    return view_table_get_state(ctx, VT_EXPOSURE, table, view, m1, m2, t, "exposure_get_state");
+    return param_table_get_state(ctx, PT_EXPOSURE, table, view, m1, m2, t, "exposure_get_state");
 }
 
 int bh_exposure_set_state(bh_ctx* ctx, bh_exposure* table, uint32_t view, const double* m1, const double* m2, uint32_t t) {
-    return view_table_set_state(ctx, VT_EXPOSURE, table, view, m1, m2, t, "exposure_set_state");
+    return param_table_set_state(ctx, PT_EXPOSURE, table, view, m1, m2, t, "exposure_set_state");
 }
 
 int bh_exposure_set_adam(bh_ctx* ctx, bh_exposure* table, double lr, double beta1, double beta2, double eps) {
-    return view_table_set_adam(ctx, VT_EXPOSURE, table, lr, beta1, beta2, eps, "exposure_set_adam");
+    return param_table_set_adam(ctx, PT_EXPOSURE, table, lr, beta1, beta2, eps, "exposure_set_adam");
 }
 
 int bh_exposure_apply(bh_ctx* ctx, bh_exposure* table, uint32_t view, const float* img_hwc4, uint32_t h, uint32_t w, float* out_hwc4) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !out_hwc4) return set_error(ctx, BH_ERR_INVALID_ARG, "exposure_apply: null argument");
-    if (h == 0 || w == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "exposure_apply: an image of zero size");
-    BH_TRY(check_rows(ctx, VT_EXPOSURE, table, view, 1, "exposure_apply"));
+    BH_TRY(check_image(ctx, h, w, /*below_2_31=*/false, "exposure_apply"));   // (the kernels count pixels in 64 bits)
+    BH_TRY(check_rows(ctx, PT_EXPOSURE, table, view, 1, "exposure_apply"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_exposure_apply(ctx, table, view, img_hwc4, h, w, out_hwc4);
 }
@@ -173,15 +173,15 @@ int bh_exposure_backward(bh_ctx* ctx, bh_exposure* table, uint32_t view, const f
                          float* v_img, int update) {
     if (!ctx) return BH_ERR_INVALID_ARG;
     if (!img_hwc4 || !v_exposed || !v_img) return set_error(ctx, BH_ERR_INVALID_ARG, "exposure_backward: null argument");
-    if (h == 0 || w == 0) return set_error(ctx, BH_ERR_INVALID_ARG, "exposure_backward: an image of zero size");
-    BH_TRY(check_rows(ctx, VT_EXPOSURE, table, view, 1, "exposure_backward"));
+    BH_TRY(check_image(ctx, h, w, /*below_2_31=*/false, "exposure_backward"));
+    BH_TRY(check_rows(ctx, PT_EXPOSURE, table, view, 1, "exposure_backward"));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     return launch_exposure_backward(ctx, table, view, img_hwc4, v_exposed, h, w, v_img, update != 0);
 }
 
 int bh_train_set_exposure(bh_ctx* ctx, bh_exposure* table) {
     if (!ctx) return BH_ERR_INVALID_ARG;
-    BH_TRY(view_table_attachable(ctx, VT_EXPOSURE, table, "train_set_exposure"));
+    BH_TRY(param_table_attachable(ctx, PT_EXPOSURE, table, "train_set_exposure"));
     ctx->terms.exposure = table;
     return 0;
 }

@@ -6,7 +6,7 @@
 #include <string>
 
 #include "context.h"
-#include "view_table.h"
+#include "param_table.h"
 
 using namespace bh;
 
@@ -547,7 +547,7 @@ int step_grad_exchange(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWo
     // ... and the environment map's v_E by one more: 6 R R 3 floats (brush_hip_envmap.h)
     if (p.envmap && p.exchanging) {
         ProfScope ps(ctx, "EnvMapExchange");
-        BH_TRY(sum_over_ranks(ctx, a, envmap_grad(p.envmap), envmap_floats(p.envmap)));
+        BH_TRY(sum_over_ranks(ctx, a, p.envmap->grad, p.envmap->row));
     }
     return 0;
 }

@@ -1148,8 +1148,8 @@ class PoseOptimizer:
 
 
 # ---------------------------------------------------------------------------
-# Per-view colour tables: exposure compensation (include/brush_hip_exposure.h) and bilateral grids
-# (include/brush_hip_bilagrid.h)
+# Learned device tables: per-view exposure compensation (include/brush_hip_exposure.h) and bilateral grids
+# (include/brush_hip_bilagrid.h), and the environment map (include/brush_hip_envmap.h)
 # ---------------------------------------------------------------------------
 def _hwc4_out(img, out):
     """The result tensor of an [H,W,4] operator on `img`: a new one, or the caller's `out` once it fits."""
@@ -1160,21 +1160,29 @@ def _hwc4_out(img, out):
     return out
 
 
-class _ViewTable:
-    """What the per-view device tables share (csrc/view_table.h): V rows of `shape` f32 parameters, numbered from 1, each with its
-    gradient, its Adam moments (of the kind's dtype) and its step count.  A subclass names the C symbols' prefix and the moment type,
-    opens the table with `_open` and checks the moments it is handed in `_moment`."""
-    _prefix = None                      # "bh_exposure" | "bh_bilagrid"
+class _ParamTable:
+    """What the learned device tables share (csrc/param_table.h): rows of `shape` f32 parameters, each with its gradient, its Adam
+    moments (of the kind's dtype) and its step count.  A per-view kind has `n_views` rows, numbered from 1, and its arrays a leading
+    [V] axis; a kind without views (`_per_view` = False) is its one row, and its C entry points take no row arguments.  A subclass
+    names the C symbols' prefix and the moment type, opens the table with `_open`, checks the moments it is handed in `_moment` and
+    words its shape in `_params_shape_text`."""
+    _prefix = None                      # "bh_exposure" | "bh_bilagrid" | "bh_envmap"
     _moment_np, _moment_c = None, None  # the moments' numpy dtype and ctypes type
+    _per_view = True
 
     def _fn(self, name):
         return getattr(self.lib, "%s_%s" % (self._prefix, name))
 
+    def _rows(self, *rows):
+        """The row arguments of a C call."""
+        return tuple(int(r) for r in rows) if self._per_view else ()
+
     def _open(self, ctx, n_views, shape, create_args, lr, beta1, beta2, eps):
         ctx = ctx or get_context()
-        self.ctx, self.lib, self.n_views, self.shape = ctx, ctx.lib, int(n_views), tuple(shape)   # shape: one view's row
+        self.ctx, self.lib, self.n_views, self.shape = ctx, ctx.lib, int(n_views), tuple(shape)   # shape: one row
+        self._all = ((self.n_views,) if self._per_view else ()) + self.shape                      # ... and every row
         h = C.c_void_p()
-        ctx.check(self._fn("create")(ctx._h, self.n_views, *create_args, C.byref(h)))
+        ctx.check(self._fn("create")(ctx._h, *self._rows(n_views), *create_args, C.byref(h)))
         self._h = h
         self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
         self.set_lr(lr)
@@ -1186,29 +1194,31 @@ class _ViewTable:
 
     def _get(self, fn):
         import numpy as np
-        out = np.empty((self.n_views,) + self.shape, np.float32)
-        self.ctx.check(fn(self.ctx._h, self._h, 1, self.n_views, out.ctypes.data_as(C.POINTER(C.c_float))))
+        out = np.empty(self._all, np.float32)
+        self.ctx.check(fn(self.ctx._h, self._h, *self._rows(1, self.n_views), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     def _set_rows(self, first, count, a):
-        self.ctx.check(self._fn("set_params")(self.ctx._h, self._h, int(first), int(count), a.ctypes.data_as(C.POINTER(C.c_float))))
+        self.ctx.check(self._fn("set_params")(self.ctx._h, self._h, *self._rows(first, count), a.ctypes.data_as(C.POINTER(C.c_float))))
 
     @property
     def params(self):
-        """[V, *shape] f32 numpy copy of every row (one synchronisation); assign an array of the same shape to set them."""
+        """f32 numpy copy of the whole table (one synchronisation): [V, *shape], or [*shape] for a kind without views; assign an array of
+        the same shape to set it."""
         return self._get(self._fn("get_params"))
 
     @params.setter
     def params(self, value):
         import numpy as np
         a = np.ascontiguousarray(np.asarray(value, np.float32))
-        if a.shape != (self.n_views,) + self.shape:
+        if a.shape != self._all:
             raise ValueError("params must be " + self._params_shape_text())
         self._set_rows(1, self.n_views, a)
 
     @property
     def grads(self):
-        """[V, *shape] f32: the last gradient written for each row, a TV term's included (zeros for a row no backward has touched)."""
+        """f32, shaped like `params`: the last gradient written for each row, a TV term's included (zeros for a row no backward or train
+        step has touched)."""
         return self._get(self._fn("get_grad"))
 
     def state(self, view):
@@ -1216,14 +1226,14 @@ class _ViewTable:
         import numpy as np
         m1, m2, t = np.empty(self.shape, self._moment_np), np.empty(self.shape, self._moment_np), C.c_uint32()
         p = C.POINTER(self._moment_c)
-        self.ctx.check(self._fn("get_state")(self.ctx._h, self._h, int(view), m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
+        self.ctx.check(self._fn("get_state")(self.ctx._h, self._h, *self._rows(view), m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
         return m1, m2, int(t.value)
 
     def set_state(self, view, m1, m2, t):
         """Puts a row's Adam state back (resuming from a checkpoint)."""
-        a, b = self._moment(m1), self._moment(m2)
+        a, b = self._moment(m1, "m1"), self._moment(m2, "m2")
         p = C.POINTER(self._moment_c)
-        self.ctx.check(self._fn("set_state")(self.ctx._h, self._h, int(view), a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+        self.ctx.check(self._fn("set_state")(self.ctx._h, self._h, *self._rows(view), a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1238,7 +1248,7 @@ class _ViewTable:
             pass
 
 
-class ExposureTable(_ViewTable):
+class ExposureTable(_ParamTable):
     """A device table of one affine colour transform m[12] (row-major 3x4, column 3 the offset) per training view, with its Adam
     moments (f64) and update on the device (bh_exposure_*): y = A x + b on the rasterizer's image before the loss.  Views are numbered
     from 1 (row i is view id i + 1, as SceneLoader numbers them).  Nothing here reads back except the getters (`params`, `grads`
@@ -1252,7 +1262,7 @@ class ExposureTable(_ViewTable):
     def _params_shape_text(self):
         return "[%d, 12]" % self.n_views
 
-    def _moment(self, m):
+    def _moment(self, m, what):
         import numpy as np
         return np.ascontiguousarray(m, np.float64).reshape(12)
 
@@ -1282,70 +1292,36 @@ class ExposureTable(_ViewTable):
         return out
 
 
-class EnvironmentMap:
+class EnvironmentMap(_ParamTable):
     """A learned cubemap E[6,R,R,3] f32 behind the splats (include/brush_hip_envmap.h): what the splats leave
     uncovered shows the map along the pixel's world ray, out = img + (1 - alpha) E(d), with the exact integer gradient to the table, its
     Adam moments (f32) and the update on the device.  Faces are +X, -X, +Y, -Y, +Z, -Z in world axes, the library's own table (no
     OpenGL flips); pinhole cameras only.  A new map is black.  Nothing here reads back except the getters (`params`, `grads`
     [6,R,R,3] f32, `state` (m1, m2 [6,R,R,3] f32, t)) and `backward`, which fetches four bytes to refuse a cotangent that is not
     finite.  SplatTrainer(envmap=map) attaches it to the train step."""
+    _prefix, _moment_np, _moment_c, _per_view = "bh_envmap", "float32", C.c_float, False
 
     def __init__(self, resolution=64, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-15, ctx: Optional[Context] = None):
-        ctx = ctx or get_context()
-        self.ctx, self.lib, self.resolution = ctx, ctx.lib, int(resolution)
-        self.shape = (6, self.resolution, self.resolution, 3)
-        h = C.c_void_p()
-        ctx.check(self.lib.bh_envmap_create(ctx._h, self.resolution, C.byref(h)))
-        self._h = h
-        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
-        self.set_lr(lr)
+        self.resolution = int(resolution)
+        self._open(ctx, 1, (6, self.resolution, self.resolution, 3), (self.resolution,), lr, beta1, beta2, eps)
 
-    def set_lr(self, lr):
-        """The learning rate of every following update (bh_envmap_set_adam); 0 freezes the table while its moments still move."""
-        self.ctx.check(self.lib.bh_envmap_set_adam(self.ctx._h, self._h, float(lr), self.beta1, self.beta2, self.eps))
-        self.lr = float(lr)
+    def _params_shape_text(self):
+        return "[6, %d, %d, 3]" % (self.resolution, self.resolution)
 
-    def _get(self, fn):
+    def _moment(self, m, what):
         import numpy as np
-        out = np.empty(self.shape, np.float32)
-        self.ctx.check(fn(self.ctx._h, self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
-
-    def _cells(self, a, what):
-        import numpy as np
-        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        a = np.ascontiguousarray(np.asarray(m, np.float32))
         if a.shape != self.shape:
-            raise ValueError("%s must be [6, %d, %d, 3]" % (what, self.resolution, self.resolution))
+            raise ValueError("%s must be %s" % (what, self._params_shape_text()))
         return a
-
-    @property
-    def params(self):
-        """[6,R,R,3] f32 numpy copy of the table (one synchronisation); assign an array of the same shape to set it."""
-        return self._get(self.lib.bh_envmap_get_params)
-
-    @params.setter
-    def params(self, value):
-        a = self._cells(value, "params")
-        self.ctx.check(self.lib.bh_envmap_set_params(self.ctx._h, self._h, a.ctypes.data_as(C.POINTER(C.c_float))))
-
-    @property
-    def grads(self):
-        """[6,R,R,3] f32: v_E of the last backward (or train step) on the map; zeros before the first."""
-        return self._get(self.lib.bh_envmap_get_grad)
 
     def state(self):
         """(m1, m2 [6,R,R,3] f32, t): the Adam moments and the step count."""
-        import numpy as np
-        m1, m2, t = np.empty(self.shape, np.float32), np.empty(self.shape, np.float32), C.c_uint32()
-        p = C.POINTER(C.c_float)
-        self.ctx.check(self.lib.bh_envmap_get_state(self.ctx._h, self._h, m1.ctypes.data_as(p), m2.ctypes.data_as(p), C.byref(t)))
-        return m1, m2, int(t.value)
+        return super().state(1)
 
     def set_state(self, m1, m2, t):
         """Puts the Adam state back (resuming from a checkpoint)."""
-        a, b = self._cells(m1, "m1"), self._cells(m2, "m2")
-        p = C.POINTER(C.c_float)
-        self.ctx.check(self.lib.bh_envmap_set_state(self.ctx._h, self._h, a.ctypes.data_as(p), b.ctypes.data_as(p), int(t)))
+        super().set_state(1, m1, m2, t)
 
     @staticmethod
     def _camera(camera, img):
@@ -1372,20 +1348,8 @@ class EnvironmentMap:
                                                    1 if update else 0))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self.ctx, "_h", None):   # (a closed context has freed its maps)
-                self.lib.bh_envmap_destroy(self.ctx._h, self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BilateralGridTable(_ViewTable):
+class BilateralGridTable(_ParamTable):
     """A device table of one bilateral grid per training view: g[Hg,Wg,L,12] f32, a grid of row-major 3x4 colour matrices looked up
     by trilinear interpolation at (x, y, luminance) and applied to the rasterizer's image before the loss, with its Adam moments
     (f32) and update on the device (bh_bilagrid_*; gsplat's lib_bilagrid).  `grid` is (Wg, Hg, L), gsplat's (grid_X, grid_Y, grid_W).
@@ -1401,7 +1365,7 @@ class BilateralGridTable(_ViewTable):
     def _params_shape_text(self):
         return "%r" % ((self.n_views,) + self.shape,)
 
-    def _moment(self, m):
+    def _moment(self, m, what):
         import numpy as np
         a = np.ascontiguousarray(m, np.float32)
         if a.shape != self.shape:

@@ -229,3 +229,60 @@ def test_refusals(ctx, dev):
     m.close()                                           # destroying an attached map detaches it
     assert lib.bh_train_set_envmap(h, None) == 0
     assert _same(vr.composite(c["table"], c["img"], c["cam"]), c["out"])   # the shared case is as it was
+
+
+def test_a_handle_of_another_kind_of_table_is_a_stranger(ctx):
+    import brush_amd as ba
+    import util
+    util.assert_wrong_kind_handles_refused(ba, ctx)
+
+
+def test_closing_the_context_frees_tables_of_every_kind(dev):
+    """bh_destroy frees what is left on the ctx's one list of tables — the device's free memory says so: the three tables are about
+    75 MB each (no image, no kernel beyond the fills of their creation), so one of them left behind is a third of the total, against
+    a tenth allowed for whatever else moves on the device — and a table's own close() then must not touch the library."""
+    import brush_amd as ba
+    torch.cuda.synchronize(dev)
+    before = torch.cuda.mem_get_info(dev)[0]
+    c = ba.Context(dev)
+    tables = (ba.ExposureTable(1 << 18, ctx=c), ba.BilateralGridTable(192, grid=(16, 16, 8), ctx=c), ba.EnvironmentMap(416, ctx=c))
+    total = (1 << 18) * (12 * (2 * 8 + 8) + 4) + 192 * ((16 * 16 * 8 * 12) * (2 * 4 + 8) + 4) + 6 * 416 * 416 * 3 * (8 + 2 * 4 + 8)
+    assert before - torch.cuda.mem_get_info(dev)[0] >= 0.9 * total
+    assert c.lib.bh_train_set_envmap(c._h, tables[2]._h) == 0   # (attached ones included)
+
+    class NoLibrary:
+        def __getattr__(self, name):
+            raise AssertionError("close() of a table whose context is closed called %s" % name)
+
+    c.close()
+    assert before - torch.cuda.mem_get_info(dev)[0] <= 0.1 * total
+    for t in tables:
+        t.lib = NoLibrary()
+        t.close()
+        assert t._h is None
+        t.close()
+
+
+def test_a_new_map_is_black_and_a_new_colour_row_the_identity(ctx):
+    """The row pattern a kind hands to the table core: none for a map, at row lengths (18, 162) that are no multiple of twelve, and
+    the 3x4 identity for the colour tables, over every view and cell."""
+    import brush_amd as ba
+    for res in (1, 3):
+        m = ba.EnvironmentMap(res, ctx=ctx)
+        assert m.shape == (6, res, res, 3) and m.params.shape == m.shape
+        m1, m2, t = m.state()
+        for a in (m.params, m.grads, m1, m2):
+            assert a.shape == m.shape and a.dtype == np.float32 and not a.view(np.int32).any()
+        assert t == 0
+        m.close()
+    ident = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
+    grid, exp = ba.BilateralGridTable(3, grid=(2, 2, 2), ctx=ctx), ba.ExposureTable(3, ctx=ctx)
+    assert grid.params.shape == (3, 2, 2, 2, 12) and exp.params.shape == (3, 12)
+    for tab in (grid, exp):
+        p = tab.params.reshape(-1, 12)
+        assert _same(p, np.tile(ident, (p.shape[0], 1)))
+        assert not tab.grads.any()
+        for view in (1, 3):
+            m1, m2, t = tab.state(view)
+            assert not m1.any() and not m2.any() and t == 0
+        tab.close()

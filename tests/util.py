@@ -167,38 +167,44 @@ def assert_adam_close(a, b, lr, steps=1, what="", extra_abs=0.0):
 
 
 def assert_wrong_kind_handles_refused(ba, ctx):
-    """An exposure table and a bilateral-grid table on one context: each handle given to the other kind's get_params, set_adam and
-    bh_train_set_* is refused with -1 and an error that names the kind the entry point expects, and neither table's parameters,
-    gradients or Adam state move.  No image is involved."""
+    """An exposure table, a bilateral-grid table and an environment map on one context: each handle given to the other two kinds'
+    get_params, set_adam and bh_train_set_* is refused with -1 and an error that names the kind the entry point expects, and no
+    table's parameters, gradients or Adam state move.  No image is involved."""
     import ctypes as C
     lib, h = ctx.lib, ctx._h
-    exp, grid = ba.ExposureTable(1, ctx=ctx), ba.BilateralGridTable(1, grid=(1, 1, 1), ctx=ctx)
+    exp, grid, env = ba.ExposureTable(1, ctx=ctx), ba.BilateralGridTable(1, grid=(1, 1, 1), ctx=ctx), ba.EnvironmentMap(resolution=1, ctx=ctx)
     exp.set_view(1, np.arange(12) * 0.25)
     exp.set_state(1, np.arange(12) + 1.0, np.arange(12) + 2.0, 3)
     grid.set_view(1, (np.arange(12, dtype=np.float32) * 0.5).reshape(1, 1, 1, 12))
     grid.set_state(1, np.full((1, 1, 1, 12), 4.0, np.float32), np.full((1, 1, 1, 12), 5.0, np.float32), 6)
+    env.params = (np.arange(18, dtype=np.float32) * 0.125).reshape(6, 1, 1, 3)
+    env.set_state(np.full((6, 1, 1, 3), 8.0, np.float32), np.full((6, 1, 1, 3), 9.0, np.float32), 7)
 
-    def snap(t):
-        return (t.params, t.grads) + t.state(1)
+    def snap():
+        return (exp.params, exp.grads) + exp.state(1) + (grid.params, grid.grads) + grid.state(1) + (env.params, env.grads) + env.state()
 
-    before = snap(exp) + snap(grid)
-    buf = (C.c_float * 12)()
-    calls = (
-        ("not an exposure table of this context", lambda: lib.bh_exposure_get_params(h, grid._h, 1, 1, buf)),
-        ("not an exposure table of this context", lambda: lib.bh_exposure_set_adam(h, grid._h, 0.5, 0.9, 0.999, 1e-8)),
-        ("not an exposure table of this context", lambda: lib.bh_train_set_exposure(h, grid._h)),
-        ("not a bilateral-grid table of this context", lambda: lib.bh_bilagrid_get_params(h, exp._h, 1, 1, buf)),
-        ("not a bilateral-grid table of this context", lambda: lib.bh_bilagrid_set_adam(h, exp._h, 0.5, 0.9, 0.999, 1e-15)),
-        ("not a bilateral-grid table of this context", lambda: lib.bh_train_set_bilagrid(h, exp._h, 1.0)),
+    before = snap()
+    assert (before[4], before[9], before[14]) == (3, 6, 7)
+    buf = (C.c_float * 18)()   # (the longest row of the three)
+    kinds = (
+        ("not an exposure table of this context", lambda t: lib.bh_exposure_get_params(h, t, 1, 1, buf),
+         lambda t: lib.bh_exposure_set_adam(h, t, 0.5, 0.9, 0.999, 1e-8), lambda t: lib.bh_train_set_exposure(h, t)),
+        ("not a bilateral-grid table of this context", lambda t: lib.bh_bilagrid_get_params(h, t, 1, 1, buf),
+         lambda t: lib.bh_bilagrid_set_adam(h, t, 0.5, 0.9, 0.999, 1e-15), lambda t: lib.bh_train_set_bilagrid(h, t, 1.0)),
+        ("not an environment map of this context", lambda t: lib.bh_envmap_get_params(h, t, buf),
+         lambda t: lib.bh_envmap_set_adam(h, t, 0.5, 0.9, 0.999, 1e-15), lambda t: lib.bh_train_set_envmap(h, t)),
     )
-    for text, call in calls:
-        assert call() == -1
-        assert text in lib.bh_last_error(h).decode()
+    tables = (exp, grid, env)
+    for k, (text, *calls) in enumerate(kinds):
+        for other in tables[:k] + tables[k + 1:]:
+            for call in calls:
+                assert call(other._h) == -1
+                assert lib.bh_last_error(h).decode().endswith(text)
     assert not any(buf)
-    for a, b in zip(before, snap(exp) + snap(grid)):
+    for a, b in zip(before, snap()):
         assert np.array_equal(a, b)
-    exp.close()
-    grid.close()
+    for t in tables:
+        t.close()
 
 
 def random_camera(seed):
