@@ -464,7 +464,10 @@ _lib_th = None
 # the test suite's fault-injection build (csrc/Makefile, -DBH_TEST_HOOKS): never loaded by product code
 TEST_HOOKS_LIB_PATH = os.path.join(_DIR, "libbrush_hip_testhooks.so")
 TEST_HOOK_SYMBOLS = {"bh_debug_fill_train_scratch": (C.c_int, [C.c_void_p, C.c_uint32]),
-                     "bh_debug_split_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)])}
+                     "bh_debug_split_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+                     # (ctx, keys, minmax, counts, n, out_keys, out_vals, cum, spl, spl_written, totals_out[512]): api.hip
+                     "bh_debug_depth_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_uint32)])}
 
 
 class BrushHipError(RuntimeError):

@@ -1469,4 +1469,24 @@ extern "C" int bh_debug_split_counts(bh_ctx* ctx, uint32_t* out) {
     BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 1;
 }
+// depth_sort_scan (depth_sort.hip) on the caller's device buffers, without the counter readback, and the ctx stream synchronised behind
+// it.  keys / counts [n], minmax [2 * COUNTER_SLOTS] in K1's format (max key | max ~key per slot, zeros neutral), out_keys / out_vals /
+// cum [n]; spl: a device table of DSORT_SPL_STRIDE words or NULL (the ctx's own); *spl_written: the host's note for that table, in and
+// out (spl == NULL: out only, the ctx's note, and may be NULL); totals_out [512] (host): the digit totals of keys | of tile counts the LAST launch set left at the head
+// of SLOT_SORT_HIST.
+extern "C" int bh_debug_depth_sort(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys, uint32_t* out_vals,
+                                   uint32_t* cum, uint32_t* spl, int* spl_written, uint32_t* totals_out) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!keys || !minmax || !counts || !out_keys || !out_vals || !cum || !totals_out || (spl && !spl_written))
+        return set_error(ctx, BH_ERR_INVALID_ARG, "debug_depth_sort: null argument");
+    if (n == 0 || !depth_sort_supported(n)) return set_error(ctx, BH_ERR_INVALID_ARG, "debug_depth_sort: n is outside the fused sort's reach");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    bool written = spl_written ? *spl_written != 0 : false;
+    BH_TRY(depth_sort_scan(ctx, keys, minmax, counts, n, out_keys, out_vals, cum, nullptr, nullptr, nullptr, 0u, nullptr, spl, spl ? &written : nullptr));
+    if (spl) *spl_written = written ? 1 : 0;
+    else if (spl_written) *spl_written = ctx->dsort_spl_written ? 1 : 0;
+    BH_HIP(ctx, hipMemcpyAsync(totals_out, ctx->slots[SLOT_SORT_HIST].ptr, 2 * 256 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 #endif
