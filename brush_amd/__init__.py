@@ -30,6 +30,8 @@ Names and argument meaning follow the reference (paths under
                                          image::imageops::resize of LoadImage::load, DESIGN.md §6h)
     RenderNode.backward(pose=True) / pose_twist / Camera.apply_twist / PoseOptimizer   camera pose gradients and their host
                                          optimizer (not in the reference; gsplat's v_viewmats)
+    RenderNode.backward(intrinsics=True) / Camera.with_intrinsics / IntrinsicsOptimizer   camera intrinsics gradients (focal,
+                                         principal point) and their per-sensor host optimizer
     ExposureTable / SplatTrainer(exposure=)   per-view exposure compensation: an affine colour transform per training view with
                                          Adam on the device (not in the reference; the INRIA trainer's exposure)
     depth_loss_value_and_grad / eval_depth_metrics / SceneBatch(depth=) / TrainConfig.depth_loss_weight   depth supervision: a fused
@@ -83,7 +85,7 @@ from .host import (  # noqa: F401
     render_splats_diff, RenderNode, compute_pup_scores, decimate_to_count, lod_target_count, pup_accumulate, pup_accumulate_view, pup_scores,
     knn_log_scales, to_init_splats, load_init_splats, ply_vertex_has_property, EvalSample, EvalResult, eval_metrics, eval_stats, run_eval,
     Lpips, lpips, lpips_value_and_grad, splat_to_compressed_ply, view_output_size, resize_image, render_depth,
-    PoseOptimizer, pose_twist, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
+    PoseOptimizer, pose_twist, IntrinsicsOptimizer, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
     render_distortion, distortion_loss, BilateralGridTable,
     TsdfVolume, mesh_to_ply, fuse_views,

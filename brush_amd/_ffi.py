@@ -455,6 +455,19 @@ ENVMAP_SYMBOLS = {
     "bh_train_set_envmap": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/brush_hip_intrinsics.h declares (the intrinsics gradient of a saved forward, the step's attachment, the host update)
+class BhCameraGradTerms(C.Structure):
+    _fields_ = [("v_depth", C.c_void_p), ("v_normal", C.c_void_p), ("v_distortion", C.c_void_p), ("depth_mode", C.c_uint32),
+                ("normal_mode", C.c_uint32), ("distortion", BhDistortionConfig)]
+
+
+INTRINSICS_SYMBOLS = {
+    "bh_render_backward_intrinsics_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut)] + [C.c_void_p] * 10),
+    "bh_render_backward_camera_saved": (C.c_int, [C.c_void_p, C.POINTER(BhRenderOut), C.c_void_p, C.POINTER(BhCameraGradTerms)] + [C.c_void_p] * 9),
+    "bh_train_set_intrinsics_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bh_camera_set_intrinsics": (C.c_int, [C.POINTER(BhCamera), C.c_double, C.c_double, C.c_double, C.c_double]),
+}
+
 ABI_VERSION = 7   # the BH_ABI_VERSION of include/brush_hip.h these mirrors were written against
 # bh_struct_size index -> mirror (the BH_STRUCT_* order of the header)
 STRUCT_MIRRORS = (BhCamera, BhRenderOut, BhLossConfig, BhTrainConfig, BhTrainState, BhTrainBatch, BhTrainStats, BhRefineConfig, BhRefineStats, BhPlyInfo)
@@ -497,7 +510,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS))
     return _lib
 
 
@@ -506,6 +519,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

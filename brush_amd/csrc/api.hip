@@ -9,6 +9,7 @@
 #include <cstring>
 #include <new>
 
+#include "../../include/brush_hip_intrinsics.h"
 #include "context.h"
 #include "device_rng.h"
 #include "param_table.h"
@@ -497,6 +498,30 @@ struct Rt8Law {  // radial factor (1 + k1 r^2 + k2 r^4 + k3 r^6) / (1 + k4 r^2 +
         return r;
     }
 };
+
+// What bh_camera_setup_model and bh_camera_set_intrinsics (brush_hip_intrinsics.h) share: lim_* and half_max_render_fov of a camera
+// whose model, dist, fx, fy, cx, cy, img_w and img_h are written, with the f64 fields of view its focals stand for.
+void camera_limits(BhCamera* out, double fov_x, double fov_y) {
+    // calculate_jacobian_clamp_limits (camera.rs:200-254): image edges +-15 %, in normalised coordinates
+    const float wf = (float)out->img_w, hf = (float)out->img_h;
+    float lim[4] = {(1.15f * wf - out->cx) / out->fx, (1.15f * hf - out->cy) / out->fy,
+                    (-0.15f * wf - out->cx) / out->fx, (-0.15f * hf - out->cy) / out->fy};
+    if (out->model == BH_CAMERA_RADIAL_TANGENTIAL_8) {
+        // the clamp bounds the UNDISTORTED coordinate: invert the radial law at each edge
+        const Rt8Law law(out->dist);
+        for (float& e : lim) {
+            const float mag = (float)law.undistort(std::fabs((double)e));
+            e = (e != e) ? e : (std::signbit(e) ? -mag : mag);  // * f32::signum(edge)
+        }
+    } else if (out->model != BH_CAMERA_PINHOLE) {
+        for (float& e : lim) e = 0.0f;  // fisheye Jacobians are not clamped
+    }
+    out->lim_pos_x = lim[0]; out->lim_pos_y = lim[1]; out->lim_neg_x = lim[2]; out->lim_neg_y = lim[3];
+    // render.rs:70-71 (f32)
+    const float full = hypotf((float)fov_x, (float)fov_y) * 1.05f;
+    const float cap = 2.0f * 3.14159265358979323846f - 1e-6f;
+    out->half_max_render_fov = (full < cap ? full : cap) * 0.5f;
+}
 }  // namespace
 
 double bh_fov_to_focal(double fov, uint32_t pixels, uint32_t model, const float* dist) {
@@ -562,30 +587,28 @@ int bh_camera_setup_model(const float* pos, const float* rot_xyzw, double fov_x,
     out->fy = (float)bh_fov_to_focal(fov_y, img_h, model, out->dist);
     out->cx = center_u * (float)img_w;
     out->cy = center_v * (float)img_h;
-    // calculate_jacobian_clamp_limits (camera.rs:200-254): image edges +-15 %, in normalised coordinates
-    const float wf = (float)img_w, hf = (float)img_h;
-    float lim[4] = {(1.15f * wf - out->cx) / out->fx, (1.15f * hf - out->cy) / out->fy,
-                    (-0.15f * wf - out->cx) / out->fx, (-0.15f * hf - out->cy) / out->fy};
-    if (model == BH_CAMERA_RADIAL_TANGENTIAL_8) {
-        // the clamp bounds the UNDISTORTED coordinate: invert the radial law at each edge
-        const Rt8Law law(out->dist);
-        for (float& e : lim) {
-            const float mag = (float)law.undistort(std::fabs((double)e));
-            e = (e != e) ? e : (std::signbit(e) ? -mag : mag);  // * f32::signum(edge)
-        }
-    } else if (model != BH_CAMERA_PINHOLE) {
-        for (float& e : lim) e = 0.0f;  // fisheye Jacobians are not clamped
-    }
-    out->lim_pos_x = lim[0]; out->lim_pos_y = lim[1]; out->lim_neg_x = lim[2]; out->lim_neg_y = lim[3];
-    // render.rs:70-71 (f32)
-    const float full = hypotf((float)fov_x, (float)fov_y) * 1.05f;
-    const float cap = 2.0f * 3.14159265358979323846f - 1e-6f;
-    out->half_max_render_fov = (full < cap ? full : cap) * 0.5f;
-    out->cam_pos[0] = pos[0]; out->cam_pos[1] = pos[1]; out->cam_pos[2] = pos[2];
     out->img_w = img_w;
     out->img_h = img_h;
+    camera_limits(out, fov_x, fov_y);
+    out->cam_pos[0] = pos[0]; out->cam_pos[1] = pos[1]; out->cam_pos[2] = pos[2];
     out->tile_row_begin = 0;
     out->tile_row_end = 0;
+    return 0;
+}
+
+int bh_camera_set_intrinsics(BhCamera* cam, double fx, double fy, double cx, double cy) {
+    if (!cam || cam->img_w == 0 || cam->img_h == 0 || cam->model > BH_CAMERA_THIN_PRISM_FISHEYE) return BH_ERR_INVALID_ARG;
+    if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !(fx > 0.0) || !(fy > 0.0)) return BH_ERR_INVALID_ARG;
+    const double fov_x = bh_focal_to_fov(fx, cam->img_w, cam->model, cam->dist), fov_y = bh_focal_to_fov(fy, cam->img_h, cam->model, cam->dist);
+    const float f[4] = {(float)fx, (float)fy, (float)cx, (float)cy};   // (a double that is no positive finite f32 is refused too)
+    if (!std::isfinite(fov_x) || !std::isfinite(fov_y) || !(f[0] > 0.0f) || !(f[1] > 0.0f) || !std::isfinite(f[0]) || !std::isfinite(f[1]) ||
+        !std::isfinite(f[2]) || !std::isfinite(f[3]))
+        return BH_ERR_INVALID_ARG;
+    cam->fx = f[0];
+    cam->fy = f[1];
+    cam->cx = f[2];
+    cam->cy = f[3];
+    camera_limits(cam, fov_x, fov_y);
     return 0;
 }
 
@@ -1186,6 +1209,10 @@ int backward_impl(bh_ctx* ctx, const ForwardState& fs, const float* v_output, co
         BH_TRY(launch_pose_grad(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, fs.sh_degree, transforms, sh_coeffs, r.global_from_compact_gid,
                                 v_combined, call.v_viewmat));
     }
+    if (call.v_intrinsics) {   // (brush_hip_intrinsics.h: only when asked for)
+        ProfScope ps(ctx, "IntrinsicsGrad");
+        BH_TRY(launch_intrinsics_grad(ctx, fs.uniforms, nv, fs.flags & BH_FLAG_MIP, transforms, r.global_from_compact_gid, v_combined, call.v_intrinsics));
+    }
     return 0;
 }
 
@@ -1211,7 +1238,7 @@ int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t requ
     const bool takes_normal = call.normal != nullptr;
     if (!saved || !call.v_transforms || !call.v_sh_coeffs || !call.v_raw_opacities || !call.v_refine_weight || ((required & NEED_V_OUTPUT) && !v_output) ||
         ((required & NEED_V_DEPTH) && !v_depth) || ((required & NEED_V_NORMAL) && !v_normal) || ((required & NEED_V_DISTORTION) && !v_distortion) ||
-        ((required & NEED_V_VIEWMAT) && !call.v_viewmat) ||
+        ((required & NEED_V_VIEWMAT) && !call.v_viewmat) || ((required & NEED_V_INTRINSICS) && !call.v_intrinsics) ||
         ((required & NEED_V_FEATURES) && (!call.feature || !call.feature->features || !call.feature->v_map || !call.feature->v_features)))
         return set_error(ctx, BH_ERR_INVALID_ARG, name + ": null argument");
     // an optional cotangent the caller left out: no term, and its mode is not looked at

@@ -87,6 +87,7 @@ enum Slot : int {
     SLOT_IMAGE,              // bh_resize_u8: f32 intermediate | the two weight tables (image.hip)
     SLOT_DEPTH,              // launch_depth_backward: v_z [Nv] | the frame's accumulated depth [H,W] (depth.hip; nobody else looks inside: the backward hands v_z on)
     SLOT_POSE,               // bh_render_backward_pose_saved / bh_train_set_pose_grad: one f64 row of 12 per block of the pose pass (project.hip)
+    SLOT_INTRINSICS,         // bh_render_backward_intrinsics_saved / bh_train_set_intrinsics_grad: one f64 row of 4 per block of the intrinsics pass (intrinsics.hip)
     SLOT_EXPOSURE,           // bh_exposure_backward: one f64 row of 12 per block of the exposure backward (exposure.hip)
     SLOT_CORRECTED,          // bh_train_step with an exposure or a bilateral-grid table (never both): [H,W,4] the exposed / sliced frame the loss reads (out_img stays as rendered)
     SLOT_PIXEL_LOSS,         // the pixel losses' partial sums, one f64 row of 4 per block (depth_loss.hip loss_partials): depth loss and metrics, normal consistency, distortion loss — one after another on the ctx stream, each followed at once by its final block
@@ -422,6 +423,7 @@ struct BackwardCall {
     const DistortionTerm* distortion = nullptr;   // likewise, behind normal's; its v_z joins depth's or goes through the same scatter
     const FeatureTerm* feature = nullptr;         // likewise, behind distortion's; its V lands in v_features behind the other scatters
     float* v_viewmat = nullptr;    // [12] (brush_hip_pose.h): the pose pass runs behind K18 on the rows it left in v_combined
+    float* v_intrinsics = nullptr; // [4] (brush_hip_intrinsics.h): the intrinsics pass, behind the pose pass on the same rows
 };
 
 // What is attached to the train steps of a ctx: the bh_train_set_* calls write here, plan_step (train.hip) reads it.  A term counts for
@@ -430,6 +432,7 @@ struct StepTerms {
     const bh_lpips* lpips = nullptr;  // bh_train_set_lpips: the step adds lpips_weight * LPIPS (lpips.hip); NULL or 0 = off
     float lpips_weight = 0.0f;
     float* pose_grad = nullptr;       // bh_train_set_pose_grad: the step writes its v_viewmat [12] here (brush_hip_pose.h); NULL = off
+    float* intrinsics_grad = nullptr; // bh_train_set_intrinsics_grad: the step writes its v_intrinsics [4] here (brush_hip_intrinsics.h); NULL = off
     bool depth_attached = false;      // bh_train_set_depth: the step adds the depth term of depth_target (brush_hip_depth_loss.h); weight <= 0 = off
     BhDepthTarget depth_target{};
     bool normal_attached = false;     // bh_train_set_normal: the step adds the normal-consistency term (brush_hip_normal_loss.h); weight <= 0 = off
@@ -595,7 +598,7 @@ int render_forward(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out);
 // distortion-kind, normal-mode and depth-mode refusals, find_saved_bwd_forward(not_bwd_code), the null-transforms refusal (an
 // entry that accepts a normal term has it), backward_impl.  Every text carries `who`.  NEED_V_FEATURES: the feature term's four
 // pointers join the null-argument refusal, and its channel count is refused behind the depth-mode refusals.
-enum : uint32_t { NEED_V_OUTPUT = 1u, NEED_V_DEPTH = 2u, NEED_V_NORMAL = 4u, NEED_V_DISTORTION = 8u, NEED_V_VIEWMAT = 16u, NEED_V_FEATURES = 32u };
+enum : uint32_t { NEED_V_OUTPUT = 1u, NEED_V_DEPTH = 2u, NEED_V_NORMAL = 4u, NEED_V_DISTORTION = 8u, NEED_V_VIEWMAT = 16u, NEED_V_FEATURES = 32u, NEED_V_INTRINSICS = 64u };
 int backward_entry(bh_ctx* ctx, const char* who, int not_bwd_code, uint32_t required, const BhRenderOut* saved, const float* v_output, BackwardCall call);
 // depth.hip: the depth term between K17 and K18 (raw sums into v_combined; *v_z = the per-splat vector it filled), and a v_z ->
 // v_mean behind K18 (the depth term's vector, the distortion term's, or the one both filled)
@@ -647,6 +650,9 @@ int launch_loss_pair_final(bh_ctx* ctx, uint32_t rows, const double* partials, f
 // project.hip: the pose gradient v_viewmat [12] of the RasterizeGrads rows K18 left in v_combined (brush_hip_pose.h)
 int launch_pose_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, uint32_t sh_degree, const float* transforms,
                      const float* sh, const uint32_t* gid, const float* v_combined, float* v_viewmat);
+// intrinsics.hip: the intrinsics gradient v_intrinsics [4] of the same rows (brush_hip_intrinsics.h)
+int launch_intrinsics_grad(bh_ctx* ctx, const ViewUniforms& u, uint32_t nv, bool mip, const float* transforms, const uint32_t* gid,
+                           const float* v_combined, float* v_intrinsics);
 // exposure.hip: y = A x + b with the row of `view` (1 .. n_views), and its backward: v_img = A^T v_exposed (in place
 // allowed), grad[view] = v_m, and one Adam step of the row when `update` (brush_hip_exposure.h).  The view is already checked.
 int launch_exposure_apply(bh_ctx* ctx, const bh_exposure* tab, uint32_t view, const float* img, uint32_t h, uint32_t w, float* out);

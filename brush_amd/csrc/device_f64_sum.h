@@ -1,5 +1,5 @@
 // device_f64_sum.h — the deterministic f64 pieces of the streaming kernels (depth_loss.hip, normal_loss.hip, distortion.hip, exposure.hip,
-// bilagrid.hip, project.hip's pose pass): each lane adds its items in index order, a lane-exchange butterfly inside the wave, the
+// bilagrid.hip, project.hip's pose pass, intrinsics.hip): each lane adds its items in index order, a lane-exchange butterfly inside the wave, the
 // block's waves in wave order through LDS, one f64 row per block in a context slot; one block then adds the rows in index order
 // (depth_loss.hip's final kernels, dl_final_rows12 here).  And the f64 Adam step of the per-view tables' elements.
 #pragma once
@@ -41,30 +41,35 @@ BH_DEV void dl_block_store(const double (&s)[K], double (*wave_rows)[STRIDE], do
 // consecutive rows in index order, lane k then adds the runs in order and gets the total (the other lanes get 0).  The pass waits on
 // memory, one dependent f64 add per row: at 1 M splats / 1080p (3400 rows of the pose pass) 16 runs took 64 us, five times K18.
 // UNROLL: of the loop over the runs (its callers were compiled with different ones, and keep them)
+// dl_final_rows<K, CHUNKS, UNROLL>: the same for rows of K by CHUNKS * K lanes (the intrinsics pass: 4 columns, 256 runs)
 constexpr int DL_FINAL_CHUNKS = 85;
-template <int UNROLL>
-BH_DEV double dl_final_rows12(uint32_t rows, const double* __restrict__ partials, double (*runs)[12]) {
-    const uint32_t chunk = threadIdx.x / 12u, k = threadIdx.x % 12u;
-    const uint32_t per = (rows + DL_FINAL_CHUNKS - 1) / DL_FINAL_CHUNKS;
+template <int K, int CHUNKS, int UNROLL>
+BH_DEV double dl_final_rows(uint32_t rows, const double* __restrict__ partials, double (*runs)[K]) {
+    const uint32_t chunk = threadIdx.x / (uint32_t)K, k = threadIdx.x % (uint32_t)K;
+    const uint32_t per = (rows + CHUNKS - 1) / CHUNKS;
     const uint32_t r0 = chunk * per < rows ? chunk * per : rows;
     const uint32_t r1 = r0 + per < rows ? r0 + per : rows;
     double s = 0.0;
     uint32_t r = r0;
     for (; r + 4 <= r1; r += 4) {   // four loads in flight, the adds in index order
-        const double a0 = partials[(size_t)r * 12 + k], a1 = partials[(size_t)(r + 1) * 12 + k];
-        const double a2 = partials[(size_t)(r + 2) * 12 + k], a3 = partials[(size_t)(r + 3) * 12 + k];
+        const double a0 = partials[(size_t)r * K + k], a1 = partials[(size_t)(r + 1) * K + k];
+        const double a2 = partials[(size_t)(r + 2) * K + k], a3 = partials[(size_t)(r + 3) * K + k];
         s += a0; s += a1; s += a2; s += a3;
     }
-    for (; r < r1; ++r) s += partials[(size_t)r * 12 + k];
+    for (; r < r1; ++r) s += partials[(size_t)r * K + k];
     runs[chunk][k] = s;
     __syncthreads();
     double total = 0.0;
-    if (threadIdx.x < 12) {
+    if (threadIdx.x < K) {
         total = runs[0][threadIdx.x];
 #pragma unroll UNROLL
-        for (int i = 1; i < DL_FINAL_CHUNKS; ++i) total += runs[i][threadIdx.x];
+        for (int i = 1; i < CHUNKS; ++i) total += runs[i][threadIdx.x];
     }
     return total;
+}
+template <int UNROLL>
+BH_DEV double dl_final_rows12(uint32_t rows, const double* __restrict__ partials, double (*runs)[12]) {
+    return dl_final_rows<12, DL_FINAL_CHUNKS, UNROLL>(rows, partials, runs);
 }
 
 // One Adam step of an element in f64 on the unrounded gradient sum g, at step count tn >= 1: returns the new parameter; a, b are the

@@ -168,6 +168,15 @@ BH_DEV Sym2 sym2_inverse(Sym2 s) {
     const float inv_det = det > 0.0f ? 1.0f / det : 0.0f;
     return Sym2{s.c11 * inv_det, -s.c01 * inv_det, s.c00 * inv_det};
 }
+// the VJP of the 2x2 inverse at minv = M^-1: -minv v minv, v and the result as full symmetric matrices (the off-diagonal entry
+// counts once per position).  K18, the pose pass (project.hip) and the intrinsics pass (intrinsics.hip)
+BH_DEV Sym2 inverse2x2_vjp(Sym2 minv, Sym2 v) {
+    const float tmp00 = -minv.c00 * v.c00 + -minv.c01 * v.c01;
+    const float tmp01 = -minv.c01 * v.c00 + -minv.c11 * v.c01;
+    const float tmp10 = -minv.c00 * v.c01 + -minv.c01 * v.c11;
+    const float tmp11 = -minv.c01 * v.c01 + -minv.c11 * v.c11;
+    return Sym2{tmp00 * minv.c00 + tmp10 * minv.c01, tmp01 * minv.c00 + tmp11 * minv.c01, tmp01 * minv.c01 + tmp11 * minv.c11};
+}
 BH_DEV float det2_strict(Sym2 s) {
     const float ad = s.c00 * s.c11;
     const float bc = s.c01 * s.c01;

@@ -897,13 +897,6 @@ BH_DEV Quat quat_to_mat_vjp(Quat q, const Mat3& v) {
     const float z_grad = qx * (v.c0z + v.c2x) + qy * (v.c1z + v.c2y) - 2.0f * qz * (v.c0x + v.c1y) + qw * (v.c0y - v.c1x);
     return Quat{2.0f * w_grad, 2.0f * x_grad, 2.0f * y_grad, 2.0f * z_grad};
 }
-BH_DEV Sym2 inverse2x2_vjp(Sym2 minv, Sym2 v) {
-    const float tmp00 = -minv.c00 * v.c00 + -minv.c01 * v.c01;
-    const float tmp01 = -minv.c01 * v.c00 + -minv.c11 * v.c01;
-    const float tmp10 = -minv.c00 * v.c01 + -minv.c01 * v.c11;
-    const float tmp11 = -minv.c01 * v.c01 + -minv.c11 * v.c11;
-    return Sym2{tmp00 * minv.c00 + tmp10 * minv.c01, tmp01 * minv.c00 + tmp11 * minv.c01, tmp01 * minv.c01 + tmp11 * minv.c11};
-}
 // camera_model/pinhole.rs:59-123
 BH_DEV Vec3A projection_vjp_pinhole(const Mat2x3& jac, Vec3A mean_c, Sym3 cov_c, const ViewUniforms& u, Sym2 v_cov2d, Vec2 v_mean2d) {
     const float fx = u.fx, fy = u.fy;

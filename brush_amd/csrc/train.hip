@@ -88,6 +88,10 @@ int refuse_with_pose_grad(bh_ctx* ctx, const char* a_term, const char* the_term)
     return set_error(ctx, BH_ERR_INVALID_ARG, std::string("train_step: ") + a_term + " and a pose-gradient buffer cannot be attached together (the pose pass does not carry the " +
                                                   the_term + "'s gradient)");
 }
+// (brush_hip_intrinsics.h: the intrinsics pass carries every term but these two, the environment map and the normal term)
+int refuse_with_intrinsics_grad(bh_ctx* ctx, const char* a_term, const char* why) {
+    return set_error(ctx, BH_ERR_STATE, std::string("train_step: ") + a_term + " and an intrinsics-gradient buffer cannot be attached together (" + why + ")");
+}
 // ... in the order every map term meets them (`a_term` NULL: the term has no pose rule)
 int check_frame_and_pose(bh_ctx* ctx, const StepPlan& p, const char* the_term, const char* a_term) {
     if (!p.whole_frame) return refuse_partial_frame(ctx, the_term);
@@ -95,8 +99,8 @@ int check_frame_and_pose(bh_ctx* ctx, const StepPlan& p, const char* the_term, c
     return 0;
 }
 
-// Every refusal of the step, in this order: null arguments, exposure, bilagrid, environment map (camera, frame, pose, alpha), depth (map, size, kind, frame, pose), normal (camera,
-// frame, pose), distortion, feature (frame, pose, rows, size), strip_loss, LPIPS.  Nothing is queued, no device is touched.
+// Every refusal of the step, in this order: null arguments, exposure, bilagrid, environment map (camera, frame, pose, intrinsics, alpha), depth (map, size, kind, frame, pose), normal (camera,
+// frame, pose, intrinsics), distortion, feature (frame, pose, rows, size), strip_loss, LPIPS.  Nothing is queued, no device is touched.
 int plan_step(bh_ctx* ctx, const BhTrainConfig* cfg, const BhTrainState* st, const BhTrainBatch* batch, bh_grad_hook hook, const BhTrainStats* stats, StepPlan* plan) {
     if (!cfg || !st || !batch || !stats) return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: null argument");
     if (!st->transforms || !st->sh_coeffs || !st->raw_opacities || !st->m1_transforms || !st->m2_transforms || !st->m1_sh ||
@@ -133,6 +137,7 @@ int plan_step(bh_ctx* ctx, const BhTrainConfig* cfg, const BhTrainState* st, con
         if (cam.model != BH_CAMERA_PINHOLE)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the environment map needs a pinhole camera (no other model can be unprojected to a ray)");
         BH_TRY(check_frame_and_pose(ctx, p, "environment map", "an environment map"));
+        if (t.intrinsics_grad) return refuse_with_intrinsics_grad(ctx, "an environment map", "the ray directions depend on the intrinsics");
         if (batch->has_alpha && !batch->alpha_is_mask)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: an environment map and a target with real alpha cannot be combined (a mask is fine)");
         if ((uint64_t)cam.img_w * cam.img_h > 0x7FFFFFFFull)
@@ -151,6 +156,7 @@ int plan_step(bh_ctx* ctx, const BhTrainConfig* cfg, const BhTrainState* st, con
         if (cam.model != BH_CAMERA_PINHOLE)
             return set_error(ctx, BH_ERR_INVALID_ARG, "train_step: the normal term needs a pinhole camera (the normals of a depth map are defined for it alone)");
         BH_TRY(check_frame_and_pose(ctx, p, "normal term", "a normal term"));
+        if (t.intrinsics_grad) return refuse_with_intrinsics_grad(ctx, "a normal term", "its depth-to-normal stencil uses fx, fy");
     }
     // a distortion term (brush_hip_distortion.h): attached only with a weight > 0 and a checked kind
     if ((p.distortion = t.distortion_on())) BH_TRY(check_frame_and_pose(ctx, p, "distortion term", "a distortion term"));
@@ -498,6 +504,7 @@ int step_backward(bh_ctx* ctx, const StepArgs& a, const StepPlan& p, StepWork& w
     bwd.span_floats = p.exch_count - p.o_tr;
     bwd.want_refine = !skip_refine;
     bwd.v_viewmat = ctx->terms.pose_grad;
+    bwd.v_intrinsics = ctx->terms.intrinsics_grad;
     BH_TRY(backward_impl(ctx, ctx->latest, w.v_output, bwd));
     if (st->min_scale && p.n > 0) {  // chain d/d(folded) -> d/d(raw) through the fold (autodiff of gaussian_splats.rs:86-111)
         ProfScope ps(ctx, "FoldMinScaleBackward");

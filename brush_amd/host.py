@@ -288,6 +288,16 @@ class Camera:
         moved view matrix.  Returns a new Camera."""
         return self._with_pose_of(_uniforms_apply_twist(self.uniforms((16, 16)), twist))   # (vm and cam_pos do not depend on the image size)
 
+    def with_intrinsics(self, fx, fy, cx, cy, img_size) -> "Camera":
+        """This camera with the focal lengths and the principal point (pixels of an (img_w, img_h) frame) replaced: fov_x / fov_y by
+        focal_to_fov for its lens, center_uv = (cx / W, cy / H).  Returns a new Camera (include/brush_hip_intrinsics.h)."""
+        import dataclasses
+        w, h = int(img_size[0]), int(img_size[1])
+        if not (all(math.isfinite(float(v)) for v in (fx, fy, cx, cy)) and fx > 0 and fy > 0):
+            raise ValueError("Camera.with_intrinsics: fx, fy must be positive, all four finite")
+        return dataclasses.replace(self, fov_x=focal_to_fov(fx, w, self.camera_model, self.dist), fov_y=focal_to_fov(fy, h, self.camera_model, self.dist),
+                                   center_uv=(float(cx) / w, float(cy) / h))
+
     def transformed(self, T: "SceneTransform") -> "Camera":
         """The camera that sees a scene moved by T (Splats.transformed) as this one saw the original: position s R p + t, orientation
         R times its own, by bh_camera_apply_scene_transform on its uniforms (include/brush_hip_scene.h).  Returns a new Camera."""
@@ -618,20 +628,23 @@ class RenderNode:
         return render_features(self, features)
 
     def backward(self, v_output, v_depth=None, depth_mode="expected", pose=False, v_normal=None, normal_mode="accumulated", v_distortion=None,
-                 distortion="z", distortion_near=0.2, distortion_far=1000.0, v_features=None, features=None):
+                 distortion="z", distortion_near=0.2, distortion_far=1000.0, intrinsics=False, v_features=None, features=None):
         """Gradients of <v_output, img> [+ <v_depth, depth(depth_mode)>] [+ <v_normal, normal(normal_mode)>] [+ <v_distortion,
         distortion(kind `distortion`, distortion_near, distortion_far)>]; v_output may be None when another cotangent is given.
         pose=True (bh_render_backward_pose_saved): also "v_viewmat", the twelve f32 of the gradient with respect to the camera's
         view matrix in the layout of BhCamera.vm, on the device (no readback); the colour term only.
+        intrinsics=True (bh_render_backward_intrinsics_saved, or bh_render_backward_camera_saved with v_depth / v_normal /
+        v_distortion): also "v_intrinsics", the four f32 (v_fx, v_fy, v_cx, v_cy) of the gradient of the whole sum with respect to
+        the camera's fx, fy, cx, cy, on the device (no readback); combinable with pose=True (include/brush_hip_intrinsics.h).
         v_features [H,W,C] with features [N,C] (bh_render_backward_features_saved): + <v_features, features(features)>, and
         "v_features" [N,C] in the result, the gradient with respect to `features`; not together with v_depth / v_normal /
-        v_distortion / pose."""
+        v_distortion / pose / intrinsics."""
         ctx, splats, dev = self.ctx, self.splats, self.splats.device
         w, h = self.img_size
         n, c = splats.num_splats(), splats.sh_coeffs.shape[1]
         if v_features is not None or features is not None:
-            if v_depth is not None or v_normal is not None or v_distortion is not None or pose:
-                raise BrushHipError("RenderNode.backward: the feature term does not combine with v_depth / v_normal / v_distortion / pose")
+            if v_depth is not None or v_normal is not None or v_distortion is not None or pose or intrinsics:
+                raise BrushHipError("RenderNode.backward: the feature term does not combine with v_depth / v_normal / v_distortion / pose / intrinsics")
             return self._backward_features(v_output, v_features, features)
         if v_output is None and v_depth is None and v_normal is None and v_distortion is None:
             raise BrushHipError("RenderNode.backward: neither v_output nor v_depth")
@@ -652,10 +665,21 @@ class RenderNode:
         v_op = torch.empty((n,), dtype=torch.float32, device=dev)
         v_rf = torch.empty((n,), dtype=torch.float32, device=dev)
         v_vm = torch.empty((12,), dtype=torch.float32, device=dev) if pose else None
+        v_in = torch.empty((4,), dtype=torch.float32, device=dev) if intrinsics else None
         tail = (_ptr(r_t), _ptr(splats.sh_coeffs), _ptr(r_o), _ptr(v_t), _ptr(v_sh), _ptr(v_op), _ptr(v_rf))
         # the narrowest entry point that takes every cotangent given
         lib = ctx.lib
-        if p_distortion is not None or p_normal is not None:
+        if intrinsics:
+            cams = (None if v_vm is None else _ptr(v_vm), _ptr(v_in))
+            if p_depth is None and p_normal is None and p_distortion is None:
+                entry, args = lib.bh_render_backward_intrinsics_saved, tail + cams
+            else:   # the general entry: the optional term records
+                addr = lambda p: None if p is None else p.value
+                rec = _ffi.BhCameraGradTerms(v_depth=addr(p_depth), v_normal=addr(p_normal), v_distortion=addr(p_distortion), depth_mode=_depth_mode(depth_mode),
+                                             normal_mode=_normal_mode(normal_mode),
+                                             distortion=_distortion_config(distortion, distortion_near, distortion_far))
+                entry, args = lib.bh_render_backward_camera_saved, (C.byref(rec),) + tail + cams
+        elif p_distortion is not None or p_normal is not None:
             maps = (p_depth, _depth_mode(depth_mode), p_normal, _normal_mode(normal_mode))
             if p_distortion is not None:
                 cfg = _distortion_config(distortion, distortion_near, distortion_far)
@@ -675,6 +699,8 @@ class RenderNode:
         res = dict(v_transforms=v_t, v_sh_coeffs=v_sh, v_raw_opacities=v_op, v_refine_weight=v_rf)
         if v_vm is not None:
             res["v_viewmat"] = v_vm
+        if v_in is not None:
+            res["v_intrinsics"] = v_in
         return res
 
     def _backward_features(self, v_output, v_map, features):
@@ -1145,6 +1171,91 @@ class PoseOptimizer:
         if not ctx.uses_torch_stream:
             ctx.sync()
         return self.update(view_id, vm, v_viewmat_dev.detach().cpu().numpy().astype("float64"))
+
+
+# ---------------------------------------------------------------------------
+# Camera intrinsics refinement (include/brush_hip_intrinsics.h)
+# ---------------------------------------------------------------------------
+def _uniforms_set_intrinsics(cam: "_ffi.BhCamera", fx, fy, cx, cy) -> "_ffi.BhCamera":
+    """A copy of the uniforms `cam` with these intrinsics (bh_camera_set_intrinsics rewrites the clamp limits and the cull angle with them)."""
+    out = _ffi.BhCamera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(_ffi.BhCamera))
+    if _ffi.load().bh_camera_set_intrinsics(C.byref(out), float(fx), float(fy), float(cx), float(cy)) != 0:
+        raise BrushHipError("bh_camera_set_intrinsics failed: fx, fy must be positive, all four finite")
+    return out
+
+
+class IntrinsicsOptimizer:
+    """Adam on a 4-vector (s_x, s_y, du, dv) per SENSOR, on the host in f64: a view of that sensor is rendered with
+    fx = fx0 exp(s_x), fy = fy0 exp(s_y), center_uv + (du, dv) of its dataset camera — free of the resolution, so the image scales of
+    one sensor share the vector.  `sensor_of`: view id -> sensor id (a view it does not name, and every view without it, belongs to
+    sensor 0).  The gradient of a step's v_intrinsics (v_fx, v_fy, v_cx, v_cy) is (v_fx fx, v_fy fy, v_cx W, v_cy H); share_focal ties
+    s_x = s_y and sums the two.
+
+    One step of a view, as PoseOptimizer's: `camera(view_id, base, img_size)` gives the uniforms to render, `update(view_id, cam,
+    v_intrinsics)` takes the rendered uniforms and the four floats read back after the backward (`step` does the readback), `bind`
+    also names the view on the ctx (a camera that changes every step must not key the per-view tables by its hash)."""
+
+    def __init__(self, lr_focal=1e-3, lr_center=1e-4, sensor_of=None, share_focal=False, beta1=0.9, beta2=0.999, eps=1e-12):
+        self.lr_focal, self.lr_center = float(lr_focal), float(lr_center)
+        self.sensor_of = dict(sensor_of or {})
+        self.share_focal = bool(share_focal)
+        self.beta1, self.beta2, self.eps = float(beta1), float(beta2), float(eps)
+        self.sensors = {}   # sensor id -> dict(params [4], m1 [4], m2 [4], t)
+
+    def _state(self, view_id):
+        import numpy as np
+        view_id = int(view_id)
+        if view_id <= 0:
+            raise ValueError("IntrinsicsOptimizer: a view id > 0 names the view (0 = unknown)")
+        sensor = self.sensor_of.get(view_id, 0)
+        if sensor not in self.sensors:
+            self.sensors[sensor] = dict(params=np.zeros(4), m1=np.zeros(4), m2=np.zeros(4), t=0)
+        return self.sensors[sensor]
+
+    def params(self, view_id):
+        return self._state(view_id)["params"].copy()
+
+    def camera(self, view_id, base, img_size=None) -> "_ffi.BhCamera":
+        """The uniforms of view `view_id` at its sensor's current correction; `base`: its dataset Camera (with img_size) or BhCamera."""
+        if not isinstance(base, _ffi.BhCamera):
+            base = base.uniforms(img_size)
+        sx, sy, du, dv = self._state(view_id)["params"]
+        if sx == 0.0 and sy == 0.0 and du == 0.0 and dv == 0.0:   # the identity, to the bit
+            out = _ffi.BhCamera()
+            C.memmove(C.byref(out), C.byref(base), C.sizeof(_ffi.BhCamera))
+            return out
+        return _uniforms_set_intrinsics(base, float(base.fx) * math.exp(sx), float(base.fy) * math.exp(sy), float(base.cx) + du * base.img_w,
+                                        float(base.cy) + dv * base.img_h)
+
+    def bind(self, ctx, view_id, base, img_size=None) -> "_ffi.BhCamera":
+        """camera(), and names the view on `ctx` for the forwards that follow (bh_set_view_id)."""
+        ctx.check(ctx.lib.bh_set_view_id(ctx._h, int(view_id)))
+        return self.camera(view_id, base, img_size)
+
+    def update(self, view_id, cam, v_intrinsics):
+        """One Adam step of the sensor's 4-vector on `v_intrinsics` [4] of a frame rendered with the uniforms `cam`."""
+        import numpy as np
+        s = self._state(view_id)
+        v = np.asarray(v_intrinsics, np.float64).reshape(4)
+        g = np.array([v[0] * float(cam.fx), v[1] * float(cam.fy), v[2] * float(cam.img_w), v[3] * float(cam.img_h)])
+        if self.share_focal:
+            g[0] = g[1] = g[0] + g[1]
+        s["t"] += 1
+        s["m1"] = self.beta1 * s["m1"] + (1.0 - self.beta1) * g
+        s["m2"] = self.beta2 * s["m2"] + (1.0 - self.beta2) * g * g
+        m1 = s["m1"] / (1.0 - self.beta1 ** s["t"])
+        m2 = s["m2"] / (1.0 - self.beta2 ** s["t"])
+        lr = np.array([self.lr_focal] * 2 + [self.lr_center] * 2)
+        s["params"] = s["params"] - lr * m1 / (np.sqrt(m2) + self.eps)
+        return g
+
+    def step(self, view_id, cam, v_intrinsics_dev, ctx: Optional["Context"] = None):
+        """update() on a device tensor of four floats the backward on `ctx` wrote; the 16-byte readback waits as PoseOptimizer.step's."""
+        ctx = ctx or get_context(v_intrinsics_dev.device)
+        if not ctx.uses_torch_stream:
+            ctx.sync()
+        return self.update(view_id, cam, v_intrinsics_dev.detach().cpu().numpy().astype("float64"))
 
 
 # ---------------------------------------------------------------------------
@@ -2200,7 +2311,7 @@ class SplatTrainer:
                  allreduce: str = "ring", lpips: Optional["Lpips"] = None, pose_optimizer: Optional["PoseOptimizer"] = None,
                  exposure: Optional["ExposureTable"] = None, exposure_lr=None, bilagrid: Optional["BilateralGridTable"] = None, bilagrid_lr=None,
                  bilagrid_tv_weight: float = 10.0, envmap: Optional["EnvironmentMap"] = None, envmap_lr=None,
-                 feature_field: Optional["FeatureField"] = None):
+                 intrinsics_optimizer: Optional["IntrinsicsOptimizer"] = None, feature_field: Optional["FeatureField"] = None):
         """seed: an int turns on the two stochastic terms of the reference's step — the visibility-gated noise on the
         means (train.rs:389-416) and the background jitter (train.rs:896-908) — drawn by the library's counter-based
         generator as pure functions of (seed, step[, splat]); data-parallel ranks must pass the same seed.  None (the
@@ -2239,7 +2350,14 @@ class SplatTrainer:
         envmap: an EnvironmentMap (bh_train_set_envmap): every step composites its frame over the map before the loss (an exposure
         table or a bilateral grid then act on the composited frame) and updates the map on the device.  The frame is rendered on
         black: config.background_color must be (0, 0, 0) and the background jitter is not drawn.  envmap_lr: an optional callable of
-        the step number (from 1), as exposure_lr.  Not with partition "tiles" and not together with `pose_optimizer`."""
+        the step number (from 1), as exposure_lr.  Not with partition "tiles" and not together with `pose_optimizer`.
+
+        intrinsics_optimizer: an IntrinsicsOptimizer that refines the sensors' focal lengths and principal points beside the splats
+        (bh_train_set_intrinsics_grad): every step renders the batch's view with its sensor's current intrinsics, reads the step's
+        four gradient floats back and updates that sensor's 4-vector.  May be combined with `pose_optimizer`: the two readbacks
+        (48 + 16 bytes) are one copy behind one synchronisation.  Batches must carry a view_id > 0.  Not with partition "tiles", not
+        with `envmap` (the ray directions depend on the intrinsics) and not with config.normal_loss_weight > 0 (the depth-to-normal
+        stencil uses fx, fy)."""
         if partition not in ("cameras", "tiles"):
             raise ValueError("partition must be 'cameras' or 'tiles'")
         if pose_optimizer is not None and partition == "tiles":
@@ -2256,10 +2374,19 @@ class SplatTrainer:
             raise ValueError("envmap needs background_color (0, 0, 0): the map is what lies behind the splats")
         if envmap is not None and pose_optimizer is not None:
             raise ValueError("envmap and pose_optimizer cannot be combined (the pose pass does not carry the lookup's dependence on the rotation)")
+        if intrinsics_optimizer is not None and partition == "tiles":
+            raise ValueError("intrinsics_optimizer is not available with partition 'tiles'")
+        if intrinsics_optimizer is not None and envmap is not None:
+            raise ValueError("envmap and intrinsics_optimizer cannot be combined (the ray directions depend on the intrinsics)")
+        if intrinsics_optimizer is not None and float(config.normal_loss_weight) > 0.0:
+            raise ValueError("normal_loss_weight > 0 and intrinsics_optimizer cannot be combined (the depth-to-normal stencil uses fx, fy)")
         self.envmap, self.envmap_lr = envmap, envmap_lr
         self.feature_field = feature_field
         self.pose_optimizer = pose_optimizer
-        self._pose_buf = None
+        self.intrinsics_optimizer = intrinsics_optimizer
+        self._cam_buf = None    # [16] f32 on the device: the step's v_viewmat [12] | v_intrinsics [4], read back as one
+        self._pose_buf = None   # ... and the two views of it the step's buffers are attached as
+        self._intr_buf = None
         self.exposure, self.exposure_lr = exposure, exposure_lr
         if bilagrid is not None and partition == "tiles":
             raise ValueError("bilagrid is not available with partition 'tiles'")
@@ -2510,6 +2637,8 @@ class SplatTrainer:
         terms.append((lib.bh_train_set_lpips, (self.lpips._h if lw > 0.0 else None, lw if lw > 0.0 else 0.0), None))
         if self.pose_optimizer is not None:
             terms.append((lib.bh_train_set_pose_grad, (_ptr(self._pose_buf),), off))
+        if self.intrinsics_optimizer is not None:
+            terms.append((lib.bh_train_set_intrinsics_grad, (_ptr(self._intr_buf),), off))
         ex, grid = self.exposure, self.bilagrid
         if ex is not None:
             if self.exposure_lr is not None:
@@ -2573,13 +2702,16 @@ class SplatTrainer:
         stats = _ffi.BhTrainStats()
         b.exchange_mode = 1 if (self.sparse_exchange and (self.pg is not None or self.native_comm)) else 0
         b.view_id = int(batch.view_id) & 0xFFFFFFFF
-        po = self.pose_optimizer
-        if po is not None:   # the view at its current correction, named by its id (a moving camera's hash would mint a view table per step)
+        po, io = self.pose_optimizer, self.intrinsics_optimizer
+        if io is not None:   # the view with its sensor's current intrinsics ...
+            b.camera = io.camera(b.view_id, b.camera)
+        if po is not None:   # ... at its current correction, named by its id (a moving camera's hash would mint a view table per step)
             b.camera = po.camera(b.view_id, b.camera)
-            if self._pose_buf is None:
-                self._pose_buf = torch.zeros((12,), dtype=torch.float32, device=dev)
-                if not ctx.uses_torch_stream:
-                    torch.cuda.current_stream(dev).synchronize()   # the zero-fill ran on torch's stream, the step runs on the ctx's own
+        if (po is not None or io is not None) and self._cam_buf is None:
+            self._cam_buf = torch.zeros((16,), dtype=torch.float32, device=dev)
+            self._pose_buf, self._intr_buf = self._cam_buf[:12], self._cam_buf[12:]
+            if not ctx.uses_torch_stream:
+                torch.cuda.current_stream(dev).synchronize()   # the zero-fill ran on torch's stream, the step runs on the ctx's own
         hook, scale = None, 1.0
         if self.native_comm:
             scale = 1.0 if tiles else 1.0 / ctx.comm_world()
@@ -2591,8 +2723,14 @@ class SplatTrainer:
         with self._attached(ctx, terms):
             ctx.check(ctx.lib.bh_train_step(ctx._h, C.byref(cfg), C.byref(st), C.byref(b), C.cast(hook, C.c_void_p) if hook else None, None,
                                             float(scale), C.byref(stats)))
-        if po is not None:
-            po.step(b.view_id, list(b.camera.vm), self._pose_buf, ctx)
+        if po is not None or io is not None:   # one readback (48 + 16 bytes) behind one synchronisation
+            if not ctx.uses_torch_stream:
+                ctx.sync()
+            cam_grads = self._cam_buf.detach().cpu().numpy().astype("float64")
+            if po is not None:
+                po.update(b.view_id, list(b.camera.vm), cam_grads[:12])
+            if io is not None:
+                io.update(b.view_id, b.camera, cam_grads[12:])
         if ft is not None:   # the step succeeded with the term: the library applied one Adam update to the field
             self.feature_field.t += 1
         self.step_count = st.step_count

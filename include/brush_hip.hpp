@@ -26,6 +26,8 @@
 //   brush_hip::Lpips / lpips / lpips_value_and_grad / train_set_lpips   crates/lpips/src/lib.rs, train.rs:265-273 (lpips_loss_weight)
 //   RenderNode::backward_pose / train_set_pose_grad / pose_twist / camera_apply_twist   not in the reference: camera pose
 //                                                   gradients (gsplat's v_viewmats) and the host arithmetic of a pose update
+//   RenderNode::backward_intrinsics / backward_camera / train_set_intrinsics_grad / camera_set_intrinsics   not in the reference:
+//                                                   camera intrinsics gradients (focal, principal point; brush_hip_intrinsics.h)
 //   brush_hip::ExposureTable / train_set_exposure   not in the reference: per-view exposure compensation (an affine colour
 //                                                   transform per training view, Adam on the device; brush_hip_exposure.h)
 //   brush_hip::depth_loss_value_and_grad / eval_depth_metrics / train_set_depth   not in the reference: depth supervision (a fused
@@ -93,6 +95,7 @@
 #include "brush_hip_scene.h"
 #include "brush_hip_lift.h"
 #include "brush_hip_envmap.h"
+#include "brush_hip_intrinsics.h"
 
 namespace brush_hip {
 
@@ -537,6 +540,20 @@ class RenderNode {
         return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
             return bh_render_backward_pose_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf,
                                                  v_viewmat);
+        });
+    }
+    // ... and v_intrinsics [4] (device): (v_fx, v_fy, v_cx, v_cy) (brush_hip_intrinsics.h); v_viewmat may be nullptr (no pose pass)
+    SplatGrads backward_intrinsics(const float* v_output, float* v_intrinsics, float* v_viewmat = nullptr) const {
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_intrinsics_saved(ctx_.get(), &aux.raw, v_output, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op, v_rf,
+                                                       v_viewmat, v_intrinsics);
+        });
+    }
+    // ... with the optional depth, rendered-normal and distortion cotangents of `terms` (v_output may then be nullptr)
+    SplatGrads backward_camera(const float* v_output, const BhCameraGradTerms& terms, float* v_intrinsics, float* v_viewmat = nullptr) const {
+        return run_backward([&](float* v_t, float* v_sh, float* v_op, float* v_rf) {
+            return bh_render_backward_camera_saved(ctx_.get(), &aux.raw, v_output, &terms, folded_.t, splats_.sh_coeffs.data(), folded_.o, v_t, v_sh, v_op,
+                                                   v_rf, v_viewmat, v_intrinsics);
         });
     }
     RenderAux aux;
@@ -1417,6 +1434,14 @@ inline std::array<double, 6> pose_twist(const float vm[12], const float v_viewma
 // W <- exp([omega]x) W, t <- exp([omega]x) t + tau on the uniforms, vm and cam_pos together
 inline void camera_apply_twist(BhCamera& cam, const std::array<double, 6>& twist) {
     if (bh_camera_apply_twist(&cam, twist.data()) != 0) throw Error(BH_ERR_INVALID_ARG, "camera_apply_twist: null argument, a degenerate view matrix or a twist that is not finite");
+}
+
+// ---- camera intrinsics gradients (brush_hip_intrinsics.h; not in the reference) -------------------------------------
+// bh_train_step on this ctx writes the step's intrinsics gradient into v_intrinsics (device, 4 floats); nullptr detaches
+inline void train_set_intrinsics_grad(const Context& ctx, float* v_intrinsics) { ctx.check(bh_train_set_intrinsics_grad(ctx.get(), v_intrinsics)); }
+// fx, fy, cx, cy into the uniforms, with the clamp limits and the cull angle that follow from them
+inline void camera_set_intrinsics(BhCamera& cam, double fx, double fy, double cx, double cy) {
+    if (bh_camera_set_intrinsics(&cam, fx, fy, cx, cy) != 0) throw Error(BH_ERR_INVALID_ARG, "camera_set_intrinsics: fx, fy must be positive, all four finite");
 }
 
 // ---- per-view exposure compensation (brush_hip_exposure.h; not in the reference) ---------------------------------------------------

@@ -6,7 +6,8 @@
  *
  * The camera is BhCamera.vm: W (3x3 world-to-camera rotation) and t (translation).  mean_c = W mean + t, cov_c = W Sigma W^T, and
  * the SH view direction is (mean - p) / |mean - p| with p = -W^T t: the cam_pos field is treated as that function of W and t.
- * Intrinsics, distortion coefficients and the Jacobian clamp limits are constants; in Mip mode the opacity compensation is a
+ * Intrinsics, distortion coefficients and the Jacobian clamp limits are constants (the gradient with respect to fx, fy, cx, cy is
+ * brush_hip_intrinsics.h's, and bh_render_backward_intrinsics_saved returns both from one backward); in Mip mode the opacity compensation is a
  * constant of the geometry, as it is for the splat gradients.
  *
  * v_viewmat [12] f32, in the layout of BhCamera.vm (column-major 3x4), is the gradient of <v_output, image> with respect to the
