@@ -1516,4 +1516,23 @@ extern "C" int bh_debug_depth_sort(bh_ctx* ctx, const uint32_t* keys, const uint
     BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
+// launch_image_loss_fused_window (loss_fused.hip) on the caller's device buffers, with the chain factors of bh_image_loss_value_and_grad
+// (means over the WHOLE image, as the train step's strips use them), no pinned host words, and the ctx stream synchronised behind it.
+// Tile rows [tile_y0, tile_y1) of 16 pixel rows; tile_y1 is clipped to the image's; loss_out [1]: the window's share of the loss;
+// v_output [h, w, 4]: written in the window's pixel rows only.
+extern "C" int bh_debug_image_loss_window(bh_ctx* ctx, const float* img_hwc4, const uint32_t* gt_packed, uint32_t h, uint32_t w, const BhLossConfig* cfg,
+                                          float alpha_weight, uint32_t tile_y0, uint32_t tile_y1, float* loss_out, float* v_output) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!img_hwc4 || !gt_packed || !cfg || !loss_out || !v_output || h == 0 || w == 0)
+        return set_error(ctx, BH_ERR_INVALID_ARG, "debug_image_loss_window: bad argument");
+    if (tile_y0 >= tile_y1) return set_error(ctx, BH_ERR_INVALID_ARG, "debug_image_loss_window: empty tile-row window");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t hw = (size_t)h * w;
+    const bool alpha = alpha_weight > 0.0f;
+    // (a window that starts behind the last tile row is the launcher's to refuse: it clips tile_y1 first)
+    BH_TRY(launch_image_loss_fused_window(ctx, img_hwc4, gt_packed, h, w, *cfg, alpha, 1.0f / (float)(hw * 3), alpha ? alpha_weight / (float)hw : 0.0f, tile_y0,
+                                          tile_y1, loss_out, v_output, nullptr, nullptr, 0u));
+    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 #endif
