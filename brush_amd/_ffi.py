@@ -481,6 +481,11 @@ TEST_HOOK_SYMBOLS = {"bh_debug_fill_train_scratch": (C.c_int, [C.c_void_p, C.c_u
                      # (ctx, keys, minmax, counts, n, out_keys, out_vals, cum, spl, spl_written, totals_out[512]): api.hip
                      "bh_debug_depth_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+                     # (ctx, keys, minmax, counts, n, out_keys, out_vals, cum, spl, cap, stride, ctr_out[256], fell_back): api.hip
+                     "bh_debug_depth_deal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+                     "bh_debug_dsort_deal_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+                     "bh_debug_set_deal_capacity": (C.c_int, [C.c_void_p, C.c_uint32]),
                      # (ctx, img_hwc4, gt_packed, h, w, cfg, alpha_weight, tile_y0, tile_y1, loss_out, v_output): api.hip
                      "bh_debug_image_loss_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BhLossConfig), C.c_float, C.c_uint32,
                                                               C.c_uint32, C.c_void_p, C.c_void_p])}

@@ -11,6 +11,7 @@
 
 #include "../../include/brush_hip_intrinsics.h"
 #include "context.h"
+#include "depth_deal.h"
 #include "device_rng.h"
 #include "param_table.h"
 
@@ -285,6 +286,7 @@ void bh_destroy(bh_ctx* ctx) {
         if (b.ptr) (void)hipFree(b.ptr);
     if (ctx->host_counters) (void)hipHostFree(ctx->host_counters);
     if (ctx->dsort_spl) (void)hipFree(ctx->dsort_spl);
+    if (ctx->deal_ctr) (void)hipFree(ctx->deal_ctr);
     if (ctx->sort_groups) (void)hipFree(ctx->sort_groups);
     if (ctx->readback_ev) (void)hipEventDestroy(ctx->readback_ev);
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
@@ -401,6 +403,8 @@ const Option kOptions[] = {
      [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_generic_depth_sort); }},
     {"dsort_splitters", "0|1: the fused depth sort splits at the 254 depth quantiles of the view's previous frame (default 1) or always linearly over the frame's key range",
      [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_dsort_splitters); }},
+    {"dsort_deal", "0|1: K1 deals the listed splats straight into the depth sort's buckets when the view's splitter table holds quantiles (default 1) or the histogram and split launches always run",
+     [](bh_ctx* c, const char* v) { return parse_flag(v, &c->knob_dsort_deal); }},
     {"tile_sort", "auto|bucket|lsd: the forward's tile sort (auto: bucket sort unless the view's pairs are concentrated in few tiles)",
      [](bh_ctx* c, const char* v) { const std::string w(v); if (w == "auto") { c->knob_tile_sort = 0; return true; } if (w == "bucket") { c->knob_tile_sort = 1; return true; } if (w == "lsd") { c->knob_tile_sort = 2; return true; } return false; }},
     {"spec_k5", "0|1: queue the list builder before the host has read the frame's counts (default 1; 0: behind the count readback)",
@@ -742,6 +746,16 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
     float4* spec_vc = nullptr;
     uint32_t *spec_tile_ids = nullptr, *spec_isect_gids = nullptr;
     if (n > 0) {
+        fused_scan = depth_sort_supported(n) && !ctx->knob_generic_depth_sort;
+        // (the sort's first kernel adds the counter slots up and stores the sums into the pinned block itself; only the generic
+        //  sort path still needs a copy launch between K1 and the sort)
+        const bool sums_on_device = fused_scan && !ctx->knob_readback_copy;
+        // the depth sort's splitter table of this view and list mode — or, for a frame without a view, the ctx's own once a frame has made it
+        bool* spl_written = nullptr;
+        uint32_t* spl_listed = nullptr;
+        uint32_t* spl = view_splitters(view, cut_active, &spl_written, &spl_listed);
+        if (!spl && ctx->dsort_spl) { spl = ctx->dsort_spl; spl_written = &ctx->dsort_spl_written; spl_listed = &ctx->dsort_spl_keys; }
+        DealArgs dealt;   // K1 deals the listed splats into the depth sort's buckets (depth_deal.h)
         {
             ProfScope ps(ctx, "ProjectSplats");
             if (!ctx->counters_ready) BH_HIP(ctx, hipMemsetAsync(counter_pairs, 0, 2 * counter_set_bytes, ctx->stream));
@@ -779,6 +793,8 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                 prep.span_f4 = (uint32_t)(req.grad_floats / 4);
                 ctx->clears.k1_cleared_span();
             }
+            BH_TRY(depth_deal_prepare(ctx, n, spl, sums_on_device && spl_written && *spl_written && depth_deal_table_usable(*spl_listed), &prep));
+            dealt = prep.deal;
             BH_TRY(launch_project_forward(ctx, f.u, n, mip, sh_degree, transforms, sh_coeffs, raw_opacities, depth_keys, isect_counts, max_radius,
                                           f.proj_by_gid, counters, prep, cut_active ? vtab : nullptr, near_counts));
             ctx->counter_phase ^= 1u;
@@ -788,10 +804,6 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
         // and needs neither count, so it is queued BEFORE the host waits: the GPU sorts while the
         // host reads the counts, sizes the buffers and queues the rest.
         auto* hslots = reinterpret_cast<unsigned long long*>(ctx->host_counters + 16);
-        fused_scan = depth_sort_supported(n) && !ctx->knob_generic_depth_sort;
-        // (the sort's first kernel adds the counter slots up and stores the sums into the pinned block itself; only the generic
-        //  sort path still needs a copy launch between K1 and the sort)
-        const bool sums_on_device = fused_scan && !ctx->knob_readback_copy;
         // ... and the host does not wait for an event behind that kernel either: it polls a tag word the kernel stores behind the sums
         const bool poll_tag = sums_on_device && !ctx->knob_event_waits;
         if (!sums_on_device) {
@@ -809,11 +821,9 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
                 if (!cum_early) return BH_ERR_OOM;
                 // (per-tile cuts: the scan of the NEAR counts = the slot ranges of the near pass's list)
                 if (poll_tag && ++ctx->readback_tag == 0u) ctx->readback_tag = 1u;
-                bool* spl_written = nullptr;
-                uint32_t* spl = view_splitters(view, cut_active, &spl_written);
                 BH_TRY(depth_sort_scan(ctx, depth_keys, counters + COUNTER_MINMAX_WORD, cut_active ? near_counts : isect_counts, n, depths_sorted, f.gfc, cum_early,
                                        sums_on_device ? counters : nullptr, ctx->host_counters + 16, ctx->readback_ev, poll_tag ? ctx->readback_tag : 0u,
-                                       sums_on_device ? dev_sums : nullptr, spl, spl_written));
+                                       sums_on_device ? dev_sums : nullptr, spl, spl_written, &dealt));
             } else {
                 BH_TRY(radix_argsort(ctx, depth_keys, nullptr, n, 32, depths_sorted, f.gfc));
             }
@@ -862,6 +872,20 @@ int bh::forward_impl(bh_ctx* ctx, const ForwardRequest& req, BhRenderOut* out) {
         // per-tile cuts: only the splats that own a pair in front of some cut were given a real depth key (K1): the compact
         // arrays, K5's grid, the backward's accumulator and K18 are sized for THEM; num_visible stays the reference's count
         f.nv = cut_active ? (uint32_t)hc[3] : nv_true;   // (BH_CUT_SORT_ALL: K1 then listed every visible splat, hc[3] == hc[0])
+        if (dealt.ctr && reinterpret_cast<const volatile uint32_t*>(hslots)[HOST_DEAL_WORD] != 0u) {
+            // K1 ran out of slots in a bucket (depth_deal.h): the deal's bucket launch did nothing, and told the kernels queued behind it that
+            // nothing is listed.  The order comes from depth_keys and the counts through the three launches, and K5 is queued again behind them,
+            // the way a pair-buffer overflow queues it again.
+            // (The host has the counts already.  The counter set is handed over once more only because the histogram kernel's readback block is
+            //  what refreshes dev_sums, which the deal's launch zeroed and K5 reads: it stores the same sums into the pinned words again, behind
+            //  the host's read of them, clears HOST_DEAL_WORD, leaves the tag alone, and its event is one nobody waits for.)
+            ProfScope ps(ctx, "DepthSort");
+            ctx->deal_fallbacks++;
+            BH_TRY(depth_sort_scan(ctx, depth_keys, counters + COUNTER_MINMAX_WORD, cut_active ? near_counts : isect_counts, n, depths_sorted, f.gfc, cum_early,
+                                   counters, ctx->host_counters + 16, ctx->readback_ev, 0u, dev_sums, spl, spl_written));
+            k5_queued = false;
+        }
+        if (fused_scan && spl_listed && (spl_written == nullptr || *spl_written)) *spl_listed = f.nv;   // this frame's bucket kernel rewrote the table: quantiles iff f.nv >= SPL_MIN_KEYS
     } else {   // no K1 to clear them on the way
         BH_HIP(ctx, hipMemsetAsync(tile_offsets, 0, ((size_t)f.num_tiles * 2 + LPT_HEADER_WORDS) * 4, ctx->stream));
         if (visible_words) BH_HIP(ctx, hipMemsetAsync(f.visible, 0, visible_words * 4, ctx->stream));
@@ -1107,7 +1131,7 @@ int bh_forget_views(bh_ctx* ctx) {
     BH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->far_job.pending) BH_TRY(finish_far_slice(ctx, nullptr));
     // (the depth sort's splitter tables are per-ctx state of the same kind: a run that starts over starts from the linear split)
-    if (ctx->dsort_spl) { BH_HIP(ctx, hipMemsetAsync(ctx->dsort_spl, 0, DSORT_SPL_STRIDE * 4, ctx->stream)); ctx->dsort_spl_written = false; }
+    if (ctx->dsort_spl) { BH_HIP(ctx, hipMemsetAsync(ctx->dsort_spl, 0, DSORT_SPL_STRIDE * 4, ctx->stream)); ctx->dsort_spl_written = false; ctx->dsort_spl_keys = 0u; }
     if (ctx->views.empty()) return 0;
     BH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // queued kernels may still use the tables
     deliver_pending_loss(ctx);
@@ -1514,6 +1538,73 @@ extern "C" int bh_debug_depth_sort(bh_ctx* ctx, const uint32_t* keys, const uint
     else if (spl_written) *spl_written = ctx->dsort_spl_written ? 1 : 0;
     BH_HIP(ctx, hipMemcpyAsync(totals_out, ctx->slots[SLOT_SORT_HIST].ptr, 2 * 256 * 4, hipMemcpyDeviceToHost, ctx->stream));
     BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+// The dealing path of the depth order (depth_deal.h) on the caller's device buffers, the way a forward runs it: a stand-in for K1 deals the
+// listed keys (!= 0xFFFFFFFF) by the table `spl` into buckets of `cap` slots (0: deal_capacity(n)), the one-launch depth_sort_scan follows,
+// and if a bucket overflowed the three launches run behind it.  stride: the stand-in's thread t deals element (t * stride) % n — any stride
+// coprime to n deals every element once, in another arrival order.  ctr_out [256] (host): the 255 bucket words (low half: splats, high half:
+// tile counts) | the overflow word; *fell_back: the three launches ran.  spl must be a table a frame has written.
+__global__ __launch_bounds__(256) void debug_deal_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ counts, uint32_t n, uint32_t stride, bh::DealArgs d) {
+    __shared__ uint32_t s_spl[bh::DEAL_SPL_WORDS];
+    bh::deal_stage(d, s_spl);
+    __syncthreads();
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t e = (uint32_t)(((unsigned long long)t * stride) % n);
+    const uint32_t key = keys[e];
+    if (key != 0xFFFFFFFFu) bh::deal_put(d, bh::deal_take(d, s_spl, key, counts[e]), key, e);
+}
+extern "C" int bh_debug_depth_deal(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys, uint32_t* out_vals,
+                                   uint32_t* cum, uint32_t* spl, uint32_t cap, uint32_t stride, unsigned long long* ctr_out, int* fell_back) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    if (!keys || !minmax || !counts || !out_keys || !out_vals || !cum || !spl || !ctr_out || !fell_back || stride == 0u)
+        return set_error(ctx, BH_ERR_INVALID_ARG, "debug_depth_deal: bad argument");
+    if (n == 0 || !depth_sort_supported(n)) return set_error(ctx, BH_ERR_INVALID_ARG, "debug_depth_deal: n is outside the fused sort's reach");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    DealArgs d;
+    d.spl = spl;
+    d.cap = cap ? cap : deal_capacity(n);
+    d.region = (uint2*)ensure(ctx, SLOT_DEAL_REGION, (size_t)DEAL_BUCKETS * d.cap * sizeof(uint2));
+    if (!d.region) return BH_ERR_OOM;
+    if (hipMalloc((void**)&d.ctr, (size_t)DEAL_SET_U64 * 8) != hipSuccess) { (void)hipGetLastError(); return BH_ERR_OOM; }
+    int rc = check_hip(ctx, hipMemsetAsync(d.ctr, 0, (size_t)DEAL_SET_U64 * 8, ctx->stream), "debug_depth_deal: clear");
+    if (rc == 0) {
+        hipLaunchKernelGGL(debug_deal_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, keys, counts, n, stride, d);
+        rc = check_hip(ctx, hipGetLastError(), "debug_deal_kernel");
+    }
+    bool written = true;
+    if (rc == 0) rc = depth_sort_scan(ctx, keys, minmax, counts, n, out_keys, out_vals, cum, nullptr, nullptr, nullptr, 0u, nullptr, spl, &written, &d);
+    unsigned long long host[DEAL_BUCKETS + 1u];
+    if (rc == 0) rc = check_hip(ctx, hipMemcpy2DAsync(host, 8, d.ctr, (size_t)DEAL_LINE_U64 * 8, 8, DEAL_BUCKETS + 1u, hipMemcpyDeviceToHost, ctx->stream), "debug_depth_deal: counters");
+    if (rc == 0) rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "debug_depth_deal: sync");
+    if (rc == 0) {
+        for (uint32_t i = 0; i <= DEAL_BUCKETS; ++i) ctr_out[i] = host[i];
+        *fell_back = host[DEAL_BUCKETS] != 0ull ? 1 : 0;
+        if (*fell_back) {
+            ctx->deal_fallbacks++;
+            rc = depth_sort_scan(ctx, keys, minmax, counts, n, out_keys, out_vals, cum, nullptr, nullptr, nullptr, 0u, nullptr, spl, &written);
+            if (rc == 0) rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "debug_depth_deal: sync");
+        }
+    } else {
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(d.ctr);
+    return rc;
+}
+// slots per bucket for every later forward of this ctx whose K1 deals, instead of deal_capacity(n) (0: back to it): a real frame's
+// overflow recovery — the bucket launch that does nothing, the speculative K5 that hears "nothing listed", the three launches and K5
+// queued again — is reached with a small scene
+extern "C" int bh_debug_set_deal_capacity(bh_ctx* ctx, uint32_t cap) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    ctx->deal_cap_override = cap;
+    return 0;
+}
+// out[0]: forwards (and debug_depth_deal calls) whose depth order took the dealing path, out[1]: of those, the ones that fell back to the three launches
+extern "C" int bh_debug_dsort_deal_counts(bh_ctx* ctx, uint32_t* out) {
+    if (!ctx || !out) return BH_ERR_INVALID_ARG;
+    out[0] = ctx->deal_frames;
+    out[1] = ctx->deal_fallbacks;
     return 0;
 }
 // launch_image_loss_fused_window (loss_fused.hip) on the caller's device buffers, with the chain factors of bh_image_loss_value_and_grad

@@ -102,6 +102,7 @@ enum Slot : int {
     SLOT_FEATURE_TERM,       // bh_train_step with a feature term: the feature map [H,W,C] | v_map [H,W,C] | the term's loss pair (4 floats)
     SLOT_FEATURE_GRAD,       // ... and its dense v_features [N,C], from the backward to the field's update
     SLOT_ENVMAP_FRAME,       // bh_train_step with an environment map: [H,W,4] the frame composited over the map (envmap.hip; out_img stays what K17 replays)
+    SLOT_DEAL_REGION,        // depth sort, dealing K1 (depth_deal.h): [255][cap] (key, splat id) — the buckets K1 fills
     SLOT_SCENE,              // bh_splats_select_region with a count: one u32 per block of the select | the total (scene_edit.hip)
     SLOT_COUNT
 };
@@ -134,6 +135,7 @@ constexpr uint32_t FAR_GROUP_BLOCKS = 64;   // far slice: count-kernel blocks pe
 constexpr size_t COUNTER_READ_BYTES = COUNTER_SLOTS * 8 * COUNTER_K1_U64;
 // ... or, when the depth sort's first kernel adds the slots up on the device: [COUNTER_K1_U64] u64 totals
 constexpr uint32_t HOST_SUM_WORDS = 2 * COUNTER_K1_U64 + 1;   // (+ the tag word the host polls)
+constexpr uint32_t HOST_DEAL_WORD = HOST_SUM_WORDS;           // ... and behind it: != 0, K1's deal overflowed a bucket (depth_deal.h), the order is not there yet
 // pinned host block: [16] u32 scalars (refine control block / bounds picks / exchange rows) | the counter slots | the loss word.
 // The loss has a word of its own BEHIND everything the refine / bounds / exchange readbacks overwrite.
 constexpr size_t HOST_LOSS_WORD = 16 + COUNTER_READ_BYTES / 4;
@@ -178,6 +180,7 @@ struct ViewState {
     uint32_t last_pairs = 0;        // num_intersections of the view's last frame
     uint32_t complete_frames = 0;   // frames to render with complete lists because cutting saved (almost) nothing last time; then one probe frame
     bool spl_written[2] = {false, false};   // the view's depth-sort splitter tables ([0] complete lists, [1] cut lists) have been written by a frame
+    uint32_t spl_keys[2] = {0, 0};          // ... and the listed splats of the frame that wrote each last (>= SPL_MIN_KEYS: the table holds quantiles — K1 may deal by it)
     bool casual = false;            // created by a forward-only frame keyed by its camera (a viewer / eval render): these compete for CASUAL_VIEW_STATES tables only
 };
 constexpr uint32_t CUT_MIN_PAIRS = 1500000u;   // frames with fewer pairs keep complete lists (nothing to save)
@@ -231,6 +234,18 @@ constexpr uint32_t SPLIT_TAIL_WORDS = 8u + 8u * SPLIT_MAX * 4u;
 constexpr uint32_t BWD_CKPT_MAX_SLOTS = 96u * 1024u;   // 384 MB of checkpoints at most (frames with > ~11 M listed pairs split only their first tiles)
 constexpr uint32_t DSORT_SPL_STRIDE = 260;            // words of one depth-sort splitter table (depth_sort.hip SPLITTERS)
 constexpr uint32_t VIEW_SPL_WORDS = 2 * DSORT_SPL_STRIDE;   // a view keeps two behind its tile table: [0] frames with complete lists, [1] cut lists
+// DEALING K1 (depth_deal.h): K1 puts every listed splat straight into its depth-sort bucket.  One counter set: 255 bucket words
+// (low half: splats, high half: their tile counts) and the overflow word, each in a 128-byte line of its own; two sets, K1 clears the idle one.
+constexpr uint32_t DEAL_BUCKETS = 255;
+constexpr uint32_t DEAL_LINE_U64 = 16;
+constexpr uint32_t DEAL_SET_U64 = (DEAL_BUCKETS + 1u) * DEAL_LINE_U64;
+constexpr uint32_t DEAL_OVERFLOW_U64 = DEAL_BUCKETS * DEAL_LINE_U64;
+struct DealArgs {                                // all NULL: K1 does not deal
+    const uint32_t* spl = nullptr;               // the view's splitter table of this list mode (depth_sort.hip SPLITTERS)
+    unsigned long long* ctr = nullptr;           // [DEAL_SET_U64] this frame's counter set (zero on entry)
+    uint2* region = nullptr;                     // [DEAL_BUCKETS][cap] (key, splat id) in arrival order
+    uint32_t cap = 0;                            // slots per bucket; a splat that finds none sets the overflow word
+};
 constexpr size_t MAX_VIEW_STATES = 4096;
 constexpr uint64_t DIRECT_ALLREDUCE_MIN_FLOATS = 1u << 16;   // shorter messages are latency-bound: ncclAllReduce
 constexpr uint32_t AUTO_EXACT_FRAMES = 12;   // frames a view renders complete lists after a cut frame that listed > auto_exact_share of its pairs
@@ -539,6 +554,7 @@ struct bh_ctx {
     uint32_t knob_cut_margin_pct = 150;   // BH_CUT_MARGIN_PCT: margin behind a tile's last useful splat, % of its depth rank (A/B)
     bh::FarJob far_job;
     uint32_t refine_n = 0, refine_new_n = 0;  // a bh_refine_plan awaiting its bh_refine_apply
+    bool dsort_deal_lds_raised = false;   // ... and dsort_deal_bucket_kernel
     bool dsort_lds_raised = false;    // likewise dsort_bucket_kernel (depth_sort.hip)
     // the sorts' group tables (sort.hip SortGroups): two sets of sort_groups_cap words; set sort_groups_cur is all zero, the other one
     // holds the last sort's sums in its first sort_groups_dirty words
@@ -547,6 +563,12 @@ struct bh_ctx {
     uint32_t sort_groups_cur = 0;
     uint32_t* dsort_spl = nullptr;    // [DSORT_SPL_STRIDE] device: the depth sort's splitter table (depth_sort.hip SPLITTERS) of frames without a view
     bool dsort_spl_written = false;   // a frame has written it (until then a frame sorts a sample first)
+    uint32_t dsort_spl_keys = 0;      // ... and the listed splats of the frame that wrote it last (ViewState::spl_keys)
+    unsigned long long* deal_ctr = nullptr;   // [2][DEAL_SET_U64] device: the dealing K1's counter sets (depth_deal.h); every K1 launch clears the idle one
+    uint32_t deal_phase = 0;          // the set the next K1 deals into
+    uint32_t deal_frames = 0, deal_fallbacks = 0;   // diagnostics: forwards whose K1 dealt / of those, the ones whose order had to be queued again (a bucket overflowed)
+    uint32_t deal_cap_override = 0;   // != 0: slots per bucket instead of deal_capacity(n) (bh_debug_set_deal_capacity of the test-hooks library only)
+    bool knob_dsort_deal = true;      // option dsort_deal: K1 deals the listed splats into the depth sort's buckets (0: histogram + split launches)
     bool knob_dsort_splitters = true; // option dsort_splitters: the split digit from the previous frame's quantiles (0: always the linear split)
     bool adam_lds_raised = false;     // adam_rowreduced_kernel's > 64 KB dynamic-LDS opt-in was made on this ctx's device
     uint32_t update_lds_raised = 0;   // likewise train_update_kernel: one bit per instantiation (optim.hip launch_train_update)
@@ -684,7 +706,7 @@ bool cut_this_frame(const bh_ctx* ctx, ViewState* vs, bool allow_cut);
 // the view's device table: [T] depth cuts | [T] per-tile work of its last frame | [VIEW_SPL_WORDS] depth-sort splitter tables
 uint32_t* view_table(const ViewState* vs);
 // ... the splitter table a frame uses ([0] complete lists, [1] cut lists), and whether a frame has written it
-uint32_t* view_splitters(ViewState* vs, bool cut, bool** written);
+uint32_t* view_splitters(ViewState* vs, bool cut, bool** written, uint32_t** listed = nullptr);
 // margin (in % of a tile's depth rank) the blend kernel of this frame writes behind every tile's last useful splat
 uint32_t cut_margin_pct(const bh_ctx* ctx, const ViewState* vs);
 // the near slice's pair budget of a BH_FLAG_SLICED_LISTS frame with ni > 0 pairs (== ni: one slice, the complete lists).
@@ -778,6 +800,8 @@ struct ForwardPrep {
     uint32_t split_min = SPLIT_MIN_WORK;
     float split_of_max = 0.45f;                   // ... and >= this share of the band's heaviest tile
     bool list_all_visible = false;                // A/B knob BH_CUT_SORT_ALL: per-tile cuts sort and number EVERY visible splat
+    DealArgs deal;                                // the listed splats go straight into the depth sort's buckets (depth_deal.h)
+    unsigned long long* deal_next = nullptr;      // the idle deal counter set [DEAL_SET_U64], cleared for the next forward
 };
 int launch_project_forward(bh_ctx* ctx, const ViewUniforms& u, uint32_t n, bool mip, uint32_t sh_degree, const float* transforms,
                            const float* sh, const float* raw_opac, uint32_t* depth_keys, uint32_t* isect_counts, float* max_radius,
@@ -838,7 +862,10 @@ int tile_sort_offsets(bh_ctx* ctx, const uint32_t* keys, const uint32_t* vals, u
 bool depth_sort_supported(uint32_t n);
 int depth_sort_scan(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys,
                     uint32_t* out_vals, uint32_t* cum, const uint32_t* rb_set = nullptr, uint32_t* rb_host = nullptr, hipEvent_t rb_done = nullptr,
-                    uint32_t rb_tag = 0, uint32_t* rb_dev = nullptr, uint32_t* spl = nullptr, bool* spl_written = nullptr);
+                    uint32_t rb_tag = 0, uint32_t* rb_dev = nullptr, uint32_t* spl = nullptr, bool* spl_written = nullptr, const DealArgs* dealt = nullptr);
+// ... or ONE launch, when K1 dealt the listed splats into the buckets itself (depth_deal.h): decided before K1 is queued
+int depth_deal_prepare(bh_ctx* ctx, uint32_t n, const uint32_t* spl, bool table_usable, ForwardPrep* prep);
+bool depth_deal_table_usable(uint32_t listed_by_writer);
 // scan.hip — inclusive scan; if `gather` != nullptr the input is in[gather[i]]. exclusive: out[i] = sum_{j<i}.
 // gate != NULL: a device word; 0 there turns the launches into no-ops (the depth-sliced forward's second slice)
 int prefix_sum(bh_ctx* ctx, const uint32_t* in, const uint32_t* gather, uint32_t n, uint32_t* out, bool exclusive, const uint32_t* gate = nullptr);

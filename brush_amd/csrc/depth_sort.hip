@@ -20,9 +20,12 @@
 //      order on its way out.
 // The result is the same permutation the stable 32-bit sort produces (ties keep splat-id order), so everything downstream
 // stays bit-identical.  bh_radix_argsort / bh_prefix_sum (the reference's generic operators) keep the generic kernels.
+// On a frame whose K1 dealt the listed splats into the buckets itself (depth_deal.h) step 1 does not run at all: ONE launch,
+// dsort_deal_bucket_kernel — step 2 reading K1's region, with the tie rule that restores the stable order.
 #include <cstddef>
 
 #include "context.h"
+#include "depth_deal.h"
 #include "sort_groups.h"
 
 namespace bh {
@@ -140,7 +143,10 @@ BH_DEV unsigned long long ds_match(uint32_t d) {
 // is added up by one wave of the first kernel queued behind K1 and stored straight into the pinned host block — [4] u64 totals |
 // the tag word (HOST_SUM_WORDS).  A blit kernel between K1 and the sort cost 4.5 us of device time plus its two launch gaps in
 // every frame.
-BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __restrict__ host_sums, int lane, uint32_t tag, uint32_t* __restrict__ dev_sums) {
+// deal_overflow (the dealing path, depth_deal.h): != 0 says that the order behind this launch is not there — the host hears it in the word behind the tag,
+// and the kernels queued ahead of the host's answer hear "no listed splats" (they do nothing; the host queues them again behind the fallback).
+BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __restrict__ host_sums, int lane, uint32_t tag, uint32_t* __restrict__ dev_sums,
+                                 uint32_t deal_overflow = 0u) {
     const unsigned long long* c64 = reinterpret_cast<const unsigned long long*>(set);
     unsigned long long tot[COUNTER_K1_U64];
 #pragma unroll
@@ -159,11 +165,12 @@ BH_DEV void counter_sums_to_host(const uint32_t* __restrict__ set, uint32_t* __r
         //  listed splats from here, api.hip "speculative K5")
         if (dev_sums) {
 #pragma unroll
-            for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) dev_sums[c] = tot[c] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)tot[c];
+            for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) dev_sums[c] = deal_overflow ? 0u : (tot[c] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)tot[c]);
         }
         volatile unsigned long long* h64 = reinterpret_cast<volatile unsigned long long*>(host_sums);
 #pragma unroll
         for (uint32_t c = 0; c < COUNTER_K1_U64; ++c) h64[c] = tot[c];
+        reinterpret_cast<volatile uint32_t*>(host_sums)[HOST_DEAL_WORD] = deal_overflow;
         // tag != 0: the host does not wait for an event behind this kernel (a barrier packet: ~6 us of bubble in front of the next
         // kernel) but polls this word — stored last, behind a system-scope fence, so the sums are there when it is
         if (tag) {
@@ -491,22 +498,48 @@ BH_DEV void bk_write_splitters(const uint32_t* sorted /*the bucket's keys, ascen
     if (r >= start && r - start < size) spl_out[j] = sorted[r - start];
 }
 
-__global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restrict__ a_keys, uint32_t* __restrict__ a_vals /*the split's output (scratch)*/,
-                                                            uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_vals,
-                                                            const uint32_t* __restrict__ minmax, const uint32_t* __restrict__ digit_totals,
-                                                            const uint32_t* __restrict__ counts, uint32_t* __restrict__ cum /*NULL: no scan*/,
-                                                            uint32_t* __restrict__ spl_out /*NULL: no table for the next frame*/, uint32_t spl_min_keys) {
+// DEAL (depth_deal.h): the bucket comes from K1's region — (key, splat id) in ARRIVAL order, sizes and tile sums in the 255 counter words
+// — and block 0 of the launch is the counter readback the histogram kernel's extra block is on the three-launch path.  The stable
+// sort's order is restored here: a bucket is sorted by key as always (stable in arrival order), and only if two neighbours then
+// carry the same key, the ids of that run are put in order: short runs (the usual few per bucket) where they lie, by the thread at
+// their head; a run of more than TIE_RUN_MAX sends the whole bucket through LSD passes by splat id and then by key once more, so
+// equal keys end up in id order whatever order they arrived in.  The chunked path (a bucket beyond FAST_CAP: already
+// the slow one) always leads with the id passes.
+constexpr uint32_t TIE_RUN_MAX = 8;   // equal keys in a row that their first thread orders by id on its own
+struct DealIn {
+    const unsigned long long* ctr;   // [DEAL_SET_U64]
+    const uint2* region;
+    uint32_t cap;
+    const uint32_t* rb_set; uint32_t* rb_host; uint32_t rb_tag; uint32_t* rb_dev;   // the counter readback (rb_set == NULL: none)
+};
+template <bool DEAL>
+BH_DEV void dsort_bucket_body(uint32_t* __restrict__ a_keys, uint32_t* __restrict__ a_vals, uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_vals,
+                              const uint32_t* __restrict__ minmax, const uint32_t* __restrict__ digit_totals, const uint32_t* __restrict__ counts,
+                              uint32_t* __restrict__ cum, uint32_t* __restrict__ spl_out, uint32_t spl_min_keys, const DealIn& deal) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];   // FAST_LDS_WORDS: the resident path's arrays | the chunked path's ChunkLds
     __shared__ uint32_t s_base[DS_RADIX];
     __shared__ uint32_t s_hist[DS_RADIX];
     __shared__ uint32_t s_red[2 * BK_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t b = blockIdx.x;
+    if (DEAL && blockIdx.x == 0u) {   // (block-uniform: taken before the first barrier)
+        if (wave == 0 && deal.rb_set) counter_sums_to_host(deal.rb_set, deal.rb_host, tid, deal.rb_tag, deal.rb_dev, deal.ctr[DEAL_OVERFLOW_U64] != 0ull ? 1u : 0u);
+        return;
+    }
+    if (DEAL && deal.ctr[DEAL_OVERFLOW_U64] != 0ull) return;   // (grid-uniform) a bucket ran out of slots: the host queues the three launches
+    const uint32_t b = DEAL ? blockIdx.x - 1u : blockIdx.x;
+    const uint2* reg = DEAL ? deal.region + (size_t)b * deal.cap : nullptr;
     // where this bucket starts, and how many tiles the buckets in front of it hit
     uint32_t start, size, tiles_before, nv;
     {
-        const uint32_t gt = tid < DS_RADIX ? digit_totals[tid] : 0u;
-        const uint32_t ct = tid < 255 ? digit_totals[DS_RADIX + tid] : 0u;
+        uint32_t gt, ct;
+        if (DEAL) {
+            const unsigned long long w = tid < (int)DEAL_BUCKETS ? deal.ctr[(size_t)tid * DEAL_LINE_U64] : 0ull;
+            gt = (uint32_t)w;
+            ct = (uint32_t)(w >> 32);
+        } else {
+            gt = tid < DS_RADIX ? digit_totals[tid] : 0u;
+            ct = tid < 255 ? digit_totals[DS_RADIX + tid] : 0u;
+        }
         uint32_t tot;
         const uint32_t gex = bk_excl_scan(gt, nv, s_red);   // (digit 255 is never counted: the total is the number of visible keys)
         const uint32_t cex = bk_excl_scan(ct, tot, s_red);
@@ -550,31 +583,36 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
         uint32_t* fdb = fcnt + BK_WAVES * FAST_NDIG;           // [FAST_NDIG]
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
         for (uint32_t i = tid; i < size; i += BK_WG) {
-            const uint32_t k = a_keys[start + i];
+            uint32_t k, v;
+            if (DEAL) { const uint2 kv = reg[i]; k = kv.x; v = kv.y; }
+            else { k = a_keys[start + i]; v = a_vals[start + i]; }
             s_dyn[i] = k;
-            s_dyn[FAST_CAP + i] = a_vals[start + i];
+            s_dyn[FAST_CAP + i] = v;
             lo = min(lo, k);
             hi = max(hi, k);
         }
-        const uint32_t bits = bk_key_bits(lo, hi, s_red);      // the bucket's keys span less than 2^bits (0: one distinct key — nothing to sort)
-        const uint32_t passes = (bits + 8u) / 9u;              // 0 for bits == 0
-        const uint32_t base_w = passes ? bits / passes : 0u, wide = passes ? bits % passes : 0u;
+        const uint32_t kbits = bk_key_bits(lo, hi, s_red);     // the bucket's keys span less than 2^kbits (0: one distinct key — nothing to sort)
         const unsigned long long lt_mask = (1ull << lane) - 1ull;
         const uint32_t steps = (size + (uint32_t)BK_WG - 1u) / (uint32_t)BK_WG;   // rows per wave
         const uint32_t wave_first = wave * steps * 64u;
         uint32_t cur = 0;
+        // stable LSD passes over `bits` bits of (the key, or by_id the splat id) - slo
+        auto lsd_sort = [&](const bool by_id, const uint32_t slo, const uint32_t bits) {
+        const uint32_t passes = (bits + 8u) / 9u;              // 0 for bits == 0
+        const uint32_t base_w = passes ? bits / passes : 0u, wide = passes ? bits % passes : 0u;
         for (uint32_t p = 0; p < passes; ++p) {
             const uint32_t width = base_w + (p < wide ? 1u : 0u);
             const uint32_t pshift = p * base_w + (p < wide ? p : wide);
             const uint32_t mask = (1u << width) - 1u;
             const uint32_t* sk = s_dyn + cur * (2 * FAST_CAP); const uint32_t* sv = sk + FAST_CAP;
+            const uint32_t* ss = by_id ? sv : sk;   // what the digit is taken from
             uint32_t* dk = s_dyn + (cur ^ 1u) * (2 * FAST_CAP); uint32_t* dv = dk + FAST_CAP;
             for (int i = tid; i < BK_WAVES * FAST_NDIG; i += BK_WG) fcnt[i] = 0;
             __syncthreads();
             // (a) counts per (wave, digit)
             for (uint32_t r = 0; r < steps; ++r) {
                 const uint32_t e = wave_first + r * 64u + lane;
-                if (e < size) atomicAdd(&fcnt[wave * FAST_NDIG + (((sk[e] - lo) >> pshift) & mask)], 1u);
+                if (e < size) atomicAdd(&fcnt[wave * FAST_NDIG + (((ss[e] - slo) >> pshift) & mask)], 1u);
             }
             __syncthreads();
             // (b) per digit (one per thread): wave cursors; exclusive scan of the digit totals
@@ -599,7 +637,7 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
                 const bool valid = e < size;
                 const uint32_t key = valid ? sk[e] : 0u, val = valid ? sv[e] : 0u;
                 // (the row's tail takes digit `mask`: it ranks behind every valid element of that digit and is never written)
-                const uint32_t d = valid ? ((key - lo) >> pshift) & mask : mask;
+                const uint32_t d = valid ? (((by_id ? val : key) - slo) >> pshift) & mask : mask;
                 // lanes of the row with my digit: AND over the bits of (ballot of the bit) XNOR (my bit)
                 uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
                 for (uint32_t bb = 0; bb < width; ++bb) {
@@ -618,6 +656,36 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
             }
             __syncthreads();
             cur ^= 1u;
+        }
+        };
+        lsd_sort(false, lo, kbits);
+        if (DEAL) {
+            // ties: equal keys lie side by side now, in arrival order.  190 k float depths of a 1 M-splat frame hold ~900 equal pairs — a few in
+            // nearly every bucket: the thread at the head of a run of up to TIE_RUN_MAX equal keys puts the run's ids in order itself (an
+            // insertion sort in LDS; runs are disjoint); only a longer run sends the block through the id passes.
+            const uint32_t* tk = s_dyn + cur * (2 * FAST_CAP); uint32_t* tv = s_dyn + cur * (2 * FAST_CAP) + FAST_CAP;
+            int tied = 0;
+            for (uint32_t i = tid; i < size; i += BK_WG) {
+                const uint32_t k = tk[i];
+                if (i + 1u < size && tk[i + 1u] == k && (i == 0u || tk[i - 1u] != k)) {   // the head of a run
+                    uint32_t e = i + 2u;
+                    while (e < size && e - i <= TIE_RUN_MAX && tk[e] == k) ++e;
+                    if (e - i > TIE_RUN_MAX) { tied = 1; continue; }
+                    for (uint32_t a = i + 1u; a < e; ++a) {
+                        const uint32_t v = tv[a];
+                        uint32_t c = a;
+                        while (c > i && tv[c - 1u] > v) { tv[c] = tv[c - 1u]; --c; }
+                        tv[c] = v;
+                    }
+                }
+            }
+            if (__syncthreads_or(tied)) {   // (block-uniform) a long run: by id, then by key again
+                uint32_t ilo = 0xFFFFFFFFu, ihi = 0u;
+                for (uint32_t i = tid; i < size; i += BK_WG) { ilo = min(ilo, tv[i]); ihi = max(ihi, tv[i]); }
+                const uint32_t ibits = bk_key_bits(ilo, ihi, s_red);
+                lsd_sort(true, ilo, ibits);
+                lsd_sort(false, lo, kbits);
+            }
         }
         const uint32_t* fk = s_dyn + cur * (2 * FAST_CAP); const uint32_t* fv = fk + FAST_CAP;
         uint32_t* spare = s_dyn + (cur ^ 1u) * (2 * FAST_CAP);   // the other buffer: 2 * FAST_CAP words
@@ -663,6 +731,62 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
     // stable LSD passes scratch -> out -> scratch -> out, 4096 keys at a time, running digit bases carried from chunk to chunk.
     // An ODD number of passes lands in `out` (0 bits: one pass of width 0 = a stable copy).
     ChunkLds<BK_WG>& L = *reinterpret_cast<ChunkLds<BK_WG>*>(s_dyn);
+    if (DEAL) {
+        // K1's region -> [start, start + size) of scratch or output (whichever lets the last pass land in the output), then LSD passes
+        // of at most 8 bits: the ids' span first, then the keys'.  scatter_chunk moves (what the digit is taken from, the other): the id
+        // passes hand it the arrays in swapped roles.
+        uint32_t klo = 0xFFFFFFFFu, khi = 0u, ilo = 0xFFFFFFFFu, ihi = 0u;
+        for (uint32_t i = tid; i < size; i += BK_WG) {
+            const uint2 kv = reg[i];
+            klo = min(klo, kv.x); khi = max(khi, kv.x);
+            ilo = min(ilo, kv.y); ihi = max(ihi, kv.y);
+        }
+        const uint32_t kbits = bk_key_bits(klo, khi, s_red), ibits = bk_key_bits(ilo, ihi, s_red);
+        const uint32_t kpasses = (kbits + 7u) / 8u, ipasses = (ibits + 7u) / 8u, passes = kpasses + ipasses;
+        uint32_t* src_k = (passes & 1u) ? a_keys : out_keys; uint32_t* src_v = (passes & 1u) ? a_vals : out_vals;
+        uint32_t* dst_k = (passes & 1u) ? out_keys : a_keys; uint32_t* dst_v = (passes & 1u) ? out_vals : a_vals;
+        for (uint32_t i = tid; i < size; i += BK_WG) {
+            const uint2 kv = reg[i];
+            src_k[start + i] = kv.x;
+            src_v[start + i] = kv.y;
+        }
+        __threadfence_block();
+        __syncthreads();
+        const uint32_t nchunks = (size + DS_TILE - 1) / DS_TILE;
+        for (uint32_t p = 0; p < passes; ++p) {
+            const bool by_id = p < ipasses;
+            const uint32_t q = by_id ? p : p - ipasses, sbits = by_id ? ibits : kbits, np = by_id ? ipasses : kpasses, slo = by_id ? ilo : klo;
+            const uint32_t base_w = sbits / np, wide = sbits % np;
+            const uint32_t width = base_w + (q < wide ? 1u : 0u);
+            const uint32_t pshift = q * base_w + (q < wide ? q : wide);
+            const uint32_t mask = (1u << width) - 1u;
+            auto digit = [=](uint32_t x) { return ((x - slo) >> pshift) & mask; };
+            const uint32_t* dsrc = by_id ? src_v : src_k;
+            if (tid < DS_RADIX) s_hist[tid] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < size; i += BK_WG) atomicAdd(&s_hist[digit(dsrc[start + i])], 1u);
+            __syncthreads();
+            {
+                uint32_t tot;
+                const uint32_t ex = bk_excl_scan(tid < DS_RADIX ? s_hist[tid] : 0u, tot, s_red);
+                if (tid < DS_RADIX) s_base[tid] = start + ex;
+            }
+            __syncthreads();
+            for (uint32_t c = 0; c < nchunks; ++c) {
+                const uint32_t first = start + c * DS_TILE;
+                const uint32_t count = size - c * DS_TILE < (uint32_t)DS_TILE ? size - c * DS_TILE : (uint32_t)DS_TILE;
+                if (by_id) scatter_chunk<BK_WG>(L, s_base, src_v, src_k, first, count, dst_v, dst_k, digit);
+                else scatter_chunk<BK_WG>(L, s_base, src_k, src_v, first, count, dst_k, dst_v, digit);
+            }
+            __threadfence_block();
+            __syncthreads();
+            uint32_t* tk = src_k; src_k = dst_k; dst_k = tk;
+            uint32_t* tv = src_v; src_v = dst_v; dst_v = tv;
+        }
+        bk_write_splitters(out_keys + start, start, size, nv, spl_out, spl_min_keys);
+        if (cum != nullptr) bk_scan_counts(out_vals + start, size, counts, tiles_before, cum + start, &L.keys[0], s_red);
+        return;
+    }
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     for (uint32_t i = tid; i < size; i += BK_WG) {
         const uint32_t k = a_keys[start + i];
@@ -712,6 +836,21 @@ __global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restric
     if (cum != nullptr) bk_scan_counts(out_vals + start, size, counts, tiles_before, cum + start, &L.keys[0], s_red);
 }
 
+__global__ __launch_bounds__(BK_WG) void dsort_bucket_kernel(uint32_t* __restrict__ a_keys, uint32_t* __restrict__ a_vals /*the split's output (scratch)*/,
+                                                            uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_vals,
+                                                            const uint32_t* __restrict__ minmax, const uint32_t* __restrict__ digit_totals,
+                                                            const uint32_t* __restrict__ counts, uint32_t* __restrict__ cum /*NULL: no scan*/,
+                                                            uint32_t* __restrict__ spl_out /*NULL: no table for the next frame*/, uint32_t spl_min_keys) {
+    dsort_bucket_body<false>(a_keys, a_vals, out_keys, out_vals, minmax, digit_totals, counts, cum, spl_out, spl_min_keys, DealIn{});
+}
+// 1 + 255 blocks: the counter readback | the buckets K1 dealt
+__global__ __launch_bounds__(BK_WG) void dsort_deal_bucket_kernel(uint32_t* __restrict__ a_keys, uint32_t* __restrict__ a_vals /*scratch of the chunked path*/,
+                                                                 uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_vals,
+                                                                 const uint32_t* __restrict__ minmax, const uint32_t* __restrict__ counts,
+                                                                 uint32_t* __restrict__ cum, uint32_t* __restrict__ spl_out, uint32_t spl_min_keys, DealIn deal) {
+    dsort_bucket_body<true>(a_keys, a_vals, out_keys, out_vals, minmax, nullptr, counts, cum, spl_out, spl_min_keys, deal);
+}
+
 // Up to 4096 chunks of DS_TILE keys (8.4 M splats: the reach of the row scan this path had until the group sums); beyond it the generic sort + scan run.  (Until round 4 the limit was 4 M:
 // "the fused path pays off while launches, not bytes, are the cost".  With per-tile cuts only the listed sixth of the 6 M / 4K
 // scene's splats is moved at all: depth order + scan 255 -> 97 us there; with complete lists 306 -> 302.)
@@ -753,7 +892,7 @@ static int dsort_launches(bh_ctx* ctx, const uint32_t* keys, const uint32_t* min
     hipLaunchKernelGGL(dsort_split_kernel, dim3(nblocks), dim3(DS_WG), 0, ctx->stream, keys, n, nblocks, hist, grp.sums, ngroups, scanned, totals, a_keys, a_vals, out_keys, out_vals,
                        digits);
     BH_LAUNCH_CHECK(ctx, "dsort_split_kernel");
-    // buckets 0..254; the culled splats (digit 255: all keys 0xFFFFFFFF, already in splat-id order) went straight to the output
+    // buckets 0..254; the culled splats (digit 255) were neither counted nor moved: the outputs behind the listed prefix are not written
     if (!ctx->dsort_lds_raised) {   // 146 KB of dynamic LDS: above the 64 KB default, opt in once per ctx (the attribute is per device)
         BH_HIP(ctx, hipFuncSetAttribute((const void*)dsort_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FAST_LDS_WORDS * 4)));
         ctx->dsort_lds_raised = true;
@@ -764,10 +903,58 @@ static int dsort_launches(bh_ctx* ctx, const uint32_t* keys, const uint32_t* min
     return 0;
 }
 
+// Before K1 is queued: does this frame's K1 deal (depth_deal.h)?  It does when the option is on, the host knows that a frame with at
+// least SPL_MIN_KEYS listed splats wrote the table `spl` (table_usable: such a frame leaves quantiles), and n is in the fused sort's
+// reach.  Fills prep->deal (all NULL: no) and, once the counter sets exist, ALWAYS prep->deal_next: every K1 clears the idle set, so the
+// set a later frame deals into is zero whether or not the frames between dealt.
+constexpr uint32_t DEAL_MIN_N = 16384;   // (K1's grid covers a counter set; fewer splats cannot have left a table anyway)
+int depth_deal_prepare(bh_ctx* ctx, uint32_t n, const uint32_t* spl, bool table_usable, ForwardPrep* prep) {
+    prep->deal = DealArgs{};
+    prep->deal_next = nullptr;
+    if (ctx->deal_ctr == nullptr) {
+        if (!ctx->knob_dsort_deal) return 0;
+        if (hipMalloc((void**)&ctx->deal_ctr, (size_t)2 * DEAL_SET_U64 * 8) != hipSuccess) { (void)hipGetLastError(); ctx->deal_ctr = nullptr; return BH_ERR_OOM; }
+        BH_HIP(ctx, hipMemsetAsync(ctx->deal_ctr, 0, (size_t)2 * DEAL_SET_U64 * 8, ctx->stream));
+        ctx->deal_phase = 0u;
+    }
+    unsigned long long* cur = ctx->deal_ctr + (size_t)DEAL_SET_U64 * (ctx->deal_phase & 1u);
+    prep->deal_next = ctx->deal_ctr + (size_t)DEAL_SET_U64 * ((ctx->deal_phase & 1u) ^ 1u);
+    ctx->deal_phase ^= 1u;
+    if (!ctx->knob_dsort_deal || !ctx->knob_dsort_splitters || spl == nullptr || !table_usable || n < DEAL_MIN_N || !depth_sort_supported(n)) return 0;
+    const uint32_t cap = ctx->deal_cap_override ? ctx->deal_cap_override : deal_capacity(n);
+    uint2* region = (uint2*)ensure(ctx, SLOT_DEAL_REGION, (size_t)DEAL_BUCKETS * cap * sizeof(uint2));
+    if (!region) return BH_ERR_OOM;
+    prep->deal.spl = spl;
+    prep->deal.ctr = cur;
+    prep->deal.region = region;
+    prep->deal.cap = cap;
+    return 0;
+}
+bool depth_deal_table_usable(uint32_t listed_by_writer) { return listed_by_writer >= SPL_MIN_KEYS; }
+
+// dealt (optional): what this frame's K1 dealt by (depth_deal_prepare) — ONE launch then; `spl` is the table K1 read.
 int depth_sort_scan(bh_ctx* ctx, const uint32_t* keys, const uint32_t* minmax, const uint32_t* counts, uint32_t n, uint32_t* out_keys,
                     uint32_t* out_vals, uint32_t* cum, const uint32_t* rb_set, uint32_t* rb_host, hipEvent_t rb_done, uint32_t rb_tag, uint32_t* rb_dev, uint32_t* spl,
-                    bool* spl_written) {
+                    bool* spl_written, const DealArgs* dealt) {
     if (n == 0) return 0;
+    if (dealt && dealt->ctr) {
+        uint32_t* a_keys = (uint32_t*)ensure(ctx, SLOT_SORT_KEYS_A, (size_t)n * 4);
+        uint32_t* a_vals = (uint32_t*)ensure(ctx, SLOT_SORT_VALS_A, (size_t)n * 4);
+        if (!a_keys || !a_vals) return BH_ERR_OOM;
+        if (!ctx->dsort_deal_lds_raised) {
+            BH_HIP(ctx, hipFuncSetAttribute((const void*)dsort_deal_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FAST_LDS_WORDS * 4)));
+            ctx->dsort_deal_lds_raised = true;
+        }
+        DealIn in;
+        in.ctr = dealt->ctr; in.region = dealt->region; in.cap = dealt->cap;
+        in.rb_set = rb_set; in.rb_host = rb_host; in.rb_tag = rb_tag; in.rb_dev = rb_dev;
+        hipLaunchKernelGGL(dsort_deal_bucket_kernel, dim3(DEAL_BUCKETS + 1u), dim3(BK_WG), FAST_LDS_WORDS * 4, ctx->stream, a_keys, a_vals, out_keys, out_vals, minmax, counts, cum,
+                           const_cast<uint32_t*>(dealt->spl), SPL_MIN_KEYS, in);
+        BH_LAUNCH_CHECK(ctx, "dsort_deal_bucket_kernel");
+        if (rb_set && !rb_tag) BH_HIP(ctx, hipEventRecord(rb_done, ctx->stream));
+        ctx->deal_frames++;
+        return 0;
+    }
     const uint32_t nblocks = (n + DS_TILE - 1) / DS_TILE;
     // the splitter table (SPLITTERS above): the caller's (a view's) or, for a frame without a view, the ctx's own
     if (!ctx->knob_dsort_splitters) spl = nullptr;

@@ -135,8 +135,9 @@ bool cut_this_frame(const bh_ctx* ctx, ViewState* vs, bool allow_cut) {
 
 uint32_t* view_table(const ViewState* vs) { return vs ? vs->zcut : nullptr; }
 
-uint32_t* view_splitters(ViewState* vs, bool cut, bool** written) {
+uint32_t* view_splitters(ViewState* vs, bool cut, bool** written, uint32_t** listed) {
     *written = vs ? &vs->spl_written[cut ? 1 : 0] : nullptr;
+    if (listed) *listed = vs ? &vs->spl_keys[cut ? 1 : 0] : nullptr;
     return vs ? vs->zcut + 2 * (size_t)vs->tile_bw * vs->tile_bh + (cut ? DSORT_SPL_STRIDE : 0u) : nullptr;
 }
 

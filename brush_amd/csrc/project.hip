@@ -12,6 +12,7 @@
 // per-splat depth key (0xFFFFFFFF when culled) in place and lets the stable depth
 // sort do the compaction: no per-splat atomics, deterministic tie order (by id).
 #include "context.h"
+#include "depth_deal.h"
 #include "device_camera.h"
 #include "device_f64_sum.h"
 #include "device_sh.h"
@@ -283,6 +284,9 @@ __global__ __launch_bounds__(PROJ_WG) void project_forward_kernel(
     __shared__ uint32_t s_listed[PROJ_WAVES];
     __shared__ uint32_t s_kmax[PROJ_WAVES];
     __shared__ uint32_t s_nmax[PROJ_WAVES];
+    __shared__ uint32_t s_bins[ORDER_BINS];   // the order blocks' bins; behind them every block's copy of the view's splitters (depth_deal.h)
+    static_assert(DEAL_SPL_WORDS <= ORDER_BINS, "the splitters are staged in the bins' words");
+    uint32_t* const s_spl = s_bins;
     const uint32_t gid = blockIdx.x * PROJ_WG + threadIdx.x;
     // The forward blend keeps all its one-wave tiles resident at once (8160 tiles on 8192 wave slots at 1080p): its duration is the
     // SIMD whose eight tiles sum to the most work.  With the view's per-tile work of its last frame as the forecast, blocks
@@ -290,7 +294,6 @@ __global__ __launch_bounds__(PROJ_WG) void project_forward_kernel(
     // tiles of steadily decreasing work, so whatever regular pattern the dispatcher deals blocks to SIMDs with, every SIMD's
     // eight tiles are a stratified sample instead of eight neighbours.  8 of ~4000 blocks spend a few microseconds on it.
     if (prep.order_out && blockIdx.x < 8u) {   // block-uniform
-        __shared__ uint32_t s_bins[ORDER_BINS];
         // (slot i of band b names local tile band_tile(b, i): context.h XCD BANDS; a slot behind the window's last tile names none)
         const uint32_t per = band_slots(prep.order_tiles);
         __shared__ uint32_t s_band_work, s_band_cnt, s_band_tail, s_band_max;
@@ -362,11 +365,18 @@ __global__ __launch_bounds__(PROJ_WG) void project_forward_kernel(
         }
         __syncthreads();
     }
+    // dealing (depth_deal.h, kernel-uniform): the view's splitters, for the listed lanes behind the walk (the order blocks are through with
+    // the bins)
+    if (prep.deal.ctr) {
+        deal_stage(prep.deal, s_spl);
+        __syncthreads();
+    }
     // housekeeping for the kernels behind this one (coalesced stores; nobody reads these buffers before K1 retires)
     if (gid < prep.visible_words) prep.visible[gid] = 0u;
     if (gid < prep.tile_words) prep.tile_table[gid] = 0u;
     if (gid < prep.slice_words) prep.slice_table[gid] = 0u;
     if (gid < COUNTER_SET_U64 && prep.next_counters) prep.next_counters[gid] = 0ull;
+    if (gid < DEAL_SET_U64 && prep.deal_next) prep.deal_next[gid] = 0ull;
     for (size_t i = gid; i < prep.span_f4; i += (size_t)gridDim.x * PROJ_WG) prep.span[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t key = 0xFFFFFFFFu;
@@ -463,6 +473,11 @@ __global__ __launch_bounds__(PROJ_WG) void project_forward_kernel(
     // The splat's colour and its projected row (what K5 gathers by depth rank) — behind the walk since round 4: with per-tile cuts
     // only the LISTED splats are ever gathered, a quarter of the visible ones, and the SH bands above DC (180 bytes per splat at
     // degree 3) are only fetched for them.  Without cuts every visible splat is listed.
+    // the depth sort's split, here: a listed splat takes a slot in its bucket, with the tile count the scan is made of — the atomic's round trip
+    // runs while the lane does everything below (up to SH degree 2: the two registers the slot waits in cost the higher degrees a wave per SIMD)
+    constexpr bool DEAL_EARLY = DEG <= 2;
+    DealSlot deal_place = DealSlot{0u, 0u};
+    if (DEAL_EARLY && prep.deal.ctr && listed) deal_place = deal_take(prep.deal, s_spl, key, zcut ? near_hit : tiles_hit);
     if (listed) {  // project_visible.rs:56-87
         const Vec3A v = normalize(sub(mean, camera_pos(u)));
         constexpr int C = (DEG + 1) * (DEG + 1);
@@ -515,6 +530,9 @@ __global__ __launch_bounds__(PROJ_WG) void project_forward_kernel(
         s_nmax[wave] = nmax;
     }
     __syncthreads();
+    // ... and the slot is in: the splat's (key, id) goes into its bucket
+    if (!DEAL_EARLY && prep.deal.ctr && listed) deal_place = deal_take(prep.deal, s_spl, key, zcut ? near_hit : tiles_hit);
+    if (prep.deal.ctr && listed) deal_put(prep.deal, deal_place, key, gid);
     if (threadIdx.x == 0) {
         uint32_t v = 0, h = 0, nh = 0, ls = 0, km = 0, nm = 0;
 #pragma unroll
@@ -564,6 +582,10 @@ int launch_project_forward(bh_ctx* ctx, const ViewUniforms& u, uint32_t n, bool 
     if (prep.next_counters && COUNTER_SET_U64 > covered) {
         BH_HIP(ctx, hipMemsetAsync(prep.next_counters, 0, COUNTER_SET_BYTES, ctx->stream));
         prep.next_counters = nullptr;
+    }
+    if (prep.deal_next && DEAL_SET_U64 > covered) {
+        BH_HIP(ctx, hipMemsetAsync(prep.deal_next, 0, (size_t)DEAL_SET_U64 * 8, ctx->stream));
+        prep.deal_next = nullptr;
     }
     if (prep.tile_table && prep.tile_words > covered) {
         BH_HIP(ctx, hipMemsetAsync(prep.tile_table, 0, (size_t)prep.tile_words * 4, ctx->stream));
