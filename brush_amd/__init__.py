@@ -52,6 +52,8 @@ Names and argument meaning follow the reference (paths under
     TsdfVolume / fuse_views / mesh_to_ply    mesh extraction: rendered depth maps fused into a TSDF volume (8 views per pass over the
                                          volume), its zero level set by marching tetrahedra, a triangle-mesh PLY (not in the
                                          reference; include/brush_hip_mesh.h)
+    SparseTsdfVolume                     the same fusion and mesh on 8x8x8 blocks allocated only near the observed surfaces: virtual
+                                         grids of up to 8192 samples per axis (include/brush_hip_sparse_mesh.h)
     render_features / RenderNode.features / RenderNode.backward(v_features=, features=) / feature_loss_value_and_grad / FeatureField
                                          feature maps: caller-owned per-splat vectors of 1 .. 256 channels blended with the colour
                                          blend's weights, the gradient into them and the splats, fused L1 / cross-entropy losses (not
@@ -88,7 +90,7 @@ from .host import (  # noqa: F401
     PoseOptimizer, pose_twist, IntrinsicsOptimizer, ExposureTable, depth_loss_value_and_grad, eval_depth_metrics,
     splat_normals, render_normal, depth_to_normal, depth_to_normal_backward, normal_consistency_value_and_grad,
     render_distortion, distortion_loss, BilateralGridTable,
-    TsdfVolume, mesh_to_ply, fuse_views,
+    TsdfVolume, SparseTsdfVolume, mesh_to_ply, fuse_views,
     render_features, feature_loss_value_and_grad, FeatureField,
     SceneTransform, SceneRegion, select_region, crop_splats,
     LiftAccumulator, lift_labels, compact_splats,

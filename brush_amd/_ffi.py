@@ -365,6 +365,30 @@ MESH_SYMBOLS = {
     "bh_mesh_to_ply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
+# every symbol include/brush_hip_sparse_mesh.h declares (sparse TSDF volumes: block-allocated fusion and mesh extraction)
+SPTSDF_BLOCK = 8        # BH_SPTSDF_BLOCK
+SPTSDF_MAX_DIM = 8192   # BH_SPTSDF_MAX_DIM
+SPTSDF_MAX_STEPS = 64   # BH_SPTSDF_MAX_STEPS
+
+
+class BhSparseTsdf(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+                ("trunc", C.c_float), ("max_weight", C.c_float), ("n_blocks", C.c_uint32), ("bits", C.c_void_p), ("rank", C.c_void_p),
+                ("keys", C.c_void_p), ("tw", C.c_void_p), ("rgb", C.c_void_p)]
+
+
+_sptsdf_views = [C.c_void_p, C.POINTER(BhSparseTsdf), C.c_uint32, C.POINTER(BhCamera), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(BhTsdfIntegrateConfig)]
+SPARSE_MESH_SYMBOLS = {
+    "bh_sptsdf_mark_clear": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf)]),
+    "bh_sptsdf_mark": (C.c_int, _sptsdf_views),
+    "bh_sptsdf_commit": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf), C.c_uint32, u32p]),
+    "bh_sptsdf_clear": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf)]),
+    "bh_sptsdf_integrate": (C.c_int, _sptsdf_views),
+    "bh_sptsdf_extract_count": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf), u32p, u32p]),
+    "bh_sptsdf_extract": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p]),
+    "bh_sptsdf_to_dense": (C.c_int, [C.c_void_p, C.POINTER(BhSparseTsdf), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BhTsdfGrid)]),
+}
+
 # every symbol include/brush_hip_features.h declares (feature maps: N-channel splat features, their backward and the fused losses)
 FEATURE_MAX_CHANNELS = 256   # BH_FEATURE_MAX_CHANNELS
 FEATURE_LOSS_L1, FEATURE_LOSS_CROSS_ENTROPY = 0, 1   # BH_FEATURE_LOSS_*
@@ -518,7 +542,7 @@ def load():
     """Load libbrush_hip.so and bind every declared symbol. Raises if the library is absent."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS))
+        _lib = _bind(LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **SPARSE_MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS))
     return _lib
 
 
@@ -527,6 +551,6 @@ def load_test_hooks():
     pass it to Context(lib=...)."""
     global _lib_th
     if _lib_th is None:
-        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS,
+        _lib_th = _bind(TEST_HOOKS_LIB_PATH, dict(SYMBOLS, **LPIPS_SYMBOLS, **COMPRESSED_PLY_SYMBOLS, **IMAGE_SYMBOLS, **DEPTH_SYMBOLS, **POSE_SYMBOLS, **EXPOSURE_SYMBOLS, **BILAGRID_SYMBOLS, **DEPTH_LOSS_SYMBOLS, **NORMAL_SYMBOLS, **NORMAL_LOSS_SYMBOLS, **DISTORTION_SYMBOLS, **MESH_SYMBOLS, **SPARSE_MESH_SYMBOLS, **FEATURE_SYMBOLS, **FEATURE_TRAIN_SYMBOLS, **SCENE_SYMBOLS, **LIFT_SYMBOLS, **ENVMAP_SYMBOLS, **INTRINSICS_SYMBOLS,
                                                    **TEST_HOOK_SYMBOLS))
     return _lib_th

@@ -104,6 +104,7 @@ enum Slot : int {
     SLOT_ENVMAP_FRAME,       // bh_train_step with an environment map: [H,W,4] the frame composited over the map (envmap.hip; out_img stays what K17 replays)
     SLOT_DEAL_REGION,        // depth sort, dealing K1 (depth_deal.h): [255][cap] (key, splat id) — the buckets K1 fills
     SLOT_SCENE,              // bh_splats_select_region with a count: one u32 per block of the select | the total (scene_edit.hip)
+    SLOT_SPTSDF,             // sparse TSDF volumes (sparse_tsdf.hip): bh_sptsdf_commit: two bitmaps of the dilation [n_words] each | the words' bit counts [n_words]; bh_sptsdf_extract[_count]: as SLOT_TSDF, per allocated sample
     SLOT_COUNT
 };
 

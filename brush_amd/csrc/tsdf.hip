@@ -18,6 +18,7 @@
 
 #include "context.h"
 #include "device_math.h"
+#include "device_tsdf.h"
 
 namespace bh {
 
@@ -28,20 +29,6 @@ struct TsdfGridDev {
     float2* tw;
     float* rgb;
 };
-
-struct TsdfView {
-    float vm[12];
-    float fx, fy, cx, cy;
-    float wf, hf;   // (float)W, (float)H
-    uint32_t w, pad;
-    const float* depth;
-    const float* image;   // [H,W,4] or NULL
-};
-
-struct TsdfBatch {
-    TsdfView v[BH_TSDF_MAX_BATCH];
-};
-static_assert(sizeof(TsdfBatch) == 96 * BH_TSDF_MAX_BATCH, "TsdfBatch is passed by value: keep it well inside the kernel-argument segment");
 
 constexpr int TSDF_BX = 64, TSDF_BY = 4, TSDF_WG = TSDF_BX * TSDF_BY;
 constexpr uint32_t TSDF_MAX_BLOCKS = 1u << 20;   // (blocks x threads must stay below 2^32; larger volumes stride)
@@ -75,39 +62,7 @@ __global__ __launch_bounds__(TSDF_WG) void tsdf_integrate_kernel(const TsdfGridD
             const float* c = g.rgb + s * 3;
             c0 = c[0]; c1 = c[1]; c2 = c[2];
         }
-        bool touched = false;
-        for (uint32_t v = 0; v < n_views; ++v) {
-            const TsdfView& cam = b.v[v];
-            const float Z = ((cam.vm[2] * px + cam.vm[5] * py) + cam.vm[8] * pz) + cam.vm[11];
-            if (!(Z > depth_min)) continue;
-            // (one axis at a time: a sample outside in x never pays for the second division; a NaN fails every comparison)
-            const float X = ((cam.vm[0] * px + cam.vm[3] * py) + cam.vm[6] * pz) + cam.vm[9];
-            const float u = cam.fx * (X / Z) + cam.cx;
-            if (!(u >= 0.0f && u < cam.wf)) continue;
-            const float Y = ((cam.vm[1] * px + cam.vm[4] * py) + cam.vm[7] * pz) + cam.vm[10];
-            const float vv = cam.fy * (Y / Z) + cam.cy;
-            if (!(vv >= 0.0f && vv < cam.hf)) continue;
-            const size_t pix = (size_t)(uint32_t)vv * cam.w + (uint32_t)u;         // 0 <= u < W: truncation is floor
-            const float d = cam.depth[pix];
-            if (!(is_finite_f32(d) && d > 0.0f && d <= depth_max)) continue;
-            float4 px4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (cam.image) {
-                px4 = reinterpret_cast<const float4*>(cam.image)[pix];
-                if (px4.w < alpha_min) continue;
-            }
-            const float sdf = d - Z;
-            if (sdf < -g.trunc) continue;
-            const float sd = fminf(1.0f, sdf / g.trunc);
-            const float Wn = W + 1.0f;
-            T = (W * T + sd) / Wn;
-            if (COLOUR) {
-                c0 = (W * c0 + px4.x) / Wn;
-                c1 = (W * c1 + px4.y) / Wn;
-                c2 = (W * c2 + px4.z) / Wn;
-            }
-            W = fminf(Wn, g.max_weight);
-            touched = true;
-        }
+        const bool touched = tsdf_update_sample<COLOUR>(b, n_views, depth_min, depth_max, alpha_min, g.trunc, g.max_weight, px, py, pz, T, W, c0, c1, c2);
         if (touched) {
             g.tw[s] = make_float2(T, W);
             if (COLOUR) {
@@ -119,53 +74,6 @@ __global__ __launch_bounds__(TSDF_WG) void tsdf_integrate_kernel(const TsdfGridD
 }
 
 // ---- extraction -------------------------------------------------------------------------------------------------------------------
-// the 3x3x3 neighbourhood of a sample as 27 bits
-constexpr uint32_t nb_bit(int dx, int dy, int dz) { return (uint32_t)((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)); }
-// the 8 corners of the cube with min corner p - a
-constexpr uint32_t cube_mask(int ax, int ay, int az) {
-    uint32_t m = 0;
-    for (int bz = 0; bz < 2; ++bz)
-        for (int by = 0; by < 2; ++by)
-            for (int bx = 0; bx < 2; ++bx) m |= 1u << nb_bit(bx - ax, by - ay, bz - az);
-    return m;
-}
-// an edge's direction as a code x | y << 1 | z << 2, in the header's order of d; and the inverse map
-__constant__ const uint8_t TSDF_D_CODE[7] = {1, 2, 4, 3, 5, 6, 7};
-__constant__ const uint8_t TSDF_D_INDEX[8] = {0, 0, 1, 3, 2, 4, 5, 6};
-// the vertices of tetrahedron t (permutations xyz xzy yxz yzx zxy zyx) as corner codes, 4 bits each from v0 up
-__constant__ const uint16_t TSDF_TET[6] = {0x7310, 0x7510, 0x7320, 0x7620, 0x7540, 0x7640};
-constexpr uint32_t TSDF_NEGATIVE = 0x26;   // bit t: tetrahedron t is negatively oriented (xzy, yxz, zyx)
-// triangles per inside mask, 2 bits each: {0,1,1,2, 1,2,2,1, 1,2,2,1, 2,1,1,0}
-constexpr uint32_t TSDF_NTRI = 0x16696994u;
-// the header's case table: edge numbers, 3 bits each, first triple in the low 9 bits
-#define TSDF_TRI(a, b, c) ((a) | (b) << 3 | (c) << 6)
-__constant__ const uint32_t TSDF_CASE[16] = {
-    0,
-    TSDF_TRI(0, 1, 2),
-    TSDF_TRI(0, 4, 3),
-    TSDF_TRI(1, 2, 4) | TSDF_TRI(1, 4, 3) << 9,
-    TSDF_TRI(5, 1, 3),
-    TSDF_TRI(0, 3, 5) | TSDF_TRI(0, 5, 2) << 9,
-    TSDF_TRI(0, 4, 5) | TSDF_TRI(0, 5, 1) << 9,
-    TSDF_TRI(5, 2, 4),
-    TSDF_TRI(5, 4, 2),
-    TSDF_TRI(0, 1, 5) | TSDF_TRI(0, 5, 4) << 9,
-    TSDF_TRI(0, 2, 5) | TSDF_TRI(0, 5, 3) << 9,
-    TSDF_TRI(5, 3, 1),
-    TSDF_TRI(1, 3, 4) | TSDF_TRI(1, 4, 2) << 9,
-    TSDF_TRI(0, 3, 4),
-    TSDF_TRI(0, 2, 1),
-    0,
-};
-#undef TSDF_TRI
-// the ends of tetrahedron edge e (v0v1 v0v2 v0v3 v1v2 v1v3 v2v3), 2 bits each
-constexpr uint32_t TSDF_EDGE_A = 0x940, TSDF_EDGE_B = 0xFB9;
-
-BH_DEV uint32_t tet_inside_mask(uint32_t tet, uint32_t corners8) {
-    return ((corners8 >> (tet & 15u)) & 1u) | ((corners8 >> ((tet >> 4) & 15u)) & 1u) << 1 | ((corners8 >> ((tet >> 8) & 15u)) & 1u) << 2 |
-           ((corners8 >> (tet >> 12)) & 1u) << 3;
-}
-
 // info[s] = the mask of owned edges with a vertex | the cube's triangle count << 8 | the inside bits of the cube's 8 corners << 16
 __global__ __launch_bounds__(256) void tsdf_classify_kernel(const TsdfGridDev g, const uint32_t n, uint32_t* __restrict__ info, uint32_t* __restrict__ vcnt,
                                                             uint32_t* __restrict__ tcnt) {
@@ -186,41 +94,10 @@ __global__ __launch_bounds__(256) void tsdf_classify_kernel(const TsdfGridDev g,
                 obs |= (t.y > 0.0f ? 1u : 0u) << nb_bit(dx, dy, dz);
                 ins |= (t.x < 0.0f ? 1u : 0u) << nb_bit(dx, dy, dz);
             }
-    const uint32_t centre = (ins >> nb_bit(0, 0, 0)) & 1u;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int e = 0; e < 7; ++e) {
-        constexpr int codes[7] = {1, 2, 4, 3, 5, 6, 7};
-        const int dx = codes[e] & 1, dy = (codes[e] >> 1) & 1, dz = codes[e] >> 2;
-        bool has = false;
-#pragma unroll
-        for (int az = 0; az <= 1 - dz; ++az)
-#pragma unroll
-            for (int ay = 0; ay <= 1 - dy; ++ay)
-#pragma unroll
-                for (int ax = 0; ax <= 1 - dx; ++ax) {
-                    const uint32_t cm = cube_mask(ax, ay, az);
-                    has = has || (obs & cm) == cm;
-                }
-        const uint32_t other = (ins >> nb_bit(dx, dy, dz)) & 1u;
-        if (has && other != centre) mask |= 1u << e;
-    }
-    uint32_t tris = 0, corners8 = 0;
-    constexpr uint32_t own = cube_mask(0, 0, 0);
-    if ((obs & own) == own) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) corners8 |= ((ins >> nb_bit(c & 1, (c >> 1) & 1, c >> 2)) & 1u) << c;
-#pragma unroll
-        for (int t = 0; t < 6; ++t) tris += (TSDF_NTRI >> (2u * tet_inside_mask(TSDF_TET[t], corners8))) & 3u;
-    }
-    info[s] = mask | tris << 8 | corners8 << 16;
-    vcnt[s] = (uint32_t)__popc(mask);
-    tcnt[s] = tris;
-}
-
-BH_DEV uint32_t tsdf_vertex_index(const uint32_t* __restrict__ info, const uint32_t* __restrict__ vinc, size_t owner, uint32_t d) {
-    const uint32_t m = info[owner] & 0x7Fu;
-    return vinc[owner] - (uint32_t)__popc(m) + (uint32_t)__popc(m & ((1u << d) - 1u));
+    const uint32_t word = tsdf_classify_word(obs, ins);
+    info[s] = word;
+    vcnt[s] = (uint32_t)__popc(word & 0x7Fu);
+    tcnt[s] = (word >> 8) & 0xFFu;
 }
 
 __global__ __launch_bounds__(256) void tsdf_emit_kernel(const TsdfGridDev g, const uint32_t n, const uint32_t* __restrict__ info, const uint32_t* __restrict__ vinc,
@@ -229,60 +106,10 @@ __global__ __launch_bounds__(256) void tsdf_emit_kernel(const TsdfGridDev g, con
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s >= n) return;
     const uint32_t word = info[s];
-    const uint32_t mask = word & 0x7Fu, tris = (word >> 8) & 0xFFu, corners8 = word >> 16;
-    if ((mask | tris) == 0u) return;
+    if ((word & 0xFF7Fu) == 0u) return;
     const uint32_t nxy = g.nx * g.ny;
-    if (mask) {
-        const uint32_t i = s % g.nx, j = (s / g.nx) % g.ny, k = s / nxy;
-        const float ax = g.ox + g.vs * (float)i, ay = g.oy + g.vs * (float)j, az = g.oz + g.vs * (float)k;
-        const float Ta = g.tw[s].x;
-        size_t out = (size_t)(vinc[s] - (uint32_t)__popc(mask)) * 3;
-        for (uint32_t e = 0; e < 7u; ++e) {
-            if (!((mask >> e) & 1u)) continue;
-            const uint32_t code = TSDF_D_CODE[e];
-            const uint32_t dx = code & 1u, dy = (code >> 1) & 1u, dz = code >> 2;
-            const size_t sb = (size_t)s + (size_t)dz * nxy + (size_t)dy * g.nx + dx;
-            const float Tb = g.tw[sb].x;
-            const float t = Ta / (Ta - Tb);
-            const float bx = g.ox + g.vs * (float)(i + dx), by = g.oy + g.vs * (float)(j + dy), bz = g.oz + g.vs * (float)(k + dz);
-            vertices[out] = ax + t * (bx - ax);
-            vertices[out + 1] = ay + t * (by - ay);
-            vertices[out + 2] = az + t * (bz - az);
-            if (colours) {
-                const float* ca = g.rgb + (size_t)s * 3;
-                const float* cb = g.rgb + sb * 3;
-                colours[out] = ca[0] + t * (cb[0] - ca[0]);
-                colours[out + 1] = ca[1] + t * (cb[1] - ca[1]);
-                colours[out + 2] = ca[2] + t * (cb[2] - ca[2]);
-            }
-            out += 3;
-        }
-    }
-    if (tris) {
-        size_t out = (size_t)(tinc[s] - tris) * 3;
-        for (uint32_t t = 0; t < 6u; ++t) {
-            const uint32_t tet = TSDF_TET[t];
-            const uint32_t m = tet_inside_mask(tet, corners8);
-            const uint32_t count = (TSDF_NTRI >> (2u * m)) & 3u;
-            uint32_t cases = TSDF_CASE[m];
-            const bool flip = (TSDF_NEGATIVE >> t) & 1u;
-            for (uint32_t q = 0; q < count; ++q, cases >>= 9) {
-                uint32_t idx[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const uint32_t e = (cases >> (3 * c)) & 7u;
-                    const uint32_t ca = (tet >> (4u * ((TSDF_EDGE_A >> (2u * e)) & 3u))) & 15u;
-                    const uint32_t cb = (tet >> (4u * ((TSDF_EDGE_B >> (2u * e)) & 3u))) & 15u;
-                    const size_t owner = (size_t)s + (size_t)(ca >> 2) * nxy + (size_t)((ca >> 1) & 1u) * g.nx + (ca & 1u);
-                    idx[c] = tsdf_vertex_index(info, vinc, owner, TSDF_D_INDEX[ca ^ cb]);
-                }
-                triangles[out] = idx[0];
-                triangles[out + 1] = flip ? idx[2] : idx[1];
-                triangles[out + 2] = flip ? idx[1] : idx[2];
-                out += 3;
-            }
-        }
-    }
+    tsdf_emit_sample(g.ox, g.oy, g.oz, g.vs, s % g.nx, (s / g.nx) % g.ny, s / nxy, (size_t)s, word, g.tw, g.rgb, info, vinc, tinc, vertices, colours, triangles,
+                     [&](uint32_t c) { return (size_t)s + (size_t)(c >> 2) * nxy + (size_t)((c >> 1) & 1u) * g.nx + (c & 1u); });
 }
 
 // ---- mesh PLY ---------------------------------------------------------------------------------------------------------------------
@@ -386,15 +213,7 @@ int bh_tsdf_integrate(bh_ctx* ctx, const BhTsdfGrid* grid, uint32_t n_views, con
     BH_TRY(tsdf_check_grid(ctx, grid, "tsdf_integrate", &g, &n));
     if (!cfg) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: null config");
     if (n_views == 0) return 0;
-    if (!cams || !depths) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: null argument");
-    for (uint32_t v = 0; v < n_views; ++v) {
-        const BhCamera& c = cams[v];
-        if (c.model != BH_CAMERA_PINHOLE) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: pinhole cameras only");
-        if (c.tile_row_begin != 0u || c.tile_row_end != 0u) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: a camera with a tile-row window");
-        if (c.img_w == 0u || c.img_h == 0u || (uint64_t)c.img_w * c.img_h > 0x7FFFFFFFull)
-            return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: an image side of 0 or more than 2^31 - 1 pixels");
-        if (!depths[v] || (images && !images[v])) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: null depth map or image");
-    }
+    BH_TRY(tsdf_check_views(ctx, "tsdf_integrate", n_views, cams, depths, images));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     ProfScope ps(ctx, "TsdfIntegrate");
     const uint32_t blocks_x = (g.nx + TSDF_BX - 1) / TSDF_BX, blocks_y = (g.ny + TSDF_BY - 1) / TSDF_BY;
@@ -403,17 +222,7 @@ int bh_tsdf_integrate(bh_ctx* ctx, const BhTsdfGrid* grid, uint32_t n_views, con
     const bool colour = images && g.rgb;
     for (uint32_t first = 0; first < n_views; first += BH_TSDF_MAX_BATCH) {
         const uint32_t count = n_views - first < BH_TSDF_MAX_BATCH ? n_views - first : BH_TSDF_MAX_BATCH;
-        TsdfBatch b{};
-        for (uint32_t v = 0; v < count; ++v) {
-            const BhCamera& c = cams[first + v];
-            TsdfView& t = b.v[v];
-            std::memcpy(t.vm, c.vm, sizeof(t.vm));
-            t.fx = c.fx; t.fy = c.fy; t.cx = c.cx; t.cy = c.cy;
-            t.wf = (float)c.img_w; t.hf = (float)c.img_h;
-            t.w = c.img_w;
-            t.depth = depths[first + v];
-            t.image = images ? images[first + v] : nullptr;
-        }
+        const TsdfBatch b = tsdf_make_batch(first, count, cams, depths, images);
         if (colour)
             hipLaunchKernelGGL(tsdf_integrate_kernel<true>, launch, block, 0, ctx->stream, g, b, count, cfg->depth_min, cfg->depth_max, cfg->alpha_min, blocks_x,
                                blocks_y, n_blocks);

@@ -1990,21 +1990,216 @@ class TsdfVolume:
         return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
 
 
-def fuse_views(splats: "Splats", cameras, img_size, volume: TsdfVolume, depth_mode="expected", pass_: "RasterPass" = None, depth_min=0.0,
-               depth_max=math.inf, alpha_min=0.5):
+class SparseTsdfVolume:
+    """A sparse truncated signed distance volume on the device (include/brush_hip_sparse_mesh.h): a virtual grid of
+    `dims` = (nx, ny, nz) samples (each 2 .. 8192) at origin + voxel_size * (i, j, k), of which only the 8x8x8 blocks near the observed
+    surfaces are held.  mark() sets the blocks the depth maps' rays cross inside the truncation band, commit() dilates them, counts
+    them and allocates the pool (`keys` [n_blocks], `tw` [n_blocks,8,8,8,2], `rgb` [n_blocks,8,8,8,3] or None), integrate() fuses depth
+    maps by TsdfVolume's rule, extract_mesh() / to_ply() are TsdfVolume's, to_dense() writes a window into a TsdfVolume."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, max_weight=64.0, colour=True, device=None, ctx: Optional[Context] = None):
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(v) for v in dims)
+        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
+        self.max_weight = float(max_weight)
+        self.colour = bool(colour)
+        # refused here, before the device is touched (the library refuses the same)
+        if len(self.origin) != 3 or len(self.dims) != 3:
+            raise ValueError("SparseTsdfVolume: origin and dims have three entries")
+        if min(self.dims) < 2:
+            raise ValueError("SparseTsdfVolume: every dimension must be at least 2")
+        if max(self.dims) > _ffi.SPTSDF_MAX_DIM:
+            raise ValueError("SparseTsdfVolume: a dimension above %d" % _ffi.SPTSDF_MAX_DIM)
+        self.block_dims = tuple((d + _ffi.SPTSDF_BLOCK - 1) // _ffi.SPTSDF_BLOCK for d in self.dims)
+        total = self.block_dims[0] * self.block_dims[1] * self.block_dims[2]
+        if total > 2 ** 30:
+            raise ValueError("SparseTsdfVolume: more than 2^30 virtual blocks")
+        if not (math.isfinite(self.voxel_size) and self.voxel_size > 0.0):
+            raise ValueError("SparseTsdfVolume: voxel_size must be a finite number > 0")
+        if not (math.isfinite(self.trunc) and self.trunc > 0.0):
+            raise ValueError("SparseTsdfVolume: trunc must be a finite number > 0")
+        if not self.max_weight >= 1.0:
+            raise ValueError("SparseTsdfVolume: max_weight must be at least 1")
+        self.ctx = ctx or get_context(device)
+        self.device = self.ctx.device
+        self.n_words = (total + 31) // 32
+        self.bits = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
+        self.rank = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
+        self.n_blocks = 0
+        self.keys = self.tw = self.rgb = None
+
+    @classmethod
+    def from_bounds(cls, bounds, resolution, **kw):
+        """As TsdfVolume.from_bounds: `resolution` samples along the box's longest side, cubic voxels."""
+        return TsdfVolume.from_bounds.__func__(cls, bounds, resolution, **kw)
+
+    def mark_steps(self) -> int:
+        """M of bh_sptsdf_mark: the smallest integer with (float)M * (4 voxel_size) >= 2 trunc, in f32."""
+        import numpy as np
+        step, band = np.float32(4.0) * np.float32(self.voxel_size), np.float32(2.0) * np.float32(self.trunc)
+        m = 0
+        while m <= _ffi.SPTSDF_MAX_STEPS and not np.float32(m) * step >= band:
+            m += 1
+        return m
+
+    def vol(self) -> "_ffi.BhSparseTsdf":
+        v = _ffi.BhSparseTsdf()
+        v.origin = (C.c_float * 3)(*self.origin)
+        v.voxel_size = self.voxel_size
+        v.nx, v.ny, v.nz = self.dims
+        v.trunc, v.max_weight, v.n_blocks = self.trunc, self.max_weight, self.n_blocks
+        v.bits, v.rank = self.bits.data_ptr(), self.rank.data_ptr()
+        v.keys = self.keys.data_ptr() if self.keys is not None else None
+        v.tw = self.tw.data_ptr() if self.tw is not None else None
+        v.rgb = self.rgb.data_ptr() if self.rgb is not None else None
+        return v
+
+    def _views(self, depths, cameras, images, who):
+        depths, cameras = list(depths), list(cameras)
+        if len(depths) != len(cameras) or (images is not None and len(images) != len(depths)):
+            raise ValueError("SparseTsdfVolume.%s: as many cameras (and images) as depth maps" % who)
+        n = len(depths)
+        cams = TsdfVolume.check_views(cameras, [tuple(d.shape) for d in depths])
+        dev = self.device
+        depths = [_f32c(d, dev) for d in depths]
+        dptr = (C.c_void_p * max(n, 1))(*[d.data_ptr() for d in depths])
+        iptr = None
+        if images is not None:
+            images = [_f32c(im, dev).reshape(d.shape[0], d.shape[1], 4) for im, d in zip(images, depths)]
+            iptr = (C.c_void_p * max(n, 1))(*[im.data_ptr() for im in images])
+        return n, cams, dptr, iptr, (depths, images)   # (the last entry keeps the converted tensors alive across the call)
+
+    def _committed(self, who):
+        if self.n_blocks == 0:
+            raise ValueError("SparseTsdfVolume.%s: the volume has no blocks: mark() and commit() first" % who)
+
+    def mark_clear(self):
+        """Forgets every mark and the committed pool: the volume is as new."""
+        self.n_blocks = 0
+        self.keys = self.tw = self.rgb = None
+        v = self.vol()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_mark_clear(self.ctx._h, C.byref(v)))
+
+    def mark(self, depths, cameras, images=None, depth_max=math.inf, alpha_min=0.5):
+        """Marks the blocks that the rays of depths[v] [H,W] cross within trunc of the depth (bh_sptsdf_mark); any number of calls
+        before commit().  Queued: nothing is read back."""
+        if self.n_blocks:
+            raise ValueError("SparseTsdfVolume.mark: after a commit: mark_clear() first")
+        if self.mark_steps() > _ffi.SPTSDF_MAX_STEPS:
+            raise ValueError("SparseTsdfVolume.mark: trunc is more than %d steps of 4 voxels" % _ffi.SPTSDF_MAX_STEPS)
+        n, cams, dptr, iptr, keep = self._views(depths, cameras, images, "mark")
+        if n == 0:
+            return
+        cfg = _ffi.BhTsdfIntegrateConfig(0.0, float(depth_max), float(alpha_min), 0)
+        v = self.vol()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_mark(self.ctx._h, C.byref(v), n, cams, dptr, iptr, C.byref(cfg)))
+
+    def commit(self, dilate=1) -> int:
+        """Allocates every block within `dilate` (0, 1 or 2) blocks of a marked one, and clears the pool; -> the number of blocks
+        (0: nothing was marked, and the volume stays without a pool).  Blocking (one readback)."""
+        if isinstance(dilate, bool) or int(dilate) != dilate or not 0 <= int(dilate) <= 2:
+            raise ValueError("SparseTsdfVolume.commit: dilate must be 0, 1 or 2")
+        if self.n_blocks:
+            raise ValueError("SparseTsdfVolume.commit: already committed: mark_clear() starts over")
+        n = C.c_uint32()
+        v = self.vol()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_commit(self.ctx._h, C.byref(v), int(dilate), C.byref(n)))
+        n = int(n.value)
+        if n:
+            self.keys = torch.empty(n, dtype=torch.int32, device=self.device)
+            self.tw = torch.empty((n, 8, 8, 8, 2), dtype=torch.float32, device=self.device)
+            self.rgb = torch.empty((n, 8, 8, 8, 3), dtype=torch.float32, device=self.device) if self.colour else None
+            self.n_blocks = n
+            self.clear()
+        return n
+
+    def clear(self):
+        """keys from the index, and T = 1, W = 0, rgb = 0 in every sample of the pool."""
+        self._committed("clear")
+        v = self.vol()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_clear(self.ctx._h, C.byref(v)))
+
+    def integrate(self, depths, cameras, images=None, depth_min=0.0, depth_max=math.inf, alpha_min=0.5):
+        """TsdfVolume.integrate on the allocated blocks: every allocated sample ends with the bits the dense volume would hold."""
+        self._committed("integrate")
+        n, cams, dptr, iptr, keep = self._views(depths, cameras, images, "integrate")
+        if n == 0:
+            return
+        cfg = _ffi.BhTsdfIntegrateConfig(float(depth_min), float(depth_max), float(alpha_min), 0)
+        v = self.vol()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_integrate(self.ctx._h, C.byref(v), n, cams, dptr, iptr, C.byref(cfg)))
+
+    def count(self):
+        """(n_vertices, n_triangles) of the zero level set (bh_sptsdf_extract_count; blocking)."""
+        self._committed("count")
+        v = self.vol()
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_extract_count(self.ctx._h, C.byref(v), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def extract_mesh(self):
+        """(vertices [V,3] f32, colours [V,3] f32 or None, triangles [M,3] int32) on the device, as TsdfVolume.extract_mesh; vertices
+        come in pool order (by block key, then by the sample's index in its block)."""
+        n_v, n_t = self.count()
+        dev = self.device
+        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        colours = torch.empty((n_v, 3), dtype=torch.float32, device=dev) if self.rgb is not None else None
+        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        v = self.vol()
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_extract(self.ctx._h, C.byref(v), _ptr(vertices), _ptr(colours) if colours is not None else None, _ptr(triangles),
+                                                      n_v, n_t, C.byref(nv), C.byref(nt)))
+        return vertices, colours, triangles
+
+    def to_ply(self) -> bytes:
+        vertices, colours, triangles = self.extract_mesh()
+        return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
+
+    def to_dense(self, start=(0, 0, 0), dims=None, colour=None) -> TsdfVolume:
+        """The window of the virtual grid from sample `start`, `dims` samples wide (default: to the end of the grid), as a TsdfVolume:
+        allocated samples bit for bit, T = 1, W = 0, rgb = 0 elsewhere (bh_sptsdf_to_dense).  The dense volume's origin is
+        origin + voxel_size * start, so only a window from (0, 0, 0) is guaranteed to place its samples on the same f32 positions."""
+        self._committed("to_dense")
+        start = tuple(int(v) for v in start)
+        if len(start) != 3 or min(start) < 0 or any(s >= d for s, d in zip(start, self.dims)):
+            raise ValueError("SparseTsdfVolume.to_dense: start must lie inside the grid")
+        dims = tuple(d - s for s, d in zip(start, self.dims)) if dims is None else tuple(int(v) for v in dims)
+        origin = tuple(o + self.voxel_size * s for o, s in zip(self.origin, start))
+        dense = TsdfVolume(origin, self.voxel_size, dims, trunc=self.trunc, max_weight=self.max_weight, colour=self.colour if colour is None else bool(colour),
+                           ctx=self.ctx)
+        v, g = self.vol(), dense.grid()
+        self.ctx.check(self.ctx.lib.bh_sptsdf_to_dense(self.ctx._h, C.byref(v), start[0], start[1], start[2], C.byref(g)))
+        return dense
+
+
+def _fuse_render(splats, camera, size, depth_mode, pass_, ctx):
+    node = render_splats_diff(splats, camera, size, (0.0, 0.0, 0.0), pass_, ctx=ctx)
+    # (the node's image aliases ctx memory the next forward overwrites)
+    return node.depth(depth_mode), node.img.clone(), camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms(size)
+
+
+def fuse_views(splats: "Splats", cameras, img_size, volume, depth_mode="expected", pass_: "RasterPass" = None, depth_min=0.0,
+               depth_max=math.inf, alpha_min=0.5, dilate=1):
     """Renders `splats` from every camera (a BH_FLAG_BWD_INFO forward on black), takes the depth map RenderNode.depth(depth_mode)
-    and the forward's image, and fuses them into `volume` in batches of 8 views (one pass over the volume per batch)."""
+    and the forward's image, and fuses them into `volume` in batches of 8 views (one pass over the volume per batch).
+    A SparseTsdfVolume takes two passes over the cameras: render and mark(); commit(dilate); render again and integrate in batches of
+    8 — a forward more per view, and no depth map is kept alive between the passes."""
     pass_ = RasterPass.Backward if pass_ is None else pass_
     ctx = volume.ctx
     w, h = int(img_size[0]), int(img_size[1])
     cameras = list(cameras)
+    if isinstance(volume, SparseTsdfVolume):
+        for camera in cameras:
+            depth, image, cam = _fuse_render(splats, camera, (w, h), depth_mode, pass_, ctx)
+            volume.mark([depth], [cam], [image], depth_max=depth_max, alpha_min=alpha_min)
+        if volume.commit(dilate) == 0:
+            return volume
     for first in range(0, len(cameras), _ffi.TSDF_MAX_BATCH):
         cams, depths, images = [], [], []
         for camera in cameras[first:first + _ffi.TSDF_MAX_BATCH]:
-            node = render_splats_diff(splats, camera, (w, h), (0.0, 0.0, 0.0), pass_, ctx=ctx)
-            depths.append(node.depth(depth_mode))
-            images.append(node.img.clone())   # (the node's image aliases ctx memory the next forward overwrites)
-            cams.append(camera if isinstance(camera, _ffi.BhCamera) else camera.uniforms((w, h)))
+            depth, image, cam = _fuse_render(splats, camera, (w, h), depth_mode, pass_, ctx)
+            depths.append(depth); images.append(image); cams.append(cam)
         volume.integrate(depths, cams, images, depth_min=depth_min, depth_max=depth_max, alpha_min=alpha_min)
     return volume
 

@@ -90,6 +90,7 @@
 #include "brush_hip_distortion.h"
 #include "brush_hip_bilagrid.h"
 #include "brush_hip_mesh.h"
+#include "brush_hip_sparse_mesh.h"
 #include "brush_hip_features.h"
 #include "brush_hip_feature_train.h"
 #include "brush_hip_scene.h"
@@ -1732,6 +1733,130 @@ public:
 private:
     const Context* ctx_;
     BhTsdfGrid g_;
+    DeviceBuffer<float> tw_, rgb_;
+};
+
+// ---- sparse TSDF volumes (brush_hip_sparse_mesh.h; not in the reference) --------------------------------------------------------------
+static_assert(sizeof(BhSparseTsdf) == 80 && offsetof(BhSparseTsdf, voxel_size) == 12 && offsetof(BhSparseTsdf, nx) == 16 && offsetof(BhSparseTsdf, trunc) == 28 &&
+                  offsetof(BhSparseTsdf, n_blocks) == 36 && offsetof(BhSparseTsdf, bits) == 40 && offsetof(BhSparseTsdf, rank) == 48 &&
+                  offsetof(BhSparseTsdf, keys) == 56 && offsetof(BhSparseTsdf, tw) == 64 && offsetof(BhSparseTsdf, rgb) == 72,
+              "BhSparseTsdf layout");
+// A sparse TSDF volume that owns its device memory: a virtual grid of up to 8192 samples per axis of which only the 8x8x8 blocks near
+// the observed surfaces are held.  mark() the depth maps, commit() (counts the blocks, allocates and clears the pool), integrate(),
+// extract() / to_ply(); mark_clear() starts over.  Move-only.
+class SparseTsdfVolume {
+public:
+    SparseTsdfVolume(const Context& ctx, const std::array<float, 3>& origin, float voxel_size, const std::array<uint32_t, 3>& dims, float trunc = 0.0f /*0: 4 voxels*/,
+                     float max_weight = 64.0f, bool colour = true)
+        : ctx_(&ctx), colour_(colour) {
+        v_ = BhSparseTsdf{};
+        for (int a = 0; a < 3; ++a) v_.origin[a] = origin[a];
+        v_.voxel_size = voxel_size;
+        v_.nx = dims[0]; v_.ny = dims[1]; v_.nz = dims[2];
+        v_.trunc = trunc > 0.0f ? trunc : 4.0f * voxel_size;
+        v_.max_weight = max_weight;
+        for (uint32_t d : dims)
+            if (d < 2 || d > BH_SPTSDF_MAX_DIM) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume: dimensions of 2 .. 8192");
+        const uint64_t total = (uint64_t)((dims[0] + 7) / 8) * ((dims[1] + 7) / 8) * ((dims[2] + 7) / 8);
+        n_words_ = (size_t)((total + 31) / 32);
+        bits_.resize(n_words_);
+        rank_.resize(n_words_);
+        v_.bits = bits_.data();
+        v_.rank = rank_.data();
+        mark_clear();
+    }
+    SparseTsdfVolume(const SparseTsdfVolume&) = delete;
+    SparseTsdfVolume& operator=(const SparseTsdfVolume&) = delete;
+    SparseTsdfVolume(SparseTsdfVolume&&) noexcept = default;
+    const BhSparseTsdf& vol() const { return v_; }
+    uint32_t n_blocks() const { return v_.n_blocks; }
+    size_t n_words() const { return n_words_; }
+    std::vector<uint32_t> bits() const { ctx_->sync(); return bits_.download(); }
+    std::vector<uint32_t> rank() const { ctx_->sync(); return rank_.download(); }
+    std::vector<uint32_t> keys() const { ctx_->sync(); return keys_.download(); }
+    std::vector<float> tw() const { ctx_->sync(); return tw_.download(); }     // [n_blocks,8,8,8,2] on the host
+    std::vector<float> rgb() const { ctx_->sync(); return rgb_.download(); }   // [n_blocks,8,8,8,3] on the host (empty without colour)
+    void set_bits(const std::vector<uint32_t>& host) {   // a block set computed elsewhere; commit(0) allocates exactly it
+        if (host.size() != n_words_ || v_.n_blocks) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::set_bits: n_words words, before the commit");
+        ctx_->sync();
+        hip_check(hipMemcpy(bits_.data(), host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+    void set_tw(const std::vector<float>& host) {   // a field computed elsewhere, [n_blocks,8,8,8,2]
+        if (host.size() != (size_t)v_.n_blocks * 1024) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::set_tw: a pool of another size");
+        ctx_->sync();
+        hip_check(hipMemcpy(tw_.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+    // forgets the marks and the pool
+    void mark_clear() {
+        ctx_->sync();
+        v_.n_blocks = 0;
+        v_.keys = nullptr; v_.tw = nullptr; v_.rgb = nullptr;
+        keys_ = DeviceBuffer<uint32_t>(); tw_ = DeviceBuffer<float>(); rgb_ = DeviceBuffer<float>();
+        ctx_->check(bh_sptsdf_mark_clear(ctx_->get(), &v_));
+    }
+    // depths[v] [H,W] and images[v] [H,W,4] (or an empty vector: no alpha test) are device pointers of cams[v]'s size
+    void mark(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {}, float depth_max = INFINITY,
+              float alpha_min = 0.5f) {
+        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
+            throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::mark: as many depth maps (and images) as cameras");
+        if (v_.n_blocks) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::mark: after a commit: mark_clear() first");
+        const BhTsdfIntegrateConfig cfg{0.0f, depth_max, alpha_min, 0u};
+        ctx_->check(bh_sptsdf_mark(ctx_->get(), &v_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
+    }
+    // -> the number of blocks (0: nothing marked, no pool); blocking
+    uint32_t commit(uint32_t dilate = 1) {
+        if (v_.n_blocks) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::commit: already committed: mark_clear() starts over");
+        uint32_t n = 0;
+        ctx_->check(bh_sptsdf_commit(ctx_->get(), &v_, dilate, &n));
+        if (n == 0) return 0;
+        keys_.resize(n);
+        tw_.resize((size_t)n * 1024);
+        if (colour_) rgb_.resize((size_t)n * 1536);
+        v_.keys = keys_.data();
+        v_.tw = tw_.data();
+        v_.rgb = colour_ ? rgb_.data() : nullptr;
+        v_.n_blocks = n;
+        clear();
+        return n;
+    }
+    void clear() { ctx_->check(bh_sptsdf_clear(ctx_->get(), &v_)); }
+    void integrate(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {},
+                   float depth_min = 0.0f, float depth_max = INFINITY, float alpha_min = 0.5f) {
+        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
+            throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::integrate: as many depth maps (and images) as cameras");
+        const BhTsdfIntegrateConfig cfg{depth_min, depth_max, alpha_min, 0u};
+        ctx_->check(bh_sptsdf_integrate(ctx_->get(), &v_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
+    }
+    std::pair<uint32_t, uint32_t> count() const {   // (vertices, triangles); blocking
+        uint32_t nv = 0, nt = 0;
+        ctx_->check(bh_sptsdf_extract_count(ctx_->get(), &v_, &nv, &nt));
+        return {nv, nt};
+    }
+    Mesh extract() const {
+        Mesh m;
+        const auto [nv, nt] = count();
+        m.vertices.resize((size_t)nv * 3);
+        if (v_.rgb) m.colours.resize((size_t)nv * 3);
+        m.triangles.resize((size_t)nt * 3);
+        ctx_->check(bh_sptsdf_extract(ctx_->get(), &v_, m.vertices.data(), v_.rgb ? m.colours.data() : nullptr, m.triangles.data(), nv, nt, &m.n_vertices,
+                                      &m.n_triangles));
+        return m;
+    }
+    std::vector<uint8_t> to_ply() const {
+        const Mesh m = extract();
+        return mesh_to_ply(*ctx_, m.vertices.data(), v_.rgb ? m.colours.data() : nullptr, m.n_vertices, m.triangles.data(), m.n_triangles);
+    }
+    // the window of the virtual grid from sample `start`, of dense's size, into `dense` (bh_sptsdf_to_dense)
+    void to_dense(const std::array<uint32_t, 3>& start, TsdfVolume& dense) const {
+        ctx_->check(bh_sptsdf_to_dense(ctx_->get(), &v_, start[0], start[1], start[2], &dense.grid()));
+    }
+
+private:
+    const Context* ctx_;
+    bool colour_;
+    size_t n_words_ = 0;
+    BhSparseTsdf v_;
+    DeviceBuffer<uint32_t> bits_, rank_, keys_;
     DeviceBuffer<float> tw_, rgb_;
 };
 
