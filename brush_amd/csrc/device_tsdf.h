@@ -1,8 +1,12 @@
 // device_tsdf.h — what the dense volume (tsdf.hip, include/brush_hip_mesh.h) and the sparse one (sparse_tsdf.hip,
-// include/brush_hip_sparse_mesh.h) share, ONE copy each: the views a launch takes from its kernel arguments, the per-sample fusion
-// rule, the edge order and the tetrahedron case table of the extraction, the classification of a sample from the 3x3x3 bits around
-// it, and the emission of a sample's vertices and triangles.  The two volumes differ only in where a sample's neighbours live.
+// include/brush_hip_sparse_mesh.h) share, ONE copy each.  On the device: the clear kernel, the views a launch takes from its kernel
+// arguments, the per-sample fusion rule and the load / fuse / store around it, the edge order and the tetrahedron case table of the
+// extraction, the classification of a sample from the 3x3x3 bits around it and the store of its word, and the emission of a sample's
+// vertices and triangles.  On the host: the refusals of a volume's fields and of a dense grid's size, the integrate driver (refusals,
+// the batch loop, the choice of instantiation) and the extraction driver (refusals, classify, the two scans, the readback, emit).
+// A volume keeps what is its own: its struct, where a sample and its neighbours live, and hence its kernels' index arithmetic.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -66,6 +70,60 @@ BH_DEV bool tsdf_update_sample(const TsdfBatch& b, const uint32_t n_views, const
     return touched;
 }
 
+// The sample stored at s, at (px, py, pz): loaded, fused with the batch's views, stored if a view touched it.
+template <bool COLOUR>
+BH_DEV void tsdf_fuse_at(float2* tw, float* rgb, const size_t s, const float px, const float py, const float pz, const TsdfBatch& b, const uint32_t n_views,
+                         const float depth_min, const float depth_max, const float alpha_min, const float trunc, const float max_weight) {
+    const float2 t = tw[s];
+    float T = t.x, W = t.y;
+    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+    if (COLOUR) {
+        const float* c = rgb + s * 3;
+        c0 = c[0]; c1 = c[1]; c2 = c[2];
+    }
+    if (tsdf_update_sample<COLOUR>(b, n_views, depth_min, depth_max, alpha_min, trunc, max_weight, px, py, pz, T, W, c0, c1, c2)) {
+        tw[s] = make_float2(T, W);
+        if (COLOUR) {
+            float* c = rgb + s * 3;
+            c[0] = c0; c[1] = c1; c[2] = c2;
+        }
+    }
+}
+
+// T = 1, W = 0, rgb = 0 in n samples (static: both units launch it)
+static __global__ __launch_bounds__(256) void tsdf_clear_samples_kernel(float2* tw, float* rgb, const uint32_t n) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n) return;
+    tw[s] = make_float2(1.0f, 0.0f);
+    if (rgb) {
+        float* c = rgb + (size_t)s * 3;
+        c[0] = 0.0f; c[1] = 0.0f; c[2] = 0.0f;
+    }
+}
+
+inline int tsdf_clear_samples(bh_ctx* ctx, float2* tw, float* rgb, uint32_t n) {
+    hipLaunchKernelGGL(tsdf_clear_samples_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, tw, rgb, n);
+    BH_LAUNCH_CHECK(ctx, "tsdf_clear_samples_kernel");
+    return 0;
+}
+
+// What every entry point refuses about a volume's fields, dense or sparse.
+inline int tsdf_check_fields(bh_ctx* ctx, const std::string& who, uint32_t nx, uint32_t ny, uint32_t nz, float voxel_size, float trunc, float max_weight) {
+    if (nx < 2u || ny < 2u || nz < 2u) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": every dimension of the grid must be at least 2");
+    if (!(std::isfinite(voxel_size) && voxel_size > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": voxel_size must be a finite number > 0");
+    if (!(std::isfinite(trunc) && trunc > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": trunc must be a finite number > 0");
+    if (!(max_weight >= 1.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": max_weight must be at least 1");
+    return 0;
+}
+
+// The size a dense grid may have; `what` is "" for a volume of its own and "dense " for the target of bh_sptsdf_to_dense.
+inline int tsdf_check_dense_dims(bh_ctx* ctx, const std::string& who, const std::string& what, uint32_t nx, uint32_t ny, uint32_t nz) {
+    if (nx < 2u || ny < 2u || nz < 2u) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": every dimension of the " + what + "grid must be at least 2");
+    if ((uint64_t)nx * ny > 0x7FFFFFFFull || (uint64_t)nx * ny * nz > 0x7FFFFFFFull)
+        return set_error(ctx, BH_ERR_INVALID_ARG, who + ": more than 2^31 - 1 " + what + "samples");
+    return 0;
+}
+
 // What both integrate entry points refuse about their views, before the device is touched.
 inline int tsdf_check_views(bh_ctx* ctx, const std::string& who, uint32_t n_views, const BhCamera* cams, const float* const* depths, const float* const* images) {
     if (!cams || !depths) return set_error(ctx, BH_ERR_INVALID_ARG, who + ": null argument");
@@ -93,6 +151,26 @@ inline TsdfBatch tsdf_make_batch(uint32_t first, uint32_t count, const BhCamera*
         t.image = images ? images[first + v] : nullptr;
     }
     return b;
+}
+
+// The tail of both integrate entry points, after the volume's own check: the refusals, then one launch per batch of views.
+// launch(colour, batch, count) enqueues the volume's kernel, tsdf_..._kernel<colour>; `who` + "_kernel" names it in a launch error.
+template <class Launch>
+inline int tsdf_integrate_batches(bh_ctx* ctx, const char* who, const char* prof, uint32_t n_views, const BhCamera* cams, const float* const* depths,
+                                  const float* const* images, const BhTsdfIntegrateConfig* cfg, bool has_rgb, Launch launch) {
+    const std::string w(who);
+    if (!cfg) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": null config");
+    if (n_views == 0) return 0;
+    BH_TRY(tsdf_check_views(ctx, w, n_views, cams, depths, images));
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    ProfScope ps(ctx, prof);
+    const bool colour = images && has_rgb;
+    for (uint32_t first = 0; first < n_views; first += BH_TSDF_MAX_BATCH) {
+        const uint32_t count = n_views - first < BH_TSDF_MAX_BATCH ? n_views - first : BH_TSDF_MAX_BATCH;
+        launch(colour, tsdf_make_batch(first, count, cams, depths, images), count);
+        BH_LAUNCH_CHECK(ctx, (w + "_kernel").c_str());
+    }
+    return 0;
 }
 
 // ---- extraction -------------------------------------------------------------------------------------------------------------------
@@ -176,6 +254,12 @@ BH_DEV uint32_t tsdf_classify_word(const uint32_t obs, const uint32_t ins) {
     return mask | tris << 8 | corners8 << 16;
 }
 
+BH_DEV void tsdf_store_class(uint32_t* __restrict__ info, uint32_t* __restrict__ vcnt, uint32_t* __restrict__ tcnt, const size_t s, const uint32_t word) {
+    info[s] = word;
+    vcnt[s] = (uint32_t)__popc(word & 0x7Fu);
+    tcnt[s] = (word >> 8) & 0xFFu;
+}
+
 BH_DEV uint32_t tsdf_vertex_index(const uint32_t* __restrict__ info, const uint32_t* __restrict__ vinc, size_t owner, uint32_t d) {
     const uint32_t m = info[owner] & 0x7Fu;
     return vinc[owner] - (uint32_t)__popc(m) + (uint32_t)__popc(m & ((1u << d) - 1u));
@@ -238,6 +322,46 @@ BH_DEV void tsdf_emit_sample(const float ox, const float oy, const float oz, con
             }
         }
     }
+}
+
+// All four extraction entry points, after the volume's own check, over its n stored samples: the refusals, classify into the scratch
+// slot, the two inclusive scans, the counts read back (blocking) and, unless count_only, emit.  classify(info, vcnt, tcnt) and
+// emit(info, vinc, tinc) enqueue the volume's kernels and return their launch check; prof names the stages Classify, Scan, Emit.
+template <class Classify, class Emit>
+inline int tsdf_extract_run(bh_ctx* ctx, const char* who, Slot slot, uint32_t n, bool has_rgb, Classify classify, Emit emit, const float* vertices, const float* colours,
+                            const uint32_t* triangles, uint32_t cap_v, uint32_t cap_t, uint32_t* n_vertices, uint32_t* n_triangles, bool count_only,
+                            const char* const prof[3]) {
+    const std::string w(who);
+    if (!n_vertices || !n_triangles) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": null count pointer");
+    if (colours && !has_rgb) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": colours of a volume without rgb");
+    BH_HIP(ctx, hipSetDevice(ctx->device));
+    auto* info = (uint32_t*)ensure(ctx, slot, (size_t)n * 12);
+    if (!info) return BH_ERR_OOM;
+    uint32_t *vinc = info + n, *tinc = info + 2 * (size_t)n, counts[2] = {0, 0};
+    {
+        ProfScope ps(ctx, prof[0]);
+        BH_TRY(classify(info, vinc, tinc));
+    }
+    {
+        ProfScope ps(ctx, prof[1]);
+        BH_TRY(prefix_sum(ctx, vinc, nullptr, n, vinc, /*exclusive=*/false));
+        BH_TRY(prefix_sum(ctx, tinc, nullptr, n, tinc, /*exclusive=*/false));
+    }
+    BH_HIP(ctx, hipMemcpyAsync(&counts[0], vinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
+    BH_HIP(ctx, hipMemcpyAsync(&counts[1], tinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
+    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_vertices = counts[0];
+    *n_triangles = counts[1];
+    if (count_only) return 0;
+    if (counts[0] > cap_v || counts[1] > cap_t) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": output capacity too small");
+    if ((counts[0] && !vertices) || (counts[1] && !triangles)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": null output");
+    if (counts[0] == 0u) return 0;   // (no vertex, hence no triangle)
+    {
+        ProfScope ps(ctx, prof[2]);
+        BH_TRY(emit(info, vinc, tinc));
+    }
+    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 }  // namespace bh

@@ -9,12 +9,16 @@
 // every word — is written without looking at a bit.
 //
 // Integration: a workgroup takes a pool block, a wave owns z-slices of it (64 consecutive pool entries, 512 contiguous bytes of tw);
-// the cameras come from the kernel arguments, the per-sample arithmetic is tsdf_update_sample, the dense kernel's.  No rejection of
+// the cameras come from the kernel arguments, the sample's load / fuse / store is tsdf_fuse_at, the dense kernel's.  No rejection of
 // whole blocks against a view: none was shown to leave every bit alone.
 //
 // Extraction is the dense path's three phases (classify, two inclusive scans over n_blocks * 512 entries, emit) without atomics.
 // Classify stages the {observed, inside} bits of a block's 10x10x10 neighbourhood in LDS (1000 bytes) — the up to 26 neighbour blocks
 // are looked up once per workgroup through bits and rank — where the dense kernel pays 27 scattered loads per sample.
+//
+// The clear kernel and the host side of clear, integrate, extract_count and extract are the dense volume's (device_tsdf.h:
+// tsdf_clear_samples, tsdf_check_fields, tsdf_integrate_batches, tsdf_extract_run); this unit supplies its struct, its check and its
+// launches.  Marking, commit, keys and to_dense have no dense twin.
 #include <cmath>
 #include <string>
 
@@ -57,6 +61,15 @@ BH_DEV uint32_t sp_neighbour_slot(const SpVolDev& g, const uint32_t bx, const ui
     if (x < 0 || y < 0 || z < 0 || x >= (int)g.nbx || y >= (int)g.nby || z >= (int)g.nbz) return SP_NONE;
     return sp_slot_of(g, ((uint32_t)z * g.nby + (uint32_t)y) * g.nbx + (uint32_t)x);
 }
+
+// the block coordinates of `key`
+BH_DEV void sp_block_coords(const SpVolDev& g, const uint32_t key, uint32_t& bx, uint32_t& by, uint32_t& bz) {
+    const uint32_t rest = key / g.nbx;
+    bx = key % g.nbx; by = rest % g.nby; bz = rest / g.nby;
+}
+
+// where the sample (x, y, z) of the virtual grid, or of a block, lies in its block's 512 pool entries
+BH_DEV uint32_t sp_local_index(const uint32_t x, const uint32_t y, const uint32_t z) { return ((z & 7u) * 8u + (y & 7u)) * 8u + (x & 7u); }
 
 // ---- marking ----------------------------------------------------------------------------------------------------------------------
 struct SpMarkView {
@@ -180,16 +193,6 @@ __global__ __launch_bounds__(256) void sptsdf_keys_kernel(const SpVolDev g) {
     }
 }
 
-__global__ __launch_bounds__(256) void sptsdf_clear_kernel(const SpVolDev g, const uint32_t n) {
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    g.tw[s] = make_float2(1.0f, 0.0f);
-    if (g.rgb) {
-        float* c = g.rgb + (size_t)s * 3;
-        c[0] = 0.0f; c[1] = 0.0f; c[2] = 0.0f;
-    }
-}
-
 // ---- integration ------------------------------------------------------------------------------------------------------------------
 // COLOUR: the volume has rgb and the batch has images (then every view has one)
 template <bool COLOUR>
@@ -198,8 +201,8 @@ __global__ __launch_bounds__(256) void sptsdf_integrate_kernel(const SpVolDev g,
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
         const uint32_t key = g.keys[blk];
-        const uint32_t bx = key % g.nbx, rest = key / g.nbx;
-        const uint32_t by = rest % g.nby, bz = rest / g.nby;
+        uint32_t bx, by, bz;
+        sp_block_coords(g, key, bx, by, bz);
         const uint32_t i = bx * 8u + (lane & 7u), j = by * 8u + (lane >> 3);
         if (i >= g.nx || j >= g.ny) continue;
         const float px = g.ox + g.vs * (float)i, py = g.oy + g.vs * (float)j;
@@ -208,20 +211,7 @@ __global__ __launch_bounds__(256) void sptsdf_integrate_kernel(const SpVolDev g,
             if (k >= g.nz) break;
             const float pz = g.oz + g.vs * (float)k;
             const size_t s = (size_t)blk * 512u + lz * 64u + lane;
-            const float2 tw = g.tw[s];
-            float T = tw.x, W = tw.y;
-            float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-            if (COLOUR) {
-                const float* c = g.rgb + s * 3;
-                c0 = c[0]; c1 = c[1]; c2 = c[2];
-            }
-            if (tsdf_update_sample<COLOUR>(b, n_views, depth_min, depth_max, alpha_min, g.trunc, g.max_weight, px, py, pz, T, W, c0, c1, c2)) {
-                g.tw[s] = make_float2(T, W);
-                if (COLOUR) {
-                    float* c = g.rgb + s * 3;
-                    c[0] = c0; c[1] = c1; c[2] = c2;
-                }
-            }
+            tsdf_fuse_at<COLOUR>(g.tw, g.rgb, s, px, py, pz, b, n_views, depth_min, depth_max, alpha_min, g.trunc, g.max_weight);
         }
     }
 }
@@ -233,8 +223,8 @@ __global__ __launch_bounds__(256) void sptsdf_classify_kernel(const SpVolDev g, 
     __shared__ uint8_t s_nb[1000];   // the block's 10x10x10 neighbourhood: observed | inside << 1
     for (uint32_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
         const uint32_t key = g.keys[blk];
-        const uint32_t bx = key % g.nbx, rest = key / g.nbx;
-        const uint32_t by = rest % g.nby, bz = rest / g.nby;
+        uint32_t bx, by, bz;
+        sp_block_coords(g, key, bx, by, bz);
         if (threadIdx.x < 27u) {
             const int t = (int)threadIdx.x;
             s_slot[t] = sp_neighbour_slot(g, bx, by, bz, t % 3 - 1, (t / 3) % 3 - 1, t / 9 - 1);
@@ -246,7 +236,7 @@ __global__ __launch_bounds__(256) void sptsdf_classify_kernel(const SpVolDev g, 
             uint8_t byte = 0;
             // (a neighbour block that exists has coordinates >= 0; the sample itself must exist too)
             if (slot != SP_NONE && (int)(bx * 8u) + lx < (int)g.nx && (int)(by * 8u) + ly < (int)g.ny && (int)(bz * 8u) + lz < (int)g.nz) {
-                const float2 t = g.tw[(size_t)slot * 512u + (uint32_t)(((lz & 7) * 8 + (ly & 7)) * 8 + (lx & 7))];
+                const float2 t = g.tw[(size_t)slot * 512u + sp_local_index((uint32_t)lx, (uint32_t)ly, (uint32_t)lz)];
                 byte = (uint8_t)((t.y > 0.0f ? 1u : 0u) | (t.x < 0.0f ? 2u : 0u));
             }
             s_nb[e] = byte;
@@ -267,11 +257,7 @@ __global__ __launch_bounds__(256) void sptsdf_classify_kernel(const SpVolDev g, 
                         obs |= (v & 1u) << nb_bit(dx, dy, dz);
                         ins |= (v >> 1) << nb_bit(dx, dy, dz);
                     }
-            const uint32_t word = tsdf_classify_word(obs, ins);
-            const size_t s = (size_t)blk * 512u + local;
-            info[s] = word;
-            vcnt[s] = (uint32_t)__popc(word & 0x7Fu);
-            tcnt[s] = (word >> 8) & 0xFFu;
+            tsdf_store_class(info, vcnt, tcnt, (size_t)blk * 512u + local, tsdf_classify_word(obs, ins));
         }
         __syncthreads();   // (the next block's staging overwrites s_slot and s_nb)
     }
@@ -283,8 +269,8 @@ __global__ __launch_bounds__(256) void sptsdf_emit_kernel(const SpVolDev g, cons
     __shared__ uint32_t s_slot[8];   // the blocks at (+0|1, +0|1, +0|1)
     for (uint32_t blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
         const uint32_t key = g.keys[blk];
-        const uint32_t bx = key % g.nbx, rest = key / g.nbx;
-        const uint32_t by = rest % g.nby, bz = rest / g.nby;
+        uint32_t bx, by, bz;
+        sp_block_coords(g, key, bx, by, bz);
         if (threadIdx.x < 8u) {
             const int t = (int)threadIdx.x;
             s_slot[t] = t == 0 ? blk : sp_neighbour_slot(g, bx, by, bz, t & 1, (t >> 1) & 1, t >> 2);
@@ -301,7 +287,7 @@ __global__ __launch_bounds__(256) void sptsdf_emit_kernel(const SpVolDev g, cons
                                  const uint32_t x = lx + (c & 1u), y = ly + ((c >> 1) & 1u), z = lz + (c >> 2);
                                  const uint32_t slot = s_slot[(x >> 3) | (y >> 3) << 1 | (z >> 3) << 2];
                                  // (an edge or a cube that emits has observed ends, so their blocks are allocated; never index with SP_NONE)
-                                 return slot == SP_NONE ? s : (size_t)slot * 512u + (((z & 7u) * 8u + (y & 7u)) * 8u + (x & 7u));
+                                 return slot == SP_NONE ? s : (size_t)slot * 512u + sp_local_index(x, y, z);
                              });
         }
         __syncthreads();
@@ -319,7 +305,7 @@ __global__ __launch_bounds__(256) void sptsdf_to_dense_kernel(const SpVolDev g, 
     if (i < g.nx && j < g.ny && k < g.nz) {
         const uint32_t slot = sp_slot_of(g, (((uint32_t)k >> 3) * g.nby + ((uint32_t)j >> 3)) * g.nbx + ((uint32_t)i >> 3));
         if (slot != SP_NONE) {
-            const size_t src = (size_t)slot * 512u + ((((uint32_t)k & 7u) * 8u + ((uint32_t)j & 7u)) * 8u + ((uint32_t)i & 7u));
+            const size_t src = (size_t)slot * 512u + sp_local_index((uint32_t)i, (uint32_t)j, (uint32_t)k);
             tw = g.tw[src];
             if (g.rgb && drgb) {
                 c0 = g.rgb[src * 3]; c1 = g.rgb[src * 3 + 1]; c2 = g.rgb[src * 3 + 2];
@@ -336,15 +322,14 @@ __global__ __launch_bounds__(256) void sptsdf_to_dense_kernel(const SpVolDev g, 
 static int sp_check_vol(bh_ctx* ctx, const BhSparseTsdf* v, const char* who, bool committed, SpVolDev* dev) {
     const std::string w(who);
     if (!v || !v->bits || !v->rank) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": null volume, bits or rank");
-    if (v->nx < 2u || v->ny < 2u || v->nz < 2u) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": every dimension of the grid must be at least 2");
-    if (v->nx > BH_SPTSDF_MAX_DIM || v->ny > BH_SPTSDF_MAX_DIM || v->nz > BH_SPTSDF_MAX_DIM)
-        return set_error(ctx, BH_ERR_INVALID_ARG, w + ": a dimension of the grid above 8192");
     const uint32_t nbx = (v->nx + 7u) / 8u, nby = (v->ny + 7u) / 8u, nbz = (v->nz + 7u) / 8u;
     const uint64_t total = (uint64_t)nbx * nby * nbz;
-    if (total > (1ull << 30)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": more than 2^30 virtual blocks");
-    if (!(std::isfinite(v->voxel_size) && v->voxel_size > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": voxel_size must be a finite number > 0");
-    if (!(std::isfinite(v->trunc) && v->trunc > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": trunc must be a finite number > 0");
-    if (!(v->max_weight >= 1.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": max_weight must be at least 1");
+    if (v->nx >= 2u && v->ny >= 2u && v->nz >= 2u) {   // (a side below 2 is tsdf_check_fields' first refusal, ahead of the size limits)
+        if (v->nx > BH_SPTSDF_MAX_DIM || v->ny > BH_SPTSDF_MAX_DIM || v->nz > BH_SPTSDF_MAX_DIM)
+            return set_error(ctx, BH_ERR_INVALID_ARG, w + ": a dimension of the grid above 8192");
+        if (total > (1ull << 30)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": more than 2^30 virtual blocks");
+    }
+    BH_TRY(tsdf_check_fields(ctx, w, v->nx, v->ny, v->nz, v->voxel_size, v->trunc, v->max_weight));
     if (committed) {
         if (v->n_blocks == 0u || !v->keys || !v->tw) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": a volume before its commit (no blocks, or null keys or tw)");
         if (v->n_blocks > SP_MAX_POOL_BLOCKS) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": more than 2^31 - 1 allocated samples");
@@ -357,26 +342,27 @@ static int sp_check_vol(bh_ctx* ctx, const BhSparseTsdf* v, const char* who, boo
 
 static uint32_t sp_wgs(uint32_t n_blocks) { return n_blocks < SP_MAX_WGS ? n_blocks : SP_MAX_WGS; }
 
-// classify + the two scans; the counts are read back (blocking)
-static int sp_classify_and_scan(bh_ctx* ctx, const SpVolDev& g, uint32_t** info, uint32_t** vinc, uint32_t** tinc, uint32_t counts[2]) {
-    const uint32_t n = g.n_blocks * 512u;
-    auto* scratch = (uint32_t*)ensure(ctx, SLOT_SPTSDF, (size_t)n * 12);
-    if (!scratch) return BH_ERR_OOM;
-    *info = scratch; *vinc = scratch + n; *tinc = scratch + 2 * (size_t)n;
-    {
-        ProfScope ps(ctx, "SpTsdfClassify");
-        hipLaunchKernelGGL(sptsdf_classify_kernel, dim3(sp_wgs(g.n_blocks)), dim3(256), 0, ctx->stream, g, *info, *vinc, *tinc);
-        BH_LAUNCH_CHECK(ctx, "sptsdf_classify_kernel");
-    }
-    {
-        ProfScope ps(ctx, "SpTsdfScan");
-        BH_TRY(prefix_sum(ctx, *vinc, nullptr, n, *vinc, /*exclusive=*/false));
-        BH_TRY(prefix_sum(ctx, *tinc, nullptr, n, *tinc, /*exclusive=*/false));
-    }
-    BH_HIP(ctx, hipMemcpyAsync(&counts[0], *vinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(&counts[1], *tinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+// bh_sptsdf_extract and bh_sptsdf_extract_count: the sparse volume's two launches for tsdf_extract_run
+static int sp_extract_vol(bh_ctx* ctx, const BhSparseTsdf* vol, const char* who, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t,
+                          uint32_t* n_vertices, uint32_t* n_triangles, bool count_only) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    SpVolDev g;
+    BH_TRY(sp_check_vol(ctx, vol, who, true, &g));
+    const dim3 launch(sp_wgs(g.n_blocks)), block(256);
+    static const char* const prof[3] = {"SpTsdfClassify", "SpTsdfScan", "SpTsdfEmit"};
+    return tsdf_extract_run(
+        ctx, who, SLOT_SPTSDF, g.n_blocks * 512u, g.rgb != nullptr,
+        [&](uint32_t* info, uint32_t* vcnt, uint32_t* tcnt) {
+            hipLaunchKernelGGL(sptsdf_classify_kernel, launch, block, 0, ctx->stream, g, info, vcnt, tcnt);
+            BH_LAUNCH_CHECK(ctx, "sptsdf_classify_kernel");
+            return 0;
+        },
+        [&](const uint32_t* info, const uint32_t* vinc, const uint32_t* tinc) {
+            hipLaunchKernelGGL(sptsdf_emit_kernel, launch, block, 0, ctx->stream, g, info, vinc, tinc, vertices, colours, triangles);
+            BH_LAUNCH_CHECK(ctx, "sptsdf_emit_kernel");
+            return 0;
+        },
+        vertices, colours, triangles, cap_v, cap_t, n_vertices, n_triangles, count_only, prof);
 }
 
 }  // namespace bh
@@ -467,10 +453,7 @@ int bh_sptsdf_clear(bh_ctx* ctx, const BhSparseTsdf* vol) {
     BH_HIP(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(sptsdf_keys_kernel, dim3((g.n_words + 255u) / 256u), dim3(256), 0, ctx->stream, g);
     BH_LAUNCH_CHECK(ctx, "sptsdf_keys_kernel");
-    const uint32_t n = g.n_blocks * 512u;
-    hipLaunchKernelGGL(sptsdf_clear_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, g, n);
-    BH_LAUNCH_CHECK(ctx, "sptsdf_clear_kernel");
-    return 0;
+    return tsdf_clear_samples(ctx, g.tw, g.rgb, g.n_blocks * 512u);
 }
 
 int bh_sptsdf_integrate(bh_ctx* ctx, const BhSparseTsdf* vol, uint32_t n_views, const BhCamera* cams, const float* const* depths, const float* const* images,
@@ -478,60 +461,21 @@ int bh_sptsdf_integrate(bh_ctx* ctx, const BhSparseTsdf* vol, uint32_t n_views, 
     if (!ctx) return BH_ERR_INVALID_ARG;
     SpVolDev g;
     BH_TRY(sp_check_vol(ctx, vol, "sptsdf_integrate", true, &g));
-    if (!cfg) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_integrate: null config");
-    if (n_views == 0) return 0;
-    BH_TRY(tsdf_check_views(ctx, "sptsdf_integrate", n_views, cams, depths, images));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    ProfScope ps(ctx, "SpTsdfIntegrate");
     const dim3 launch(sp_wgs(g.n_blocks)), block(256);
-    const bool colour = images && g.rgb;
-    for (uint32_t first = 0; first < n_views; first += BH_TSDF_MAX_BATCH) {
-        const uint32_t count = n_views - first < BH_TSDF_MAX_BATCH ? n_views - first : BH_TSDF_MAX_BATCH;
-        const TsdfBatch b = tsdf_make_batch(first, count, cams, depths, images);
-        if (colour)
-            hipLaunchKernelGGL(sptsdf_integrate_kernel<true>, launch, block, 0, ctx->stream, g, b, count, cfg->depth_min, cfg->depth_max, cfg->alpha_min);
-        else
-            hipLaunchKernelGGL(sptsdf_integrate_kernel<false>, launch, block, 0, ctx->stream, g, b, count, cfg->depth_min, cfg->depth_max, cfg->alpha_min);
-        BH_LAUNCH_CHECK(ctx, "sptsdf_integrate_kernel");
-    }
-    return 0;
+    return tsdf_integrate_batches(ctx, "sptsdf_integrate", "SpTsdfIntegrate", n_views, cams, depths, images, cfg, g.rgb != nullptr,
+                                  [&](bool colour, const TsdfBatch& b, uint32_t count) {
+                                      hipLaunchKernelGGL(colour ? sptsdf_integrate_kernel<true> : sptsdf_integrate_kernel<false>, launch, block, 0, ctx->stream, g, b,
+                                                         count, cfg->depth_min, cfg->depth_max, cfg->alpha_min);
+                                  });
 }
 
 int bh_sptsdf_extract_count(bh_ctx* ctx, const BhSparseTsdf* vol, uint32_t* n_vertices, uint32_t* n_triangles) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    SpVolDev g;
-    BH_TRY(sp_check_vol(ctx, vol, "sptsdf_extract_count", true, &g));
-    if (!n_vertices || !n_triangles) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_extract_count: null count pointer");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *info, *vinc, *tinc, counts[2] = {0, 0};
-    BH_TRY(sp_classify_and_scan(ctx, g, &info, &vinc, &tinc, counts));
-    *n_vertices = counts[0];
-    *n_triangles = counts[1];
-    return 0;
+    return sp_extract_vol(ctx, vol, "sptsdf_extract_count", nullptr, nullptr, nullptr, 0, 0, n_vertices, n_triangles, /*count_only=*/true);
 }
 
 int bh_sptsdf_extract(bh_ctx* ctx, const BhSparseTsdf* vol, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t,
                       uint32_t* n_vertices, uint32_t* n_triangles) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    SpVolDev g;
-    BH_TRY(sp_check_vol(ctx, vol, "sptsdf_extract", true, &g));
-    if (!n_vertices || !n_triangles) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_extract: null count pointer");
-    if (colours && !g.rgb) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_extract: colours of a volume without rgb");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *info, *vinc, *tinc, counts[2] = {0, 0};
-    BH_TRY(sp_classify_and_scan(ctx, g, &info, &vinc, &tinc, counts));
-    *n_vertices = counts[0];
-    *n_triangles = counts[1];
-    if (counts[0] > cap_v || counts[1] > cap_t) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_extract: output capacity too small");
-    if ((counts[0] && !vertices) || (counts[1] && !triangles)) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_extract: null output");
-    if (counts[0] == 0u) return 0;   // (no vertex, hence no triangle)
-    {
-        ProfScope ps(ctx, "SpTsdfEmit");
-        hipLaunchKernelGGL(sptsdf_emit_kernel, dim3(sp_wgs(g.n_blocks)), dim3(256), 0, ctx->stream, g, info, vinc, tinc, vertices, colours, triangles);
-        BH_LAUNCH_CHECK(ctx, "sptsdf_emit_kernel");
-    }
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return sp_extract_vol(ctx, vol, "sptsdf_extract", vertices, colours, triangles, cap_v, cap_t, n_vertices, n_triangles, /*count_only=*/false);
 }
 
 int bh_sptsdf_to_dense(bh_ctx* ctx, const BhSparseTsdf* vol, uint32_t i0, uint32_t j0, uint32_t k0, const BhTsdfGrid* dense) {
@@ -539,9 +483,7 @@ int bh_sptsdf_to_dense(bh_ctx* ctx, const BhSparseTsdf* vol, uint32_t i0, uint32
     SpVolDev g;
     BH_TRY(sp_check_vol(ctx, vol, "sptsdf_to_dense", true, &g));
     if (!dense || !dense->tw) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_to_dense: null dense grid");
-    if (dense->nx < 2u || dense->ny < 2u || dense->nz < 2u) return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_to_dense: every dimension of the dense grid must be at least 2");
-    if ((uint64_t)dense->nx * dense->ny > 0x7FFFFFFFull || (uint64_t)dense->nx * dense->ny * dense->nz > 0x7FFFFFFFull)
-        return set_error(ctx, BH_ERR_INVALID_ARG, "sptsdf_to_dense: more than 2^31 - 1 dense samples");
+    BH_TRY(tsdf_check_dense_dims(ctx, "sptsdf_to_dense", "dense ", dense->nx, dense->ny, dense->nz));
     BH_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = dense->nx * dense->ny * dense->nz;
     hipLaunchKernelGGL(sptsdf_to_dense_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, g, i0, j0, k0, dense->nx, dense->ny, n,

@@ -12,6 +12,10 @@
 //
 // Extraction is three phases without atomics: classify (per sample the mask of owned edges that carry a vertex, per cube the triangle
 // count), two inclusive scans (scan.hip), emit (a vertex index is scan[owner] - popcount(mask) + popcount(mask below d)).
+//
+// Shared with sparse_tsdf.hip through device_tsdf.h: the clear kernel, a sample's load / fuse / store, the classifier and the emitter,
+// the field checks, and the host drivers behind integrate and the two extract entry points.  Here: the grid's struct and check, each
+// kernel's map from thread to sample, the launch shapes, and the mesh PLY.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -33,16 +37,6 @@ struct TsdfGridDev {
 constexpr int TSDF_BX = 64, TSDF_BY = 4, TSDF_WG = TSDF_BX * TSDF_BY;
 constexpr uint32_t TSDF_MAX_BLOCKS = 1u << 20;   // (blocks x threads must stay below 2^32; larger volumes stride)
 
-__global__ __launch_bounds__(TSDF_WG) void tsdf_clear_kernel(TsdfGridDev g, uint32_t n) {
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n) return;
-    g.tw[s] = make_float2(1.0f, 0.0f);
-    if (g.rgb) {
-        float* c = g.rgb + (size_t)s * 3;
-        c[0] = 0.0f; c[1] = 0.0f; c[2] = 0.0f;
-    }
-}
-
 // COLOUR: the volume has rgb and the batch has images (then every view has one)
 template <bool COLOUR>
 __global__ __launch_bounds__(TSDF_WG) void tsdf_integrate_kernel(const TsdfGridDev g, const TsdfBatch b, const uint32_t n_views, const float depth_min,
@@ -55,21 +49,7 @@ __global__ __launch_bounds__(TSDF_WG) void tsdf_integrate_kernel(const TsdfGridD
         if (i >= g.nx || j >= g.ny) continue;
         const size_t s = ((size_t)k * g.ny + j) * g.nx + i;
         const float px = g.ox + g.vs * (float)i, py = g.oy + g.vs * (float)j, pz = g.oz + g.vs * (float)k;
-        const float2 tw = g.tw[s];
-        float T = tw.x, W = tw.y;
-        float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-        if (COLOUR) {
-            const float* c = g.rgb + s * 3;
-            c0 = c[0]; c1 = c[1]; c2 = c[2];
-        }
-        const bool touched = tsdf_update_sample<COLOUR>(b, n_views, depth_min, depth_max, alpha_min, g.trunc, g.max_weight, px, py, pz, T, W, c0, c1, c2);
-        if (touched) {
-            g.tw[s] = make_float2(T, W);
-            if (COLOUR) {
-                float* c = g.rgb + s * 3;
-                c[0] = c0; c[1] = c1; c[2] = c2;
-            }
-        }
+        tsdf_fuse_at<COLOUR>(g.tw, g.rgb, s, px, py, pz, b, n_views, depth_min, depth_max, alpha_min, g.trunc, g.max_weight);
     }
 }
 
@@ -94,10 +74,7 @@ __global__ __launch_bounds__(256) void tsdf_classify_kernel(const TsdfGridDev g,
                 obs |= (t.y > 0.0f ? 1u : 0u) << nb_bit(dx, dy, dz);
                 ins |= (t.x < 0.0f ? 1u : 0u) << nb_bit(dx, dy, dz);
             }
-    const uint32_t word = tsdf_classify_word(obs, ins);
-    info[s] = word;
-    vcnt[s] = (uint32_t)__popc(word & 0x7Fu);
-    tcnt[s] = (word >> 8) & 0xFFu;
+    tsdf_store_class(info, vcnt, tcnt, s, tsdf_classify_word(obs, ins));
 }
 
 __global__ __launch_bounds__(256) void tsdf_emit_kernel(const TsdfGridDev g, const uint32_t n, const uint32_t* __restrict__ info, const uint32_t* __restrict__ vinc,
@@ -154,38 +131,36 @@ static std::string mesh_ply_header(uint32_t n_v, bool colours, uint32_t n_t) {
 static int tsdf_check_grid(bh_ctx* ctx, const BhTsdfGrid* g, const char* who, TsdfGridDev* dev, uint32_t* n) {
     const std::string w(who);
     if (!g || !g->tw) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": null grid");
-    if (g->nx < 2u || g->ny < 2u || g->nz < 2u) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": every dimension of the grid must be at least 2");
-    if ((uint64_t)g->nx * g->ny > 0x7FFFFFFFull || (uint64_t)g->nx * g->ny * g->nz > 0x7FFFFFFFull)
-        return set_error(ctx, BH_ERR_INVALID_ARG, w + ": more than 2^31 - 1 samples");
-    if (!(std::isfinite(g->voxel_size) && g->voxel_size > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": voxel_size must be a finite number > 0");
-    if (!(std::isfinite(g->trunc) && g->trunc > 0.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": trunc must be a finite number > 0");
-    if (!(g->max_weight >= 1.0f)) return set_error(ctx, BH_ERR_INVALID_ARG, w + ": max_weight must be at least 1");
+    BH_TRY(tsdf_check_dense_dims(ctx, w, "", g->nx, g->ny, g->nz));
+    BH_TRY(tsdf_check_fields(ctx, w, g->nx, g->ny, g->nz, g->voxel_size, g->trunc, g->max_weight));
     *dev = TsdfGridDev{g->origin[0], g->origin[1], g->origin[2], g->voxel_size, g->nx, g->ny, g->nz, g->trunc, g->max_weight,
                        reinterpret_cast<float2*>(g->tw), g->rgb};
     *n = g->nx * g->ny * g->nz;
     return 0;
 }
 
-// classify + the two scans; the counts are read back (blocking)
-static int tsdf_classify_and_scan(bh_ctx* ctx, const TsdfGridDev& g, uint32_t n, uint32_t** info, uint32_t** vinc, uint32_t** tinc, uint32_t counts[2]) {
-    auto* scratch = (uint32_t*)ensure(ctx, SLOT_TSDF, (size_t)n * 12);
-    if (!scratch) return BH_ERR_OOM;
-    *info = scratch; *vinc = scratch + n; *tinc = scratch + 2 * (size_t)n;
-    const dim3 grid((n + 255u) / 256u), block(256);
-    {
-        ProfScope ps(ctx, "TsdfClassify");
-        hipLaunchKernelGGL(tsdf_classify_kernel, grid, block, 0, ctx->stream, g, n, *info, *vinc, *tinc);
-        BH_LAUNCH_CHECK(ctx, "tsdf_classify_kernel");
-    }
-    {
-        ProfScope ps(ctx, "TsdfScan");
-        BH_TRY(prefix_sum(ctx, *vinc, nullptr, n, *vinc, /*exclusive=*/false));
-        BH_TRY(prefix_sum(ctx, *tinc, nullptr, n, *tinc, /*exclusive=*/false));
-    }
-    BH_HIP(ctx, hipMemcpyAsync(&counts[0], *vinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipMemcpyAsync(&counts[1], *tinc + (n - 1u), 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+// bh_tsdf_extract and bh_tsdf_extract_count: the dense volume's two launches for tsdf_extract_run
+static int tsdf_extract_grid(bh_ctx* ctx, const BhTsdfGrid* grid, const char* who, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t,
+                             uint32_t* n_vertices, uint32_t* n_triangles, bool count_only) {
+    if (!ctx) return BH_ERR_INVALID_ARG;
+    TsdfGridDev g;
+    uint32_t n = 0;
+    BH_TRY(tsdf_check_grid(ctx, grid, who, &g, &n));
+    const dim3 launch((n + 255u) / 256u), block(256);
+    static const char* const prof[3] = {"TsdfClassify", "TsdfScan", "TsdfEmit"};
+    return tsdf_extract_run(
+        ctx, who, SLOT_TSDF, n, g.rgb != nullptr,
+        [&](uint32_t* info, uint32_t* vcnt, uint32_t* tcnt) {
+            hipLaunchKernelGGL(tsdf_classify_kernel, launch, block, 0, ctx->stream, g, n, info, vcnt, tcnt);
+            BH_LAUNCH_CHECK(ctx, "tsdf_classify_kernel");
+            return 0;
+        },
+        [&](const uint32_t* info, const uint32_t* vinc, const uint32_t* tinc) {
+            hipLaunchKernelGGL(tsdf_emit_kernel, launch, block, 0, ctx->stream, g, n, info, vinc, tinc, vertices, colours, triangles);
+            BH_LAUNCH_CHECK(ctx, "tsdf_emit_kernel");
+            return 0;
+        },
+        vertices, colours, triangles, cap_v, cap_t, n_vertices, n_triangles, count_only, prof);
 }
 
 }  // namespace bh
@@ -200,9 +175,7 @@ int bh_tsdf_clear(bh_ctx* ctx, const BhTsdfGrid* grid) {
     uint32_t n = 0;
     BH_TRY(tsdf_check_grid(ctx, grid, "tsdf_clear", &g, &n));
     BH_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tsdf_clear_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, g, n);
-    BH_LAUNCH_CHECK(ctx, "tsdf_clear_kernel");
-    return 0;
+    return tsdf_clear_samples(ctx, g.tw, g.rgb, n);
 }
 
 int bh_tsdf_integrate(bh_ctx* ctx, const BhTsdfGrid* grid, uint32_t n_views, const BhCamera* cams, const float* const* depths, const float* const* images,
@@ -211,66 +184,23 @@ int bh_tsdf_integrate(bh_ctx* ctx, const BhTsdfGrid* grid, uint32_t n_views, con
     TsdfGridDev g;
     uint32_t n = 0;
     BH_TRY(tsdf_check_grid(ctx, grid, "tsdf_integrate", &g, &n));
-    if (!cfg) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_integrate: null config");
-    if (n_views == 0) return 0;
-    BH_TRY(tsdf_check_views(ctx, "tsdf_integrate", n_views, cams, depths, images));
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    ProfScope ps(ctx, "TsdfIntegrate");
     const uint32_t blocks_x = (g.nx + TSDF_BX - 1) / TSDF_BX, blocks_y = (g.ny + TSDF_BY - 1) / TSDF_BY;
     const uint32_t n_blocks = blocks_x * blocks_y * g.nz;   // <= nx ny nz
     const dim3 launch(n_blocks < TSDF_MAX_BLOCKS ? n_blocks : TSDF_MAX_BLOCKS), block(TSDF_WG);
-    const bool colour = images && g.rgb;
-    for (uint32_t first = 0; first < n_views; first += BH_TSDF_MAX_BATCH) {
-        const uint32_t count = n_views - first < BH_TSDF_MAX_BATCH ? n_views - first : BH_TSDF_MAX_BATCH;
-        const TsdfBatch b = tsdf_make_batch(first, count, cams, depths, images);
-        if (colour)
-            hipLaunchKernelGGL(tsdf_integrate_kernel<true>, launch, block, 0, ctx->stream, g, b, count, cfg->depth_min, cfg->depth_max, cfg->alpha_min, blocks_x,
-                               blocks_y, n_blocks);
-        else
-            hipLaunchKernelGGL(tsdf_integrate_kernel<false>, launch, block, 0, ctx->stream, g, b, count, cfg->depth_min, cfg->depth_max, cfg->alpha_min, blocks_x,
-                               blocks_y, n_blocks);
-        BH_LAUNCH_CHECK(ctx, "tsdf_integrate_kernel");
-    }
-    return 0;
+    return tsdf_integrate_batches(ctx, "tsdf_integrate", "TsdfIntegrate", n_views, cams, depths, images, cfg, g.rgb != nullptr,
+                                  [&](bool colour, const TsdfBatch& b, uint32_t count) {
+                                      hipLaunchKernelGGL(colour ? tsdf_integrate_kernel<true> : tsdf_integrate_kernel<false>, launch, block, 0, ctx->stream, g, b, count,
+                                                         cfg->depth_min, cfg->depth_max, cfg->alpha_min, blocks_x, blocks_y, n_blocks);
+                                  });
 }
 
 int bh_tsdf_extract_count(bh_ctx* ctx, const BhTsdfGrid* grid, uint32_t* n_vertices, uint32_t* n_triangles) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    TsdfGridDev g;
-    uint32_t n = 0;
-    BH_TRY(tsdf_check_grid(ctx, grid, "tsdf_extract_count", &g, &n));
-    if (!n_vertices || !n_triangles) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_extract_count: null count pointer");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *info, *vinc, *tinc, counts[2] = {0, 0};
-    BH_TRY(tsdf_classify_and_scan(ctx, g, n, &info, &vinc, &tinc, counts));
-    *n_vertices = counts[0];
-    *n_triangles = counts[1];
-    return 0;
+    return tsdf_extract_grid(ctx, grid, "tsdf_extract_count", nullptr, nullptr, nullptr, 0, 0, n_vertices, n_triangles, /*count_only=*/true);
 }
 
 int bh_tsdf_extract(bh_ctx* ctx, const BhTsdfGrid* grid, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t,
                     uint32_t* n_vertices, uint32_t* n_triangles) {
-    if (!ctx) return BH_ERR_INVALID_ARG;
-    TsdfGridDev g;
-    uint32_t n = 0;
-    BH_TRY(tsdf_check_grid(ctx, grid, "tsdf_extract", &g, &n));
-    if (!n_vertices || !n_triangles) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_extract: null count pointer");
-    if (colours && !g.rgb) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_extract: colours of a volume without rgb");
-    BH_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *info, *vinc, *tinc, counts[2] = {0, 0};
-    BH_TRY(tsdf_classify_and_scan(ctx, g, n, &info, &vinc, &tinc, counts));
-    *n_vertices = counts[0];
-    *n_triangles = counts[1];
-    if (counts[0] > cap_v || counts[1] > cap_t) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_extract: output capacity too small");
-    if ((counts[0] && !vertices) || (counts[1] && !triangles)) return set_error(ctx, BH_ERR_INVALID_ARG, "tsdf_extract: null output");
-    if (counts[0] == 0u) return 0;   // (no vertex, hence no triangle)
-    {
-        ProfScope ps(ctx, "TsdfEmit");
-        hipLaunchKernelGGL(tsdf_emit_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, g, n, info, vinc, tinc, vertices, colours, triangles);
-        BH_LAUNCH_CHECK(ctx, "tsdf_emit_kernel");
-    }
-    BH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return tsdf_extract_grid(ctx, grid, "tsdf_extract", vertices, colours, triangles, cap_v, cap_t, n_vertices, n_triangles, /*count_only=*/false);
 }
 
 int bh_mesh_to_ply(bh_ctx* ctx, const float* vertices, const float* colours, uint32_t n_v, const uint32_t* triangles, uint32_t n_t, void* out, uint64_t cap,

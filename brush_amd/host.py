@@ -1865,13 +1865,13 @@ def mesh_to_ply(vertices, triangles, colours=None, ctx: Optional[Context] = None
     return bytes(buf)
 
 
-class TsdfVolume:
-    """A dense truncated signed distance volume on the device (include/brush_hip_mesh.h): `dims` = (nx, ny, nz) samples at
-    origin + voxel_size * (i, j, k), x fastest.  `tw` [nz,ny,nx,2] f32 holds {tsdf in units of trunc, weight}, `rgb` [nz,ny,nx,3] the
-    mean colour (None with colour=False).  integrate() fuses depth maps (KinectFusion's running mean, up to 8 views per launch),
-    extract_mesh() is marching tetrahedra at the zero level, to_ply() the mesh as a PLY file."""
+class _TsdfVolumeBase:
+    """What TsdfVolume and SparseTsdfVolume share: the fields and their refusals, from_bounds, the packing of views, and clear /
+    integrate / count / extract_mesh / to_ply over the subclass's struct (`_struct()`) and the prefix of its entry points (`_ENTRY`).
+    A subclass adds its size limit (`_check_size`) and its buffers."""
 
-    def __init__(self, origin, voxel_size, dims, trunc=None, max_weight=64.0, colour=True, device=None, ctx: Optional[Context] = None):
+    def __init__(self, origin, voxel_size, dims, trunc, max_weight, device, ctx):
+        name = type(self).__name__
         self.origin = tuple(float(v) for v in origin)
         self.voxel_size = float(voxel_size)
         self.dims = tuple(int(v) for v in dims)
@@ -1879,23 +1879,18 @@ class TsdfVolume:
         self.max_weight = float(max_weight)
         # refused here, before the device is touched (the library refuses the same)
         if len(self.origin) != 3 or len(self.dims) != 3:
-            raise ValueError("TsdfVolume: origin and dims have three entries")
+            raise ValueError("%s: origin and dims have three entries" % name)
         if min(self.dims) < 2:
-            raise ValueError("TsdfVolume: every dimension must be at least 2")
-        if self.dims[0] * self.dims[1] * self.dims[2] > 2 ** 31 - 1:
-            raise ValueError("TsdfVolume: more than 2^31 - 1 samples")
+            raise ValueError("%s: every dimension must be at least 2" % name)
+        self._check_size(name)
         if not (math.isfinite(self.voxel_size) and self.voxel_size > 0.0):
-            raise ValueError("TsdfVolume: voxel_size must be a finite number > 0")
+            raise ValueError("%s: voxel_size must be a finite number > 0" % name)
         if not (math.isfinite(self.trunc) and self.trunc > 0.0):
-            raise ValueError("TsdfVolume: trunc must be a finite number > 0")
+            raise ValueError("%s: trunc must be a finite number > 0" % name)
         if not self.max_weight >= 1.0:
-            raise ValueError("TsdfVolume: max_weight must be at least 1")
+            raise ValueError("%s: max_weight must be at least 1" % name)
         self.ctx = ctx or get_context(device)
         self.device = self.ctx.device
-        nx, ny, nz = self.dims
-        self.tw = torch.empty((nz, ny, nx, 2), dtype=torch.float32, device=self.device)
-        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if colour else None
-        self.clear()
 
     @classmethod
     def from_bounds(cls, bounds, resolution, **kw):
@@ -1912,6 +1907,87 @@ class TsdfVolume:
         origin = tuple(float(c) - 0.5 * voxel * (d - 1) for c, d in zip(center, dims))
         return cls(origin, voxel, dims, **kw)
 
+    def _committed(self, who):
+        """Raises where the volume cannot take the call `who` yet (a sparse volume before its commit)."""
+
+    def _call(self, entry, *args):
+        s = self._struct()
+        self.ctx.check(getattr(self.ctx.lib, self._ENTRY + entry)(self.ctx._h, C.byref(s), *args))
+
+    def _views(self, depths, cameras, images, who):
+        depths, cameras = list(depths), list(cameras)
+        if len(depths) != len(cameras) or (images is not None and len(images) != len(depths)):
+            raise ValueError("%s.%s: as many cameras (and images) as depth maps" % (type(self).__name__, who))
+        n = len(depths)
+        cams = TsdfVolume.check_views(cameras, [tuple(d.shape) for d in depths])
+        dev = self.device
+        depths = [_f32c(d, dev) for d in depths]
+        dptr = (C.c_void_p * max(n, 1))(*[d.data_ptr() for d in depths])
+        iptr = None
+        if images is not None:
+            images = [_f32c(im, dev).reshape(d.shape[0], d.shape[1], 4) for im, d in zip(images, depths)]
+            iptr = (C.c_void_p * max(n, 1))(*[im.data_ptr() for im in images])
+        return n, cams, dptr, iptr, (depths, images)   # (the last entry keeps the converted tensors alive across the call)
+
+    def clear(self):
+        """T = 1, W = 0, rgb = 0 in every sample held (a sparse volume: and keys from the index)."""
+        self._committed("clear")
+        self._call("clear")
+
+    def integrate(self, depths, cameras, images=None, depth_min=0.0, depth_max=math.inf, alpha_min=0.5):
+        """Fuses depths[v] [H,W] f32 (z-depth, 0 = none) seen by cameras[v] (Camera or BhCamera, pinhole) into the volume, in order;
+        images[v] [H,W,4] f32 gives the alpha test and, with colour, the colour.  Queued: nothing is read back.  A sparse volume fuses
+        into its allocated blocks: every allocated sample ends with the bits the dense volume would hold."""
+        self._committed("integrate")
+        n, cams, dptr, iptr, keep = self._views(depths, cameras, images, "integrate")
+        if n == 0:
+            return
+        cfg = _ffi.BhTsdfIntegrateConfig(float(depth_min), float(depth_max), float(alpha_min), 0)
+        self._call("integrate", n, cams, dptr, iptr, C.byref(cfg))
+
+    def count(self):
+        """(n_vertices, n_triangles) of the zero level set (bh_tsdf_extract_count / bh_sptsdf_extract_count; blocking)."""
+        self._committed("count")
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self._call("extract_count", C.byref(nv), C.byref(nt))
+        return int(nv.value), int(nt.value)
+
+    def extract_mesh(self):
+        """(vertices [V,3] f32, colours [V,3] f32 or None, triangles [M,3] int32) on the device: marching tetrahedra at the zero level
+        over the cubes whose eight corners were observed; counter-clockwise seen from outside, deterministic.  A sparse volume's
+        vertices come in pool order (by block key, then by the sample's index in its block)."""
+        n_v, n_t = self.count()
+        dev = self.device
+        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        colours = torch.empty((n_v, 3), dtype=torch.float32, device=dev) if self.rgb is not None else None
+        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self._call("extract", _ptr(vertices), _ptr(colours) if colours is not None else None, _ptr(triangles), n_v, n_t, C.byref(nv), C.byref(nt))
+        return vertices, colours, triangles
+
+    def to_ply(self) -> bytes:
+        vertices, colours, triangles = self.extract_mesh()
+        return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
+
+
+class TsdfVolume(_TsdfVolumeBase):
+    """A dense truncated signed distance volume on the device (include/brush_hip_mesh.h): `dims` = (nx, ny, nz) samples at
+    origin + voxel_size * (i, j, k), x fastest.  `tw` [nz,ny,nx,2] f32 holds {tsdf in units of trunc, weight}, `rgb` [nz,ny,nx,3] the
+    mean colour (None with colour=False).  integrate() fuses depth maps (KinectFusion's running mean, up to 8 views per launch),
+    extract_mesh() is marching tetrahedra at the zero level, to_ply() the mesh as a PLY file."""
+    _ENTRY = "bh_tsdf_"
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, max_weight=64.0, colour=True, device=None, ctx: Optional[Context] = None):
+        super().__init__(origin, voxel_size, dims, trunc, max_weight, device, ctx)
+        nx, ny, nz = self.dims
+        self.tw = torch.empty((nz, ny, nx, 2), dtype=torch.float32, device=self.device)
+        self.rgb = torch.empty((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if colour else None
+        self.clear()
+
+    def _check_size(self, name):
+        if self.dims[0] * self.dims[1] * self.dims[2] > 2 ** 31 - 1:
+            raise ValueError("%s: more than 2^31 - 1 samples" % name)
+
     def grid(self) -> "_ffi.BhTsdfGrid":
         g = _ffi.BhTsdfGrid()
         g.origin = (C.c_float * 3)(*self.origin)
@@ -1921,6 +1997,8 @@ class TsdfVolume:
         g.tw = self.tw.data_ptr()
         g.rgb = self.rgb.data_ptr() if self.rgb is not None else None
         return g
+
+    _struct = grid
 
     @staticmethod
     def check_views(cameras, shapes):
@@ -1939,100 +2017,30 @@ class TsdfVolume:
                 raise ValueError("TsdfVolume.integrate: camera %d is %dx%d, its depth map %dx%d" % (v, cams[v].img_w, cams[v].img_h, shape[1], shape[0]))
         return cams
 
-    def clear(self):
-        g = self.grid()
-        self.ctx.check(self.ctx.lib.bh_tsdf_clear(self.ctx._h, C.byref(g)))
 
-    def integrate(self, depths, cameras, images=None, depth_min=0.0, depth_max=math.inf, alpha_min=0.5):
-        """Fuses depths[v] [H,W] f32 (z-depth, 0 = none) seen by cameras[v] (Camera or BhCamera, pinhole) into the volume, in order;
-        images[v] [H,W,4] f32 gives the alpha test and, with colour, the colour.  Queued: nothing is read back."""
-        depths, cameras = list(depths), list(cameras)
-        if len(depths) != len(cameras) or (images is not None and len(images) != len(depths)):
-            raise ValueError("TsdfVolume.integrate: as many cameras (and images) as depth maps")
-        n = len(depths)
-        if n == 0:
-            return
-        cams = self.check_views(cameras, [tuple(d.shape) for d in depths])
-        dev = self.device
-        depths = [_f32c(d, dev) for d in depths]
-        dptr = (C.c_void_p * n)(*[d.data_ptr() for d in depths])
-        iptr = None
-        if images is not None:
-            images = [_f32c(im, dev).reshape(d.shape[0], d.shape[1], 4) for im, d in zip(images, depths)]
-            iptr = (C.c_void_p * n)(*[im.data_ptr() for im in images])
-        cfg = _ffi.BhTsdfIntegrateConfig(float(depth_min), float(depth_max), float(alpha_min), 0)
-        g = self.grid()
-        self.ctx.check(self.ctx.lib.bh_tsdf_integrate(self.ctx._h, C.byref(g), n, cams, dptr, iptr, C.byref(cfg)))
-
-    def count(self):
-        """(n_vertices, n_triangles) of the zero level set (bh_tsdf_extract_count; blocking)."""
-        g = self.grid()
-        nv, nt = C.c_uint32(), C.c_uint32()
-        self.ctx.check(self.ctx.lib.bh_tsdf_extract_count(self.ctx._h, C.byref(g), C.byref(nv), C.byref(nt)))
-        return int(nv.value), int(nt.value)
-
-    def extract_mesh(self):
-        """(vertices [V,3] f32, colours [V,3] f32 or None, triangles [M,3] int32) on the device: marching tetrahedra at the zero level
-        over the cubes whose eight corners were observed; counter-clockwise seen from outside, deterministic."""
-        n_v, n_t = self.count()
-        dev = self.device
-        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-        colours = torch.empty((n_v, 3), dtype=torch.float32, device=dev) if self.rgb is not None else None
-        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
-        g = self.grid()
-        nv, nt = C.c_uint32(), C.c_uint32()
-        self.ctx.check(self.ctx.lib.bh_tsdf_extract(self.ctx._h, C.byref(g), _ptr(vertices), _ptr(colours) if colours is not None else None, _ptr(triangles),
-                                                    n_v, n_t, C.byref(nv), C.byref(nt)))
-        return vertices, colours, triangles
-
-    def to_ply(self) -> bytes:
-        vertices, colours, triangles = self.extract_mesh()
-        return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
-
-
-class SparseTsdfVolume:
+class SparseTsdfVolume(_TsdfVolumeBase):
     """A sparse truncated signed distance volume on the device (include/brush_hip_sparse_mesh.h): a virtual grid of
     `dims` = (nx, ny, nz) samples (each 2 .. 8192) at origin + voxel_size * (i, j, k), of which only the 8x8x8 blocks near the observed
     surfaces are held.  mark() sets the blocks the depth maps' rays cross inside the truncation band, commit() dilates them, counts
     them and allocates the pool (`keys` [n_blocks], `tw` [n_blocks,8,8,8,2], `rgb` [n_blocks,8,8,8,3] or None), integrate() fuses depth
     maps by TsdfVolume's rule, extract_mesh() / to_ply() are TsdfVolume's, to_dense() writes a window into a TsdfVolume."""
+    _ENTRY = "bh_sptsdf_"
 
     def __init__(self, origin, voxel_size, dims, trunc=None, max_weight=64.0, colour=True, device=None, ctx: Optional[Context] = None):
-        self.origin = tuple(float(v) for v in origin)
-        self.voxel_size = float(voxel_size)
-        self.dims = tuple(int(v) for v in dims)
-        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
-        self.max_weight = float(max_weight)
+        super().__init__(origin, voxel_size, dims, trunc, max_weight, device, ctx)
         self.colour = bool(colour)
-        # refused here, before the device is touched (the library refuses the same)
-        if len(self.origin) != 3 or len(self.dims) != 3:
-            raise ValueError("SparseTsdfVolume: origin and dims have three entries")
-        if min(self.dims) < 2:
-            raise ValueError("SparseTsdfVolume: every dimension must be at least 2")
-        if max(self.dims) > _ffi.SPTSDF_MAX_DIM:
-            raise ValueError("SparseTsdfVolume: a dimension above %d" % _ffi.SPTSDF_MAX_DIM)
-        self.block_dims = tuple((d + _ffi.SPTSDF_BLOCK - 1) // _ffi.SPTSDF_BLOCK for d in self.dims)
-        total = self.block_dims[0] * self.block_dims[1] * self.block_dims[2]
-        if total > 2 ** 30:
-            raise ValueError("SparseTsdfVolume: more than 2^30 virtual blocks")
-        if not (math.isfinite(self.voxel_size) and self.voxel_size > 0.0):
-            raise ValueError("SparseTsdfVolume: voxel_size must be a finite number > 0")
-        if not (math.isfinite(self.trunc) and self.trunc > 0.0):
-            raise ValueError("SparseTsdfVolume: trunc must be a finite number > 0")
-        if not self.max_weight >= 1.0:
-            raise ValueError("SparseTsdfVolume: max_weight must be at least 1")
-        self.ctx = ctx or get_context(device)
-        self.device = self.ctx.device
-        self.n_words = (total + 31) // 32
+        self.n_words = (self.block_dims[0] * self.block_dims[1] * self.block_dims[2] + 31) // 32
         self.bits = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
         self.rank = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
         self.n_blocks = 0
         self.keys = self.tw = self.rgb = None
 
-    @classmethod
-    def from_bounds(cls, bounds, resolution, **kw):
-        """As TsdfVolume.from_bounds: `resolution` samples along the box's longest side, cubic voxels."""
-        return TsdfVolume.from_bounds.__func__(cls, bounds, resolution, **kw)
+    def _check_size(self, name):
+        if max(self.dims) > _ffi.SPTSDF_MAX_DIM:
+            raise ValueError("%s: a dimension above %d" % (name, _ffi.SPTSDF_MAX_DIM))
+        self.block_dims = tuple((d + _ffi.SPTSDF_BLOCK - 1) // _ffi.SPTSDF_BLOCK for d in self.dims)
+        if self.block_dims[0] * self.block_dims[1] * self.block_dims[2] > 2 ** 30:
+            raise ValueError("%s: more than 2^30 virtual blocks" % name)
 
     def mark_steps(self) -> int:
         """M of bh_sptsdf_mark: the smallest integer with (float)M * (4 voxel_size) >= 2 trunc, in f32."""
@@ -2055,20 +2063,7 @@ class SparseTsdfVolume:
         v.rgb = self.rgb.data_ptr() if self.rgb is not None else None
         return v
 
-    def _views(self, depths, cameras, images, who):
-        depths, cameras = list(depths), list(cameras)
-        if len(depths) != len(cameras) or (images is not None and len(images) != len(depths)):
-            raise ValueError("SparseTsdfVolume.%s: as many cameras (and images) as depth maps" % who)
-        n = len(depths)
-        cams = TsdfVolume.check_views(cameras, [tuple(d.shape) for d in depths])
-        dev = self.device
-        depths = [_f32c(d, dev) for d in depths]
-        dptr = (C.c_void_p * max(n, 1))(*[d.data_ptr() for d in depths])
-        iptr = None
-        if images is not None:
-            images = [_f32c(im, dev).reshape(d.shape[0], d.shape[1], 4) for im, d in zip(images, depths)]
-            iptr = (C.c_void_p * max(n, 1))(*[im.data_ptr() for im in images])
-        return n, cams, dptr, iptr, (depths, images)   # (the last entry keeps the converted tensors alive across the call)
+    _struct = vol
 
     def _committed(self, who):
         if self.n_blocks == 0:
@@ -2078,8 +2073,7 @@ class SparseTsdfVolume:
         """Forgets every mark and the committed pool: the volume is as new."""
         self.n_blocks = 0
         self.keys = self.tw = self.rgb = None
-        v = self.vol()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_mark_clear(self.ctx._h, C.byref(v)))
+        self._call("mark_clear")
 
     def mark(self, depths, cameras, images=None, depth_max=math.inf, alpha_min=0.5):
         """Marks the blocks that the rays of depths[v] [H,W] cross within trunc of the depth (bh_sptsdf_mark); any number of calls
@@ -2092,8 +2086,7 @@ class SparseTsdfVolume:
         if n == 0:
             return
         cfg = _ffi.BhTsdfIntegrateConfig(0.0, float(depth_max), float(alpha_min), 0)
-        v = self.vol()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_mark(self.ctx._h, C.byref(v), n, cams, dptr, iptr, C.byref(cfg)))
+        self._call("mark", n, cams, dptr, iptr, C.byref(cfg))
 
     def commit(self, dilate=1) -> int:
         """Allocates every block within `dilate` (0, 1 or 2) blocks of a marked one, and clears the pool; -> the number of blocks
@@ -2103,8 +2096,7 @@ class SparseTsdfVolume:
         if self.n_blocks:
             raise ValueError("SparseTsdfVolume.commit: already committed: mark_clear() starts over")
         n = C.c_uint32()
-        v = self.vol()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_commit(self.ctx._h, C.byref(v), int(dilate), C.byref(n)))
+        self._call("commit", int(dilate), C.byref(n))
         n = int(n.value)
         if n:
             self.keys = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -2113,48 +2105,6 @@ class SparseTsdfVolume:
             self.n_blocks = n
             self.clear()
         return n
-
-    def clear(self):
-        """keys from the index, and T = 1, W = 0, rgb = 0 in every sample of the pool."""
-        self._committed("clear")
-        v = self.vol()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_clear(self.ctx._h, C.byref(v)))
-
-    def integrate(self, depths, cameras, images=None, depth_min=0.0, depth_max=math.inf, alpha_min=0.5):
-        """TsdfVolume.integrate on the allocated blocks: every allocated sample ends with the bits the dense volume would hold."""
-        self._committed("integrate")
-        n, cams, dptr, iptr, keep = self._views(depths, cameras, images, "integrate")
-        if n == 0:
-            return
-        cfg = _ffi.BhTsdfIntegrateConfig(float(depth_min), float(depth_max), float(alpha_min), 0)
-        v = self.vol()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_integrate(self.ctx._h, C.byref(v), n, cams, dptr, iptr, C.byref(cfg)))
-
-    def count(self):
-        """(n_vertices, n_triangles) of the zero level set (bh_sptsdf_extract_count; blocking)."""
-        self._committed("count")
-        v = self.vol()
-        nv, nt = C.c_uint32(), C.c_uint32()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_extract_count(self.ctx._h, C.byref(v), C.byref(nv), C.byref(nt)))
-        return int(nv.value), int(nt.value)
-
-    def extract_mesh(self):
-        """(vertices [V,3] f32, colours [V,3] f32 or None, triangles [M,3] int32) on the device, as TsdfVolume.extract_mesh; vertices
-        come in pool order (by block key, then by the sample's index in its block)."""
-        n_v, n_t = self.count()
-        dev = self.device
-        vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-        colours = torch.empty((n_v, 3), dtype=torch.float32, device=dev) if self.rgb is not None else None
-        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
-        v = self.vol()
-        nv, nt = C.c_uint32(), C.c_uint32()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_extract(self.ctx._h, C.byref(v), _ptr(vertices), _ptr(colours) if colours is not None else None, _ptr(triangles),
-                                                      n_v, n_t, C.byref(nv), C.byref(nt)))
-        return vertices, colours, triangles
-
-    def to_ply(self) -> bytes:
-        vertices, colours, triangles = self.extract_mesh()
-        return mesh_to_ply(vertices, triangles, colours, ctx=self.ctx)
 
     def to_dense(self, start=(0, 0, 0), dims=None, colour=None) -> TsdfVolume:
         """The window of the virtual grid from sample `start`, `dims` samples wide (default: to the end of the grid), as a TsdfVolume:
@@ -2168,8 +2118,8 @@ class SparseTsdfVolume:
         origin = tuple(o + self.voxel_size * s for o, s in zip(self.origin, start))
         dense = TsdfVolume(origin, self.voxel_size, dims, trunc=self.trunc, max_weight=self.max_weight, colour=self.colour if colour is None else bool(colour),
                            ctx=self.ctx)
-        v, g = self.vol(), dense.grid()
-        self.ctx.check(self.ctx.lib.bh_sptsdf_to_dense(self.ctx._h, C.byref(v), start[0], start[1], start[2], C.byref(g)))
+        g = dense.grid()
+        self._call("to_dense", start[0], start[1], start[2], C.byref(g))
         return dense
 
 

@@ -1667,6 +1667,53 @@ inline std::vector<uint8_t> mesh_to_ply(const Context& ctx, const float* vertice
     ctx.check(bh_mesh_to_ply(ctx.get(), vertices, colours, n_v, triangles, n_t, out.data(), need, &need));
     return out;
 }
+namespace detail {
+// what TsdfVolume and SparseTsdfVolume share: the fields of their structs, the view vectors' check, and extraction over the
+// volume's struct, whose type picks the two C entry points
+inline int tsdf_extract_count(bh_ctx* c, const BhTsdfGrid* v, uint32_t* nv, uint32_t* nt) { return bh_tsdf_extract_count(c, v, nv, nt); }
+inline int tsdf_extract_count(bh_ctx* c, const BhSparseTsdf* v, uint32_t* nv, uint32_t* nt) { return bh_sptsdf_extract_count(c, v, nv, nt); }
+inline int tsdf_extract(bh_ctx* c, const BhTsdfGrid* v, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t, uint32_t* nv, uint32_t* nt) {
+    return bh_tsdf_extract(c, v, vertices, colours, triangles, cap_v, cap_t, nv, nt);
+}
+inline int tsdf_extract(bh_ctx* c, const BhSparseTsdf* v, float* vertices, float* colours, uint32_t* triangles, uint32_t cap_v, uint32_t cap_t, uint32_t* nv, uint32_t* nt) {
+    return bh_sptsdf_extract(c, v, vertices, colours, triangles, cap_v, cap_t, nv, nt);
+}
+template <class V>
+inline V tsdf_fields(const std::array<float, 3>& origin, float voxel_size, const std::array<uint32_t, 3>& dims, float trunc, float max_weight) {
+    V v{};
+    for (int a = 0; a < 3; ++a) v.origin[a] = origin[a];
+    v.voxel_size = voxel_size;
+    v.nx = dims[0]; v.ny = dims[1]; v.nz = dims[2];
+    v.trunc = trunc > 0.0f ? trunc : 4.0f * voxel_size;
+    v.max_weight = max_weight;
+    return v;
+}
+inline void tsdf_check_views(const char* who, const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images) {
+    if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
+        throw Error(BH_ERR_INVALID_ARG, std::string(who) + ": as many depth maps (and images) as cameras");
+}
+template <class V>
+inline std::pair<uint32_t, uint32_t> tsdf_count(const Context& ctx, const V& v) {
+    uint32_t nv = 0, nt = 0;
+    ctx.check(tsdf_extract_count(ctx.get(), &v, &nv, &nt));
+    return {nv, nt};
+}
+template <class V>
+inline Mesh tsdf_mesh(const Context& ctx, const V& v) {
+    Mesh m;
+    const auto [nv, nt] = tsdf_count(ctx, v);
+    m.vertices.resize((size_t)nv * 3);
+    if (v.rgb) m.colours.resize((size_t)nv * 3);
+    m.triangles.resize((size_t)nt * 3);
+    ctx.check(tsdf_extract(ctx.get(), &v, m.vertices.data(), v.rgb ? m.colours.data() : nullptr, m.triangles.data(), nv, nt, &m.n_vertices, &m.n_triangles));
+    return m;
+}
+template <class V>
+inline std::vector<uint8_t> tsdf_to_ply(const Context& ctx, const V& v) {
+    const Mesh m = tsdf_mesh(ctx, v);
+    return mesh_to_ply(ctx, m.vertices.data(), v.rgb ? m.colours.data() : nullptr, m.n_vertices, m.triangles.data(), m.n_triangles);
+}
+}  // namespace detail
 // A dense TSDF volume that owns its device memory: nx x ny x nz samples at origin + voxel_size * (i, j, k), x fastest; tw holds
 // { tsdf in units of trunc, weight }, rgb the mean colour.  integrate() fuses depth maps (KinectFusion's running mean, up to
 // BH_TSDF_MAX_BATCH views per pass over the volume), extract() is marching tetrahedra at the zero level.  Move-only.
@@ -1674,13 +1721,7 @@ class TsdfVolume {
 public:
     TsdfVolume(const Context& ctx, const std::array<float, 3>& origin, float voxel_size, const std::array<uint32_t, 3>& dims, float trunc = 0.0f /*0: 4 voxels*/,
                float max_weight = 64.0f, bool colour = true)
-        : ctx_(&ctx) {
-        g_ = BhTsdfGrid{};
-        for (int a = 0; a < 3; ++a) g_.origin[a] = origin[a];
-        g_.voxel_size = voxel_size;
-        g_.nx = dims[0]; g_.ny = dims[1]; g_.nz = dims[2];
-        g_.trunc = trunc > 0.0f ? trunc : 4.0f * voxel_size;
-        g_.max_weight = max_weight;
+        : ctx_(&ctx), g_(detail::tsdf_fields<BhTsdfGrid>(origin, voxel_size, dims, trunc, max_weight)) {
         const uint64_t n = (uint64_t)dims[0] * dims[1] * dims[2];
         if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2 || n > 0x7FFFFFFFull) throw Error(BH_ERR_INVALID_ARG, "TsdfVolume: dimensions of 2 or more, at most 2^31 - 1 samples");
         tw_.resize((size_t)n * 2);
@@ -1705,30 +1746,13 @@ public:
     // depths[v] [H,W] and images[v] [H,W,4] (or an empty vector: no alpha test, no colour) are device pointers of cams[v]'s size
     void integrate(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {},
                    float depth_min = 0.0f, float depth_max = INFINITY, float alpha_min = 0.5f) {
-        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
-            throw Error(BH_ERR_INVALID_ARG, "TsdfVolume::integrate: as many depth maps (and images) as cameras");
+        detail::tsdf_check_views("TsdfVolume::integrate", cams, depths, images);
         const BhTsdfIntegrateConfig cfg{depth_min, depth_max, alpha_min, 0u};
         ctx_->check(bh_tsdf_integrate(ctx_->get(), &g_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
     }
-    std::pair<uint32_t, uint32_t> count() const {   // (vertices, triangles); blocking
-        uint32_t nv = 0, nt = 0;
-        ctx_->check(bh_tsdf_extract_count(ctx_->get(), &g_, &nv, &nt));
-        return {nv, nt};
-    }
-    Mesh extract() const {
-        Mesh m;
-        const auto [nv, nt] = count();
-        m.vertices.resize((size_t)nv * 3);
-        if (g_.rgb) m.colours.resize((size_t)nv * 3);
-        m.triangles.resize((size_t)nt * 3);
-        ctx_->check(bh_tsdf_extract(ctx_->get(), &g_, m.vertices.data(), g_.rgb ? m.colours.data() : nullptr, m.triangles.data(), nv, nt, &m.n_vertices,
-                                    &m.n_triangles));
-        return m;
-    }
-    std::vector<uint8_t> to_ply() const {
-        const Mesh m = extract();
-        return mesh_to_ply(*ctx_, m.vertices.data(), g_.rgb ? m.colours.data() : nullptr, m.n_vertices, m.triangles.data(), m.n_triangles);
-    }
+    std::pair<uint32_t, uint32_t> count() const { return detail::tsdf_count(*ctx_, g_); }   // (vertices, triangles); blocking
+    Mesh extract() const { return detail::tsdf_mesh(*ctx_, g_); }
+    std::vector<uint8_t> to_ply() const { return detail::tsdf_to_ply(*ctx_, g_); }
 
 private:
     const Context* ctx_;
@@ -1748,13 +1772,7 @@ class SparseTsdfVolume {
 public:
     SparseTsdfVolume(const Context& ctx, const std::array<float, 3>& origin, float voxel_size, const std::array<uint32_t, 3>& dims, float trunc = 0.0f /*0: 4 voxels*/,
                      float max_weight = 64.0f, bool colour = true)
-        : ctx_(&ctx), colour_(colour) {
-        v_ = BhSparseTsdf{};
-        for (int a = 0; a < 3; ++a) v_.origin[a] = origin[a];
-        v_.voxel_size = voxel_size;
-        v_.nx = dims[0]; v_.ny = dims[1]; v_.nz = dims[2];
-        v_.trunc = trunc > 0.0f ? trunc : 4.0f * voxel_size;
-        v_.max_weight = max_weight;
+        : ctx_(&ctx), colour_(colour), v_(detail::tsdf_fields<BhSparseTsdf>(origin, voxel_size, dims, trunc, max_weight)) {
         for (uint32_t d : dims)
             if (d < 2 || d > BH_SPTSDF_MAX_DIM) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume: dimensions of 2 .. 8192");
         const uint64_t total = (uint64_t)((dims[0] + 7) / 8) * ((dims[1] + 7) / 8) * ((dims[2] + 7) / 8);
@@ -1797,8 +1815,7 @@ public:
     // depths[v] [H,W] and images[v] [H,W,4] (or an empty vector: no alpha test) are device pointers of cams[v]'s size
     void mark(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {}, float depth_max = INFINITY,
               float alpha_min = 0.5f) {
-        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
-            throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::mark: as many depth maps (and images) as cameras");
+        detail::tsdf_check_views("SparseTsdfVolume::mark", cams, depths, images);
         if (v_.n_blocks) throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::mark: after a commit: mark_clear() first");
         const BhTsdfIntegrateConfig cfg{0.0f, depth_max, alpha_min, 0u};
         ctx_->check(bh_sptsdf_mark(ctx_->get(), &v_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
@@ -1822,30 +1839,13 @@ public:
     void clear() { ctx_->check(bh_sptsdf_clear(ctx_->get(), &v_)); }
     void integrate(const std::vector<BhCamera>& cams, const std::vector<const float*>& depths, const std::vector<const float*>& images = {},
                    float depth_min = 0.0f, float depth_max = INFINITY, float alpha_min = 0.5f) {
-        if (depths.size() != cams.size() || (!images.empty() && images.size() != cams.size()))
-            throw Error(BH_ERR_INVALID_ARG, "SparseTsdfVolume::integrate: as many depth maps (and images) as cameras");
+        detail::tsdf_check_views("SparseTsdfVolume::integrate", cams, depths, images);
         const BhTsdfIntegrateConfig cfg{depth_min, depth_max, alpha_min, 0u};
         ctx_->check(bh_sptsdf_integrate(ctx_->get(), &v_, (uint32_t)cams.size(), cams.data(), depths.data(), images.empty() ? nullptr : images.data(), &cfg));
     }
-    std::pair<uint32_t, uint32_t> count() const {   // (vertices, triangles); blocking
-        uint32_t nv = 0, nt = 0;
-        ctx_->check(bh_sptsdf_extract_count(ctx_->get(), &v_, &nv, &nt));
-        return {nv, nt};
-    }
-    Mesh extract() const {
-        Mesh m;
-        const auto [nv, nt] = count();
-        m.vertices.resize((size_t)nv * 3);
-        if (v_.rgb) m.colours.resize((size_t)nv * 3);
-        m.triangles.resize((size_t)nt * 3);
-        ctx_->check(bh_sptsdf_extract(ctx_->get(), &v_, m.vertices.data(), v_.rgb ? m.colours.data() : nullptr, m.triangles.data(), nv, nt, &m.n_vertices,
-                                      &m.n_triangles));
-        return m;
-    }
-    std::vector<uint8_t> to_ply() const {
-        const Mesh m = extract();
-        return mesh_to_ply(*ctx_, m.vertices.data(), v_.rgb ? m.colours.data() : nullptr, m.n_vertices, m.triangles.data(), m.n_triangles);
-    }
+    std::pair<uint32_t, uint32_t> count() const { return detail::tsdf_count(*ctx_, v_); }   // (vertices, triangles); blocking
+    Mesh extract() const { return detail::tsdf_mesh(*ctx_, v_); }
+    std::vector<uint8_t> to_ply() const { return detail::tsdf_to_ply(*ctx_, v_); }
     // the window of the virtual grid from sample `start`, of dense's size, into `dense` (bh_sptsdf_to_dense)
     void to_dense(const std::array<uint32_t, 3>& start, TsdfVolume& dense) const {
         ctx_->check(bh_sptsdf_to_dense(ctx_->get(), &v_, start[0], start[1], start[2], &dense.grid()));

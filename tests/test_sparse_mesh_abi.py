@@ -83,8 +83,11 @@ def test_header_declares_the_binding_and_the_library_exports_it():
     csrc = os.path.join(ROOT, "brush_amd", "csrc")
     for unit in ("tsdf.hip", "sparse_tsdf.hip"):
         text = open(os.path.join(csrc, unit)).read()
-        assert '#include "device_tsdf.h"' in text and "TSDF_CASE[16]" not in text and "tsdf_update_sample<" in text and "tsdf_classify_word(" in text, unit
-    assert open(os.path.join(csrc, "device_tsdf.h")).read().count("TSDF_CASE[16]") == 1
+        # (the fusion rule is reached through the one load / fuse / store around it, tsdf_fuse_at)
+        assert '#include "device_tsdf.h"' in text and "TSDF_CASE[16]" not in text and "tsdf_fuse_at<" in text and "tsdf_classify_word(" in text, unit
+        assert "tsdf_update_sample<" not in text, unit
+    shared = open(os.path.join(csrc, "device_tsdf.h")).read()
+    assert shared.count("TSDF_CASE[16]") == 1 and shared.count("tsdf_update_sample<COLOUR>(") == 1
 
 
 def test_python_mirror_has_the_surface():
